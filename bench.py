@@ -12,12 +12,17 @@ Pipeline of one run (every rank; rows in random order, experiments.shuffle_rows)
      product's own `inference.observed_sweep` with one sub-batch: upload of the replicated latent tables,
      the HIP sweep (proposal scoring, draws, particle weights, final choice), the exchange of the CRP
      sufficient statistics (all-reduce, RCCL for N>1) and of new-row records / moved rows, the host commit;
-  5. one extra, untimed sweep with the library's per-phase HIP-event profile on (`phases_ms`).
+  5. `--dump-outputs DIR`: what the last timed step left to its caller, as DIR/<name>.npy (`dump_outputs`).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = block 0's
-root scan, HIP-event timed on the library's stream; algorithmic bytes = what THIS algorithm has to move, see
-`roofline_model`) and `cpu_baseline` (the CPU oracle's sequential-schedule sweep on a bounded sample of the
-same workload, single thread).
+A plain run stops there: F1 of the timed state and ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`ms_per_step` = milliseconds of one timed step, ...).  `--full` measures everything else as well, each in
+sweeps of its own after the timed region: the unrestricted-DL kernel on one table, F1 after the
+initialisation, the same sweep cut into 32 sub-batches and into two half windows, the Measure slot's root
+launch group, one extra sweep with the library's per-phase HIP-event profile on (`phases_ms`), two
+steady-state full iterations, `roofline` (dominant kernel = block 0's root scan, HIP-event timed on the
+library's stream; algorithmic bytes = what THIS algorithm has to move, see `roofline_model`) and
+`cpu_baseline` (the CPU oracle's sequential-schedule sweep on a bounded sample of the same workload,
+single thread).
 
 `python bench.py --gpus N` without a torchrun environment re-launches itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU).
@@ -255,6 +260,36 @@ def cpu_baseline(lw, obs, tr, eng, cfg, seed, min_rows, target_seconds):
     return out
 
 
+DUMP_BYTES = 64 << 20  # at most this much in all under --dump-outputs
+
+
+def dump_outputs(path, tr, changed):
+    """What the last timed step left to its caller, one DIR/<name>.npy each, in float64 (every id and count is exact):
+    `cur` (the referent of every observed row per block, as trace.cur), `locals_<block>` (own enumerated choices of the
+    chosen particles, where the model has any), `<class>_cols` / `<class>_counts` of every latent table (value columns
+    and reference counts, as LatentTable.view) and `changed` (referents the step changed).  Should the arrays exceed
+    DUMP_BYTES in all, each keeps the same seeded sample of its rows and `<name>_sample` names them."""
+    arrays = {"changed": (np.array([changed]), 0), "cur": (tr.cur, 1)}
+    for bi, loc in sorted(tr.locals.items()):
+        arrays[f"locals_{bi}"] = (loc, 0)
+    for cname, t in sorted(tr.tables.items()):
+        cols, counts = t.view()
+        arrays[f"{cname}_cols"] = (cols, 1)
+        arrays[f"{cname}_counts"] = (counts, 0)
+    total = sum(8 * a.size for a, _ in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, (a, axis) in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        n = a.shape[axis]
+        keep = n if total <= DUMP_BYTES else max(1, n * (DUMP_BYTES // 2) // total)  # (half: room for the sample ids)
+        if keep < n:
+            idx = np.sort(np.random.default_rng(20250926).choice(n, keep, replace=False))
+            a = np.take(a, idx, axis=axis)
+            np.save(os.path.join(path, f"{name}_sample.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+    log(f"[bench] outputs of the last timed step written to {path}: {len(arrays)} arrays, {total / 1e6:.1f} MB")
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` outside torchrun: one rank per GPU through torch.distributed.run."""
     port = int(os.environ.get("MASTER_PORT", "29533"))
@@ -291,7 +326,14 @@ def main():
                     help="strong (default, the BASELINE metric): --rows rows in total, sharded over the ranks; weak: --rows "
                          "rows PER RANK (the table grows with the ranks, the number of true hospitals stays: the pair "
                          "tables scale with unique values squared and would not fit otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well (the module docstring lists it); a plain run sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -334,7 +376,7 @@ def main():
 
     # the unrestricted-DL kernel (what the three real programs build their tables with) on one table of the workload
     dl_sample = None
-    if rank == 0 and not args.no_dl_sample:
+    if rank == 0 and args.full and not args.no_dl_sample:
         def cells_of(v):
             return int(lw.pool.lens[v[1].id_array()].astype(np.int64).sum()) * int(lw.pool.lens[v[2].id_array()].astype(np.int64).sum())
 
@@ -369,8 +411,9 @@ def main():
     initialize_trace(eng, tr, cfg1, args.seed, max_batch=args.init_batch, comm=comm)
     torch.cuda.synchronize()
     init_s = time.time() - t0
-    acc_init = f1_now(tr)
-    log(f"[bench] initialize_trace {init_s:.1f}s: F1 {acc_init['f1']:.4f} " + " ".join(f"{c}={t.n_live}" for c, t in tr.tables.items()))
+    acc_init = f1_now(tr) if args.full else None
+    log(f"[bench] initialize_trace {init_s:.1f}s: " + (f"F1 {acc_init['f1']:.4f} " if acc_init else "")
+        + " ".join(f"{c}={t.n_live}" for c, t in tr.tables.items()))
     full_ms = None
     from pclean_amd import inference as inf
     # one-time set-up of the device-resident commit (tables re-uploaded with spare capacity, scratch, log tables):
@@ -430,99 +473,104 @@ def main():
     elapsed = comm.max_float(time.perf_counter() - t0)
     log(f"[bench] timed region, host phases (ms per step over {args.warmup + args.steps} sweeps): "
         + ", ".join(f"{k} {1e3 * v / (args.warmup + args.steps):.2f}" for k, v in sorted(inf.TIMERS.items(), key=lambda kv: -kv[1])))
-    rs = eng.hip.get_root_stats()
-    lo, hi = shard_bounds(args.rows, rank, world)
-    alg_bytes, alg_bytes_rows_once = roofline_model(rs, obs[:, lo:hi], cfg.num_particles)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, changed)
 
-    # ---- the same sweep cut into 32 sub-batches (upload / sweep / exchange / commit per sub-batch): what a class WITH
-    # learned parameters costs under the default max_sub_batches (reported beside the headline, not as it) --------------
-    comm.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    n_sub = 2
-    for i in range(n_sub):
-        observed_sweep(eng, tr, cfg, args.seed, 1000 + i, comm, batch_rows=-(-args.rows // 32))
-    torch.cuda.synchronize()
-    comm.barrier()
-    ms_32 = 1e3 * comm.max_float(time.perf_counter() - t0) / n_sub
+    # ---- --full: everything else, each in sweeps of its own after the timed region ----------------------------------
+    if args.full:
+        rs = eng.hip.get_root_stats()
+        lo, hi = shard_bounds(args.rows, rank, world)
+        alg_bytes, alg_bytes_rows_once = roofline_model(rs, obs[:, lo:hi], cfg.num_particles)
 
-    # ---- fixed / proportional split of the step: the same sweep as TWO half windows costs 2 x fixed + proportional ---
-    comm.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    n_half = 8  # (with three the estimate moved by a millisecond from run to run)
-    for i in range(n_half):
-        observed_sweep(eng, tr, cfg, args.seed, 2000 + i, comm, batch_rows=-(-args.rows // 2))
-    torch.cuda.synchronize()
-    comm.barrier()
-    ms_2 = 1e3 * comm.max_float(time.perf_counter() - t0) / n_half
-
-    # ... against the same number of whole-window sweeps timed the same way, right beside them
-    comm.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    # (these sweeps also time the LAST reference slot's root launch group — the Measure slot, the longest kernel of the step —
-    # with the same HIP events the timed region spent on block 0's: pclean_set_timed_block)
-    last_slot = max(bi for bi, blk in enumerate(lw.blocks) if not blk.get("score"))
-    eng.hip.set_timed_block(last_slot)
-    m_ms, m_launches = 0.0, 0
-    for i in range(n_half):
-        observed_sweep(eng, tr, cfg, args.seed, 3000 + i, comm)
-        tm = eng.hip.get_timing()
-        m_ms += tm.hot_kernel_ms
-        m_launches += tm.hot_kernel_launches
-    torch.cuda.synchronize()
-    comm.barrier()
-    ms_1 = 1e3 * comm.max_float(time.perf_counter() - t0) / n_half
-    rs_m = eng.hip.get_root_stats()
-    eng.hip.set_timed_block(0)
-    alg_bytes_m, _ = roofline_model(rs_m, obs[:, lo:hi], cfg.num_particles) if last_slot != 0 else (None, None)
-    sector64_m, which_m = getattr(roofline_model, "sector64", None), getattr(roofline_model, "which", None)
-    alg_bytes, alg_bytes_rows_once = roofline_model(rs, obs[:, lo:hi], cfg.num_particles)  # (restores roofline_model.sector64 for block 0)
-
-    # ---- several ranks: what one small collective costs on this node (the per-sweep exchange is two of them) ----------
-    coll_ms = None
-    if getattr(eng, "_dev_comm", False):
-        blocks_ = [bi for bi, blk in enumerate(lw.blocks) if not blk.get("score")]
-        tids_ = [lw.table_id[lw.blocks[bi]["root_class"]] for bi in blocks_]
-        ns_ = [tr.tables[lw.blocks[bi]["root_class"]].n for bi in blocks_]
+        # ---- the same sweep cut into 32 sub-batches (upload / sweep / exchange / commit per sub-batch): what a class WITH
+        # learned parameters costs under the default max_sub_batches (reported beside the headline, not as it) --------------
         comm.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(20):
-            eng.hip.allreduce_stats_fused(tids_, ns_, True)
-        coll_ms = 1e3 * comm.max_float(time.perf_counter() - t0) / 20
-        log(f"[bench] rank {rank}: one fused all-reduce of the delta counts ({sum(ns_)} int64, synchronised): {coll_ms:.3f} ms; "
-            f"step as 1 window {ms_1:.2f} ms, as 2 half windows {ms_2:.2f} ms -> fixed {max(ms_2 - ms_1, 0):.2f} ms, "
-            f"row-proportional {max(2 * ms_1 - ms_2, 0):.2f} ms per step and rank")
+        n_sub = 2
+        for i in range(n_sub):
+            observed_sweep(eng, tr, cfg, args.seed, 1000 + i, comm, batch_rows=-(-args.rows // 32))
+        torch.cuda.synchronize()
+        comm.barrier()
+        ms_32 = 1e3 * comm.max_float(time.perf_counter() - t0) / n_sub
 
-    # ---- several ranks: what every rank's exchange moved, how often its device commit was refused (rank 0 prints them) ------
-    per_rank = None
-    if comm.dist is not None:
-        mine = {"rank": rank, "rows": int(shard_bounds(args.rows, rank, world)[1] - shard_bounds(args.rows, rank, world)[0]),
-                "device_commits": (eng._dc or {}).get("commits"), "device_commit_refusals": (eng._dc or {}).get("fallbacks"),
-                "step_fixed_ms": max(ms_2 - ms_1, 0.0), "step_proportional_ms": max(2 * ms_1 - ms_2, 0.0)}
+        # ---- fixed / proportional split of the step: the same sweep as TWO half windows costs 2 x fixed + proportional ---
+        comm.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_half = 8  # (with three the estimate moved by a millisecond from run to run)
+        for i in range(n_half):
+            observed_sweep(eng, tr, cfg, args.seed, 2000 + i, comm, batch_rows=-(-args.rows // 2))
+        torch.cuda.synchronize()
+        comm.barrier()
+        ms_2 = 1e3 * comm.max_float(time.perf_counter() - t0) / n_half
+
+        # ... against the same number of whole-window sweeps timed the same way, right beside them
+        comm.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        # (these sweeps also time the LAST reference slot's root launch group — the Measure slot, the longest kernel of the step —
+        # with the same HIP events the timed region spent on block 0's: pclean_set_timed_block)
+        last_slot = max(bi for bi, blk in enumerate(lw.blocks) if not blk.get("score"))
+        eng.hip.set_timed_block(last_slot)
+        m_ms, m_launches = 0.0, 0
+        for i in range(n_half):
+            observed_sweep(eng, tr, cfg, args.seed, 3000 + i, comm)
+            tm = eng.hip.get_timing()
+            m_ms += tm.hot_kernel_ms
+            m_launches += tm.hot_kernel_launches
+        torch.cuda.synchronize()
+        comm.barrier()
+        ms_1 = 1e3 * comm.max_float(time.perf_counter() - t0) / n_half
+        rs_m = eng.hip.get_root_stats()
+        eng.hip.set_timed_block(0)
+        alg_bytes_m, _ = roofline_model(rs_m, obs[:, lo:hi], cfg.num_particles) if last_slot != 0 else (None, None)
+        sector64_m, which_m = getattr(roofline_model, "sector64", None), getattr(roofline_model, "which", None)
+        alg_bytes, alg_bytes_rows_once = roofline_model(rs, obs[:, lo:hi], cfg.num_particles)  # (restores roofline_model.sector64 for block 0)
+
+        # ---- several ranks: what one small collective costs on this node (the per-sweep exchange is two of them) ----------
+        coll_ms = None
         if getattr(eng, "_dev_comm", False):
-            cs = eng.hip.comm_stats()
-            mine.update({"allgather_calls": cs["allgather_calls"], "allgather_bytes_sent_last": cs["allgather_bytes_per_rank_last"],
-                         "allgather_bytes_received_last": cs["allgather_bytes_per_rank_last"] * world,
-                         "allgather_device_ms_mean": cs["allgather_device_ms"] / max(cs["allgather_calls"], 1),
-                         "allreduce_calls": cs["allreduce_calls"], "allreduce_bytes_last": cs["allreduce_bytes_last"],
-                         "allreduce_device_ms_mean": cs["allreduce_device_ms"] / max(cs["allreduce_calls"], 1)})
-        per_rank = [None] * world
-        comm.dist.all_gather_object(per_rank, mine)
+            blocks_ = [bi for bi, blk in enumerate(lw.blocks) if not blk.get("score")]
+            tids_ = [lw.table_id[lw.blocks[bi]["root_class"]] for bi in blocks_]
+            ns_ = [tr.tables[lw.blocks[bi]["root_class"]].n for bi in blocks_]
+            comm.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                eng.hip.allreduce_stats_fused(tids_, ns_, True)
+            coll_ms = 1e3 * comm.max_float(time.perf_counter() - t0) / 20
+            log(f"[bench] rank {rank}: one fused all-reduce of the delta counts ({sum(ns_)} int64, synchronised): {coll_ms:.3f} ms; "
+                f"step as 1 window {ms_1:.2f} ms, as 2 half windows {ms_2:.2f} ms -> fixed {max(ms_2 - ms_1, 0):.2f} ms, "
+                f"row-proportional {max(2 * ms_1 - ms_2, 0):.2f} ms per step and rank")
 
-    # ---- per-phase profile of one more (untimed) sweep ----------------------------------------------------------
-    eng.hip.set_profiling(True)
-    step(args.warmup + args.steps)
-    phases = eng.hip.get_profile()
-    eng.hip.set_profiling(False)
+        # ---- several ranks: what every rank's exchange moved, how often its device commit was refused (rank 0 prints them) ------
+        per_rank = None
+        if comm.dist is not None:
+            mine = {"rank": rank, "rows": int(shard_bounds(args.rows, rank, world)[1] - shard_bounds(args.rows, rank, world)[0]),
+                    "device_commits": (eng._dc or {}).get("commits"), "device_commit_refusals": (eng._dc or {}).get("fallbacks"),
+                    "step_fixed_ms": max(ms_2 - ms_1, 0.0), "step_proportional_ms": max(2 * ms_1 - ms_2, 0.0)}
+            if getattr(eng, "_dev_comm", False):
+                cs = eng.hip.comm_stats()
+                mine.update({"allgather_calls": cs["allgather_calls"], "allgather_bytes_sent_last": cs["allgather_bytes_per_rank_last"],
+                             "allgather_bytes_received_last": cs["allgather_bytes_per_rank_last"] * world,
+                             "allgather_device_ms_mean": cs["allgather_device_ms"] / max(cs["allgather_calls"], 1),
+                             "allreduce_calls": cs["allreduce_calls"], "allreduce_bytes_last": cs["allreduce_bytes_last"],
+                             "allreduce_device_ms_mean": cs["allreduce_device_ms"] / max(cs["allreduce_calls"], 1)})
+            per_rank = [None] * world
+            comm.dist.all_gather_object(per_rank, mine)
+
+        # ---- per-phase profile of one more (untimed) sweep ----------------------------------------------------------
+        eng.hip.set_profiling(True)
+        step(args.warmup + args.steps)
+        phases = eng.hip.get_profile()
+        eng.hip.set_profiling(False)
     acc = f1_now(tr)
 
     # ---- full iterations in the steady state (after everything the line reports): the first one after the initialisation
     # (full_iteration_ms) also pays the first build of every latent class's compact tables, caches and scratch buffers ---
     full_steady_ms = None
-    if not args.no_full_iteration and not args.no_steady_iterations:
+    if args.full and not args.no_full_iteration and not args.no_steady_iterations:
         comm.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -538,36 +586,6 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = args.rows * args.steps / elapsed
-        per_launch_s = 1e-3 * hot_ms / max(hot_launches, 1)
-        achieved = (alg_bytes / per_launch_s / 1e9) if (alg_bytes and per_launch_s > 0) else None
-        traffic, traffic_src, traffic_parts = hbm_traffic(args, world)
-        st = step_traffic(args, world)
-        step_model = None
-        # per-kernel byte model of the step's largest movers besides the root scans (an algorithmic denominator for the
-        # whole step, beside the counters)
-        blk1 = lw.blocks[1]
-        n_obs_c, kpad_c = [], []
-        for t_ in blk1["terms"][blk1["nodes"][0][2]:blk1["nodes"][0][2] + blk1["nodes"][0][3]]:
-            if t_[5] < 0:  # plain (compact-table) terms of the Measure slot
-                pid = t_[2]
-                n_obs_c.append(next(len(v[1]) for v in lw.pair_id.values() if v[0] == pid))
-                kpad_c.append(((eng._dc["cap"].get(blk1["root_class"], 0) if eng._dc else tr.tables[blk1["root_class"]].n) + 15) // 16 * 16)
-        created = (eng._dc or {}).get("created", {}).get(blk1["root_class"], 0)
-        per_kernel = step_byte_model(hi - lo, cfg.num_particles, rs, 0, n_obs_c, kpad_c, max(created, 1))
-        per_kernel.pop("root scans of the Measure slot + nested slots (group descriptors + draws)", None)
-        if alg_bytes:
-            per_kernel["block-0 root scan (roofline.alg_bytes_per_launch)"] = alg_bytes
-        if st:  # the whole step against the HBM roof: counter bytes of every kernel of a sweep / this run's device time
-            dev_s = 1e-3 * dev_ms / args.steps
-            step_model = {"hbm_bytes_per_step": st["hbm_bytes_per_step"], "device_ms_per_step": 1e3 * dev_s,
-                          "GBps": st["hbm_bytes_per_step"] / dev_s / 1e9, "frac_of_hbm_peak": st["hbm_bytes_per_step"] / dev_s / 8e12,
-                          "dispatches_per_step": st.get("dispatches"), "source": st.get("source"),
-                          "by_kernel_counters": st.get("by_kernel")}
-        step_model = dict(step_model or {}, alg_bytes_model=per_kernel, alg_bytes_modelled=sum(per_kernel.values()),
-                          note="alg_bytes_model: what each kernel group of the round-5 step has to read and write once "
-                               "(bench.step_byte_model); the Measure slot's root scan, the new-row sampling and the commit are "
-                               "covered by counters only, so hbm_bytes_per_step / alg_bytes_modelled over-states the waste",
-                          traffic_over_alg_modelled=(st["hbm_bytes_per_step"] / sum(per_kernel.values())) if st and per_kernel else None)
         out = {
             "metric": "rows/sec per Gibbs sweep on 1M-row synthetic hospital; F1 vs ground truth",
             "value": value, "unit": "rows/s/sweep", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -582,13 +600,13 @@ def main():
                        "parallelism": f"rows sharded over {world} GPU(s)",
                        "init": f"the build's own initialize_trace from an empty trace (batches <= {args.init_batch})"
                                + ("" if args.no_full_iteration else " + 1 full run_inference iteration"),
-                       "init_s": init_s, "f1_after_init": acc_init["f1"],
+                       "init_s": init_s,
                        "f1_reference": f"none at this setting: the +-0.5 pt band against the sequential references is tested with the "
                                        f"product's default initialisation batches (<= 256 rows) on <= 50 000 rows "
                                        f"(tests/test_gpu_f1_vs_sequential.py); this run initialises in batches <= {args.init_batch}, "
                                        "and a larger initialisation batch moves F1 upwards (DESIGN.md §9) — the f1 below "
                                        "is a sanity figure for the timed state, not a parity claim", "full_iteration_ms": full_ms,
-                       "full_iteration_steady_ms": full_steady_ms, "prepare_ms": prepare_ms,
+                       "prepare_ms": prepare_ms,
                        "device_ms_per_step": dev_ms / args.steps,
                        "commit": (("device-resident on every rank (pclean_commit_device_dist): delta counts all-reduced, moved rows and "
                                    "new-row records all-gathered in HBM (RCCL), the same commit kernel everywhere"
@@ -596,27 +614,7 @@ def main():
                                    "device-resident (pclean_commit_device): tables, counts, free lists and referents stay in HBM")
                                   + ", one synchronisation per step" if dc_on else "host (parallel.exchange_and_commit)"),
                        "device_commit_setup_ms": dc_enable_ms,
-                       "device_commits": (eng._dc or {}).get("commits"), "device_commit_refusals": (eng._dc or {}).get("fallbacks"),
-                       "ms_per_step_32_sub_batches": ms_32,
-                       # what does not shrink with the rows a rank sweeps (launches, count read-backs, the commit kernel, table
-                       # refreshes) vs what does: from the same sweep run as two half windows (2 x fixed + proportional)
-                       "step_fixed_ms": max(ms_2 - ms_1, 0.0), "step_proportional_ms": max(2 * ms_1 - ms_2, 0.0),
-                       "ms_per_step_2_windows": ms_2, "ms_per_step_1_window_same_loop": ms_1, "fixed_split_sweeps": n_half,
-                       "collective_ms_fused_allreduce": coll_ms,
-                       # several ranks (also PCLEAN_FORCE_DIST=1 on one): per rank its shard, refused device commits, the fixed
-                       # capacity all-gather of moved rows + new-row records (bytes of the last one, mean device time from HIP events
-                       # on the library's stream) and the fused all-reduce of the delta counts
-                       "per_rank": per_rank,
-                       # the decomposition a strong-scaling number comes with: on N ranks a step costs fixed + collectives +
-                       # proportional / N; `--scaling weak` in a separate invocation measures rows-per-rank fixed instead
-                       "scaling_model": {"fixed_ms": max(ms_2 - ms_1, 0.0), "proportional_ms": max(2 * ms_1 - ms_2, 0.0),
-                                         "collectives_device_ms": (sum((r or {}).get(k, 0.0) or 0.0 for r in per_rank[:1]
-                                                                       for k in ("allgather_device_ms_mean", "allreduce_device_ms_mean"))
-                                                                   if per_rank else None),
-                                         "projected_speedup_at": {str(n): ms_1 / (max(ms_2 - ms_1, 0.0) + max(2 * ms_1 - ms_2, 0.0) / n)
-                                                                  for n in (2, 4, 8)} if ms_1 > 0 and world == 1 else None,
-                                         "note": "one-GPU split of the same sweep run as two half windows; the projection leaves the "
-                                                 "collectives out (two small ones per step) and is printed for world == 1 only"}},
+                       "device_commits": (eng._dc or {}).get("commits"), "device_commit_refusals": (eng._dc or {}).get("fallbacks")},
             "f1": acc["f1"], "accuracy": acc,
             "table_build": {"seconds": eng.pair_build_s, "pairs": eng.pair_count, "dp_cells": eng.pair_cells,
                             "dp_cells_per_s": eng.pair_cells / max(eng.pair_build_s, 1e-9),
@@ -627,80 +625,132 @@ def main():
                                  "per pair, latent strings sorted by length): the product's default distance; --distance osa builds "
                                  "the restricted (bit-parallel) tables of rounds 1-4 in 0.45 s instead",
                             "unrestricted_dl_sample": dl_sample},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": (achieved / 8000.0) if achieved else None, "traffic": traffic,
-                         "traffic_source": traffic_src, "traffic_components": traffic_parts,
-                         "traffic_over_alg": (traffic / alg_bytes) if (traffic and alg_bytes) else None,
-                         "measure_root": getattr(hbm_traffic, "measure_root", None),
-                         "kernel": "group_gate_kernel + group_desc_kernel + group_settle_kernel + worklist_pack_kernel + fk_root_wave_kernel<12> + "
-                                   "group_lse_kernel (block 0 root: rows x candidate hospitals); alg bytes, launch time and counter "
-                                   "traffic all cover these launches",
-                         "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": 1e3 * per_launch_s,
-                         "gather_model": {"bytes_per_gather": LINE,
-                                          "alg_bytes_per_launch_64B_sector": getattr(roofline_model, "sector64", None),
-                                          "frac_64B_sector": (getattr(roofline_model, "sector64", 0.0) / per_launch_s / 8e12)
-                                          if (per_launch_s > 0 and getattr(roofline_model, "sector64", None)) else None,
-                                          "note": "rounds 1-3 charged a random gather the 64-byte sector, rounds 4-5 the 128-byte "
-                                                  "line the counters see (FETCH_SIZE x 2 on gfx950): `frac` uses the line; the "
-                                                  "sector figure is kept so that the rounds compare"},
-                         "groups": rs.n_groups, "items": rs.n_items, "kpad": rs.kpad, "overflow_items": rs.overflow_items,
-                         "full_scans": rs.full_scans, "fine_blocks": rs.fine_blocks, "scored_terms": rs.scored_terms,
-                         "settled_groups": rs.resolved_groups,
-                         "rows_streamed_once_model": {"bytes_per_launch": alg_bytes_rows_once,
-                                                      "GBps": (alg_bytes_rows_once / per_launch_s / 1e9) if (alg_bytes_rows_once and per_launch_s > 0) else None,
-                                                      "note": "round 2's byte model (every distinct pre-filter byte row "
-                                                              "streamed once): what the scan read before its block-minimum "
-                                                              "level; kept for comparison across rounds"},
-                         "step": step_model,
-                         "enumeration_equivalent": {"bytes_per_launch": enum_bytes / max(hot_launches, 1),
-                                                    "GBps": enum_bytes / max(hot_launches, 1) / max(per_launch_s, 1e-12) / 1e9,
-                                                    "note": "SURVEY §8d full-enumeration bytes (920 296 B/row) / kernel time: "
-                                                            "work the kernel provably skips, not a bandwidth claim"},
-                         "note": "achieved = bytes the implemented algorithm has to move once (bench.roofline_model: block-minimum "
-                                 "rows + the fine blocks and gathers the kernel counted, every random gather at the 128-byte line "
-                                 "+ descriptors + ids + outputs) / HIP-event time of the launch group on "
-                                 "the library's stream; traffic = HBM bytes per launch from this round's rocprofv3 PMC passes "
-                                 "(profiles/), not measured in this run"},
-            "phases_ms": {k: {"ms": round(v[0], 4), "intervals": v[1]} for k, v in sorted(phases.items(), key=lambda kv: -kv[1][0])},
         }
-        # ---- the Measure slot's root launch group, timed and modelled the same way; `roofline` describes whichever of the two
-        # launch groups is LONGER per launch, the other one rides along
-        if alg_bytes_m and m_launches:
-            per_m = 1e-3 * m_ms / m_launches
-            mr = getattr(hbm_traffic, "measure_root", None) or {}
-            meas = {"bound": "hbm", "achieved": alg_bytes_m / per_m / 1e9, "peak": 8000.0, "unit": "GB/s",
-                    "frac": alg_bytes_m / per_m / 8e12, "traffic": mr.get("group_bytes_per_launch"),
-                    "traffic_source": mr.get("source"), "traffic_components": mr.get("group_components"),
-                    "traffic_over_alg": (mr["group_bytes_per_launch"] / alg_bytes_m) if mr.get("group_bytes_per_launch") else None,
-                    "kernel": "group_gate_kernel (when it runs) + group_desc_kernel + group_settle_kernel + fk_root_wave_kernel<4> + "
-                              f"group_lse_kernel (root of block {last_slot}, the Measure slot: (row, context) items x candidate measures); "
-                              "alg bytes, launch time and counter traffic all cover these launches",
-                    "alg_bytes_per_launch": alg_bytes_m, "alg_bytes_model": which_m, "avg_launch_ms": 1e3 * per_m, "launches_timed": m_launches,
-                    "timed_over": f"the {n_half} whole-window sweeps run right after the timed region (config.ms_per_step_1_window_same_loop), "
-                                  "HIP events on the library's stream (pclean_set_timed_block)",
-                    "gather_model": {"bytes_per_gather": LINE, "alg_bytes_per_launch_64B_sector": sector64_m,
-                                     "frac_64B_sector": (sector64_m / per_m / 8e12) if sector64_m else None},
-                    "groups": rs_m.n_groups, "items": rs_m.n_items, "kpad": rs_m.kpad, "overflow_items": rs_m.overflow_items,
-                    "full_scans": rs_m.full_scans, "fine_blocks": rs_m.fine_blocks, "scored_terms": rs_m.scored_terms,
-                    "settled_groups": rs_m.resolved_groups, "lazy_entries": rs_m.lazy_entries,
-                    "counters": {k: v for k, v in mr.items() if k not in ("group_components", "group_avg_ms")} or None,
-                    "note": "bench.roofline_model, each byte once: descriptors, ids, log marginals, the survivor lists left for the lazy "
-                            "draw (12 B per entry) + the smaller of (block-minimum rows + the fine blocks and gathers the kernel "
-                            "counted at the 128-byte line) and (every distinct pre-filter byte row once); latency- and "
-                            "instruction-bound (DESIGN.md §5), not a bandwidth-bound kernel: frac says how far"}
-            b0 = out["roofline"]
-            if per_m > per_launch_s:  # the longer launch group is the line's `roofline`
-                step_ = b0.pop("step", None)
-                out["roofline"] = dict(meas, step=step_, block0_root_group=b0,
-                                       chosen="the longest launch group of the step (this one: "
-                                              f"{1e3 * per_m:.3f} ms against {1e3 * per_launch_s:.3f} ms of block 0's root group)")
-            else:
-                b0["measure_root_group"] = meas
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(lw, obs, tr, eng, cfg, args.seed, args.cpu_rows, args.cpu_seconds)
-            out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-            if out["cpu_baseline"].get("pruned", {}).get("value"):  # what the GPU buys over ONE core running the same savers
-                out["cpu_baseline"]["pruned"]["gpu_over_cpu"] = value / out["cpu_baseline"]["pruned"]["value"]
+        if args.full:
+            per_launch_s = 1e-3 * hot_ms / max(hot_launches, 1)
+            achieved = (alg_bytes / per_launch_s / 1e9) if (alg_bytes and per_launch_s > 0) else None
+            traffic, traffic_src, traffic_parts = hbm_traffic(args, world)
+            st = step_traffic(args, world)
+            step_model = None
+            # per-kernel byte model of the step's largest movers besides the root scans (an algorithmic denominator for the
+            # whole step, beside the counters)
+            blk1 = lw.blocks[1]
+            n_obs_c, kpad_c = [], []
+            for t_ in blk1["terms"][blk1["nodes"][0][2]:blk1["nodes"][0][2] + blk1["nodes"][0][3]]:
+                if t_[5] < 0:  # plain (compact-table) terms of the Measure slot
+                    pid = t_[2]
+                    n_obs_c.append(next(len(v[1]) for v in lw.pair_id.values() if v[0] == pid))
+                    kpad_c.append(((eng._dc["cap"].get(blk1["root_class"], 0) if eng._dc else tr.tables[blk1["root_class"]].n) + 15) // 16 * 16)
+            created = (eng._dc or {}).get("created", {}).get(blk1["root_class"], 0)
+            per_kernel = step_byte_model(hi - lo, cfg.num_particles, rs, 0, n_obs_c, kpad_c, max(created, 1))
+            per_kernel.pop("root scans of the Measure slot + nested slots (group descriptors + draws)", None)
+            if alg_bytes:
+                per_kernel["block-0 root scan (roofline.alg_bytes_per_launch)"] = alg_bytes
+            if st:  # the whole step against the HBM roof: counter bytes of every kernel of a sweep / this run's device time
+                dev_s = 1e-3 * dev_ms / args.steps
+                step_model = {"hbm_bytes_per_step": st["hbm_bytes_per_step"], "device_ms_per_step": 1e3 * dev_s,
+                              "GBps": st["hbm_bytes_per_step"] / dev_s / 1e9, "frac_of_hbm_peak": st["hbm_bytes_per_step"] / dev_s / 8e12,
+                              "dispatches_per_step": st.get("dispatches"), "source": st.get("source"),
+                              "by_kernel_counters": st.get("by_kernel")}
+            step_model = dict(step_model or {}, alg_bytes_model=per_kernel, alg_bytes_modelled=sum(per_kernel.values()),
+                              note="alg_bytes_model: what each kernel group of the round-5 step has to read and write once "
+                                   "(bench.step_byte_model); the Measure slot's root scan, the new-row sampling and the commit are "
+                                   "covered by counters only, so hbm_bytes_per_step / alg_bytes_modelled over-states the waste",
+                              traffic_over_alg_modelled=(st["hbm_bytes_per_step"] / sum(per_kernel.values())) if st and per_kernel else None)
+            out["config"].update({"f1_after_init": acc_init["f1"], "full_iteration_steady_ms": full_steady_ms,
+                                  "ms_per_step_32_sub_batches": ms_32,
+                                  # what does not shrink with the rows a rank sweeps (launches, count read-backs, the commit kernel, table
+                                  # refreshes) vs what does: from the same sweep run as two half windows (2 x fixed + proportional)
+                                  "step_fixed_ms": max(ms_2 - ms_1, 0.0), "step_proportional_ms": max(2 * ms_1 - ms_2, 0.0),
+                                  "ms_per_step_2_windows": ms_2, "ms_per_step_1_window_same_loop": ms_1, "fixed_split_sweeps": n_half,
+                                  "collective_ms_fused_allreduce": coll_ms,
+                                  # several ranks (also PCLEAN_FORCE_DIST=1 on one): per rank its shard, refused device commits, the fixed
+                                  # capacity all-gather of moved rows + new-row records (bytes of the last one, mean device time from HIP events
+                                  # on the library's stream) and the fused all-reduce of the delta counts
+                                  "per_rank": per_rank,
+                                  # the decomposition a strong-scaling number comes with: on N ranks a step costs fixed + collectives +
+                                  # proportional / N; `--scaling weak` in a separate invocation measures rows-per-rank fixed instead
+                                  "scaling_model": {"fixed_ms": max(ms_2 - ms_1, 0.0), "proportional_ms": max(2 * ms_1 - ms_2, 0.0),
+                                                    "collectives_device_ms": (sum((r or {}).get(k, 0.0) or 0.0 for r in per_rank[:1]
+                                                                                  for k in ("allgather_device_ms_mean", "allreduce_device_ms_mean"))
+                                                                              if per_rank else None),
+                                                    "projected_speedup_at": {str(n): ms_1 / (max(ms_2 - ms_1, 0.0) + max(2 * ms_1 - ms_2, 0.0) / n)
+                                                                             for n in (2, 4, 8)} if ms_1 > 0 and world == 1 else None,
+                                                    "note": "one-GPU split of the same sweep run as two half windows; the projection leaves the "
+                                                            "collectives out (two small ones per step) and is printed for world == 1 only"}})
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                               "frac": (achieved / 8000.0) if achieved else None, "traffic": traffic,
+                               "traffic_source": traffic_src, "traffic_components": traffic_parts,
+                               "traffic_over_alg": (traffic / alg_bytes) if (traffic and alg_bytes) else None,
+                               "measure_root": getattr(hbm_traffic, "measure_root", None),
+                               "kernel": "group_gate_kernel + group_desc_kernel + group_settle_kernel + worklist_pack_kernel + fk_root_wave_kernel<12> + "
+                                         "group_lse_kernel (block 0 root: rows x candidate hospitals); alg bytes, launch time and counter "
+                                         "traffic all cover these launches",
+                               "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": 1e3 * per_launch_s,
+                               "gather_model": {"bytes_per_gather": LINE,
+                                                "alg_bytes_per_launch_64B_sector": getattr(roofline_model, "sector64", None),
+                                                "frac_64B_sector": (getattr(roofline_model, "sector64", 0.0) / per_launch_s / 8e12)
+                                                if (per_launch_s > 0 and getattr(roofline_model, "sector64", None)) else None,
+                                                "note": "rounds 1-3 charged a random gather the 64-byte sector, rounds 4-5 the 128-byte "
+                                                        "line the counters see (FETCH_SIZE x 2 on gfx950): `frac` uses the line; the "
+                                                        "sector figure is kept so that the rounds compare"},
+                               "groups": rs.n_groups, "items": rs.n_items, "kpad": rs.kpad, "overflow_items": rs.overflow_items,
+                               "full_scans": rs.full_scans, "fine_blocks": rs.fine_blocks, "scored_terms": rs.scored_terms,
+                               "settled_groups": rs.resolved_groups,
+                               "rows_streamed_once_model": {"bytes_per_launch": alg_bytes_rows_once,
+                                                            "GBps": (alg_bytes_rows_once / per_launch_s / 1e9) if (alg_bytes_rows_once and per_launch_s > 0) else None,
+                                                            "note": "round 2's byte model (every distinct pre-filter byte row "
+                                                                    "streamed once): what the scan read before its block-minimum "
+                                                                    "level; kept for comparison across rounds"},
+                               "step": step_model,
+                               "enumeration_equivalent": {"bytes_per_launch": enum_bytes / max(hot_launches, 1),
+                                                          "GBps": enum_bytes / max(hot_launches, 1) / max(per_launch_s, 1e-12) / 1e9,
+                                                          "note": "SURVEY §8d full-enumeration bytes (920 296 B/row) / kernel time: "
+                                                                  "work the kernel provably skips, not a bandwidth claim"},
+                               "note": "achieved = bytes the implemented algorithm has to move once (bench.roofline_model: block-minimum "
+                                       "rows + the fine blocks and gathers the kernel counted, every random gather at the 128-byte line "
+                                       "+ descriptors + ids + outputs) / HIP-event time of the launch group on "
+                                       "the library's stream; traffic = HBM bytes per launch from this round's rocprofv3 PMC passes "
+                                       "(profiles/), not measured in this run"}
+            out["phases_ms"] = {k: {"ms": round(v[0], 4), "intervals": v[1]} for k, v in sorted(phases.items(), key=lambda kv: -kv[1][0])}
+            # ---- the Measure slot's root launch group, timed and modelled the same way; `roofline` describes whichever of the two
+            # launch groups is LONGER per launch, the other one rides along
+            if alg_bytes_m and m_launches:
+                per_m = 1e-3 * m_ms / m_launches
+                mr = getattr(hbm_traffic, "measure_root", None) or {}
+                meas = {"bound": "hbm", "achieved": alg_bytes_m / per_m / 1e9, "peak": 8000.0, "unit": "GB/s",
+                        "frac": alg_bytes_m / per_m / 8e12, "traffic": mr.get("group_bytes_per_launch"),
+                        "traffic_source": mr.get("source"), "traffic_components": mr.get("group_components"),
+                        "traffic_over_alg": (mr["group_bytes_per_launch"] / alg_bytes_m) if mr.get("group_bytes_per_launch") else None,
+                        "kernel": "group_gate_kernel (when it runs) + group_desc_kernel + group_settle_kernel + fk_root_wave_kernel<4> + "
+                                  f"group_lse_kernel (root of block {last_slot}, the Measure slot: (row, context) items x candidate measures); "
+                                  "alg bytes, launch time and counter traffic all cover these launches",
+                        "alg_bytes_per_launch": alg_bytes_m, "alg_bytes_model": which_m, "avg_launch_ms": 1e3 * per_m, "launches_timed": m_launches,
+                        "timed_over": f"the {n_half} whole-window sweeps run right after the timed region (config.ms_per_step_1_window_same_loop), "
+                                      "HIP events on the library's stream (pclean_set_timed_block)",
+                        "gather_model": {"bytes_per_gather": LINE, "alg_bytes_per_launch_64B_sector": sector64_m,
+                                         "frac_64B_sector": (sector64_m / per_m / 8e12) if sector64_m else None},
+                        "groups": rs_m.n_groups, "items": rs_m.n_items, "kpad": rs_m.kpad, "overflow_items": rs_m.overflow_items,
+                        "full_scans": rs_m.full_scans, "fine_blocks": rs_m.fine_blocks, "scored_terms": rs_m.scored_terms,
+                        "settled_groups": rs_m.resolved_groups, "lazy_entries": rs_m.lazy_entries,
+                        "counters": {k: v for k, v in mr.items() if k not in ("group_components", "group_avg_ms")} or None,
+                        "note": "bench.roofline_model, each byte once: descriptors, ids, log marginals, the survivor lists left for the lazy "
+                                "draw (12 B per entry) + the smaller of (block-minimum rows + the fine blocks and gathers the kernel "
+                                "counted at the 128-byte line) and (every distinct pre-filter byte row once); latency- and "
+                                "instruction-bound (DESIGN.md §5), not a bandwidth-bound kernel: frac says how far"}
+                b0 = out["roofline"]
+                if per_m > per_launch_s:  # the longer launch group is the line's `roofline`
+                    step_ = b0.pop("step", None)
+                    out["roofline"] = dict(meas, step=step_, block0_root_group=b0,
+                                           chosen="the longest launch group of the step (this one: "
+                                                  f"{1e3 * per_m:.3f} ms against {1e3 * per_launch_s:.3f} ms of block 0's root group)")
+                else:
+                    b0["measure_root_group"] = meas
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(lw, obs, tr, eng, cfg, args.seed, args.cpu_rows, args.cpu_seconds)
+                out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
+                if out["cpu_baseline"].get("pruned", {}).get("value"):  # what the GPU buys over ONE core running the same savers
+                    out["cpu_baseline"]["pruned"]["gpu_over_cpu"] = value / out["cpu_baseline"]["pruned"]["value"]
         json_line = json.dumps(out)
     eng.close()
     import torch.distributed as dist

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 1200 rocprofv3 --kernel-trace --pmc $CTRS -d "$OUT/pmc_SQ" -- python "$ROOT/bench.py" --steps 3 --warmup 2 --no-cpu-baseline \
+timeout 1200 rocprofv3 --kernel-trace --pmc $CTRS -d "$OUT/pmc_SQ" -- python "$ROOT/bench.py" --steps 3 --warmup 2 --full --no-cpu-baseline \
   > "$OUT/bench_SQ.json" 2> "$OUT/bench_SQ.log"
 echo "SQ rc=$?"
 cd "$ROOT"

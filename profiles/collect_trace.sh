@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 2 --no-cpu-baseline $*"
+ARGS="--steps 3 --warmup 2 --full --no-cpu-baseline $*"
 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -- python "$ROOT/bench.py" $ARGS \
   > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.log"
 echo "trace rc=$?"

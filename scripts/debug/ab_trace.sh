@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in pad nopad; do
   if [ $v = nopad ]; then export PCLEAN_DC_NOPAD=1; fi
   OUT=$ROOT/gpurun_out/ab_$v; mkdir -p $OUT
-  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-dl-sample > $OUT/b.json 2> $OUT/b.log
+  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -- python $ROOT/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-dl-sample > $OUT/b.json 2> $OUT/b.log
   T=$(find $OUT/trace -name "*.db" | head -1)
   python $ROOT/profiles/summarize_rocpd.py "$T" $OUT/kernel_trace.txt > /dev/null
   find $OUT -name "*.db" -delete

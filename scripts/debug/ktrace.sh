@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/kt_${1:-a}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace -d "$OUT/trace" -- python "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-dl-sample --no-full-iteration \
+timeout 600 rocprofv3 --kernel-trace -d "$OUT/trace" -- python "$ROOT/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline --no-dl-sample --no-full-iteration \
   > "$OUT/b.json" 2> "$OUT/b.log"
 cd "$ROOT"
 T=$(find "$OUT/trace" -name "*.db" | head -1)

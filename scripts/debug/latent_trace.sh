@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/lat_${1:-a}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace -d "$OUT/trace" -- python "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-dl-sample \
+timeout 600 rocprofv3 --kernel-trace -d "$OUT/trace" -- python "$ROOT/bench.py" --steps 1 --warmup 0 --full --no-cpu-baseline --no-dl-sample \
   > "$OUT/b.json" 2> "$OUT/b.log"
 echo "rc=$?"
 cd "$ROOT"
