@@ -26,8 +26,9 @@ def reconstructed_pool_ids(lowered, trace, row_slice=None):
                 and lw.gauss_spec["gauss_attr"] == q.obsmap[col]:
             # corrected = round(unit.backward(x)) (experiments/rents/run.jl:25): numeric, compared as a number
             spec = lw.gauss_spec
-            bi = next(iter(lw.locals))
-            u = np.maximum(trace.locals[bi][:, spec["t_local"]], 0)
+            bi = lw.gauss_block
+            u = (np.zeros(trace.cur.shape[1], dtype=np.int32) if spec["t_local"] is None  # AddNoise: round(x)
+                 else np.maximum(trace.locals[bi][:, spec["t_local"]], 0))
             out[col] = ("numeric", np.round(lw.gauss_backward(np.arange(trace.cur.shape[1]), u)))
             continue
         if "." in ref:

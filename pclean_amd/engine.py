@@ -26,7 +26,8 @@ def make_gauss(spec, mean_table_id=0):
     for l in range(2):
         g.local_n[l] = spec["local_n"][l] if l < len(spec["local_n"]) else 1
         g.local_obs_col[l] = spec["local_obs"][l] if l < len(spec["local_obs"]) else -1
-    g.transform_src_kind, g.transform_src = _lib.GSRC[spec["transform"][0]], int(spec["transform"][1])
+    kind, src = spec["transform"]  # ("none", -1): AddNoise, no Transformation to choose (option 0, the identity)
+    g.transform_src_kind, g.transform_src = (-1, -1) if kind == "none" else (_lib.GSRC[kind], int(src))
     for u in range(4):
         g.t_scale[u] = spec["t_scale"][u] if u < len(spec["t_scale"]) else 1.0
         g.t_logabsderiv[u] = spec["t_lad"][u] if u < len(spec["t_lad"]) else 0.0

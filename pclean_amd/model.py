@@ -113,6 +113,14 @@ class TransformedGaussian:
         self.mean, self.std, self.unit = mean, float(std), unit
 
 
+class AddNoise:
+    """add_noise.jl:1-7: AddNoise(mean, std), logpdf(Normal(mean, std), x); `mean` names an IndexedLookup julia
+    attribute, as TransformedGaussian's does.  No Transformation and no unit choice."""
+
+    def __init__(self, mean, std):
+        self.mean, self.std = mean, float(std)
+
+
 class IndexedMeanParameter:
     """`@learned x::Dict{String, MeanParameter{mean, std}}` (add_noise.jl:15-45, distributions.jl:45-55)."""
 
@@ -327,7 +335,7 @@ class LoweredModel:
                 self.latent_dom[(cname, a.name)] = dom
         ocls = m.classes[self.query.cls]
         self.direct_obs = {}   # obs name -> (path or own attr name) observed without noise (clean == dirty)
-        self.numeric_obs = {}  # own TransformedGaussian attr -> numeric column index
+        self.numeric_obs = {}  # own TransformedGaussian / AddNoise attr -> numeric column index
         self.num_cols = []
         self.num_derived = []  # (source numeric column, Transformation, "backward" | "logabsderiv"): see _lower_gaussian
         for col, dirty in self.query.obsmap.items():
@@ -337,7 +345,7 @@ class LoweredModel:
             if own is not None and own.kind == "choice" and isinstance(own.dist, (AddTypos, MaybeSwap)):
                 vals = [v for v in dirty_columns[col] if v is not None]
                 self.obs_dom[dirty] = Domain(self.pool, list(dict.fromkeys(vals)))
-            elif own is not None and own.kind == "choice" and isinstance(own.dist, TransformedGaussian):
+            elif own is not None and own.kind == "choice" and isinstance(own.dist, (TransformedGaussian, AddNoise)):
                 self.numeric_obs[dirty] = len(self.num_cols)
                 self.num_cols.append(col)
                 continue
@@ -363,7 +371,8 @@ class LoweredModel:
 
     def gauss_backward(self, rows, unit_idx):
         """unit.backward(x) of the Gaussian observation of `rows` under the Transformation options unit_idx (one per row):
-        x * c for the linear ones, the derived column for the others (transformed_gaussian.jl:16, 27-34)."""
+        x * c for the linear ones, the derived column for the others (transformed_gaussian.jl:16, 27-34); AddNoise: x * 1.0
+        (its one option, 0)."""
         spec = self.gauss_spec
         rows = np.asarray(rows)
         unit_idx = np.asarray(unit_idx)
@@ -775,19 +784,26 @@ class LoweredModel:
 
     def _lower_gaussian(self, bi, blk, ocls, names, root_fk):
         """`x ~ TransformedGaussian(param[f(root values, own choices)], std, unit)` with own
-        ChooseUniformly choices (experiments/rents/run.jl:19-25) -> pclean_gauss specs."""
+        ChooseUniformly choices (experiments/rents/run.jl:19-25), or `x ~ AddNoise(param[..], std)`
+        (add_noise.jl:7: no Transformation, no unit choice) -> pclean_gauss specs."""
         m = self.model
-        ga = [ocls.attr(n) for n in names if ocls.attr(n).kind == "choice" and isinstance(ocls.attr(n).dist, TransformedGaussian)]
+        ga = [ocls.attr(n) for n in names
+              if ocls.attr(n).kind == "choice" and isinstance(ocls.attr(n).dist, (TransformedGaussian, AddNoise))]
         if not ga:
             return
         if len(ga) > 1:
             raise NotImplementedError("one Gaussian observation per block (so far)")
         g = ga[0]
+        add_noise = isinstance(g.dist, AddNoise)
         look = ocls.attr(g.dist.mean)
         if look.kind != "julia" or not isinstance(look.fn, IndexedLookup):
-            raise NotImplementedError("TransformedGaussian mean must be an IndexedLookup")
-        unit_attr = ocls.attr(g.dist.unit)
-        units = unit_attr.dist.options
+            raise NotImplementedError(f"{type(g.dist).__name__} mean must be an IndexedLookup")
+        if add_noise:
+            # one fixed identity option: backward(x) = x * 1.0, log|deriv| = 0.0; no choice picks it (transform
+            # source "none": the kernels and the oracle take option 0), so the score is logpdf(Normal(mean, std), x)
+            units = [Transformation(lambda x: x, lambda x: x, lambda x: 1.0)]
+        else:
+            units = ocls.attr(g.dist.unit).dist.options
         if len(units) > 4:
             raise NotImplementedError("at most four Transformations to choose from (pclean_gauss::t_scale[4])")
         # A LINEAR unit (backward(x) = c x, |deriv| constant: the rents program's) is evaluated by the kernels as x * c and a
@@ -820,7 +836,7 @@ class LoweredModel:
                 if arg not in locs:
                     locs.append(arg)
                 dims.append(("local", locs.index(arg), len(oa.dist.options), None))
-        if g.dist.unit not in locs:
+        if not add_noise and g.dist.unit not in locs:
             locs.append(g.dist.unit)
         if len(locs) > 2:
             raise NotImplementedError("at most two enumerated own choices")
@@ -831,11 +847,13 @@ class LoweredModel:
             strides.append(acc)
             acc *= d[2]
         strides = strides[::-1]
-        self.locals[bi] = locs
+        if locs:  # (an AddNoise whose mean is indexed by candidate-side values alone enumerates nothing: one combination)
+            self.locals[bi] = locs
+        self.gauss_block = bi
         spec = dict(x_col=self.numeric_obs[g.name], param=(self.query.cls, look.fn.param), n_mean=acc, dims=dims,
                     strides=strides, locals=locs, local_n=[len(ocls.attr(l).dist.options) for l in locs],
                     local_obs=[self.obs_index.get(l, -1) if l in self.direct_obs else -1 for l in locs],
-                    t_local=locs.index(g.dist.unit), sigma=g.dist.std, gauss_attr=g.name,
+                    t_local=None if add_noise else locs.index(g.dist.unit), sigma=g.dist.std, gauss_attr=g.name,
                     t_scale=[float(u.backward(1.0)) if lin else 1.0 for u, lin in zip(units, t_linear)],
                     t_lad=[float(np.log(abs(u.deriv(u.backward(1.0))))) if lin else 0.0 for u, lin in zip(units, t_linear)],
                     units=units, t_linear=t_linear, t_x_col=[-1] * len(units), t_lad_col=[-1] * len(units))
@@ -848,10 +866,11 @@ class LoweredModel:
                 spec["t_lad_col"][ui] = len(self.num_cols) + len(self.num_derived)
                 self.num_derived.append((spec["x_col"], units[ui], "logabsderiv"))
         self.gauss_spec = spec
+        transform = ("none", -1) if add_noise else ("local", spec["t_local"])
         # (a) block root: candidate-side index values come from the candidate's columns
         rc = root_fk.target
         self.gauss[(bi, 0)] = dict(spec, kinds=[("cand", self.colidx[rc][d[1]]) if d[0] == "cand" else ("local", d[1])
-                                                 for d in dims], n_locals=len(locs), transform=("local", spec["t_local"]))
+                                                 for d in dims], n_locals=len(locs), transform=transform)
         # (b) new-row branch: the leaf of the one candidate-side value that is not always observed
         #     carries the term; the others are read from their direct observations
         open_dims = [d for d in dims if d[0] == "cand" and not self._always_observed(root_fk.name + "." + d[1])]
@@ -867,7 +886,7 @@ class LoweredModel:
                         kinds.append(("cand", 0))
                     else:
                         kinds.append(("obs", self.obs_index[root_fk.name + "." + d[1]]))
-                self.gauss[(bi, nid)] = dict(spec, kinds=kinds, n_locals=len(locs), transform=("local", spec["t_local"]))
+                self.gauss[(bi, nid)] = dict(spec, kinds=kinds, n_locals=len(locs), transform=transform)
                 node = list(blk["nodes"][nid])
                 node[8] = 0  # not cacheable any more
                 blk["nodes"][nid] = tuple(node)
@@ -952,8 +971,10 @@ class LoweredModel:
             src = self.gauss[(bi, nid)]
             kinds = [("evctx", k[1]) if k[0] == "local" else k for k in src["kinds"]]
             self.gauss[(plan["block_id"], new_id)] = dict(src, kinds=kinds, n_locals=0,
-                                                          transform=("evctx", src["t_local"]))
-            self.latent_ev_locals[plan["cls"]] = bi
+                                                          transform=("none", -1) if src["t_local"] is None
+                                                          else ("evctx", src["t_local"]))
+            if src["locals"]:
+                self.latent_ev_locals[plan["cls"]] = bi
         kids = []
         if node[0] == _lib.NODE_FK:
             remap = {}

@@ -277,8 +277,8 @@ class Trace:
         """(rows, mean-table index, backward-transformed x) of every assigned observed row."""
         lw = self.lw
         spec = lw.gauss_spec
-        bi = next(iter(lw.locals))
-        rows = np.nonzero((self.cur[bi] >= 0) & (self.locals[bi][:, 0] >= 0))[0]
+        bi = lw.gauss_block
+        rows = np.nonzero((self.cur[bi] >= 0) & (self.locals[bi][:, 0] >= 0 if spec["locals"] else True))[0]
         root = lw.blocks[bi]["root_class"]
         t = self.tables[root]
         idx = np.zeros(len(rows), dtype=np.int64)
@@ -287,7 +287,9 @@ class Trace:
                 idx += st * t.cols[lw.colidx[root][d[1]], self.cur[bi][rows]]
             else:
                 idx += st * self.locals[bi][rows, d[1]]
-        x = lw.gauss_backward(rows, self.locals[bi][rows, spec["t_local"]])
+        unit = (np.zeros(len(rows), dtype=np.int32) if spec["t_local"] is None  # (AddNoise: the identity, option 0)
+                else self.locals[bi][rows, spec["t_local"]])
+        x = lw.gauss_backward(rows, unit)
         ok = ~np.isnan(x)
         return rows[ok], idx[ok], x[ok]
 
