@@ -1,0 +1,641 @@
+"""Exact output distributions of the batched sweep, from the LITERAL interpreter (TEST INFRASTRUCTURE, CPU only).
+
+In a batched sweep the latent tables are frozen, so one row's update is a Markov kernel whose output distribution has
+a closed form in the row's exact conditional posterior pi.  pi comes from oracle/literal.py (model description +
+strings, nothing of the product's lowering, fixed-point arithmetic or Philox streams); the probabilities are formed in
+high precision (mpmath when it imports, else math.fsum of shifted exponentials).  The closed forms:
+
+  * no current referent (cur = -1): no retained particle, every particle draws from pi          -> pi
+  * PG, current referent s, ONE enumerated block: all weights equal, the chosen particle is
+    uniform on 0..P-1                                                                            -> (1/P) d_s + (1 - 1/P) pi
+  * MH (P = 2), one block: w0 == w1, accepted with 0.5 / (1e-10 + 0.5)                           -> pi (up to 2e-10)
+  * MH (P = 2), two blocks, block 1 depends on block 0's value: proposal q(t) = pi0(t0) pi1(t1 | t0),
+    accepted with a(t) = min(1, exp(Z1(t0) - Z1(s0)))                                             -> q a + [t == s] (1 - sum q a)
+
+A candidate is a referent key of the block's root table, or ('NEW', value) — a fresh row together with its sampled
+own choice (the nested conditional of the new-row branch: the option's prior mass times its likelihood).  PG with
+P > 2 over two dependent blocks (conditional SMC with resampling) has no short closed form and is not covered; neither
+are rows that can draw a ProposalDummyValue (the weight correction changes the kernel): root classes here hold a
+single ChooseUniformly choice, which has none.
+
+gof() is the one goodness-of-fit routine: a G-test pooled over rows (rows with identical expected distributions are
+summed first), cells with an expected count below 5 merged, p-value from scipy.stats.chi2, and the worst cells named.
+"""
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if os.path.join(ROOT, "oracle") not in sys.path:
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import literal as lit  # noqa: E402
+
+try:
+    import mpmath
+    mpmath.mp.dps = 40
+except ImportError:  # optional: math.fsum below is exact enough for probabilities of 1e5 draws
+    mpmath = None
+
+MH_ACCEPT = 0.5 / (1e-10 + 0.5)  # run_smc!'s min(1, w1 / (1e-10 + w0)) at w0 == w1 = 1/2
+
+
+def normalise(scores):
+    """{candidate: log score} -> {candidate: probability} (zero-probability candidates dropped)."""
+    finite = {k: v for k, v in scores.items() if v > -math.inf}
+    if not finite:
+        raise ValueError("no candidate has positive probability")
+    if mpmath is not None:
+        w = {k: mpmath.exp(mpmath.mpf(v)) for k, v in finite.items()}
+        z = mpmath.fsum(w.values())
+        return {k: float(x / z) for k, x in w.items() if x > 0}
+    m = max(finite.values())
+    w = {k: math.exp(v - m) for k, v in finite.items()}
+    z = math.fsum(w.values())
+    return {k: x / z for k, x in w.items() if x > 0}
+
+
+def log_marginal(scores):
+    """log sum exp of the candidates' scores, in high precision."""
+    vals = [v for v in scores.values() if v > -math.inf]
+    if mpmath is not None:
+        return float(mpmath.log(mpmath.fsum(mpmath.exp(mpmath.mpf(v)) for v in vals)))
+    m = max(vals)
+    return m + math.log(math.fsum(math.exp(v - m) for v in vals))
+
+
+# ---- exact conditionals -------------------------------------------------------------------------------------------
+class RowConditionals:
+    """Exact block conditionals of observed rows of a program whose blocks each hold ONE reference slot to a class
+    with a single own choice (a ChooseUniformly attribute): scores of every existing row and of every (new row, own
+    value) from the literal interpreter, the row's own references removed first (run_smc!, row_inference.jl:115-126).
+
+    S: {lw, trace, query, dirty}; the literal trace is built once (keys = the product's row ids)."""
+
+    def __init__(self, S):
+        self.lw, self.tr, self.q, self.dirty = S["lw"], S["trace"], S["query"], S["dirty"]
+        self.m = self.lw.model
+        self.lt = lit.lit_trace_from(self.lw, self.tr)
+        self.ocls = self.m.classes[self.q.cls]
+        self.blocks = [list(b) for b in self.ocls.blocks]
+        self.fks = [[a for a in b if self.ocls.attr(a).kind == "fk"][0] for b in self.blocks]
+        self.own = []
+        for fk in self.fks:
+            cls = self.m.classes[self.ocls.attr(fk).target]
+            (a,) = [a for a in cls.attrs if a.kind != "param"]
+            assert a.kind == "choice", "root classes with a single own choice only"
+            self.own.append((cls.name, a))
+        self._memo = {}
+
+    def observed(self, i):
+        return {self.q.obsmap[c]: self.dirty[c][i] for c in self.q.obsmap}
+
+    def _unincorporated(self, i):
+        """snapshot for restoring the literal trace after the row's references were dropped"""
+        lt = self.lt
+        saved = {c: (dict(lt.tables[c]), dict(lt.counts[c])) for c in lt.tables}
+        for bi, fk in enumerate(self.fks):
+            if self.tr.cur[bi, i] >= 0:
+                lt.unrefer(self.ocls.attr(fk).target, int(self.tr.cur[bi, i]))
+        return saved
+
+    def _restore(self, saved):
+        for c, (t, n) in saved.items():
+            self.lt.tables[c], self.lt.counts[c] = t, n
+
+    def _block_scores(self, i, bi, ctx):
+        """{key | ('NEW', own value string): log score} of block bi of row i given the earlier blocks' values ctx"""
+        bp = lit.BlockProposal(self.lt, self.q, self.blocks[bi], self.observed(i), ctx, restricted=False)
+        sc = bp.scores()
+        new = sc.pop("NEW")
+        cname, a = self.own[bi]
+        path = a.name
+        terms = [t for t in bp.terms if path in t["paths"]]
+        options, lps, dummy = lit.discrete_proposal(self.lt, cname, a)
+        assert dummy is None, "rows that can draw a ProposalDummyValue are out of scope"
+        own = {o: lp + sum(bp._lik(t, {path: o}) for t in terms) for o, lp in zip(options, lps)}
+        z_own = lit.logsumexp(list(own.values()))
+        for o, v in own.items():  # the new row's mass split over its own value: nested conditional
+            sc[("NEW", o)] = new - z_own + v
+        return sc, lit.logsumexp([v for k, v in sc.items() if not isinstance(k, tuple)] + [new])
+
+    def value(self, bi, cand):
+        """own value string of a candidate of block bi"""
+        if isinstance(cand, tuple):
+            return cand[1]
+        cname, a = self.own[bi]
+        return self.lt.tables[cname][cand][a.name] if cand in self.lt.tables[cname] else None
+
+    def _key(self, i, what):
+        """rows with the same observations and the same current referents have the same conditionals"""
+        return what, tuple(sorted((k, v) for k, v in self.observed(i).items())), tuple(int(c) for c in self.tr.cur[:, i])
+
+    def block0(self, i):
+        """(pi over candidates, log-marginal Z) of the first block of row i"""
+        key = self._key(i, 0)
+        if key not in self._memo:
+            self._memo[key] = self._block0(i)
+        return self._memo[key]
+
+    def _block0(self, i):
+        saved = self._unincorporated(i)
+        try:
+            sc, z = self._block_scores(i, 0, {})
+        finally:
+            self._restore(saved)
+        return normalise(sc), z
+
+    def two_blocks(self, i):
+        """pi0, Z0 and, per distinct block-0 value x reachable under pi0 or held by the current referent:
+        (pi1(. | x), Z1(x)) — the context of block 1 is the value of block 0 its JuliaNode reads."""
+        key = self._key(i, 2)
+        if key not in self._memo:
+            self._memo[key] = self._two_blocks(i)
+        return self._memo[key]
+
+    def _two_blocks(self, i):
+        saved = self._unincorporated(i)
+        try:
+            sc0, z0 = self._block_scores(i, 0, {})
+            pi0 = normalise(sc0)
+            ctx_path = self._ctx_path()
+            xs = {self.value(0, t) for t, p in pi0.items() if p >= 1e-13}  # (two_block_expected's floor)
+            cur0 = int(self.tr.cur[0, i])
+            xs.add(self._cur_value(0, cur0))
+            b1 = {}
+            for x in xs:
+                sc1, z1 = self._block_scores(i, 1, {ctx_path: x})
+                b1[x] = (normalise(sc1), z1)
+        finally:
+            self._restore(saved)
+        return pi0, z0, b1
+
+    def _cur_value(self, bi, key):
+        cname, a = self.own[bi]
+        return self.lw.latent_dom[(cname, a.name)].string(int(self.tr.tables[cname].cols[self.lw.colidx[cname][a.name], key]))
+
+    def _ctx_path(self):
+        (j,) = [a for a in self.ocls.attrs if a.kind == "julia"]
+        (p,) = [x for x in j.args if x.split(".", 1)[0] == self.fks[0]]
+        return p
+
+
+# ---- closed-form kernels ------------------------------------------------------------------------------------------
+def pg_one_block(pi, s, P):
+    """output of one enumerated block under PG with P particles; s = current referent (None: no referent)"""
+    if s is None:
+        return dict(pi)
+    out = {k: (1.0 - 1.0 / P) * v for k, v in pi.items()}
+    out[s] = out.get(s, 0.0) + 1.0 / P
+    return {k: v for k, v in out.items() if v > 0}
+
+
+def mh_one_block(pi, s):
+    out = {k: MH_ACCEPT * v for k, v in pi.items()}
+    out[s] = out.get(s, 0.0) + (1.0 - MH_ACCEPT)
+    return out
+
+
+def mh_two_blocks(pi0, b1, s, value0, invert=False):
+    """output over (t0, t1) of MH with two blocks, block 1 given block 0's value: b1[x] = (pi1(. | x), Z1(x)),
+    value0(t0) = block-0 value of candidate t0, s = (s0, s1) the current referents.  invert: the acceptance of the
+    reversed ratio (a mutation for the power self-test)."""
+    z_s = b1[value0(s[0])][1]
+    out, acc = {}, []
+    for t0, p0 in pi0.items():
+        pi1, z1 = b1[value0(t0)]
+        d = (z_s - z1) if invert else (z1 - z_s)
+        a = 1.0 if d >= 0 else math.exp(d)
+        for t1, p1 in pi1.items():
+            qa = p0 * p1 * a
+            out[(t0, t1)] = qa
+            acc.append(qa)
+    stay = 1.0 - math.fsum(acc)
+    out[s] = out.get(s, 0.0) + stay
+    return {k: v for k, v in out.items() if v > 0}
+
+
+# ---- goodness of fit ----------------------------------------------------------------------------------------------
+def _merge(exp, obs, min_exp=5.0):
+    """cells sorted by expectation; the small ones pooled until the pool reaches min_exp"""
+    order = sorted(range(len(exp)), key=lambda j: exp[j])
+    cells, pool_e, pool_o, pool_n = [], 0.0, 0, []
+    for j in order:
+        if exp[j] < min_exp or pool_e and pool_e < min_exp:
+            pool_e += exp[j]
+            pool_o += obs[j]
+            pool_n.append(j)
+        else:
+            cells.append((exp[j], obs[j], [j]))
+    if pool_n:
+        if pool_e < min_exp and cells:  # fold the remainder into the smallest full cell
+            e, o, js = cells.pop(0)
+            pool_e, pool_o, pool_n = pool_e + e, pool_o + o, pool_n + js
+        cells.append((pool_e, pool_o, pool_n))
+    return cells
+
+
+def gof(items, n_worst=5):
+    """G-test of observed draws against expected distributions, pooled over rows.
+
+    items: [(label, expected {cand: prob}, observed {cand: count})].  Rows with the same expected distribution are
+    summed first; each group's G is divided by Williams' correction factor.  A draw of a candidate of probability 0 fails outright (p = 0).  Returns dict(p, G, df, n, worst)
+    with worst = [(label, cand, observed, expected)] by standardized residual."""
+    from scipy.stats import chi2
+    groups = {}
+    for label, exp, obs in items:
+        sig = tuple(sorted((repr(k), round(v, 13)) for k, v in exp.items()))
+        g = groups.get(sig)
+        if g is None:
+            groups[sig] = g = [label, exp, {}]
+        for k, c in obs.items():
+            g[2][k] = g[2].get(k, 0) + c
+    G, df, n, worst = 0.0, 0, 0, []
+    impossible = []
+    for label, exp, obs in groups.values():
+        tot = sum(obs.values())
+        n += tot
+        for k, c in obs.items():
+            if k not in exp:
+                impossible.append((label, k, c, 0.0))
+        keys = list(exp)
+        e = [tot * exp[k] for k in keys]
+        o = [obs.get(k, 0) for k in keys]
+        cells = _merge(e, o)
+        g = 0.0
+        for ce, co, js in cells:
+            if co > 0:
+                g += 2.0 * co * math.log(co / ce)
+            g -= 2.0 * (co - ce)  # (sum o = sum e up to rounding: keeps G exact when some mass was dropped)
+            cand = keys[js[0]] if len(js) == 1 else f"{len(js)} merged"
+            worst.append(((co - ce) / math.sqrt(ce), label, cand, co, ce))
+        k = len(cells)
+        if k > 1:  # Williams' correction: G overshoots chi2(k - 1) by about a factor q when cells hold few draws
+            q = 1.0 + (sum(tot / ce for ce, _, _ in cells) - 1.0) / (6.0 * tot * (k - 1))
+            G += g / q
+        df += max(k - 1, 0)
+    worst.sort(key=lambda w: -abs(w[0]))
+    if impossible:
+        return dict(p=0.0, G=math.inf, df=df, n=n, worst=impossible[:n_worst])
+    p = float(chi2.sf(G, df)) if df > 0 else 1.0
+    return dict(p=p, G=G, df=df, n=n, worst=[w[1:] for w in worst[:n_worst]])
+
+
+def describe(res):
+    w = "; ".join(f"row {lab} cand {c!r}: {o} drawn, {e:.1f} expected" for lab, c, o, e in res["worst"])
+    return f"p = {res['p']:.3g} (G = {res['G']:.1f}, df = {res['df']}, {res['n']} draws); worst cells: {w}"
+
+
+def tabulate(draws):
+    """[per-sweep list of candidates] for one row -> {cand: count}"""
+    out = {}
+    for d in draws:
+        out[d] = out.get(d, 0) + 1
+    return out
+
+
+def logml_bound(n_terms, z):
+    """the quantisation bound of include/pclean_detmath.h on a log-sum-exp of n_terms: n 2^-40 + 1e-12 |Z|"""
+    return n_terms * 2.0 ** -40 + 1e-12 * abs(z)
+
+
+# ---- the programs of the draw tests -------------------------------------------------------------------------------
+def _words(rng, n, lo=18, hi=25, alphabet="abcdefghijklmnop", taken=()):
+    out, seen = [], set(taken)
+    while len(out) < n:
+        w = "".join(rng.choice(list(alphabet), size=int(rng.integers(lo, hi))))
+        if w not in seen:
+            seen.add(w)
+            out.append(w)
+    return out
+
+
+def _typo(rng, w, alphabet="abcdefghijklmnop"):
+    j = int(rng.integers(len(w)))
+    c = w[j]
+    while c == w[j]:
+        c = str(rng.choice(list(alphabet)))
+    return w[:j] + c + w[j + 1:]
+
+
+def draw_program(n_table, seed=0, n_dead=0, two_blocks=False):
+    """`A: x ~ ChooseUniformly(words)`, `Obs: a ~ A; y, y2, y3 ~ AddTypos(a.x)` with a latent table of n_table rows (n_dead of
+    them dead, below the high-water mark) and observed rows of every posterior shape the sweep's kernels tell apart;
+    row kind in S['kind']:
+      peaked — the observation equals its entity's far-away word (the "decided" groups of the fast path);
+      spread — clusters of five entities one or two edits apart: 3-10 candidates within a few nats;
+      tied   — pairs of entities with identical values;
+      flat   — a missing observation: the CRP prior over every live row (more than 256 survivors);
+      new    — the row is its entity's only reference and observes a word no entity holds: the new-row branch wins;
+      filler — single-reference entities observed exactly; the filler words repeat, so the row's own value is held
+               by other single-reference entities as well (ties against the new row with that word).
+    y2 and y3 repeat y on the peaked, new and filler rows and are missing elsewhere.
+    Words are 18-24 letters long, so that the fast path's pre-filter (about ten edits) tells candidates apart.
+    two_blocks: a second block `b ~ B; w ~ AddTypos(b.z); v ~ AddTypos(j)` with the JuliaNode j = x + "_" + z reading
+    block 0's value (block 1 depends on block 0: the MH closed form of two blocks)."""
+    from pclean_amd.model import AddTypos, ChooseUniformly, LoweredModel, Model, Query
+    from pclean_amd.trace import Trace
+    rng = np.random.default_rng(seed)
+    ents, rows = [], []  # ents: word per latent row (None = dead); rows: (kind, entity, observed word | None)
+
+    def ent(w):
+        ents.append(w)
+        return len(ents) - 1
+
+    far = _words(rng, 30)
+    for w in far:
+        e = ent(w)
+        rows += [("peaked", e, w)] * 3
+    used = set(far)
+    for _ in range(12):
+        (base,) = _words(rng, 1, taken=used)
+        cl = [base]
+        while len(cl) < 5:
+            v = _typo(rng, base)
+            if v not in cl and v not in used:
+                cl.append(v)
+        used.update(cl)
+        es = [ent(w) for w in cl]
+        for e in es:
+            rows += [("spread", e, _typo(rng, base)), ("spread", e, base)]
+    for w in _words(rng, 12, taken=used):
+        used.add(w)
+        e1, e2 = ent(w), ent(w)
+        rows += [("tied", e1, _typo(rng, w)), ("tied", e2, w), ("tied", e1, w), ("tied", e2, _typo(rng, w))]
+    hub = ent(_words(rng, 1, taken=used)[0])
+    used.add(ents[hub])
+    rows += [("flat", hub, None)] * 60
+    fresh = _words(rng, 24, taken=used)
+    used.update(fresh)
+    n_dead_at = set(range(len(ents) + 10, len(ents) + 10 + 7 * n_dead, 7)) if n_dead else set()
+    pool = _words(rng, 60, taken=used)  # filler entities share their words: few distinct strings, many candidates
+    used.update(pool)
+    for w in fresh:
+        while len(ents) in n_dead_at:
+            ents.append(None)
+        rows.append(("new", ent(pool[len(ents) % len(pool)]), w))
+    n_fill = n_table - len(ents)
+    assert n_fill > 0
+    for w in (pool[k % len(pool)] for k in range(n_fill)):
+        while len(ents) in n_dead_at:
+            ents.append(None)
+        if len(ents) >= n_table:
+            break
+        rows.append(("filler", ent(w), w))
+    extra = _words(rng, 20, taken=used)
+    words = sorted({w for w in ents if w is not None} | set(fresh) | set(extra))
+    m = Model()
+    a = m.add_class("A")
+    a.choice("x", ChooseUniformly(words))
+    bwords = None
+    if two_blocks:
+        bwords = _words(rng, 12, lo=3, hi=5, alphabet="qrstuvwxyz")
+        b = m.add_class("B")
+        b.choice("z", ChooseUniformly(bwords))
+    o = m.add_class("Obs")
+    with o.block():
+        o.fk("a", "A")
+        o.choice("y", AddTypos("a.x"))
+        o.choice("y2", AddTypos("a.x"))
+        o.choice("y3", AddTypos("a.x"))
+    bind = {"Y": ("a.x", "y"), "Y2": ("a.x", "y2"), "Y3": ("a.x", "y3")}
+    if two_blocks:
+        with o.block():
+            o.fk("b", "B")
+            o.choice("w", AddTypos("b.z"))
+            o.julia("j", lambda x, z: f"{x}_{z}", ["a.x", "b.z"])
+            o.choice("v", AddTypos("j"))
+        bind.update({"W": ("b.z", "w"), "V": ("j", "v")})
+    q = Query(m, "Obs", bind)
+    n = len(rows)
+    dirty = {"Y": [r[2] for r in rows]}
+    # rows whose referent is decided observe it three times (y2, y3): the fast path's pre-filter sums three terms; the
+    # other shapes leave y2 and y3 missing
+    decided = [r[0] in ("peaked", "new", "filler") for r in rows]
+    dirty["Y2"] = [r[2] if d else None for r, d in zip(rows, decided)]
+    dirty["Y3"] = list(dirty["Y2"])
+    bcur = None
+    if two_blocks:  # block 1: B rows with one of 12 short words, three references each; w and v noisy copies
+        n_b = 40
+        bvals = [bwords[k % len(bwords)] for k in range(n_b)]
+        bcur = rng.integers(0, n_b, size=n)
+        dirty["W"] = [bvals[k] if i % 3 else _typo(rng, bvals[k], "qrstuvwxyz") for i, k in enumerate(bcur)]
+        dirty["V"] = [None if r[2] is None else f"{ents[r[1]]}_{bvals[k]}" for r, k in zip(rows, bcur)]
+    lw = LoweredModel(m, q, dirty)
+    obs = lw.encode_observations(dirty)
+    tr = Trace(lw, n, seed)
+    dom = lw.latent_dom[("A", "x")]
+    t = tr.tables["A"]
+    ids = [tr.insert_row("A", np.array([dom.index_of(w if w is not None else words[0])], np.int32)) for w in ents]
+    for k, w in enumerate(ents):
+        assert ids[k] == k
+    for i, r in enumerate(rows):
+        tr.cur[0, i] = r[1]
+        t.counts[r[1]] += 1
+    for k, w in enumerate(ents):
+        if w is None:
+            tr.delete_row("A", k)
+    assert t.n == n_table and int((~t.live[:t.n]).sum()) == len([w for w in ents if w is None])
+    if two_blocks:
+        bdom, tb = lw.latent_dom[("B", "z")], tr.tables["B"]
+        for k in range(n_b):
+            assert tr.insert_row("B", np.array([bdom.index_of(bvals[k])], np.int32)) == k
+        for i, k in enumerate(bcur):
+            tr.cur[1, i] = k
+            tb.counts[k] += 1
+    return dict(lw=lw, trace=tr, obs=obs, query=q, dirty=dirty, model=m, kind=np.array([r[0] for r in rows]))
+
+
+# ---- draws of the product's sweeps as candidates ------------------------------------------------------------------
+class Encoder:
+    """candidate <-> int code of one block: an existing key k is k, a new row with option j of its own choice is
+    n_table + j (what the sweep outputs: the referent, PCLEAN_CHOICE_NEW = -1 with the option index in new_rows)."""
+
+    def __init__(self, lw, tr, bi):
+        blk = lw.blocks[bi]
+        self.cname = blk["root_class"]
+        self.n_table = tr.tables[self.cname].n
+        (self.attr,) = [c.name for c in lw.layout[self.cname] if c.kind == "val"]
+        dom = lw.latent_dom[(self.cname, self.attr)]
+        self.opt = {dom.string(int(v)): j for j, v in enumerate(lw.option_values[(self.cname, self.attr)])}
+        (self.leaf,) = [k for k in range(1, len(blk["nodes"]))]
+
+    def code(self, cand):
+        return self.n_table + self.opt[cand[1]] if isinstance(cand, tuple) else int(cand)
+
+    def codes(self, choice_row, new_rows, n):
+        """int codes of one block's outputs over rows 0..n-1 of a sweep"""
+        out = np.asarray(choice_row[:n], dtype=np.int64).copy()
+        if new_rows is not None:
+            rows, vals = new_rows
+            sel = rows < n
+            out[rows[sel]] = self.n_table + vals[sel, self.leaf]
+        assert (out >= 0).all(), "a new referent without its new-row record"
+        return out
+
+
+ALPHA = 1e-4  # a case fails below this pooled p-value (its seeds are fixed: the outcome is deterministic)
+
+# the particle counts of the cases: the edges of the DISPATCH_PMAX buckets of the sweep kernels; (P, MH)
+PARTICLES = [(1, False), (2, False), (2, True), (3, False), (8, False), (9, False), (32, False), (33, False), (64, False)]
+
+
+def check_rows(S, every_filler=4):
+    """rows whose draws are tabulated: every row of a shape of interest, every k-th filler row"""
+    kind = S["kind"]
+    rows = [i for i in range(len(kind)) if kind[i] != "filler" or i % every_filler == 0]
+    return np.array(rows, dtype=np.int64)
+
+
+def one_block_case(eng, S, rc, rows, P, mh, n_sweeps, seed):
+    """S sweeps (sweep_idx 0..n_sweeps-1, nothing committed in between) of a one-block program; draws of `rows`
+    against the closed form, logml against the exact log-marginal.  Returns (gof result, max |logml - Z| / bound,
+    number of new-row records)."""
+    from pclean_amd.engine import InferenceConfig
+    tr = S["trace"]
+    enc = Encoder(S["lw"], tr, 0)
+    cfg = InferenceConfig(1, P, use_mh_instead_of_pg=mh)
+    n = tr.cur.shape[1]
+    D = np.empty((n_sweeps, len(rows)), dtype=np.int64)
+    dev, n_new = 0.0, 0
+    exact = [rc.block0(int(i)) for i in rows]
+    for s in range(n_sweeps):
+        choice, chosen, logml, new_rows = eng.sweep(tr, cfg, seed, s)
+        n_new += len(new_rows[0][0]) if 0 in new_rows else 0
+        D[s] = enc.codes(choice[0], new_rows.get(0), n)[rows]
+        if s == 0:
+            for j, i in enumerate(rows):
+                z = exact[j][1]
+                dev = max(dev, abs(float(logml[i]) - z) / logml_bound(enc.n_table + len(enc.opt) + 1, z))
+    items = []
+    for j, i in enumerate(rows):
+        pi = {enc.code(k): v for k, v in exact[j][0].items()}
+        s0 = int(tr.cur[0, i])
+        s0 = None if s0 < 0 else s0
+        e = mh_one_block(pi, s0) if (mh and s0 is not None) else pg_one_block(pi, s0, P)
+        items.append((int(i), e, tabulate(D[:, j].tolist())))
+    return gof(items), dev, n_new
+
+
+def two_block_expected(S, rc, rows, invert=False, floor=1e-13):
+    """closed form of MH over the two blocks of draw_program(two_blocks=True) per row, in the encoders' codes
+    (t0 code, t1 code); block-0 candidates below `floor` are left out (their mass, < 1e-10 in all, stays put)"""
+    tr = S["trace"]
+    e0, e1 = Encoder(S["lw"], tr, 0), Encoder(S["lw"], tr, 1)
+    out = []
+    for i in rows:
+        pi0, z0, b1 = rc.two_blocks(int(i))
+        pi0 = {k: v for k, v in pi0.items() if v >= floor}
+        val = {k: rc.value(0, k) for k in pi0}
+        cur = (int(tr.cur[0, i]), int(tr.cur[1, i]))
+        val[cur[0]] = rc._cur_value(0, cur[0])
+        ex = mh_two_blocks(pi0, b1, cur, lambda t: val[t], invert=invert)
+        out.append({(e0.code(t[0]), e1.code(t[1])): v for t, v in ex.items()})
+    return out
+
+
+def two_block_case(eng, S, rc, rows, n_sweeps, seed):
+    from pclean_amd.engine import InferenceConfig
+    tr = S["trace"]
+    e0, e1 = Encoder(S["lw"], tr, 0), Encoder(S["lw"], tr, 1)
+    cfg = InferenceConfig(1, 2, use_mh_instead_of_pg=True)
+    n = tr.cur.shape[1]
+    D0 = np.empty((n_sweeps, len(rows)), dtype=np.int64)
+    D1 = np.empty_like(D0)
+    for s in range(n_sweeps):
+        choice, chosen, logml, new_rows = eng.sweep(tr, cfg, seed, s)
+        D0[s] = e0.codes(choice[0], new_rows.get(0), n)[rows]
+        D1[s] = e1.codes(choice[1], new_rows.get(1), n)[rows]
+    exp = two_block_expected(S, rc, rows)
+    items = [(int(i), exp[j], tabulate(list(zip(D0[:, j].tolist(), D1[:, j].tolist())))) for j, i in enumerate(rows)]
+    return gof(items)
+
+
+# ---- the cases both legs share --------------------------------------------------------------------------------------
+S_GPU = 200            # sweeps per case of the device leg (the power self-test samples at this S)
+SPREAD_SWEEPS = 2000   # sweeps of the spread-row case: a 0.1-nat shift moves p by ~0.1 p (1 - p), visible only there
+SPREAD_P = 2
+PROGRAMS = {"generic": dict(n_table=300, seed=0, n_dead=0), "fast": dict(n_table=1090, seed=0, n_dead=5)}
+TWO_BLOCK = dict(n_table=1090, seed=1, two_blocks=True)
+
+
+def two_block_rows(S):
+    return np.array([i for i, k in enumerate(S["kind"]) if k in ("peaked", "spread", "tied", "new")][::2])
+
+
+def near_candidate(pi, s):
+    """the most probable existing row other than s among those holding 10%..90% (None when there is none)"""
+    near = [k for k, v in pi.items() if k != s and not isinstance(k, tuple) and 0.1 < v < 0.9]
+    return max(near, key=lambda c: pi[c]) if near else None
+
+
+def shift_near(pi, s, nats=0.1):
+    """pi with its near candidate's score shifted by `nats` (a mutation for the power self-test)"""
+    k = near_candidate(pi, s)
+    if k is None:
+        return pi
+    out = dict(pi)
+    out[k] *= math.exp(nats)
+    z = sum(out.values())
+    return {c: v / z for c, v in out.items()}
+
+
+def spread_rows(S, rc):
+    """rows whose posterior holds a near candidate: the row set of the spread case (SPREAD_SWEEPS draws each)"""
+    tr = S["trace"]
+    return np.array([i for i in range(tr.cur.shape[1]) if near_candidate(rc.block0(i)[0], int(tr.cur[0, i])) is not None],
+                    dtype=np.int64)
+
+
+# ---- latent rows: the own choice x of class A against its evidence set ----------------------------------------------
+def latent_setup(S):
+    """(live, ev_off, ev_rows, ev_ctx, excl) of class A for sweep_latent"""
+    from pclean_amd.engine import InferenceConfig
+    from pclean_amd.inference import build_evidence, latent_current_choices
+    live, ev_off, ev_rows, ev_ctx = build_evidence(S["lw"], S["trace"], "A")
+    excl = latent_current_choices(S["lw"], S["trace"], "A", live, InferenceConfig(1, 2))
+    return live, ev_off, ev_rows, ev_ctx, excl
+
+
+def latent_exact(S, rc, live, ev_off, ev_rows, items):
+    """pi over option indices of x for the latent rows live[items] (LatentProposal: every AddTypos observation of every
+    referring row) and the option index of each row's current value"""
+    lw, tr = S["lw"], S["trace"]
+    enc = Encoder(lw, tr, 0)
+    col = lw.colidx["A"]["x"]
+    dom = lw.latent_dom[("A", "x")]
+    memo, out = {}, []
+    for t in items:
+        ev = [rc.observed(int(r)) for r in ev_rows[ev_off[t]:ev_off[t + 1]]]
+        key = tuple(tuple(sorted(o.items())) for o in ev)
+        if key not in memo:
+            lp = lit.LatentProposal(rc.lt, rc.q, rc.blocks[0], "", [(o, {}) for o in ev])
+            memo[key] = {enc.opt[o]: v for o, v in normalise(lp.leaf_scores("A", "x")).items()}
+        cur = enc.opt[dom.string(int(tr.tables["A"].cols[col, live[t]]))]
+        out.append((memo[key], cur))
+    return out
+
+
+def latent_case(eng, S, rc, P, mh, n_sweeps, seed, every=3):
+    """sweep_latent over every live row of A, n_sweeps times (sweep_idx 0..n_sweeps-1): the chosen particle 0 keeps
+    the current value, any other draws from pi -> (1/P) d_cur + (1 - 1/P) pi under PG, MH_ACCEPT pi + ... under MH"""
+    from pclean_amd.engine import InferenceConfig
+    live, ev_off, ev_rows, ev_ctx, excl = latent_setup(S)
+    items = np.arange(0, len(live), every)
+    exact = latent_exact(S, rc, live, ev_off, ev_rows, items)
+    root = S["lw"].latent_plans["A"]["roots"][0]
+    cfg = InferenceConfig(1, P, use_mh_instead_of_pg=mh)
+    D = np.empty((n_sweeps, len(items)), dtype=np.int64)
+    for s in range(n_sweeps):
+        chosen, vals = eng.sweep_latent(S["trace"], "A", cfg, seed, s, live, ev_off, ev_rows, ev_ctx, excl)
+        keep = np.array([c for _, c in exact])
+        got = np.where(chosen[items] == 0, keep, vals[items, root])
+        assert (got >= 0).all(), "a latent row chose a particle without its draw"
+        D[s] = got
+    res = []
+    for j, t in enumerate(items):
+        pi, cur = exact[j]
+        e = mh_one_block(pi, cur) if mh else pg_one_block(pi, cur, P)
+        res.append((int(t), e, tabulate(D[:, j].tolist())))
+    return gof(res)
