@@ -1324,6 +1324,8 @@ static int ensure_tuple_ids(pclean_ctx* ctx, int block_id, int node_id, const st
   for (int q = 0; q < n_pre; ++q) sig = sig * 1000003ull + (uint64_t)(pre_cols[q] + 7);
   if (t.sig != sig || !t.id.p) {
     const int n = ctx->n_rows;
+    for (auto& w : t.windows) w.release();  // (static orders of the ids that are about to be renumbered)
+    t.windows.clear();
     if (t.id.alloc(std::max(n, 1)) || t.pre.alloc(std::max(n, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
     KeyColsDev kc{};
     for (int c : cols) kc.col[kc.n_cols++] = ctx->obs.p + (size_t)c * ctx->n_rows;
@@ -1581,6 +1583,201 @@ static int make_item_groups_hash(pclean_ctx* ctx, const ItemList& il, const int3
   return PCLEAN_OK;
 }
 
+// ---- grouping from a static tuple order -------------------------------------------------------------------------------
+// When the items are the rows of the active window themselves and the key holds no context value, the key of item i is
+// (tuple_id[i], excl[i]): the tuple id never changes, only the referent does.  The rows are sorted ONCE per loaded table
+// by (hash of the pre-filter values, tuple id) — rows of one tuple form a segment, the segments of one pre-filter family
+// are neighbours (what root_wave.hip's survivor-list reuse wants of the group order) — and the order is cut into tiles
+// of at most 64 positions along the segment boundaries (a segment longer than 64 is cut at multiples of 64).  A sweep
+// then only splits every tile by referent: one wavefront per tile finds the classes of its <= 64 (tuple id, referent)
+// pairs by ballots and writes the members as a permutation of its own positions; a scan over the tiles' piece counts
+// numbers the groups; a streaming pass writes uid / grp_off.  No table, no probing, no atomics.  Two rows of one group
+// that a tile boundary separates become two groups: a split, which the contract above allows (it happens only inside
+// segments longer than 64).  PCLEAN_NO_STATIC_GROUPS=1: the hash table for these items too.
+#define STATIC_ORDER_WINDOWS 8  // cached windows per (block, node); their rows together: at most 2 x the loaded rows
+__global__ void static_key_kernel(int n, const int32_t* __restrict__ tuple_id, const uint32_t* __restrict__ pre_hash,
+                                  uint64_t* __restrict__ key, int32_t* __restrict__ idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  key[i] = ((uint64_t)pre_hash[i] << 32) | (uint32_t)tuple_id[i];
+  idx[i] = i;
+}
+__global__ void static_tid_kernel(int n, const uint64_t* __restrict__ key_s, int32_t* __restrict__ tid) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) tid[j] = (int32_t)(uint32_t)key_s[j];
+}
+// The static order of the active window's rows for the tuple ids of (block, node) (ensure_tuple_ids has just run).
+// *out stays null when the window does not fit the cache: the caller falls back to the hash table.  A full cache gives
+// up its smallest window for a LARGER one only (the short windows of an initialisation make room for the sweeps' windows;
+// a sweep cut into more equal windows than the cache holds keeps the first ones and never rebuilds an order per sweep).
+static int ensure_static_order(pclean_ctx* ctx, int block_id, int node_id, int n, const SweepState::TupleIds::StaticOrder** out) {
+  typedef SweepState::TupleIds::StaticOrder StaticOrder;
+  *out = nullptr;
+  SweepState::TupleIds& t = st(ctx)->tuple_ids[block_id * 64 + node_id];
+  const int begin = ctx->active_begin;
+  if (!t.id.p || !t.pre.p || n <= 0 || (size_t)begin + (size_t)n > t.id.n) return PCLEAN_OK;
+  for (const StaticOrder& w : t.windows)
+    if (w.begin == begin && w.n == n) {
+      *out = &w;
+      return PCLEAN_OK;
+    }
+  for (;;) {
+    size_t held = 0, smallest = 0;
+    for (size_t k = 0; k < t.windows.size(); ++k) {
+      held += (size_t)t.windows[k].n;
+      if (t.windows[k].n < t.windows[smallest].n) smallest = k;
+    }
+    if (t.windows.size() < STATIC_ORDER_WINDOWS && held + (size_t)n <= 2 * (size_t)ctx->n_rows) break;
+    if (t.windows.empty() || t.windows[smallest].n >= n) {
+      static const bool trace = getenv("PCLEAN_TRACE_SYNC") != nullptr;
+      if (trace) fprintf(stderr, "[pclean static groups] block %d node %d rows %d+%d: window not cached, hash table\n", block_id, node_id, begin, n);
+      return PCLEAN_OK;
+    }
+    t.windows[smallest].release();
+    t.windows.erase(t.windows.begin() + smallest);
+  }
+  StaticOrder w;
+  w.begin = begin;
+  w.n = n;
+  DevBuf<uint64_t> key, key_s;
+  DevBuf<int32_t> idx;
+  DevBuf<unsigned char> tmp;
+  int32_t* h_tid = nullptr;
+  int32_t* h_off = nullptr;
+  auto cleanup = [&]() {
+    key.release(); key_s.release(); idx.release(); tmp.release();
+    if (h_tid) (void)hipHostFree(h_tid);
+    if (h_off) (void)hipHostFree(h_off);
+  };
+  auto fail = [&](const char* what) {
+    cleanup();
+    w.release();
+    return pclean_fail(ctx, PCLEAN_ERR_HIP, "%s", what);
+  };
+  if (key.alloc(n) || key_s.alloc(n) || idx.alloc(n) || w.order.alloc(n) || w.tid.alloc(n)) return fail("device alloc failed");
+  hipLaunchKernelGGL(static_key_kernel, grid1(n), dim3(256), 0, ctx->stream, n, t.id.p + begin, t.pre.p + begin, key.p, idx.p);
+  size_t tmp_sort = 0;
+  if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, key.p, key_s.p, idx.p, w.order.p, n, 0, 64, ctx->stream) != hipSuccess ||
+      tmp.alloc(std::max<size_t>(tmp_sort, 16)) ||
+      hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_sort, key.p, key_s.p, idx.p, w.order.p, n, 0, 64, ctx->stream) != hipSuccess)
+    return fail("static order: sort failed");
+  hipLaunchKernelGGL(static_tid_kernel, grid1(n), dim3(256), 0, ctx->stream, n, key_s.p, w.tid.p);
+  // the tiles: a serial walk over the segments, on the host (once per window; page-locked staging: see HostStage)
+  if (hipHostMalloc((void**)&h_tid, (size_t)n * sizeof(int32_t)) != hipSuccess) { h_tid = nullptr; return fail("host alloc failed"); }
+  if (hipHostMalloc((void**)&h_off, ((size_t)n + 1) * sizeof(int32_t)) != hipSuccess) { h_off = nullptr; return fail("host alloc failed"); }
+  if (hipMemcpyAsync(h_tid, w.tid.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return fail("static order: read-back failed");
+  int n_off = 0, start = 0;
+  h_off[n_off++] = 0;
+  for (int sb = 0; sb < n;) {
+    int se = sb + 1;
+    while (se < n && h_tid[se] == h_tid[sb]) ++se;
+    if (se - start > 64) {  // the segment [sb, se) does not fit the open tile
+      if (sb > start) h_off[n_off++] = start = sb;
+      while (se - start > 64) h_off[n_off++] = start = start + 64;
+    }
+    sb = se;
+  }
+  h_off[n_off++] = n;
+  w.n_tiles = n_off - 1;
+  if (w.tile_off.alloc(n_off)) return fail("device alloc failed");
+  if (hipMemcpyAsync(w.tile_off.p, h_off, (size_t)n_off * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return fail("static order: upload failed");
+  cleanup();
+  t.windows.push_back(w);
+  *out = &t.windows.back();
+  return PCLEAN_OK;
+}
+// One wavefront per tile: lane = position of the tile.  Classes of the lanes by (tuple id, referent), in the order of their
+// first lanes; a class of more than 2 split_m - 1 lanes is cut into pieces of split_m (the last piece takes the remainder),
+// exactly as HgPacked / hg_fill_kernel do.  loc[position] = (piece index within the tile) << 1 | first member of its piece.
+__global__ __launch_bounds__(256) void sg_class_kernel(int n_tiles, const int32_t* __restrict__ tile_off,
+                                                       const int32_t* __restrict__ order, const int32_t* __restrict__ tid_sorted,
+                                                       const int32_t* __restrict__ excl, int split_m,
+                                                       int32_t* __restrict__ members, int32_t* __restrict__ loc,
+                                                       int32_t* __restrict__ tile_cnt) {
+  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (tile >= n_tiles) return;
+  const int t0 = tile_off[tile], len = tile_off[tile + 1] - t0;
+  const bool on = lane < len;
+  int i = 0, kt = 0, ke = 0;
+  if (on) {
+    i = order[t0 + lane];
+    kt = tid_sorted[t0 + lane];
+    ke = excl[i];
+  }
+  int pos_acc = 0, piece_acc = 0, my_at = 0, my_loc = 0;
+  for (unsigned long long pend = __ballot(on); pend;) {
+    const int ld = __builtin_ctzll(pend);
+    const int lt = __builtin_amdgcn_readlane(kt, ld), le = __builtin_amdgcn_readlane(ke, ld);
+    const unsigned long long cls = __ballot(on && kt == lt && ke == le) & pend;
+    const int c = __popcll(cls);
+    const int pieces = split_m > 0 ? max(c / split_m, 1) : 1;
+    if ((cls >> lane) & 1ull) {
+      const int r = __popcll(cls & ((1ull << lane) - 1ull));
+      const int piece = split_m > 0 ? min(r / split_m, pieces - 1) : 0;
+      const bool first = split_m > 0 ? r == piece * split_m : r == 0;
+      my_at = pos_acc + r;
+      my_loc = ((piece_acc + piece) << 1) | (first ? 1 : 0);
+    }
+    pos_acc += c;
+    piece_acc += pieces;
+    pend &= ~cls;
+  }
+  if (on) {
+    members[t0 + my_at] = i;
+    loc[t0 + my_at] = my_loc;
+  }
+  if (lane == 0) tile_cnt[tile] = piece_acc;
+}
+__global__ __launch_bounds__(256) void sg_fill_kernel(int n, int n_tiles, const int32_t* __restrict__ tile_off,
+                                                      const int32_t* __restrict__ loc, const int32_t* __restrict__ tile_cnt,
+                                                      const int32_t* __restrict__ incl, int32_t* __restrict__ uid,
+                                                      int32_t* __restrict__ grp_off) {
+  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (tile >= n_tiles) return;
+  const int t0 = tile_off[tile], len = tile_off[tile + 1] - t0;
+  const int base = incl[tile] - tile_cnt[tile];
+  if (lane < len) {
+    const int v = loc[t0 + lane], grp = base + (v >> 1);
+    uid[t0 + lane] = grp + 1;
+    if (v & 1) grp_off[grp] = t0 + lane;
+  }
+  if (tile == 0 && lane == 0) grp_off[incl[n_tiles - 1]] = n;
+}
+static int make_item_groups_static(pclean_ctx* ctx, const SweepState::TupleIds::StaticOrder& so, const ItemList& il,
+                                   const int32_t* excl, int split_m, ItemGroups& g) {
+  const int n = il.n, nt = so.n_tiles;
+  int32_t* members = scratch<int32_t>(ctx, n);
+  int32_t* loc = scratch<int32_t>(ctx, n);
+  int32_t* tile_cnt = scratch<int32_t>(ctx, nt);
+  int32_t* incl = scratch<int32_t>(ctx, nt);
+  size_t tmp_scan = 0;
+  HIPCHK(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, tile_cnt, incl, nt, ctx->stream));
+  unsigned char* tmp = scratch<unsigned char>(ctx, std::max<size_t>(tmp_scan, 16));
+  if (!members || !loc || !tile_cnt || !incl || !tmp) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(sg_class_kernel, grid1(nt, 4), dim3(256), 0, ctx->stream, nt, so.tile_off.p, so.order.p, so.tid.p, excl,
+                     split_m, members, loc, tile_cnt);
+  HIPCHK(ctx, hipcub::DeviceScan::InclusiveSum(tmp, tmp_scan, tile_cnt, incl, nt, ctx->stream));
+  int32_t n_unique = 0;
+  PCLEAN_READ_COUNT(ctx, incl + (nt - 1), &n_unique);
+  if (n_unique <= 0 || (double)n_unique > 0.75 * n) return PCLEAN_OK;  // not worth the indirection
+  int32_t* uid = scratch<int32_t>(ctx, n);
+  int32_t* grp_off = scratch<int32_t>(ctx, (size_t)n_unique + 1);
+  if (!uid || !grp_off) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(sg_fill_kernel, grid1(nt, 4), dim3(256), 0, ctx->stream, n, nt, so.tile_off.p, loc, tile_cnt, incl, uid, grp_off);
+  g.n_groups = n_unique;
+  g.grp_off = grp_off;
+  g.members = members;
+  g.head = nullptr;
+  g.uid = uid;
+  return PCLEAN_OK;
+}
+
 // Groups the items of `il` by (observed values of the sub-tree of node_id, ctx, excl).  g.n_groups == 0
 // when the sub-tree cannot be keyed, the list is small, or fewer than a quarter of the items are duplicates.
 static int make_item_groups(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, const int32_t* excl,
@@ -1624,6 +1821,14 @@ static int make_item_groups(pclean_ctx* ctx, int block_id, int node_id, const It
     if (np2 == 0) kc.pre_hash = nullptr;
   }
   static const bool sort_groups = getenv("PCLEAN_SORT_GROUPS") != nullptr;
+  // the window's own rows, keyed by (tuple id, referent) alone: split the static tuple order by referent
+  static const bool no_static = getenv("PCLEAN_NO_STATIC_GROUPS") != nullptr;
+  if (want_members && excl && !il.row && (!kc.use_ctx || !il.ctx) && kc.tuple_id && !sort_groups && !no_static) {
+    const SweepState::TupleIds::StaticOrder* so = nullptr;
+    int rc = ensure_static_order(ctx, block_id, node_id, n, &so);
+    if (rc) return rc;
+    if (so) return make_item_groups_static(ctx, *so, il, excl, split_m, g);
+  }
   if (!sort_groups) return make_item_groups_hash(ctx, il, excl, kc, split_m, want_members, g);
   uint64_t* key = scratch<uint64_t>(ctx, n);
   uint64_t* key_s = scratch<uint64_t>(ctx, n);

@@ -1044,10 +1044,7 @@ void pclean_sweep_state_free(pclean_ctx* ctx) {
     f.zero_row.release();
   }
   s->tail_counts.release();
-  for (auto& kv : s->tuple_ids) {
-    kv.second.id.release();
-    kv.second.pre.release();
-  }
+  for (auto& kv : s->tuple_ids) kv.second.release();
   for (auto& kv : s->memo) {
     kv.second.keys.release();
     kv.second.vals.release();

@@ -107,6 +107,21 @@ struct SweepState {
     DevBuf<int32_t> id;
     DevBuf<uint32_t> pre;
     uint64_t sig = 0;
+    // static order of the rows of one active window (eval.hip: ensure_static_order): the window's items sorted by
+    // (pre-filter hash, tuple id), their tuple ids in that order, and the order cut into tiles of at most 64 positions
+    // along the tuple segments.  Immutable between rebuilds of `id`; a few windows per entry (STATIC_ORDER_WINDOWS)
+    struct StaticOrder {
+      int begin = 0, n = 0, n_tiles = 0;
+      DevBuf<int32_t> order, tid, tile_off;  // [n], [n], [n_tiles + 1]
+      void release() { order.release(); tid.release(); tile_off.release(); }
+    };
+    std::vector<StaticOrder> windows;
+    void release() {
+      id.release();
+      pre.release();
+      for (auto& w : windows) w.release();
+      windows.clear();
+    }
   };
   std::map<int, TupleIds> tuple_ids;
   // gate of the new-row branch (eval.hip): a node whose gate let EVERY item through three evaluations in a row (the
