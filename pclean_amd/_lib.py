@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PCLEAN_HIP_LIB") or os.path.join(HERE, "libpclean_hip.so")
 
 MAX_CTX = 4
+MAX_GAUSS = 4  # PCLEAN_MAX_GAUSS
 EV_MAX_STEPS = 4  # PCLEAN_EV_MAX_STEPS
 CHOICE_NEW = -1
 DIST_OSA, DIST_DL = 0, 1
@@ -293,6 +294,11 @@ class HipContext:
     def set_node_gauss(self, block_id, node_id, g):
         check(self.h, self.lib.pclean_set_node_gauss(self.h, C.c_int32(block_id), C.c_int32(node_id), C.byref(g)),
               "pclean_set_node_gauss")
+
+    def add_node_gauss(self, block_id, node_id, g):
+        """a further Gaussian term of a node that has one (set_node_gauss): same own choices, declaration order"""
+        check(self.h, self.lib.pclean_add_node_gauss(self.h, C.c_int32(block_id), C.c_int32(node_id), C.byref(g)),
+              "pclean_add_node_gauss")
 
     def set_cur_locals(self, block_id, locals_):
         """current own choices of EVERY observed row ([n_rows][2] int32; None clears): the retained particle of a sweep with

@@ -22,14 +22,16 @@ def reconstructed_pool_ids(lowered, trace, row_slice=None):
             dom = lw.latent_dom[(q.cls, ref)]
             out[col] = dom.id_array()[np.maximum(trace.locals[bi][:, li], 0)]
             continue
-        if own is not None and own.kind == "julia" and getattr(lw, "gauss_spec", None) is not None \
-                and lw.gauss_spec["gauss_attr"] == q.obsmap[col]:
+        gi = None
+        if own is not None and own.kind == "julia":  # a queried numeric column is reported through its own Gaussian term
+            gi = next((g for g, sp in enumerate(lw.gauss_specs) if sp["gauss_attr"] == q.obsmap[col]), None)
+        if gi is not None:
             # corrected = round(unit.backward(x)) (experiments/rents/run.jl:25): numeric, compared as a number
-            spec = lw.gauss_spec
+            spec = lw.gauss_specs[gi]
             bi = lw.gauss_block
             u = (np.zeros(trace.cur.shape[1], dtype=np.int32) if spec["t_local"] is None  # AddNoise: round(x)
                  else np.maximum(trace.locals[bi][:, spec["t_local"]], 0))
-            out[col] = ("numeric", np.round(lw.gauss_backward(np.arange(trace.cur.shape[1]), u)))
+            out[col] = ("numeric", np.round(lw.gauss_backward(np.arange(trace.cur.shape[1]), u, gi)))
             continue
         if "." in ref:
             head, rest = ref.split(".", 1)

@@ -634,19 +634,47 @@ extern "C" int pclean_set_mean_table(pclean_ctx* ctx, int32_t table_id, int32_t 
   return PCLEAN_OK;
 }
 
-extern "C" int pclean_set_node_gauss(pclean_ctx* ctx, int32_t block_id, int32_t node_id, const pclean_gauss* g) {
+static int check_node_gauss(pclean_ctx* ctx, int32_t block_id, int32_t node_id, const pclean_gauss* g, const char* who) {
   if (!ctx || block_id < 0 || block_id >= PCLEAN_MAX_BLOCKS || !ctx->block[block_id].valid || !g)
-    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_node_gauss: bad arguments");
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "%s: bad arguments", who);
   Block& b = ctx->block[block_id];
   if (node_id < 0 || node_id >= (int)b.nodes.size() || g->n_dims < 0 || g->n_dims > 4 || g->n_locals < 0 ||
       g->n_locals > 2 || g->mean_table < 0 || g->mean_table >= PCLEAN_MAX_TABLES)
-    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_node_gauss: malformed spec");
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "%s: malformed spec", who);
   int combos = 1;
   for (int l = 0; l < g->n_locals; ++l) combos *= g->local_n[l];
   if (combos > 16 || (g->n_locals == 2 && g->local_n[1] > 16))
-    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "pclean_set_node_gauss: more than 16 local combinations");
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "%s: more than 16 local combinations", who);
   if (b.node_gauss.size() != b.nodes.size()) b.node_gauss.assign(b.nodes.size(), -1);
+  if (b.node_gauss_more.size() != b.nodes.size()) b.node_gauss_more.assign(b.nodes.size(), {});
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_set_node_gauss(pclean_ctx* ctx, int32_t block_id, int32_t node_id, const pclean_gauss* g) {
+  int rc = check_node_gauss(ctx, block_id, node_id, g, "pclean_set_node_gauss");
+  if (rc) return rc;
+  Block& b = ctx->block[block_id];
   b.node_gauss[node_id] = (int32_t)b.gauss.size();
+  b.node_gauss_more[node_id].clear();  // (terms the node had stay in b.gauss, unreferenced, until the next pclean_load_block)
+  b.gauss.push_back(*g);
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_add_node_gauss(pclean_ctx* ctx, int32_t block_id, int32_t node_id, const pclean_gauss* g) {
+  int rc = check_node_gauss(ctx, block_id, node_id, g, "pclean_add_node_gauss");
+  if (rc) return rc;
+  Block& b = ctx->block[block_id];
+  if (b.node_gauss[node_id] < 0)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_add_node_gauss: node %d has no Gaussian term yet (pclean_set_node_gauss)", node_id);
+  const pclean_gauss& f = b.gauss[b.node_gauss[node_id]];
+  bool same = g->n_locals == f.n_locals && g->fixed_locals == f.fixed_locals;
+  for (int l = 0; l < f.n_locals && same; ++l) same = g->local_n[l] == f.local_n[l] && g->local_obs_col[l] == f.local_obs_col[l];
+  if (!same)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_add_node_gauss: the terms of a node share its own choices (n_locals, local_n, "
+                                            "local_obs_col, fixed_locals must equal the first term's)");
+  if ((int)b.node_gauss_more[node_id].size() + 1 >= PCLEAN_MAX_GAUSS)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "pclean_add_node_gauss: more than %d Gaussian terms on node %d", PCLEAN_MAX_GAUSS, node_id);
+  b.node_gauss_more[node_id].push_back((int32_t)b.gauss.size());
   b.gauss.push_back(*g);
   return PCLEAN_OK;
 }
@@ -812,6 +840,7 @@ extern "C" int pclean_load_block(pclean_ctx* ctx, int32_t block_id, int32_t n_no
     }
   b.gauss.clear();
   b.node_gauss.assign(n_nodes, -1);
+  b.node_gauss_more.assign(n_nodes, {});
   b.group = -1;
   b.version = ++g_pclean_version;
   b.valid = true;

@@ -168,7 +168,8 @@ struct Block {
   std::vector<ScoreTerm> score_terms;
   int32_t prob_fn = -1, prob_a_block = -1, prob_a_col = -1, prob_b_block = -1, prob_b_col = -1;
   std::vector<pclean_gauss> gauss;   // Gaussian terms of this block's nodes
-  std::vector<int32_t> node_gauss;   // per node: index into gauss, -1 none
+  std::vector<int32_t> node_gauss;   // per node: index into gauss of its first term, -1 none
+  std::vector<std::vector<int32_t>> node_gauss_more;  // per node: its further terms (pclean_add_node_gauss), in order
   std::vector<pclean_node> nodes;
   std::vector<pclean_term> terms;
   std::vector<int32_t> children;

@@ -36,8 +36,9 @@ struct GaussDev {
 };
 
 struct NodeDev {
-  int32_t kind, n_cand, n_terms, pad;
+  int32_t kind, n_cand, n_terms, n_gmore;  // n_gmore: further Gaussian terms of the node (pclean_add_node_gauss)
   GaussDev g;
+  const GaussDev* gmore;  // [n_gmore] device array, in declaration order behind g (eval.hip: build_gauss_more); null: none
   const int64_t* counts;
   const double* logc_full;
   const double* logc_m1;

@@ -92,14 +92,11 @@ __device__ __forceinline__ ItemView item_view(const NodeDev& nd, const ItemsDev&
 // fp64 operation order — prior, then terms in plan order — is identical)
 // Gaussian term of candidate k for observed row `row` (evctx = ctx of the evidence row, may be null)
 __device__ __forceinline__ double gauss_term(const NodeDev& nd, const ItemView& v, int k, int row, const int32_t* evctx) {
-  const GaussDev& g = nd.g;
-  const double xv = g.x[row];
-  if (xv != xv) return 0.0;  // missing numeric observation
   double sc[16];
   int codes[16];
   const int n = gauss_combo_scores(
-      g, row, evctx,
-      [&](int d) -> int {
+      nd.g, nd.gmore, nd.n_gmore, row, evctx,
+      [&](const GaussDev& g, int d) -> int {
         switch (g.src_kind[d]) {
           case PCLEAN_GSRC_CAND: return g.src_ptr[d][k];
           case PCLEAN_GSRC_OBS: return g.src_ptr[d][row];
@@ -108,6 +105,7 @@ __device__ __forceinline__ double gauss_term(const NodeDev& nd, const ItemView& 
         }
       },
       sc, codes);
+  if (n == 0) return 0.0;  // every numeric observation of the row is missing
   return gauss_lse(sc, n);
 }
 

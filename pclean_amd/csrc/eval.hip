@@ -55,6 +55,43 @@ int build_gauss_dev(pclean_ctx* ctx, const pclean_gauss& g, const CandTable* t, 
   return PCLEAN_OK;
 }
 
+// the further Gaussian terms of a node travel as a kernel argument (taken at the launch: the host copy may go at once, and
+// nothing waits) and are written to the call's scratch word by word
+struct GaussMoreArg {
+  GaussDev g[PCLEAN_MAX_GAUSS - 1];
+};
+static_assert(sizeof(GaussMoreArg) % 4 == 0 && sizeof(GaussMoreArg) <= 1024, "GaussMoreArg: one block of 256 words");
+__global__ __launch_bounds__(256) void gauss_more_store_kernel(GaussMoreArg a, int n_words, uint32_t* __restrict__ dst) {
+  const int i = threadIdx.x;
+  if (i < n_words) dst[i] = reinterpret_cast<const uint32_t*>(&a)[i];
+}
+
+// The further Gaussian terms of node `node_id` (pclean_add_node_gauss) resolved to device pointers, as a device array in
+// declaration order; *n_more = 0 when the node has one term or none.  The array lies in the call's scratch (never handed
+// out twice within a call) and is written on ctx->stream, so it is valid for every kernel the caller launches on that
+// stream afterwards, and for those only: nothing is kept between calls, nothing is ever freed under a kernel.
+int build_gauss_more(pclean_ctx* ctx, const Block& b, int node_id, const CandTable* t, const GaussDev** more, int* n_more) {
+  *more = nullptr;
+  *n_more = 0;
+  if (node_id >= (int)b.node_gauss_more.size() || b.node_gauss_more[node_id].empty()) return PCLEAN_OK;
+  const std::vector<int32_t>& ids = b.node_gauss_more[node_id];
+  if ((int)ids.size() > PCLEAN_MAX_GAUSS - 1) return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "too many Gaussian terms on one node");
+  GaussMoreArg a;
+  memset(&a, 0, sizeof a);
+  for (size_t i = 0; i < ids.size(); ++i) {
+    int rc = build_gauss_dev(ctx, b.gauss[ids[i]], t, a.g[i]);
+    if (rc) return rc;
+  }
+  GaussDev* d = scratch<GaussDev>(ctx, ids.size());
+  if (!d) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(gauss_more_store_kernel, dim3(1), dim3(256), 0, ctx->stream, a, (int)(ids.size() * sizeof(GaussDev) / 4),
+                     (uint32_t*)d);
+  HIPCHK(ctx, hipGetLastError());
+  *more = d;
+  *n_more = (int)ids.size();
+  return PCLEAN_OK;
+}
+
 int build_node_dev(pclean_ctx* ctx, const Block& b, int node_id, NodeDev& nd) {
   const pclean_node& n = b.nodes[node_id];
   const CandTable& t = ctx->cand[n.table];
@@ -70,8 +107,12 @@ int build_node_dev(pclean_ctx* ctx, const Block& b, int node_id, NodeDev& nd) {
   nd.logc_m1 = t.logc_m1.p;
   memcpy(nd.scal, t.scal, sizeof nd.scal);
   memset(&nd.g, 0, sizeof nd.g);
+  nd.n_gmore = 0;
+  nd.gmore = nullptr;
   if (node_id < (int)b.node_gauss.size() && b.node_gauss[node_id] >= 0) {
     int rc = build_gauss_dev(ctx, b.gauss[b.node_gauss[node_id]], &t, nd.g);
+    // (prior mode drops the node's Gaussian part below: the first term is still checked, the further ones are not written)
+    if (!rc && !ctx->prior_mode) rc = build_gauss_more(ctx, b, node_id, &t, &nd.gmore, &nd.n_gmore);
     if (rc) return rc;
   }
   if (ctx->prior_mode) {  // prior proposals: candidates are drawn from the prior alone (block_proposal.jl:42-56, 68-84)

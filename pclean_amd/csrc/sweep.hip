@@ -783,7 +783,8 @@ __global__ __launch_bounds__(256) void tail_scatter_kernel(int n_rows, int nb, T
 // choice is scored (62-64), the retained particle keeps the row's current ones (cur_locals), and the observed number is
 // scored given the particle's referent and own choices.  One thread per (particle, row) slot; the oracle restates the order
 // of the additions (oracle/sweep.h: gauss_prior_term): observed choices' densities, Normal log-density, - log |derivative|.
-__global__ void gauss_prior_kernel(int n_rows, int P, GaussDev g, PlanDev plan, const int32_t* __restrict__ pchoice,
+__global__ void gauss_prior_kernel(int n_rows, int P, GaussDev g0, const GaussDev* __restrict__ more, int n_more, PlanDev plan,
+                                   const int32_t* __restrict__ pchoice,
                                    const int32_t* __restrict__ pnewpos, const int32_t* __restrict__ vals, int n_nodes,
                                    const int32_t* __restrict__ cur_b, const int32_t* __restrict__ cur_locals, uint64_t seed,
                                    uint32_t sweep, uint32_t block, int64_t row_offset, double* __restrict__ w,
@@ -797,37 +798,40 @@ __global__ void gauss_prior_kernel(int n_rows, int P, GaussDev g, PlanDev plan, 
   const uint32_t rr = (uint32_t)((int64_t)i + row_offset);
   int l[2] = {0, 0}, out[2] = {-1, -1};
   double s = 0.0;
-  for (int k = 0; k < g.n_locals; ++k) {
-    const int o = g.local_obs[k] ? g.local_obs[k][i] : -1;
+  for (int k = 0; k < g0.n_locals; ++k) {  // (the own choices are the block's: every term carries the same ones)
+    const int o = g0.local_obs[k] ? g0.local_obs[k][i] : -1;
     if (o >= 0) {
       l[k] = o;
-      s += g.local_logp[k];
+      s += g0.local_logp[k];
     } else if (keep && cur_locals[2 * (size_t)i + k] >= 0) {
       l[k] = cur_locals[2 * (size_t)i + k];
     } else {
       l[k] = (int)pclean_mulhi64(pclean_rand64(seed, rr, PCLEAN_SITE_LOCALS(block), (uint32_t)p | ((uint32_t)(k + 1) << 16), sweep),
-                                 (uint64_t)g.local_n[k]);
+                                 (uint64_t)g0.local_n[k]);
     }
     out[k] = l[k];
   }
   plocals[2 * slot] = out[0];
   plocals[2 * slot + 1] = out[1];
-  const double xv = g.x[i];
-  if (xv == xv) {
-    int idx = 0;
-    for (int d = 0; d < g.n_dims; ++d) {
-      int val;
-      if (g.src_kind[d] == PCLEAN_GSRC_LOCAL)
-        val = l[g.src_slot[d]];
-      else if (g.src_kind[d] == PCLEAN_GSRC_CAND)
-        val = choice >= 0 ? g.src_ptr[d][choice] : resolve_new_value(plan, 0, g.src_slot[d], v);
-      else
-        val = g.src_ptr[d][i];  // PCLEAN_GSRC_OBS
-      idx += g.stride[d] * val;
+  for (int t = 0; t <= n_more; ++t) {  // the terms in declaration order, a missing number skipped
+    const GaussDev& g = t == 0 ? g0 : more[t - 1];
+    const double xv = g.x[i];
+    if (xv == xv) {
+      int idx = 0;
+      for (int d = 0; d < g.n_dims; ++d) {
+        int val;
+        if (g.src_kind[d] == PCLEAN_GSRC_LOCAL)
+          val = l[g.src_slot[d]];
+        else if (g.src_kind[d] == PCLEAN_GSRC_CAND)
+          val = choice >= 0 ? g.src_ptr[d][choice] : resolve_new_value(plan, 0, g.src_slot[d], v);
+        else
+          val = g.src_ptr[d][i];  // PCLEAN_GSRC_OBS
+        idx += g.stride[d] * val;
+      }
+      const int u = g.t_kind == PCLEAN_GSRC_LOCAL ? l[g.t_src] : 0;
+      s += gauss_normal_logpdf(g.tx[u] ? g.tx[u][i] : xv * g.t_scale[u], g.mu[idx], g.sigma, g.log_sigma);
+      s -= g.tl[u] ? g.tl[u][i] : g.t_lad[u];
     }
-    const int u = g.t_kind == PCLEAN_GSRC_LOCAL ? l[g.t_src] : 0;
-    s += gauss_normal_logpdf(g.tx[u] ? g.tx[u][i] : xv * g.t_scale[u], g.mu[idx], g.sigma, g.log_sigma);
-    s -= g.tl[u] ? g.tl[u][i] : g.t_lad[u];
   }
   w[slot] += s;
 }
@@ -841,7 +845,8 @@ __global__ void locals_pick_kernel(int n_rows, const int32_t* __restrict__ chose
   locals[2 * i + 1] = plocals[2 * slot + 1];
 }
 
-__global__ void locals_tail_kernel(int n_rows, int P, GaussDev g, PlanDev plan, const int32_t* chosen,
+__global__ void locals_tail_kernel(int n_rows, int P, GaussDev g, const GaussDev* __restrict__ more, int n_more, PlanDev plan,
+                                   const int32_t* chosen,
                                    const int32_t* pchoice, const int32_t* pnewpos, const int32_t* vals, int n_nodes,
                                    uint64_t seed, uint32_t sweep, uint32_t block, int64_t row_offset, int32_t* locals) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -851,20 +856,17 @@ __global__ void locals_tail_kernel(int n_rows, int P, GaussDev g, PlanDev plan, 
   const int choice = pchoice[slot];
   const int32_t* v = choice >= 0 ? nullptr : vals + (size_t)pnewpos[slot] * n_nodes;
   locals[2 * i] = locals[2 * i + 1] = -1;
-  const double xv = g.x[i];
   double sc[16];
   int codes[16];
-  int n = 0;
-  if (xv == xv)
-    n = gauss_combo_scores(
-        g, i, nullptr,
-        [&](int d) -> int {
-          if (g.src_kind[d] == PCLEAN_GSRC_CAND)
-            return choice >= 0 ? g.src_ptr[d][choice] : resolve_new_value(plan, 0, g.src_slot[d], v);
-          return g.src_ptr[d][i];  // PCLEAN_GSRC_OBS
-        },
-        sc, codes);
-  else {  // no numeric evidence: the locals follow their (uniform) priors, observed ones stay fixed
+  int n = gauss_combo_scores(
+      g, more, n_more, i, nullptr,
+      [&](const GaussDev& gt, int d) -> int {
+        if (gt.src_kind[d] == PCLEAN_GSRC_CAND)
+          return choice >= 0 ? gt.src_ptr[d][choice] : resolve_new_value(plan, 0, gt.src_slot[d], v);
+        return gt.src_ptr[d][i];  // PCLEAN_GSRC_OBS
+      },
+      sc, codes);
+  if (n == 0) {  // no numeric evidence: the locals follow their (uniform) priors, observed ones stay fixed
     for (int l0 = 0; l0 < g.local_n[0]; ++l0)
       for (int l1 = 0; l1 < g.local_n[1]; ++l1) {
         const bool ok0 = !g.local_obs[0] || g.local_obs[0][i] < 0 || g.local_obs[0][i] == l0;
@@ -1563,15 +1565,18 @@ int prior_mode_supported(pclean_ctx* ctx, const Block& b, const char* who) {
   const bool root_g = !b.node_gauss.empty() && b.node_gauss[0] >= 0;
   for (size_t i = 0; i < b.node_gauss.size() && ok; ++i) {
     if (b.node_gauss[i] < 0) continue;
-    const pclean_gauss& g = b.gauss[b.node_gauss[i]];
-    if (i != 0) {
-      ok = !(g.n_locals > 0 && !root_g);
-      continue;
+    const size_t n_more = i < b.node_gauss_more.size() ? b.node_gauss_more[i].size() : 0;
+    for (size_t t = 0; t <= n_more && ok; ++t) {  // every term of the node
+      const pclean_gauss& g = b.gauss[t == 0 ? b.node_gauss[i] : b.node_gauss_more[i][t - 1]];
+      if (i != 0) {
+        ok = !(g.n_locals > 0 && !root_g);
+        continue;
+      }
+      bool plain = g.transform_src_kind != PCLEAN_GSRC_EVCTX;
+      for (int d = 0; d < g.n_dims; ++d)
+        plain = plain && (g.src_kind[d] == PCLEAN_GSRC_CAND || g.src_kind[d] == PCLEAN_GSRC_OBS || g.src_kind[d] == PCLEAN_GSRC_LOCAL);
+      ok = plain || g.n_locals == 0;
     }
-    bool plain = g.transform_src_kind != PCLEAN_GSRC_EVCTX;
-    for (int d = 0; d < g.n_dims; ++d)
-      plain = plain && (g.src_kind[d] == PCLEAN_GSRC_CAND || g.src_kind[d] == PCLEAN_GSRC_OBS || g.src_kind[d] == PCLEAN_GSRC_LOCAL);
-    ok = plain || g.n_locals == 0;
   }
   if (!ok)
     return pclean_fail(ctx, PCLEAN_ERR_ARG, "%s: use_dd_proposals = false (prior proposals, block_proposal.jl:168) is implemented "
@@ -1899,12 +1904,15 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
       if (b.node_gauss.empty() || b.node_gauss[0] < 0) return PCLEAN_OK;
       GaussDev gd;
       const CandTable& rt = ctx->cand[b.nodes[0].table];
+      const GaussDev* gmore;
+      int n_gmore;
       int rcg = build_gauss_dev(ctx, b.gauss[b.node_gauss[0]], &rt, gd);
+      if (!rcg) rcg = build_gauss_more(ctx, b, 0, &rt, &gmore, &n_gmore);
       if (rcg) return rcg;
       if (r.plocals.alloc((size_t)NP * 2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
       const int32_t* cl = (b.cur_locals.p && b.cur_locals_rows == ctx->n_rows) ? b.cur_locals.p + (size_t)ctx->active_begin * 2 : nullptr;
-      hipLaunchKernelGGL(gauss_prior_kernel, grid1(NP), dim3(256), 0, ctx->stream, N, P, gd, r.plan, r.pchoice.p, r.pnewpos.p,
-                         r.vals.p, (int)b.nodes.size(), cur_b, cl, seed, sweep_idx, (uint32_t)bi,
+      hipLaunchKernelGGL(gauss_prior_kernel, grid1(NP), dim3(256), 0, ctx->stream, N, P, gd, gmore, n_gmore, r.plan, r.pchoice.p,
+                         r.pnewpos.p, r.vals.p, (int)b.nodes.size(), cur_b, cl, seed, sweep_idx, (uint32_t)bi,
                          s->row_offset + ctx->active_begin, s->w.p, r.plocals.p);
       r.plocals_on = true;
       return PCLEAN_OK;
@@ -2297,16 +2305,20 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
       if (choice)
         HIPCHK(ctx, hipMemcpyAsync(choice + (size_t)bi * N, r.choice.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
       if (!bb.node_gauss.empty() && bb.node_gauss[0] >= 0 && bb.gauss[bb.node_gauss[0]].n_locals > 0) {
-        GaussDev gd;
-        int rc = build_gauss_dev(ctx, bb.gauss[bb.node_gauss[0]], &rt, gd);
-        if (rc) return rc;
         if (r.locals.alloc((size_t)N * 2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-        if (r.plocals_on)  // prior proposals: what the chosen particle sampled (or kept)
+        if (r.plocals_on) {  // prior proposals: what the chosen particle sampled (or kept)
           hipLaunchKernelGGL(locals_pick_kernel, grid1(N), dim3(256), 0, ctx->stream, N, s->chosen.p, r.plocals.p, r.locals.p);
-        else
-          hipLaunchKernelGGL(locals_tail_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, gd, r.plan, s->chosen.p,
+        } else {
+          GaussDev gd;
+          const GaussDev* gmore;
+          int n_gmore;
+          int rc = build_gauss_dev(ctx, bb.gauss[bb.node_gauss[0]], &rt, gd);
+          if (!rc) rc = build_gauss_more(ctx, bb, 0, &rt, &gmore, &n_gmore);
+          if (rc) return rc;
+          hipLaunchKernelGGL(locals_tail_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, gd, gmore, n_gmore, r.plan, s->chosen.p,
                              r.pchoice.p, r.pnewpos.p, r.vals.p, (int)bb.nodes.size(), seed, sweep_idx, (uint32_t)bi,
                              s->row_offset + ctx->active_begin, r.locals.p);
+        }
         r.locals_rows = N;
         if (!defer) {  // (deferred outputs: pclean_get_locals copies them when asked)
           bb.locals_host.resize((size_t)N * 2);

@@ -293,6 +293,7 @@ int prior_mode_supported(pclean_ctx* ctx, const Block& b, const char* who);
 int upload_plan_nodes(pclean_ctx* ctx, int bi, const NodeDev** nds, const int32_t** n_children,
                              const int32_t** child_begin, const int32_t** children);
 int build_gauss_dev(pclean_ctx* ctx, const pclean_gauss& g, const CandTable* t, GaussDev& d);
+int build_gauss_more(pclean_ctx* ctx, const Block& b, int node_id, const CandTable* t, const GaussDev** more, int* n_more);
 int build_node_dev(pclean_ctx* ctx, const Block& b, int node_id, NodeDev& nd);
 int ensure_leaf_cache(pclean_ctx* ctx, int block_id, int node_id, const double** out, const int32_t** obs_col,
                              int* n_obs);

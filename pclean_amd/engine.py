@@ -16,8 +16,11 @@ from .model import ChooseProportionally, ChooseUniformly, StringPrior, TimePrior
 _TIME_RE = re.compile(r"^[0-9]?[0-9]:[0-9][0-9] [ap]\.m\.$")
 
 
-def make_gauss(spec, mean_table_id=0):
-    """pclean_gauss from a lowered Gaussian spec (model.LoweredModel.gauss)."""
+def make_gauss(spec, mean_table_id=None):
+    """pclean_gauss from a lowered Gaussian spec (model.LoweredModel.gauss / gauss_more); the block's g-th Gaussian
+    observation reads mean table g."""
+    if mean_table_id is None:
+        mean_table_id = spec.get("mean_table", 0)
     g = _lib.Gauss()
     g.x_col, g.mean_table, g.n_dims = spec["x_col"], mean_table_id, len(spec["kinds"])
     for i, (kind, payload) in enumerate(spec["kinds"]):
@@ -134,6 +137,8 @@ class Engine:
         lw, hip = self.lw, self.hip
         for (bid, nid), spec in getattr(lw, "gauss", {}).items():
             hip.set_node_gauss(bid, nid, make_gauss(spec))
+            for more in getattr(lw, "gauss_more", {}).get((bid, nid), ()):
+                hip.add_node_gauss(bid, nid, make_gauss(more))
 
     def _upload_static(self):
         lw, hip = self.lw, self.hip
@@ -295,10 +300,11 @@ class Engine:
                 hip.set_prob_table(pt)
                 last["prob"] = pt.copy()
         if getattr(lw, "gauss", None):
-            mv = trace.mean_param.value
-            if last.get("mean") is None or not np.array_equal(last["mean"], mv):
-                hip.set_mean_table(0, mv)
-                last["mean"] = mv.copy()
+            for g, mp in enumerate(trace.mean_params):  # term g reads mean table g
+                mv, key = mp.value, "mean" if g == 0 else ("mean", g)
+                if last.get(key) is None or not np.array_equal(last[key], mv):
+                    hip.set_mean_table(g, mv)
+                    last[key] = mv.copy()
             if self._gauss_pending:  # needs the mean table to exist
                 self._upload_gauss()
                 self._gauss_pending = False

@@ -297,7 +297,9 @@ class LoweredModel:
         self.eq_pairs = {}
         self.same_pairs = {}   # pair id -> (observed domain, latent domain): 0 iff same string
         self.prob_spec = None
-        self.gauss = {}        # (block id, node id) -> dict spec (resolved by the engine)
+        self.gauss = {}        # (block id, node id) -> dict spec (resolved by the engine): the node's first Gaussian term
+        self.gauss_more = {}   # (block id, node id) -> [dict spec, ...]: its further terms, in declaration order
+        self.gauss_specs = []  # the block's Gaussian observations in declaration order (gauss_spec is gauss_specs[0])
         self.locals = {}       # block index -> [own ChooseUniformly attrs enumerated with the Gaussian]
         self.latent_ev_locals = {}  # latent class -> block index whose locals feed the evidence ctx
         self.latent_ev_prob = {}    # latent class -> scoring block whose error-prob index feeds the evidence ctx
@@ -369,11 +371,11 @@ class LoweredModel:
         self._never_missing = {dirty for col, dirty in self.query.obsmap.items()
                                if all(v is not None for v in dirty_columns[col])}
 
-    def gauss_backward(self, rows, unit_idx):
-        """unit.backward(x) of the Gaussian observation of `rows` under the Transformation options unit_idx (one per row):
-        x * c for the linear ones, the derived column for the others (transformed_gaussian.jl:16, 27-34); AddNoise: x * 1.0
-        (its one option, 0)."""
-        spec = self.gauss_spec
+    def gauss_backward(self, rows, unit_idx, g=0):
+        """unit.backward(x) of the g-th Gaussian observation of `rows` under the Transformation options unit_idx (one per
+        row): x * c for the linear ones, the derived column for the others (transformed_gaussian.jl:16, 27-34); AddNoise:
+        x * 1.0 (its one option, 0)."""
+        spec = self.gauss_specs[g]
         rows = np.asarray(rows)
         unit_idx = np.asarray(unit_idx)
         x = self.xnum[spec["x_col"], rows] * np.asarray(spec["t_scale"])[unit_idx]
@@ -785,19 +787,96 @@ class LoweredModel:
     def _lower_gaussian(self, bi, blk, ocls, names, root_fk):
         """`x ~ TransformedGaussian(param[f(root values, own choices)], std, unit)` with own
         ChooseUniformly choices (experiments/rents/run.jl:19-25), or `x ~ AddNoise(param[..], std)`
-        (add_noise.jl:7: no Transformation, no unit choice) -> pclean_gauss specs."""
+        (add_noise.jl:7: no Transformation, no unit choice) -> pclean_gauss specs.  A block may hold up to
+        PCLEAN_MAX_GAUSS such observations: each reads its own IndexedMeanParameter, all share the block's own
+        choices, which are enumerated once (proposal_compiler.jl:55-129 adds every observed choice's logdensity
+        inside the enumeration of the block's own choices)."""
         m = self.model
         ga = [ocls.attr(n) for n in names
               if ocls.attr(n).kind == "choice" and isinstance(ocls.attr(n).dist, (TransformedGaussian, AddNoise))]
         if not ga:
             return
-        if len(ga) > 1:
-            raise NotImplementedError("one Gaussian observation per block (so far)")
-        g = ga[0]
+        if len(ga) > _lib.MAX_GAUSS:
+            raise NotImplementedError(f"{ga[_lib.MAX_GAUSS].name}: more than {_lib.MAX_GAUSS} Gaussian observations in one "
+                                      "block (PCLEAN_MAX_GAUSS)")
+        looks, seen = [], {}
+        for g in ga:
+            look = ocls.attr(g.dist.mean)
+            if look.kind != "julia" or not isinstance(look.fn, IndexedLookup):
+                raise NotImplementedError(f"{type(g.dist).__name__} mean must be an IndexedLookup")
+            if look.fn.param in seen:
+                # (each term resamples its own parameter from its own rows: a shared one would need joint statistics)
+                raise NotImplementedError(f"{g.name}: only one Gaussian observation per block may read the mean parameter "
+                                          f"{look.fn.param} ({seen[look.fn.param]} already does)")
+            seen[look.fn.param] = g.name
+            looks.append(look)
+        # own enumerated choices, shared by the terms: index arguments that are own attrs, plus the units, in the order
+        # the terms name them (a choice that only some terms index is still enumerated once)
+        locs = []
+        for g, look in zip(ga, looks):
+            for arg in look.args:
+                if "." not in arg:
+                    if not isinstance(ocls.attr(arg).dist, ChooseUniformly):
+                        raise NotImplementedError("own index arguments must be ChooseUniformly choices")
+                    if arg not in locs:
+                        locs.append(arg)
+            if not isinstance(g.dist, AddNoise) and g.dist.unit not in locs:
+                locs.append(g.dist.unit)
+        if len(locs) > 2:
+            raise NotImplementedError("at most two enumerated own choices")
+        if int(np.prod([len(ocls.attr(l).dist.options) for l in locs])) > 16:
+            raise NotImplementedError("at most 16 combinations of the enumerated own choices (gauss_combo_scores: sc[16])")
+        if locs:  # (an AddNoise whose mean is indexed by candidate-side values alone enumerates nothing: one combination)
+            self.locals[bi] = locs
+        self.gauss_block = bi
+        self.num_derived = []
+        self.gauss_specs = []
+        open_leaf = None
+        for gi, (g, look) in enumerate(zip(ga, looks)):
+            spec, dims, transform = self._gaussian_term(gi, g, look, ocls, root_fk, locs)
+            self.gauss_specs.append(spec)
+            # (a) block root: candidate-side index values come from the candidate's columns
+            rc = root_fk.target
+            self._add_gauss(bi, 0, dict(spec, kinds=[("cand", self.colidx[rc][d[1]]) if d[0] == "cand" else ("local", d[1])
+                                                    for d in dims], n_locals=len(locs), transform=transform))
+            # (b) new-row branch: the leaf of the one candidate-side value that is not always observed
+            #     carries the term; the others are read from their direct observations
+            open_dims = [d for d in dims if d[0] == "cand" and not self._always_observed(root_fk.name + "." + d[1])]
+            if len(open_dims) != 1:
+                raise NotImplementedError(f"{g.name}: exactly one candidate-side index value may be unobserved")
+            if open_leaf is not None and open_dims[0][1] != open_leaf:
+                raise NotImplementedError(f"{g.name}: the Gaussian observations of a block must leave the same candidate-side "
+                                          f"index value unobserved ({open_leaf}, not {open_dims[0][1]})")
+            open_leaf = open_dims[0][1]
+            for nid, info in enumerate(blk["node_info"]):
+                if info["kind"] == "leaf" and info["path"] == open_dims[0][1]:
+                    kinds = []
+                    for d in dims:
+                        if d[0] == "local":
+                            kinds.append(("local", d[1]))
+                        elif d is open_dims[0]:
+                            kinds.append(("cand", 0))
+                        else:
+                            kinds.append(("obs", self.obs_index[root_fk.name + "." + d[1]]))
+                    self._add_gauss(bi, nid, dict(spec, kinds=kinds, n_locals=len(locs), transform=transform))
+                    node = list(blk["nodes"][nid])
+                    node[8] = 0  # not cacheable any more
+                    blk["nodes"][nid] = tuple(node)
+                    if gi == 0:
+                        self.gauss_open = (bi, open_dims[0])
+        self.gauss_spec = self.gauss_specs[0]
+
+    def _add_gauss(self, bid, nid, term):
+        """the node's first term goes to self.gauss, further ones (declaration order) to self.gauss_more"""
+        if (bid, nid) not in self.gauss:
+            self.gauss[(bid, nid)] = term
+        else:
+            self.gauss_more.setdefault((bid, nid), []).append(term)
+
+    def _gaussian_term(self, gi, g, look, ocls, root_fk, locs):
+        """(spec, index dimensions, transform source) of the block's gi-th Gaussian observation `g`; its mean table id is gi"""
+        m = self.model
         add_noise = isinstance(g.dist, AddNoise)
-        look = ocls.attr(g.dist.mean)
-        if look.kind != "julia" or not isinstance(look.fn, IndexedLookup):
-            raise NotImplementedError(f"{type(g.dist).__name__} mean must be an IndexedLookup")
         if add_noise:
             # one fixed identity option: backward(x) = x * 1.0, log|deriv| = 0.0; no choice picks it (transform
             # source "none": the kernels and the oracle take option 0), so the score is logpdf(Normal(mean, std), x)
@@ -822,7 +901,6 @@ class LoweredModel:
             except (ValueError, ZeroDivisionError, OverflowError, FloatingPointError):
                 lin = False  # (a probe outside the function's domain: log of a negative number ...)
             t_linear.append(bool(lin))
-        locs = []  # own enumerated choices: index arguments that are own attrs, plus the unit
         dims = []  # (kind, payload, n_values)
         for arg in look.args:
             if "." in arg:
@@ -830,67 +908,28 @@ class LoweredModel:
                 cn, la = m.resolve(root_fk.target, rest)
                 dims.append(("cand", rest, len(self.latent_dom[(cn, la.name)]), (cn, la.name)))
             else:
-                oa = ocls.attr(arg)
-                if not isinstance(oa.dist, ChooseUniformly):
-                    raise NotImplementedError("own index arguments must be ChooseUniformly choices")
-                if arg not in locs:
-                    locs.append(arg)
-                dims.append(("local", locs.index(arg), len(oa.dist.options), None))
-        if not add_noise and g.dist.unit not in locs:
-            locs.append(g.dist.unit)
-        if len(locs) > 2:
-            raise NotImplementedError("at most two enumerated own choices")
-        if int(np.prod([len(ocls.attr(l).dist.options) for l in locs])) > 16:
-            raise NotImplementedError("at most 16 combinations of the enumerated own choices (gauss_combo_scores: sc[16])")
+                dims.append(("local", locs.index(arg), len(ocls.attr(arg).dist.options), None))
         strides, acc = [], 1
         for d in reversed(dims):
             strides.append(acc)
             acc *= d[2]
         strides = strides[::-1]
-        if locs:  # (an AddNoise whose mean is indexed by candidate-side values alone enumerates nothing: one combination)
-            self.locals[bi] = locs
-        self.gauss_block = bi
         spec = dict(x_col=self.numeric_obs[g.name], param=(self.query.cls, look.fn.param), n_mean=acc, dims=dims,
                     strides=strides, locals=locs, local_n=[len(ocls.attr(l).dist.options) for l in locs],
                     local_obs=[self.obs_index.get(l, -1) if l in self.direct_obs else -1 for l in locs],
                     t_local=None if add_noise else locs.index(g.dist.unit), sigma=g.dist.std, gauss_attr=g.name,
                     t_scale=[float(u.backward(1.0)) if lin else 1.0 for u, lin in zip(units, t_linear)],
                     t_lad=[float(np.log(abs(u.deriv(u.backward(1.0))))) if lin else 0.0 for u, lin in zip(units, t_linear)],
-                    units=units, t_linear=t_linear, t_x_col=[-1] * len(units), t_lad_col=[-1] * len(units))
-        # derived numeric columns of the non-linear units: appended behind the observed ones (encode_observations)
-        self.num_derived = []
+                    units=units, t_linear=t_linear, t_x_col=[-1] * len(units), t_lad_col=[-1] * len(units), mean_table=gi)
+        # derived numeric columns of the non-linear units: appended behind the observed ones, term by term
+        # (encode_observations)
         for ui, lin in enumerate(t_linear):
             if not lin:
                 spec["t_x_col"][ui] = len(self.num_cols) + len(self.num_derived)
                 self.num_derived.append((spec["x_col"], units[ui], "backward"))
                 spec["t_lad_col"][ui] = len(self.num_cols) + len(self.num_derived)
                 self.num_derived.append((spec["x_col"], units[ui], "logabsderiv"))
-        self.gauss_spec = spec
-        transform = ("none", -1) if add_noise else ("local", spec["t_local"])
-        # (a) block root: candidate-side index values come from the candidate's columns
-        rc = root_fk.target
-        self.gauss[(bi, 0)] = dict(spec, kinds=[("cand", self.colidx[rc][d[1]]) if d[0] == "cand" else ("local", d[1])
-                                                 for d in dims], n_locals=len(locs), transform=transform)
-        # (b) new-row branch: the leaf of the one candidate-side value that is not always observed
-        #     carries the term; the others are read from their direct observations
-        open_dims = [d for d in dims if d[0] == "cand" and not self._always_observed(root_fk.name + "." + d[1])]
-        if len(open_dims) != 1:
-            raise NotImplementedError("exactly one candidate-side index value may be unobserved")
-        for nid, info in enumerate(blk["node_info"]):
-            if info["kind"] == "leaf" and info["path"] == open_dims[0][1]:
-                kinds = []
-                for d in dims:
-                    if d[0] == "local":
-                        kinds.append(("local", d[1]))
-                    elif d is open_dims[0]:
-                        kinds.append(("cand", 0))
-                    else:
-                        kinds.append(("obs", self.obs_index[root_fk.name + "." + d[1]]))
-                self.gauss[(bi, nid)] = dict(spec, kinds=kinds, n_locals=len(locs), transform=transform)
-                node = list(blk["nodes"][nid])
-                node[8] = 0  # not cacheable any more
-                blk["nodes"][nid] = tuple(node)
-                self.gauss_open = (bi, open_dims[0])
+        return spec, dims, ("none", -1) if add_noise else ("local", spec["t_local"])
 
     def _always_observed(self, obsname):
         return obsname in self.direct_obs and obsname in self._never_missing
@@ -967,14 +1006,15 @@ class LoweredModel:
         nt = len(plan["terms"]) - tb
         if (bi, nid) in self.gauss and info["kind"] == "leaf":
             # latent sweep of the class owning this value: external likelihood of the referring rows'
-            # Gaussian observations, their own choices held at their current values (evidence ctx)
-            src = self.gauss[(bi, nid)]
-            kinds = [("evctx", k[1]) if k[0] == "local" else k for k in src["kinds"]]
-            self.gauss[(plan["block_id"], new_id)] = dict(src, kinds=kinds, n_locals=0,
-                                                          transform=("none", -1) if src["t_local"] is None
-                                                          else ("evctx", src["t_local"]))
-            if src["locals"]:
-                self.latent_ev_locals[plan["cls"]] = bi
+            # Gaussian observations, their own choices held at their current values (evidence ctx: the slots of the
+            # block's own choices, the same for every term of the node)
+            for src in [self.gauss[(bi, nid)]] + self.gauss_more.get((bi, nid), []):
+                kinds = [("evctx", k[1]) if k[0] == "local" else k for k in src["kinds"]]
+                self._add_gauss(plan["block_id"], new_id, dict(src, kinds=kinds, n_locals=0,
+                                                               transform=("none", -1) if src["t_local"] is None
+                                                               else ("evctx", src["t_local"])))
+                if src["locals"]:
+                    self.latent_ev_locals[plan["cls"]] = bi
         kids = []
         if node[0] == _lib.NODE_FK:
             remap = {}

@@ -217,10 +217,13 @@ class Trace:
         if lowered.prob_spec is not None:
             pp = m.classes[lowered.prob_spec["param"][0]].attr(lowered.prob_spec["param"][1]).prior
             self.prob_param = ProbTableState(len(lowered.prob_spec["keys"]), pp.a, pp.b, self.rng)
-        spec = getattr(lowered, "gauss_spec", None)
-        if spec is not None:
+        # one mean parameter per Gaussian observation of the block, in declaration order (mean_param is mean_params[0])
+        self.mean_params = []
+        for spec in lowered.gauss_specs:
             prior = m.classes[spec["param"][0]].attr(spec["param"][1]).prior
-            self.mean_param = MeanTableState(spec["n_mean"], prior.mean, prior.std, spec["sigma"], self.rng)
+            self.mean_params.append(MeanTableState(spec["n_mean"], prior.mean, prior.std, spec["sigma"], self.rng))
+        if self.mean_params:
+            self.mean_param = self.mean_params[0]
 
     def on_relower(self):
         """The lowered model was rebuilt in place with larger latent domains (LoweredModel.relower): drop the plans
@@ -273,10 +276,11 @@ class Trace:
             self.locals[bi][begin:begin + n] = loc[:n]
         self.pending_locals = {}
 
-    def gaussian_index(self):
-        """(rows, mean-table index, backward-transformed x) of every assigned observed row."""
+    def gaussian_index(self, g=0):
+        """(rows, mean-table index, backward-transformed x) of every assigned observed row whose g-th Gaussian observation
+        is present."""
         lw = self.lw
-        spec = lw.gauss_spec
+        spec = lw.gauss_specs[g]
         bi = lw.gauss_block
         rows = np.nonzero((self.cur[bi] >= 0) & (self.locals[bi][:, 0] >= 0 if spec["locals"] else True))[0]
         root = lw.blocks[bi]["root_class"]
@@ -289,7 +293,7 @@ class Trace:
                 idx += st * self.locals[bi][rows, d[1]]
         unit = (np.zeros(len(rows), dtype=np.int32) if spec["t_local"] is None  # (AddNoise: the identity, option 0)
                 else self.locals[bi][rows, spec["t_local"]])
-        x = lw.gauss_backward(rows, unit)
+        x = lw.gauss_backward(rows, unit, g)
         ok = ~np.isnan(x)
         return rows[ok], idx[ok], x[ok]
 
@@ -622,8 +626,9 @@ class Trace:
         if self.prob_param is not None and (cname is None or self.lw.prob_spec["param"][0] == cname):
             self.resample_prob_param()
         if self.mean_param is not None and (cname is None or self.lw.gauss_spec["param"][0] == cname):
-            _, idx, x = self.gaussian_index()
-            self.mean_param.resample(self.rng, idx, x)
+            for g, mp in enumerate(self.mean_params):  # each parameter's conjugate draw from its own term's rows
+                _, idx, x = self.gaussian_index(g)
+                mp.resample(self.rng, idx, x)
 
     @staticmethod
     def _py_prepare(counts):
