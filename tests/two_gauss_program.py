@@ -133,9 +133,10 @@ def with_deposit(dirty, clean, seed=11, all_missing_=False):
     return dirty, clean
 
 
-def setup(model_fn, n_rows=600, seed=3, data=None):
+def setup(model_fn, n_rows=600, seed=3, data=None, query_fn=None):
     """model_fn(dirty) on the first n_rows rows of rents + Deposit, latent state from the clean values (the state of
-    tests/addnoise_program.py: setup).  data: (dirty, clean) to use instead."""
+    tests/addnoise_program.py: setup).  data: (dirty, clean) to use instead.  query_fn: the Query of a model with other
+    columns than this module's (default: query)."""
     if data is None:
         dirty, clean = ex.rents_data()
         dirty = {c: v[:n_rows] for c, v in dirty.items()}
@@ -144,7 +145,7 @@ def setup(model_fn, n_rows=600, seed=3, data=None):
     else:
         dirty, clean = data
     m = model_fn(dirty)
-    q = query(m)
+    q = (query_fn or query)(m)
     lw = LoweredModel(m, q, dirty)
     obs = lw.encode_observations(dirty)
     n = obs.shape[1]
