@@ -42,6 +42,8 @@ CConfig(cfg::InferenceConfig) = CConfig(cfg.num_iters, cfg.num_particles, cfg.us
                                         cfg.use_mh_instead_of_pg, cfg.rejuv_frequency, cfg.reporting_frequency)
 const NODE_FK, NODE_LEAF = Int32(0), Int32(1)
 const DENS_ADD_TYPOS, DENS_EQUAL = Int32(0), Int32(1)
+const DENS_TABULATED = Int32(3)                                   # PCLEAN_DENS_TABULATED (this file's lowering emits none)
+const CLASS_SHORT_VERSION, CLASS_FORMAT_NAME = Int32(0), Int32(1)  # rules of build_class_table
 const CHOICE_NEW = Int32(-1)
 const MAX_CTX = 4
 
@@ -61,6 +63,22 @@ set_fn_table(c, id, fn::Matrix{Int32}) = GC.@preserve fn check(c,         # n_b 
     ccall((:pclean_set_fn_table, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Int32}), c.h, id, size(fn, 2), size(fn, 1), fn))
 set_lm_tables(c, init_p::Vector{Float64}, trans_p::Matrix{Float64}, letter_sym::Vector{UInt16}) = GC.@preserve init_p trans_p letter_sym check(c,
     ccall((:pclean_set_lm_tables, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt16}), c.h, init_p, trans_p, letter_sym))
+# tabulated likelihood terms (ExpandOnShortVersion, one-name FormatName): fold map over the pool's symbols, class table of a
+# (observed domain, latent domain) pair, number of options every latent string is a short version of, and the densities
+# T[class 0..2, missing][value] (4 x n_lat in Julia = T[value][4] in C)
+set_fold_table(c, fold::Vector{UInt16}) = GC.@preserve fold check(c,
+    ccall((:pclean_set_fold_table, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{UInt16}), c.h, length(fold), fold))
+build_class_table(c, id, obs_ids::Vector{Int32}, lat_ids::Vector{Int32}, rule, dot_symbol=0xFFFF) = GC.@preserve obs_ids lat_ids check(c,
+    ccall((:pclean_build_class_table, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Int32),
+          c.h, id, length(obs_ids), obs_ids, length(lat_ids), lat_ids, rule, dot_symbol))
+set_class_density(c, id, dens::Matrix{Float64}) = GC.@preserve dens check(c,
+    ccall((:pclean_set_class_density, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), c.h, id, size(dens, 2), dens))
+function count_short_versions(c, opt_ids::Vector{Int32}, lat_ids::Vector{Int32})
+    out = zeros(Int32, length(lat_ids))
+    GC.@preserve opt_ids lat_ids out check(c, ccall((:pclean_count_short_versions, lib), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}), c.h, length(opt_ids), opt_ids, length(lat_ids), lat_ids, out))
+    out
+end
 set_block_group(c, block, group) = check(c, ccall((:pclean_set_block_group, lib), Cint, (Ptr{Cvoid}, Int32, Int32), c.h, block, group))
 set_active_rows(c, first0, count) = check(c, ccall((:pclean_set_active_rows, lib), Cint, (Ptr{Cvoid}, Int32, Int32), c.h, first0, count))
 function load_block(c, id, nodes::Vector{CNode}, terms::Vector{CTerm}, children::Vector{Int32}, colmap::Vector{Int32},

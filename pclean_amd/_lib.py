@@ -17,7 +17,8 @@ MAX_GAUSS = 4  # PCLEAN_MAX_GAUSS
 EV_MAX_STEPS = 4  # PCLEAN_EV_MAX_STEPS
 CHOICE_NEW = -1
 DIST_OSA, DIST_DL = 0, 1
-DENS_ADD_TYPOS, DENS_EQUAL, DENS_MAYBE_SWAP = 0, 1, 2
+DENS_ADD_TYPOS, DENS_EQUAL, DENS_MAYBE_SWAP, DENS_TABULATED = 0, 1, 2, 3
+CLASS_SHORT_VERSION, CLASS_FORMAT_NAME = 0, 1
 NODE_FK, NODE_LEAF = 0, 1
 DUMMY_STRING_PRIOR, DUMMY_TIME_PRIOR = 1, 2
 
@@ -190,6 +191,35 @@ class HipContext:
         check(self.h, self.lib.pclean_set_pair_table(self.h, C.c_int32(table_id), C.c_int32(table.shape[0]),
                                                      C.c_int32(table.shape[1]), _p(table, C.c_uint8)),
               "pclean_set_pair_table")
+
+    # -- tabulated likelihood terms (DENS_TABULATED) ----------------------------
+    def set_fold_table(self, fold):
+        fold = np.ascontiguousarray(fold, dtype=np.uint16)
+        check(self.h, self.lib.pclean_set_fold_table(self.h, C.c_int32(len(fold)), _p(fold, C.c_uint16)),
+              "pclean_set_fold_table")
+
+    def build_class_table(self, table_id, obs_ids, lat_ids, rule, dot_symbol=0xFFFF):
+        obs_ids = np.ascontiguousarray(obs_ids, dtype=np.int32)
+        lat_ids = np.ascontiguousarray(lat_ids, dtype=np.int32)
+        check(self.h, self.lib.pclean_build_class_table(self.h, C.c_int32(table_id), C.c_int32(len(obs_ids)),
+                                                        _p(obs_ids, C.c_int32), C.c_int32(len(lat_ids)),
+                                                        _p(lat_ids, C.c_int32), C.c_int32(rule), C.c_int32(int(dot_symbol))),
+              "pclean_build_class_table")
+
+    def set_class_density(self, table_id, dens):
+        """dens: float64 [n_lat][4] = T[value][class 0..2, missing observation]"""
+        dens = np.ascontiguousarray(dens, dtype=np.float64).reshape(-1, 4)
+        check(self.h, self.lib.pclean_set_class_density(self.h, C.c_int32(table_id), C.c_int32(len(dens)),
+                                                        _p(dens, C.c_double)), "pclean_set_class_density")
+
+    def count_short_versions(self, opt_ids, lat_ids):
+        opt_ids = np.ascontiguousarray(opt_ids, dtype=np.int32)
+        lat_ids = np.ascontiguousarray(lat_ids, dtype=np.int32)
+        out = np.zeros(len(lat_ids), dtype=np.int32)
+        check(self.h, self.lib.pclean_count_short_versions(self.h, C.c_int32(len(opt_ids)), _p(opt_ids, C.c_int32),
+                                                           C.c_int32(len(lat_ids)), _p(lat_ids, C.c_int32),
+                                                           _p(out, C.c_int32)), "pclean_count_short_versions")
+        return out
 
     def get_pair_table(self, table_id, n_obs, n_lat):
         out = np.empty((n_obs, n_lat), dtype=np.uint16)

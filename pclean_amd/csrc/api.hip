@@ -53,7 +53,9 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
     p.d.release();
     p.lat_len.release();
     p.obs_ids.release();
+    p.cls.release();
   }
+  ctx->fold.release();
   ctx->lm_init.release();
   ctx->lm_trans.release();
   ctx->letter_sym.release();
@@ -206,6 +208,7 @@ extern "C" int pclean_build_pair_table(pclean_ctx* ctx, int32_t table_id, int32_
     sum_lb += len;
   }
   pt.mean_lat_len = (double)sum_lb / (double)n_lat;
+  pt.cls_valid = false;
   pt.n_obs = n_obs;
   pt.n_lat = n_lat;
   pt.max_obs_len = max_la;
@@ -231,6 +234,143 @@ extern "C" int pclean_build_pair_table(pclean_ctx* ctx, int32_t table_id, int32_
   return PCLEAN_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Tabulated likelihood terms (PCLEAN_DENS_TABULATED): case folding, class tables built on the device
+// (class_kernels.hip) and their class densities, evaluated once on the host like the AddTypos pieces above.
+extern "C" int pclean_set_fold_table(pclean_ctx* ctx, int32_t n_symbols, const uint16_t* fold) {
+  if (!ctx || n_symbols < 0 || n_symbols >= 0xfffe || (n_symbols > 0 && !fold))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_fold_table: bad arguments");
+  for (int s = 0; s < n_symbols; ++s)
+    if ((int)fold[s] > s || fold[fold[s]] != fold[s])
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_fold_table: fold[%d] = %d is not the smallest symbol of its class", s,
+                         (int)fold[s]);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->fold.alloc((size_t)std::max(n_symbols, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  if (n_symbols) HIPCHK(ctx, hipMemcpy(ctx->fold.p, fold, n_symbols * sizeof(uint16_t), hipMemcpyHostToDevice));
+  ctx->n_fold = n_symbols;
+  return PCLEAN_OK;
+}
+
+// pool string ids of a class-table call: in range; *max_len = the longest
+static int check_string_ids(pclean_ctx* ctx, int n, const int32_t* ids, const char* what, int* max_len) {
+  *max_len = 0;
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= ctx->n_strings) return pclean_fail(ctx, PCLEAN_ERR_ARG, "%s id out of range", what);
+    *max_len = std::max(*max_len, (int)(ctx->h_off[ids[i] + 1] - ctx->h_off[ids[i]]));
+  }
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_build_class_table(pclean_ctx* ctx, int32_t table_id, int32_t n_obs, const int32_t* obs_ids,
+                                        int32_t n_lat, const int32_t* lat_ids, int32_t rule, int32_t dot_symbol) {
+  if (!ctx || table_id < 0 || table_id >= PCLEAN_MAX_TABLES || n_obs < 0 || n_lat <= 0 || (n_obs > 0 && !obs_ids) || !lat_ids ||
+      (rule != PCLEAN_CLASS_SHORT_VERSION && rule != PCLEAN_CLASS_FORMAT_NAME))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_build_class_table: bad arguments");
+  if (ctx->n_strings == 0) return pclean_fail(ctx, PCLEAN_ERR_STATE, "load strings first");
+  if (ctx->n_fold < ctx->n_symbols)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_build_class_table: the fold table covers %d of the pool's %d symbols "
+                                              "(pclean_set_fold_table first)", ctx->n_fold, ctx->n_symbols);
+  if (dot_symbol != 0xFFFF && (dot_symbol < 0 || dot_symbol >= ctx->n_fold))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_build_class_table: dot_symbol out of range");
+  if (n_obs > 65535) return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "n_obs > 65535 not supported yet");
+  int max_la = 0, max_lb = 0;
+  int rc = check_string_ids(ctx, n_obs, obs_ids, "obs", &max_la);
+  if (!rc) rc = check_string_ids(ctx, n_lat, lat_ids, "lat", &max_lb);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = pclean_ensure_density(ctx, 64);
+  if (rc) return rc;
+  PairTable& pt = ctx->pair[table_id];
+  pt.valid = false;
+  pt.cls_valid = false;
+  pt.n_obs = n_obs;
+  pt.n_lat = n_lat;
+  pt.elem_bytes = 1;
+  pt.max_obs_len = max_la;
+  pt.max_lat_len = max_lb;
+  pt.mean_lat_len = 0.0;
+  pt.obs_ids.release();
+  DevBuf<int32_t> d_obs, d_lat;
+  if (pt.d.alloc(std::max<size_t>((size_t)n_obs * n_lat, 16)) || pt.lat_len.alloc(n_lat) || d_obs.alloc(std::max(n_obs, 1)) ||
+      d_lat.alloc(n_lat)) {
+    d_obs.release();
+    d_lat.release();
+    return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  }
+  hipError_t e = hipMemset(pt.lat_len.p, 0, n_lat * sizeof(uint16_t));
+  if (e == hipSuccess && n_obs) e = hipMemcpy(d_obs.p, obs_ids, n_obs * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_lat.p, lat_ids, n_lat * sizeof(int32_t), hipMemcpyHostToDevice);
+  rc = PCLEAN_OK;
+  if (e == hipSuccess) {
+    rc = pclean_launch_class_table(ctx, pt, d_obs.p, d_lat.p, rule, dot_symbol);
+    e = hipStreamSynchronize(ctx->stream);
+  }
+  d_obs.release();
+  d_lat.release();
+  if (rc) return rc;
+  if (e != hipSuccess) return pclean_fail(ctx, PCLEAN_ERR_HIP, "class table build failed: %s", hipGetErrorString(e));
+  pt.valid = true;
+  pt.version = ++g_pclean_version;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_set_class_density(pclean_ctx* ctx, int32_t table_id, int32_t n_lat, const double* dens) {
+  if (!ctx || table_id < 0 || table_id >= PCLEAN_MAX_TABLES || !dens)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_class_density: bad arguments");
+  PairTable& pt = ctx->pair[table_id];
+  if (!pt.valid) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_class_density: pair table %d is not valid", table_id);
+  if (n_lat != pt.n_lat)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_class_density: n_lat %d, pair table %d has %d latent values", n_lat,
+                       table_id, pt.n_lat);
+  for (size_t i = 0; i < (size_t)n_lat * 4; ++i)
+    if (!(dens[i] <= 0.0))  // (NaN fails the comparison too)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_class_density: entry [%lld][%d] = %g is not a log-probability <= 0",
+                         (long long)(i / 4), (int)(i % 4), dens[i]);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  (void)hipStreamSynchronize(ctx->stream);  // (no kernel reads the old values any more)
+  if (pt.cls.alloc((size_t)n_lat * 4)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemcpy(pt.cls.p, dens, (size_t)n_lat * 4 * sizeof(double), hipMemcpyHostToDevice));
+  pt.cls_valid = true;
+  pt.version = ++g_pclean_version;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_count_short_versions(pclean_ctx* ctx, int32_t n_opt, const int32_t* opt_ids, int32_t n_lat,
+                                           const int32_t* lat_ids, int32_t* out) {
+  if (!ctx || n_opt < 0 || n_lat <= 0 || (n_opt > 0 && !opt_ids) || !lat_ids || !out)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_count_short_versions: bad arguments");
+  if (ctx->n_strings == 0) return pclean_fail(ctx, PCLEAN_ERR_STATE, "load strings first");
+  if (ctx->n_fold < ctx->n_symbols)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_count_short_versions: the fold table covers %d of the pool's %d symbols "
+                                              "(pclean_set_fold_table first)", ctx->n_fold, ctx->n_symbols);
+  int max_la = 0, max_lb = 0;
+  int rc = check_string_ids(ctx, n_opt, opt_ids, "option", &max_la);
+  if (!rc) rc = check_string_ids(ctx, n_lat, lat_ids, "lat", &max_lb);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DevBuf<int32_t> d_opt, d_lat, d_out;
+  hipError_t e = hipSuccess;
+  rc = PCLEAN_OK;
+  if (d_opt.alloc(std::max(n_opt, 1)) || d_lat.alloc(n_lat) || d_out.alloc(n_lat)) {
+    rc = pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  } else {
+    if (n_opt) e = hipMemcpy(d_opt.p, opt_ids, n_opt * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_lat.p, lat_ids, n_lat * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.p, 0, n_lat * sizeof(int32_t), ctx->stream);
+    if (e == hipSuccess) {
+      rc = pclean_launch_short_count(ctx, n_opt, d_opt.p, n_lat, d_lat.p, d_out.p);
+      e = hipStreamSynchronize(ctx->stream);
+    }
+    if (!rc && e == hipSuccess) e = hipMemcpy(out, d_out.p, n_lat * sizeof(int32_t), hipMemcpyDeviceToHost);
+  }
+  d_opt.release();
+  d_lat.release();
+  d_out.release();
+  if (rc) return rc;
+  if (e != hipSuccess) return pclean_fail(ctx, PCLEAN_ERR_HIP, "short-version count failed: %s", hipGetErrorString(e));
+  return PCLEAN_OK;
+}
+
 extern "C" int pclean_set_lm_tables(pclean_ctx* ctx, const double* init_p, const double* trans_p, const uint16_t* letter_sym) {
   if (!ctx || !init_p || !trans_p || !letter_sym) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_lm_tables: bad arguments");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -249,6 +389,7 @@ extern "C" int pclean_set_pair_table(pclean_ctx* ctx, int32_t table_id, int32_t 
     return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_pair_table: bad arguments");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   PairTable& pt = ctx->pair[table_id];
+  pt.cls_valid = false;
   pt.n_obs = n_obs;
   pt.n_lat = n_lat;
   pt.elem_bytes = 1;
@@ -801,12 +942,20 @@ extern "C" int pclean_load_block(pclean_ctx* ctx, int32_t block_id, int32_t n_no
         return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_load_block: MaybeSwap term %d malformed", i);
       continue;
     }
+    if (tm.dens_kind == PCLEAN_DENS_TABULATED && tm.ctx_slot >= 0)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_load_block: tabulated term %d with a ctx slot (a tabulated likelihood of "
+                                              "a JuliaNode value) is not supported", i);
     if (tm.pair_table < 0 || tm.pair_table >= PCLEAN_MAX_TABLES || tm.ctx_slot >= n_ctx ||
         (tm.ctx_slot >= 0 && (tm.fn_table < 0 || tm.fn_table >= PCLEAN_MAX_TABLES)))
       return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_load_block: term %d malformed", i);
   }
   b.nodes.assign(nodes, nodes + n_nodes);
   b.terms.assign(terms, terms + n_terms);
+  // an option list with a tabulated term is never cached per observed value (a missing observation of the term counts)
+  for (pclean_node& nd : b.nodes)
+    if (nd.kind == PCLEAN_NODE_LEAF && nd.cacheable)
+      for (int i = 0; i < nd.n_terms; ++i)
+        if (terms[nd.term_begin + i].dens_kind == PCLEAN_DENS_TABULATED) nd.cacheable = 0;
   b.children.assign(children, children + n_children);
   b.colmap.assign(colmap, colmap + n_colmap);
   b.n_ctx = n_ctx;

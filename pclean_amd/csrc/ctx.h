@@ -86,6 +86,8 @@ struct PairTable {
   int32_t dist_mode = PCLEAN_DIST_DL;  // flavour the table was built with (dummy_dev.h scores drawn strings with it)
   int32_t max_lat_len = 0, max_obs_len = 0;
   double mean_lat_len = 0.0;  // AddTypos tables built on the device: mean length of the latent strings
+  DevBuf<double> cls;         // [n_lat][4] class densities of a PCLEAN_DENS_TABULATED term (pclean_set_class_density)
+  bool cls_valid = false;     // ... uploaded since the table was last built
 };
 
 struct CandTable {
@@ -203,6 +205,8 @@ struct pclean_ctx {
   DevBuf<int64_t> off;
   std::vector<int64_t> h_off;
   int32_t n_symbols = 0;
+  DevBuf<uint16_t> fold;  // case-folding map over the symbols (pclean_set_fold_table)
+  int32_t n_fold = 0;
 
   // observed columns
   int32_t n_rows = 0, n_cols = 0;
@@ -292,6 +296,11 @@ inline int pclean_fail(pclean_ctx* ctx, int code, const char* fmt, ...) {
 // dist_kernels.hip
 int pclean_launch_dist(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids, const int32_t* d_lat_ids,
                        int dist_mode, const int32_t* h_lat_ids);  // h_lat_ids: the latent string ids on the host
+// class_kernels.hip
+int pclean_launch_class_table(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids, const int32_t* d_lat_ids, int rule,
+                              int dot_symbol);
+int pclean_launch_short_count(pclean_ctx* ctx, int n_opt, const int32_t* d_opt_ids, int n_lat, const int32_t* d_lat_ids,
+                              int32_t* d_out);
 // density tables (api.hip)
 int pclean_ensure_density(pclean_ctx* ctx, int max_len);
 // sweep.hip

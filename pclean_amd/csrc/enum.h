@@ -13,7 +13,10 @@ struct TermDev {
   const int32_t* fn;        // ctx lookup table or nullptr
   int32_t n_lat, elem_bytes, dens_kind, max_typos, ctx_slot, fn_nb;
   int32_t ctx_mode, pad;    // 0: ctx of the item; 1: ctx of the evidence row, fn[ctx][cand]; 2: fn[cand][ctx]
-  const int32_t* aux_col;   // MAYBE_SWAP: [n_cand] number of options of the candidate's key group
+  union {                   // (one slot: a term is of one kind, and NodeDev travels as a kernel argument)
+    const int32_t* aux_col; // MAYBE_SWAP: [n_cand] number of options of the candidate's key group
+    const double* cls;      // TABULATED: T[n_lat][4], class densities by (latent value, class; 3 = missing observation)
+  };
   int32_t other_val, pad2;  // MAYBE_SWAP: first latent value that is "not one of the options" (the dummy; strings drawn for a chosen dummy follow it)
 };
 

@@ -50,6 +50,13 @@ __device__ __forceinline__ double term_density(const TermDev& tm, const DensDev&
   return l;
 }
 
+// Tabulated term (PCLEAN_DENS_TABULATED): T[val][class of (observed value o, val)], T[val][3] for a missing observation —
+// which counts (expand_on_short_version.jl:31-35, format_name.jl:34-43).  Class tables are byte tables.
+__device__ __forceinline__ double tabulated_density(const TermDev& tm, int o, int val) {
+  const int c = o < 0 ? 3 : ((int)tm.pair[(size_t)o * tm.n_lat + val] & 3);  // (& 3: T has four columns, whatever the byte)
+  return tm.cls[(size_t)val * 4 + c];
+}
+
 // MaybeSwap (maybe_swap.jl:13-28): o = observed value index (-1 missing), same = strings equal
 __device__ __forceinline__ double maybe_swap_density(const TermDev& tm, const DensDev& dn, int o, int d, int val, int k,
                                                      int pidx) {
@@ -131,6 +138,28 @@ __device__ __forceinline__ double candidate_score_ev(const NodeDev& nd, const De
         const int c = tm.ctx_mode == 0 ? v.ctxv[tm.ctx_slot] : ec;
         const int d = o < 0 ? 1 : (int)tm.pair[(size_t)o * tm.n_lat + val];
         sk += mult * maybe_swap_density(tm, dn, o, d, val, k, c);
+      }
+      continue;
+    }
+    if (tm.dens_kind == PCLEAN_DENS_TABULATED) {  // missing is key 0 and counts; the entries CS_TC at a time, as below
+      const int val = tm.cand_col[k];
+      const double* Tv = tm.cls + (size_t)val * 4;
+      for (int rb = ag.off[oi]; rb < r1; rb += CS_TC) {
+        int o[CS_TC], cn[CS_TC], c[CS_TC];
+        double tv[CS_TC];
+#pragma unroll
+        for (int u = 0; u < CS_TC; ++u) {
+          const int r = min(rb + u, r1 - 1);
+          o[u] = (int)(ag.key[r] & 0xffffffull) - 1;
+          cn[u] = ag.cnt[r];
+        }
+#pragma unroll
+        for (int u = 0; u < CS_TC; ++u) c[u] = (int)tm.pair[o[u] >= 0 ? (size_t)o[u] * tm.n_lat + val : (size_t)0];
+#pragma unroll
+        for (int u = 0; u < CS_TC; ++u) tv[u] = Tv[o[u] >= 0 ? (c[u] & 3) : 3];
+#pragma unroll
+        for (int u = 0; u < CS_TC; ++u)
+          if (rb + u < r1) sk += (double)cn[u] * tv[u];
       }
       continue;
     }
@@ -235,6 +264,10 @@ __device__ __forceinline__ double candidate_score(const NodeDev& nd, const DensD
   for (int ti = 0; ti < nd.n_terms; ++ti) {
     const TermDev& tm = nd.terms[ti];
     const int o = tm.obs_col[v.row];
+    if (tm.dens_kind == PCLEAN_DENS_TABULATED) {  // (a missing observation is not skipped)
+      sk += tabulated_density(tm, o, tm.cand_col[k]);
+      continue;
+    }
     if (o < 0) continue;  // explicitly missing observation (add_typos.jl:51-53)
     int val = tm.cand_col[k];
     if (tm.ctx_slot >= 0) val = tm.fn[(size_t)v.ctxv[tm.ctx_slot] * tm.fn_nb + val];
@@ -280,12 +313,28 @@ __device__ __forceinline__ void candidate_score_batch(const NodeDev& nd, const D
   for (int ti = 0; ti < nd.n_terms; ++ti) {
     const TermDev& tm = nd.terms[ti];
     const int o = tm.obs_col[v.row];
-    if (o < 0) continue;  // explicitly missing observation (add_typos.jl:51-53)
+    if (o < 0 && tm.dens_kind != PCLEAN_DENS_TABULATED) continue;  // explicitly missing observation (add_typos.jl:51-53)
     int val[CPT], d[CPT];
 #pragma unroll
     for (int c = 0; c < CPT; ++c) val[c] = tm.cand_col[kk[c]];
 #pragma unroll
     for (int c = 0; c < CPT; ++c) val[c] = on[c] ? val[c] : 0;
+    if (tm.dens_kind == PCLEAN_DENS_TABULATED) {  // class bytes, then the T loads of the CPT candidates together
+      const size_t cbase = o < 0 ? (size_t)0 : (size_t)o * tm.n_lat;
+      double tv[CPT];
+      if (o < 0) {  // (a missing observation counts: column 3)
+#pragma unroll
+        for (int c = 0; c < CPT; ++c) d[c] = 3;
+      } else {
+#pragma unroll
+        for (int c = 0; c < CPT; ++c) d[c] = (int)tm.pair[cbase + val[c]] & 3;
+      }
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) tv[c] = tm.cls[(size_t)val[c] * 4 + d[c]];
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) sk[c] += on[c] ? tv[c] : 0.0;
+      continue;
+    }
     if (tm.ctx_slot >= 0) {
       const int32_t* fr = tm.fn + (size_t)v.ctxv[tm.ctx_slot] * tm.fn_nb;
 #pragma unroll
@@ -339,6 +388,10 @@ __device__ __forceinline__ double candidate_terms(const NodeDev& nd, const DensD
   for (int ti = 0; ti < nd.n_terms; ++ti) {
     const TermDev& tm = nd.terms[ti];
     const int o = tm.obs_col[v.row];
+    if (tm.dens_kind == PCLEAN_DENS_TABULATED) {
+      sk += tabulated_density(tm, o, tm.cand_col[k]);
+      continue;
+    }
     if (o < 0) continue;
     int val = tm.cand_col[k];
     if (tm.ctx_slot >= 0) val = tm.fn[(size_t)v.ctxv[tm.ctx_slot] * tm.fn_nb + val];

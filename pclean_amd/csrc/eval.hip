@@ -151,6 +151,15 @@ int build_node_dev(pclean_ctx* ctx, const Block& b, int node_id, NodeDev& nd) {
       td.other_val = tm.fn_table;
       continue;
     }
+    if (tm.dens_kind == PCLEAN_DENS_TABULATED) {
+      if (tm.ctx_slot >= 0 || pt.elem_bytes != 1)
+        return pclean_fail(ctx, PCLEAN_ERR_ARG, "tabulated term %d: needs a 1-byte class table and no ctx slot", n.term_begin + i);
+      if (!pt.cls_valid)
+        return pclean_fail(ctx, PCLEAN_ERR_STATE, "tabulated term %d: pair table %d has no class densities "
+                                                  "(pclean_set_class_density)", n.term_begin + i, tm.pair_table);
+      td.cls = pt.cls.p;
+      continue;
+    }
     if (tm.ctx_slot >= 0) {
       const FnTable& f = ctx->fn[tm.fn_table];
       if (!f.valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "fn table %d not set", tm.fn_table);
@@ -323,6 +332,14 @@ static int cols_union(pclean_ctx* ctx, CandTable& t, uint64_t base, uint64_t col
   return 1;
 }
 
+// a node with a tabulated term (PCLEAN_DENS_TABULATED) goes through the generic enumeration kernels alone: no compact byte
+// tables, no per-observed-value cache (a missing observation of such a term counts)
+static bool node_has_tabulated(const Block& b, const pclean_node& n) {
+  for (int i = 0; i < n.n_terms; ++i)
+    if (b.terms[n.term_begin + i].dens_kind == PCLEAN_DENS_TABULATED) return true;
+  return false;
+}
+
 static int try_fast_root(pclean_ctx* ctx, int block_id, int node_id, FastRootDev& fr, bool ev_mode = false) {
   Block& b = ctx->block[block_id];
   if (node_id >= 64) return 0;
@@ -331,7 +348,7 @@ static int try_fast_root(pclean_ctx* ctx, int block_id, int node_id, FastRootDev
   const bool leaf = n.kind == PCLEAN_NODE_LEAF;
   static const bool no_leaf = getenv("PCLEAN_NO_FAST_LEAF") != nullptr;
   if (!t.valid || t.n_rows < 1024 || n.n_terms < 1 || n.n_terms > PCLEAN_MAX_TERMS || (leaf && no_leaf)) return 0;
-  if (leaf != t.is_options) return 0;
+  if (leaf != t.is_options || node_has_tabulated(b, n)) return 0;
   int lmax = 0, dmax = 0;
   for (int i = 0; i < n.n_terms; ++i) {
     const pclean_term& tm = b.terms[n.term_begin + i];
@@ -687,6 +704,7 @@ int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, co
   }
   FastRootDev fr;
   int fast = 0, fast_ev = 0;
+  const bool tabulated = node_has_tabulated(b, n);  // (generic kernels only; guarded below the way nd.g.on is)
   // a reference slot whose groups are made BEFORE its new-row branch is looked at (below): the gate and the children of
   // the branch then run once per group of identical rows instead of once per row
   ItemGroups g_pre;
@@ -743,8 +761,8 @@ int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, co
       // the new row's fixed-point weight is exactly 0 skip the evaluation of the open children.
       static const bool no_group_gate = getenv("PCLEAN_NO_GROUP_GATE") != nullptr;
       bool pre_grouped = false;
-      if (n_open > 0 && n_draws > 0 && excl && !scores_out && !ctx->force_generic && !nd.g.on && !il.rng_row && !il.ev_lo &&
-          !no_group_gate) {
+      if (n_open > 0 && n_draws > 0 && excl && !scores_out && !ctx->force_generic && !nd.g.on && !tabulated && !il.rng_row &&
+          !il.ev_lo && !no_group_gate) {
         fast = try_fast_root(ctx, block_id, node_id, fr);
         if (fast < 0) return fast;
         fast_tried = true;
@@ -923,7 +941,7 @@ int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, co
   // cacheable option list: log-marginal and draws from the per-observed-value coarse prefix (leaf_coarse_draw_kernel)
   static const bool no_coarse = getenv("PCLEAN_NO_COARSE_LEAF") != nullptr;
   if (n.kind == PCLEAN_NODE_LEAF && n.cacheable && !il.ev_lo && !scores_out && !ctx->force_generic && !ctx->obs_override &&
-      !no_coarse && !nd.g.on && !ctx->prior_mode) {
+      !no_coarse && !nd.g.on && !tabulated && !ctx->prior_mode) {
     const double* cache = nullptr;
     const int32_t* ocol = nullptr;
     int n_obs = 0;
@@ -941,7 +959,8 @@ int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, co
   static const bool no_small_generic = getenv("PCLEAN_NO_SMALL_GENERIC") != nullptr;
   const bool small_lse = !no_small_generic && n_draws == 0 && il.n <= 1024 && !il.ev_lo &&
                          (size_t)(nd.n_cand + 2) * 8 + (16 + 64) * 8 <= (size_t)160 * 1024;
-  if (!fast_tried && !scores_out && !snew_override && !ctx->force_generic && !nd.g.on && !ctx->prior_mode && !small_lse) {
+  if (!fast_tried && !scores_out && !snew_override && !ctx->force_generic && !nd.g.on && !tabulated && !ctx->prior_mode &&
+      !small_lse) {
     static const int ev_slot_min_items = getenv("PCLEAN_EV_SLOT_MIN_ITEMS") ? atoi(getenv("PCLEAN_EV_SLOT_MIN_ITEMS")) : 64;
     if (!il.ev_lo)
       fast = try_fast_root(ctx, block_id, node_id, fr);

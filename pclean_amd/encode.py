@@ -86,6 +86,23 @@ class StringPool:
         self._build()
         return self.sym, self.off, self.lm, self.cp
 
+    def fold_symbols(self):
+        """Case-folding map over the pool's dense symbols (pclean_set_fold_table): fold[s] = the smallest symbol whose
+        single-character lowercase equals that of s — the rule `lm` is built with above: a character whose lowercase
+        is not one character stands for itself.  Equal fold ids = equal after `lowercase`."""
+        self._build()
+        fold = np.zeros(len(self._sym_of_cp), dtype=np.uint16)
+        first = {}
+        for c, sid in sorted(self._sym_of_cp.items(), key=lambda kv: kv[1]):
+            low = chr(c).lower()
+            fold[sid] = first.setdefault(low if len(low) == 1 else chr(c), sid)
+        return fold
+
+    def symbol_of(self, ch):
+        """pool symbol of character ch, 0xFFFF when no pool string holds it"""
+        self._build()
+        return self._sym_of_cp.get(ord(ch), 0xFFFF)
+
     def letter_symbols(self):
         """Pool symbol id of each of the 28 letters random(StringPrior) emits (string_prior.jl:28-39), 0xFFFF for a
         letter that occurs in no pool string (it then equals no observed symbol)."""

@@ -40,6 +40,27 @@ def make_gauss(spec, mean_table_id=None):
     return g
 
 
+def class_density_rows(rule, strings, options=None, counts=None):
+    """T[value][class 0, 1, 2, missing observation] of a tabulated term, float64 [n][4] (pclean_set_class_density).
+    ExpandOnShortVersion (expand_on_short_version.jl:30-41): -log(#options the value is a short version of) when it is
+    a short version of the observed string, -1000 when not; missing: 0 if the value is one of the options (string
+    membership), else -1000.  FormatName (format_name.jl:33-55): log(0.9999) / log(0.0001) / -1000 for equal / initial /
+    neither, all -1000 for the empty name; missing: 0 for the empty name, -1000 for a name holding "*", else -5."""
+    T = np.full((len(strings), 4), -1000.0)
+    if rule == _lib.CLASS_SHORT_VERSION:
+        opts = set(options)
+        c = np.asarray(counts, dtype=np.float64)
+        # (count 0: the value is a short version of no option, so of no observed string either — never looked up)
+        T[:, 0] = np.where(c > 0, -np.log(np.maximum(c, 1.0)), -1000.0)
+        T[:, 3] = [0.0 if s in opts else -1000.0 for s in strings]
+    else:
+        for v, s in enumerate(strings):
+            if s != "":
+                T[v, 0], T[v, 1] = np.log(0.9999), np.log(0.0001)
+            T[v, 3] = 0.0 if s == "" else (-1000.0 if "*" in s else -5.0)
+    return T
+
+
 def lw_locals(lw):
     return getattr(lw, "locals", {})
 
@@ -163,6 +184,7 @@ class Engine:
             hip.set_pair_table(pid, (1 - np.eye(n, dtype=np.uint8)))
         for pid in lw.same_pairs:  # MaybeSwap: 0 iff the observed string is the latent value
             hip.set_pair_table(pid, lw.same_pair_table(pid))
+        self._upload_class_tables()
         if getattr(lw, "xnum", None) is not None and lw.xnum.shape[0]:
             hip.load_numeric_columns(lw.xnum)
         init_l, trans_l = lm_log_tables()
@@ -227,6 +249,22 @@ class Engine:
             hip.set_options(tid, lw.option_values[(cname, aname)], logp)
         lw.load_blocks_into(hip)
         self._gauss_pending = bool(getattr(lw, "gauss", {}))
+
+    def _upload_class_tables(self):
+        """Tabulated terms (ExpandOnShortVersion / FormatName): the class table of every such pair, built on the device,
+        and its densities T[value][class 0..2, missing], evaluated here once in float64 (class_density_rows)."""
+        lw, hip = self.lw, self.hip
+        if not getattr(lw, "class_pairs", None):
+            return
+        hip.set_fold_table(lw.pool.fold_symbols())
+        for pid, (rule, odom, ldom, options) in lw.class_pairs.items():
+            li = ldom.id_array()
+            hip.build_class_table(pid, odom.id_array(), li, rule, lw.pool.symbol_of("."))
+            strings = [ldom.string(v) for v in range(len(ldom))]
+            counts = None
+            if options is not None:
+                counts = hip.count_short_versions(lw.pool.add_all(options), li)
+            hip.set_class_density(pid, class_density_rows(rule, strings, options, counts))
 
     # -- dynamic data ---------------------------------------------------------
     def upload_trace(self, trace):

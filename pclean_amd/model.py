@@ -58,6 +58,26 @@ class AddTypos:
         self.ref, self.max_typos = ref, max_typos
 
 
+class ExpandOnShortVersion:
+    """expand_on_short_version.jl: ExpandOnShortVersion(val, options); `ref` names the short (clean) value, the
+    observation is one of the `options` that `val` is a case-insensitive subsequence of."""
+
+    def __init__(self, ref, options):
+        self.ref, self.options = ref, list(options)
+
+
+class FormatName:
+    """format_name.jl:29-55, the one-name method: FormatName(name) is the name itself or its initial + "."."""
+
+    def __init__(self, ref, *more):
+        if more:
+            raise NotImplementedError("FormatName(first, middle, last): first / middle / last form: not lowered")
+        self.ref = ref
+
+
+TABULATED = (ExpandOnShortVersion, FormatName)
+
+
 class TimePrior:
     """time_prior.jl: TimePrior(proposal_atoms); atoms keyed by another attribute of the class
     (`times_for_flight["$flight_id-field"]`, experiments/flights/run.jl:17-20)."""
@@ -296,6 +316,8 @@ class LoweredModel:
         self.cross_terms = []
         self.eq_pairs = {}
         self.same_pairs = {}   # pair id -> (observed domain, latent domain): 0 iff same string
+        self.class_pairs = {}  # pair id -> (class rule, observed domain, latent domain, options or None): tabulated terms
+        self._class_key = {}
         self.prob_spec = None
         self.gauss = {}        # (block id, node id) -> dict spec (resolved by the engine): the node's first Gaussian term
         self.gauss_more = {}   # (block id, node id) -> [dict spec, ...]: its further terms, in declaration order
@@ -344,8 +366,15 @@ class LoweredModel:
             own = None
             if "." not in dirty:
                 own = ocls.attr(dirty)
-            if own is not None and own.kind == "choice" and isinstance(own.dist, (AddTypos, MaybeSwap)):
+            if own is not None and own.kind == "choice" and isinstance(own.dist, (AddTypos, MaybeSwap) + TABULATED):
                 vals = [v for v in dirty_columns[col] if v is not None]
+                if isinstance(own.dist, ExpandOnShortVersion):
+                    # logdensity would be -log(0) for a value no option list can have produced
+                    # (expand_on_short_version.jl:38): with this check every "is a short version" pair has a count >= 1
+                    stray = sorted(set(vals) - set(own.dist.options))
+                    if stray:
+                        raise ValueError(f"{dirty}: observed value {stray[0]!r} is not among the options of "
+                                         "ExpandOnShortVersion")
                 self.obs_dom[dirty] = Domain(self.pool, list(dict.fromkeys(vals)))
             elif own is not None and own.kind == "choice" and isinstance(own.dist, (TransformedGaussian, AddNoise)):
                 self.numeric_obs[dirty] = len(self.num_cols)
@@ -475,7 +504,7 @@ class LoweredModel:
         out = []
         for n in names:
             a = ocls.attr(n)
-            if a.kind == "choice" and isinstance(a.dist, AddTypos):
+            if a.kind == "choice" and isinstance(a.dist, (AddTypos,) + TABULATED):
                 out.append(a)
         return out
 
@@ -493,6 +522,19 @@ class LoweredModel:
             self.pair_id[key] = (self._next_pair, self.obs_dom[dirty], lat_dom)
             self._next_pair += 1
         return self.pair_id[key][0]
+
+    def _class_pair_for(self, dirty, lat_dom_key, dist):
+        """class table of a tabulated observation (ExpandOnShortVersion / FormatName) over obs domain x latent domain"""
+        key = (dirty, lat_dom_key)
+        if key not in self._class_key:
+            rule, options = ((_lib.CLASS_SHORT_VERSION, list(dist.options)) if isinstance(dist, ExpandOnShortVersion)
+                             else (_lib.CLASS_FORMAT_NAME, None))
+            if options is not None:
+                self.pool.add_all(options)  # (the device counts over the option strings: they live in the pool)
+            self.class_pairs[self._next_pair] = (rule, self.obs_dom[dirty], self.latent_dom[lat_dom_key], options)
+            self._class_key[key] = self._next_pair
+            self._next_pair += 1
+        return self._class_key[key]
 
     def _build_blocks(self):
         m = self.model
@@ -554,6 +596,19 @@ class LoweredModel:
             terms = []
             for a in self._obs_terms_of_block(ocls, names):
                 ref = a.dist.ref
+                if isinstance(a.dist, TABULATED):
+                    # a term DENS_TABULATED exactly where an AddTypos term of the same `ref` would go
+                    if "." not in ref:
+                        raise NotImplementedError(f"{a.name}: {type(a.dist).__name__} of a JuliaNode value is not lowered")
+                    head, rest = ref.split(".", 1)
+                    if head != root_fk.name:
+                        raise NotImplementedError(f"{a.name}: reference outside the block's root slot")
+                    cname, la = m.resolve(root_fk.target, rest)
+                    if (cname, la.name) not in self.latent_dom:
+                        raise NotImplementedError(f"{a.name}: {type(a.dist).__name__} of a value without a string domain")
+                    pid = self._class_pair_for(a.name, (cname, la.name), a.dist)
+                    terms.append(dict(obs=a.name, path=rest, pair=pid, max_typos=None, ctx=None, dens=_lib.DENS_TABULATED))
+                    continue
                 if "." in ref:
                     head, rest = ref.split(".", 1)
                     if head != root_fk.name:
@@ -669,7 +724,9 @@ class LoweredModel:
                         raise NotImplementedError("keyed atoms need their key attribute observed directly")
                     self._emit_term(blk, kt[0], 1)
                     n_leaf_terms += 1
-                cacheable = int(n_leaf_terms == 1 and len(sub) == 1 and sub[0]["ctx"] is None)
+                # (the per-observed-value cache has no slot for the missing observation a tabulated term scores)
+                cacheable = int(n_leaf_terms == 1 and len(sub) == 1 and sub[0]["ctx"] is None
+                                and sub[0].get("dens") != _lib.DENS_TABULATED)
                 # the ProposalDummyValue of the proposal (string_prior.jl:16-26, time_prior.jl:15-19): which latent
                 # value is the placeholder and what random(dist) samples when the dummy is chosen
                 dval, dspec = 0, 0
