@@ -20,7 +20,9 @@ It shares NOTHING with the product's lowering (LoweredModel's nodes / terms / co
 option tables): plans are derived here from the attribute references, JuliaNodes are evaluated by calling the
 model's Python function on strings.  tests/golden/literal_scores.json holds its per-candidate scores for rows of
 hospital_dirty.csv; the C++ oracle (CPU suite) and the HIP path (-m gpu) must reproduce them to 1e-12 relative.
-Scope: programs built from reference slots, AddTypos, StringPrior (plain and keyed atoms), ChooseUniformly,
+Scope: programs built from reference slots, AddTypos, the one-name FormatName and ExpandOnShortVersion (on the strings,
+format_name.jl:33-55 and expand_on_short_version.jl:6-41; a missing observation of these two is scored), StringPrior
+(plain and keyed atoms), ChooseUniformly,
 ChooseProportionally, JuliaNodes (hospital) and — GaussBlockProposal below — directly observed latent attributes, own
 ChooseUniformly choices and a TransformedGaussian observation with an IndexedLookup mean (rents), — PriorSlotProposal / score_block — slots with nothing but noise-free observations,
 TimePrior and a block of MaybeSwap observations (flights), and — LatentProposal — the rejuvenation of a LATENT row's
@@ -109,6 +111,74 @@ def add_typos_logpdf(observed, word, max_typos=None, restricted=False):
             v -= math.log(26) * d / 2
         _typo_memo[key] = v
     return v
+
+
+def _lower_chars(s):
+    """Julia's lowercase(::String) maps character by character; a character whose lowercase is not one character
+    (Python's str.lower of U+0130) stands for itself."""
+    out = []
+    for ch in s:
+        low = ch.lower()
+        out.append(low if len(low) == 1 else ch)
+    return out
+
+
+def format_name_logpdf(observed, name):
+    """format_name.jl:33-55, the one-name method.  A missing observation is an observed value: 0 under the empty
+    name, -1000 under a name holding "*", -5 otherwise."""
+    if observed is None:
+        if name == "":
+            return 0.0
+        return -1000.0 if "*" in name else -5.0
+    if name == "":
+        return -1000.0
+    v = _format_memo.get((observed, name))
+    if v is None:
+        seen = _lower_chars(observed)
+        if seen == _lower_chars(name):
+            v = math.log(0.9999)
+        elif seen == _lower_chars(name[0] + "."):
+            v = math.log(0.0001)
+        else:
+            v = -1000.0
+        _format_memo[(observed, name)] = v
+    return v
+
+
+_format_memo = {}  # (observed, name) -> density
+_short_memo = {}   # (short, options tuple) -> number of options `short` is a short version of
+_is_short_memo = {}
+
+
+def _is_short_version(short, long):
+    """expand_on_short_version.jl:6-19: `short` is a subsequence of `long`, ignoring case."""
+    r = _is_short_memo.get((short, long))
+    if r is None:
+        s, l = _lower_chars(short), _lower_chars(long)
+        a = 0
+        for ch in l:
+            if a == len(s):
+                break
+            if s[a] == ch:
+                a += 1
+        r = _is_short_memo[(short, long)] = a == len(s)
+    return r
+
+
+def expand_on_short_version_logpdf(observed, short, options):
+    """expand_on_short_version.jl:30-41.  A missing observation is an observed value: 0 when `short` is itself one
+    of the options (string membership), else -1000."""
+    if observed is None:
+        return 0.0 if short in options else -1000.0
+    if not _is_short_version(short, observed):
+        return -1000.0
+    key = (short, options) if isinstance(options, tuple) else None
+    n = _short_memo.get(key) if key is not None else None
+    if n is None:
+        n = sum(1 for x in options if _is_short_version(short, x))
+        if key is not None:
+            _short_memo[key] = n
+    return -math.log(n) if n > 0 else math.inf  # (-log(0) in the reference; unreachable when observed is an option)
 
 
 def string_prior_logpdf(s, min_len, max_len):
@@ -203,29 +273,38 @@ class BlockProposal:
         self.fk = self.ocls.attr(fks[0])
         # likelihood terms: (observed string, function of {path below the slot: string} -> latent word, max_typos, paths used)
         self.terms = []
-        from pclean_amd.model import AddTypos
+        from pclean_amd.model import AddTypos, ExpandOnShortVersion, FormatName
         for an in block_attrs:
             a = self.ocls.attr(an)
             if a.kind != "choice":
                 continue
-            assert isinstance(a.dist, AddTypos)
+            assert isinstance(a.dist, (AddTypos, ExpandOnShortVersion, FormatName))
             self.terms.append(self._term(a))
 
     def _term(self, a):
+        from pclean_amd.model import ExpandOnShortVersion, FormatName
         ref = a.dist.ref
         pre = self.fk.name + "."
         if ref.startswith(pre):
             path = ref[len(pre):]
-            return dict(obs=self.observed[a.name], paths=[path], word=lambda vals, p=path: vals[p], max_typos=a.dist.max_typos)
+            t = dict(obs=self.observed[a.name], paths=[path], word=lambda vals, p=path: vals[p], kind="typos")
+            if isinstance(a.dist, FormatName):
+                t["kind"] = "format_name"
+            elif isinstance(a.dist, ExpandOnShortVersion):
+                t["kind"], t["options"] = "short_version", tuple(a.dist.options)
+            else:
+                t["max_typos"] = a.dist.max_typos
+            return t
         j = self.ocls.attr(ref)  # a JuliaNode of the row: its arguments are below this slot or another block's
         assert j.kind == "julia"
+        assert not isinstance(a.dist, (ExpandOnShortVersion, FormatName)), "a tabulated term reads an attribute, not a JuliaNode"
         mine = [arg[len(pre):] for arg in j.args if arg.startswith(pre)]
 
         def word(vals, j=j):
             args = [vals[arg[len(pre):]] if arg.startswith(pre) else self.ctx[arg] for arg in j.args]
             return j.fn(*args)
 
-        return dict(obs=self.observed[a.name], paths=mine, word=word, max_typos=a.dist.max_typos)
+        return dict(obs=self.observed[a.name], paths=mine, word=word, kind="typos", max_typos=a.dist.max_typos)
 
     # -- helpers -------------------------------------------------------------------------------------------------
     def _crp(self, cls):
@@ -235,6 +314,10 @@ class BlockProposal:
         return s, d, counts, total
 
     def _lik(self, term, vals):
+        if term["kind"] == "format_name":
+            return format_name_logpdf(term["obs"], term["word"](vals))
+        if term["kind"] == "short_version":
+            return expand_on_short_version_logpdf(term["obs"], term["word"](vals), term["options"])
         return add_typos_logpdf(term["obs"], term["word"](vals), term["max_typos"], self.restricted)
 
     def _flat(self, cls, key, prefix=""):
@@ -528,7 +611,7 @@ class LatentProposal(BlockProposal):
         fks = [a for a in top_attrs if self.ocls.attr(a).kind == "fk"]
         assert len(fks) == 1
         self.fk = self.ocls.attr(fks[0])
-        from pclean_amd.model import AddTypos
+        from pclean_amd.model import AddTypos, ExpandOnShortVersion, FormatName
         self.terms = []
         pre = self.fk.name + "."
         import copy
@@ -536,7 +619,7 @@ class LatentProposal(BlockProposal):
             row = copy.copy(self)  # (_term's closures read .observed / .ctx of the object they were made on: one per row)
             row.observed, row.ctx = observed, ctx
             for a in self.ocls.attrs:  # EVERY observed choice of the referring row that depends on a value below the slot,
-                if a.kind != "choice" or not isinstance(a.dist, AddTypos):  # whatever block of the observed class it sits in
+                if a.kind != "choice" or not isinstance(a.dist, (AddTypos, ExpandOnShortVersion, FormatName)):  # whatever block of the observed class it sits in
                     continue
                 ref = a.dist.ref
                 if "." in ref and not ref.startswith(pre):

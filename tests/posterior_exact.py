@@ -18,6 +18,9 @@ P > 2 over two dependent blocks (conditional SMC with resampling) has no short c
 are rows that can draw a ProposalDummyValue (the weight correction changes the kernel): root classes here hold a
 single ChooseUniformly choice, which has none.
 
+draw_program holds AddTypos observations; tab_draw_program the tabulated kind (FormatName, ExpandOnShortVersion) next
+to one AddTypos term, whose pi comes from the literal interpreter's densities on the strings.
+
 gof() is the one goodness-of-fit routine: a G-test pooled over rows (rows with identical expected distributions are
 summed first), cells with an expected count below 5 merged, p-value from scipy.stats.chi2, and the worst cells named.
 """
@@ -46,6 +49,8 @@ def normalise(scores):
     finite = {k: v for k, v in scores.items() if v > -math.inf}
     if not finite:
         raise ValueError("no candidate has positive probability")
+    top = max(finite.values())  # (a candidate 745 nats below the best has a probability below the smallest double: dropped
+    finite = {k: v for k, v in finite.items() if v > top - 745.0}  # here, as its float(x / z) == 0 was below)
     if mpmath is not None:
         w = {k: mpmath.exp(mpmath.mpf(v)) for k, v in finite.items()}
         z = mpmath.fsum(w.values())
@@ -138,13 +143,20 @@ class RowConditionals:
             self._memo[key] = self._block0(i)
         return self._memo[key]
 
-    def _block0(self, i):
+    def _block0(self, i, bi=0):
         saved = self._unincorporated(i)
         try:
-            sc, z = self._block_scores(i, 0, {})
+            sc, z = self._block_scores(i, bi, {})
         finally:
             self._restore(saved)
         return normalise(sc), z
+
+    def block_alone(self, i, bi):
+        """(pi, Z) of block bi of row i when the block reads no other block's value (independent blocks)"""
+        key = self._key(i, ("alone", bi))
+        if key not in self._memo:
+            self._memo[key] = self._block0(i, bi)
+        return self._memo[key]
 
     def two_blocks(self, i):
         """pi0, Z0 and, per distinct block-0 value x reachable under pi0 or held by the current referent:
@@ -280,6 +292,20 @@ def gof(items, n_worst=5):
         return dict(p=0.0, G=math.inf, df=df, n=n, worst=impossible[:n_worst])
     p = float(chi2.sf(G, df)) if df > 0 else 1.0
     return dict(p=p, G=G, df=df, n=n, worst=[w[1:] for w in worst[:n_worst]])
+
+
+def pooled_mass(expected, n):
+    """largest share of a group's expected mass that gof() would put into its pooled cell (expectations below 5) when
+    every row of `expected` ([{cand: prob}]) is drawn n times; rows with one expected distribution form one group"""
+    groups = {}
+    for exp in expected:
+        sig = tuple(sorted((repr(k), round(v, 13)) for k, v in exp.items()))
+        g = groups.setdefault(sig, [exp, 0])
+        g[1] += n
+    worst = 0.0
+    for exp, tot in groups.values():
+        worst = max(worst, sum(v for v in exp.values() if tot * v < 5.0))  # (the cells _merge pools for being small)
+    return worst
 
 
 def describe(res):
@@ -447,6 +473,248 @@ def draw_program(n_table, seed=0, n_dead=0, two_blocks=False):
     return dict(lw=lw, trace=tr, obs=obs, query=q, dirty=dirty, model=m, kind=np.array([r[0] for r in rows]))
 
 
+# ---- the draw program of the tabulated terms (FormatName, ExpandOnShortVersion) -------------------------------------
+TAB_CROWD = ["Jack", "jane", "JILL", "Joan", "john", "Jude", "JENS", "Judy", "Jo", "jUNE"]  # one initial, mixed case
+TAB_CROWD_IN_LONGS = ["jane", "Joan", "Jude", "Jo"]  # crowd names that are themselves options (exact strings)
+TAB_STAR = "J*"  # the name holding "*": -1000 against a missing name_obs, the initial class against "J."
+# every crowd name and TAB_STAR is a short version of this option
+TAB_CROWD_LONG = "Jack*JaneJillJoanJohnJudeJensJudyJune"
+TAB_CROWD_MORE = ["Jackson", "Joanne", "Johanna", "Judith", "Jensen", "Jolene", "Juliane", "Jeanette"]  # so that n differs
+
+
+def _insert(rng, w, k, letters="xyzwvq"):
+    w = list(w)
+    for _ in range(k):
+        w.insert(int(rng.integers(0, len(w) + 1)), letters[int(rng.integers(0, len(letters)))])
+    return "".join(ch.upper() if rng.random() < 0.3 else ch for ch in w)
+
+
+def _mixed_names(rng, n, taken):
+    """n names of 4-7 letters over a-p in mixed case, no two equal ignoring case, none starting with j or q"""
+    out, seen = [], {t.lower() for t in taken}
+    while len(out) < n:
+        w = "".join(rng.choice(list("abcdefghiklmnop"), size=int(rng.integers(4, 8))))
+        if w in seen:
+            continue
+        seen.add(w)
+        out.append(w.capitalize() if len(out) % 3 == 0 else (w.upper() if len(out) % 3 == 1 else w))
+    return out
+
+
+def _swapped(w):
+    return w.swapcase()
+
+
+def _tab_free(kinds):
+    """the rows the cases without a current referent free: the flat rows and every third initial row"""
+    ini = [i for i, k in enumerate(kinds) if k == "initial"]
+    return np.array(sorted(ini[::3] + [i for i, k in enumerate(kinds) if k == "flat"]), dtype=np.int64)
+
+
+def tab_free_rows(S):
+    return _tab_free(list(S["kind"]))
+
+
+def free_rows(S, rows, blocks=(0,)):
+    """cur = -1 on `rows` (initialize_trace's state): the referents lose the reference, none loses its last one"""
+    tr = S["trace"]
+    for bi in blocks:
+        t = tr.tables[S["lw"].blocks[bi]["root_class"]]
+        for i in rows:
+            t.counts[tr.cur[bi, i]] -= 1
+            assert t.counts[tr.cur[bi, i]] >= 1
+            tr.cur[bi, i] = -1
+
+
+def tab_spread_rows(S):
+    """the initial rows: about ten candidates of the initial class within a few nats of each other"""
+    return np.flatnonzero(S["kind"] == "initial").astype(np.int64)
+
+
+def tab_draw_program(n_table, seed=0, n_dead=0, as_typos=False, second_block=0):
+    """`A: x ~ ChooseUniformly(names)`,
+    `Obs: a ~ A; name_obs ~ FormatName(a.x); long_obs ~ ExpandOnShortVersion(a.x, longs); typo ~ AddTypos(a.x)`
+    with a latent table of n_table rows (n_dead of them dead, below the high-water mark).  Row kind in S['kind']:
+      equal   — name_obs is the entity's name in another case, the other two missing (the name is one of longs: the
+                short rule's missing column is 0 for it and -1000 for every name outside longs);
+      initial — name_obs is "J." / "j.", long_obs the option every crowd name is a short version of: ten names and
+                TAB_STAR in the initial class, weighted by their CRP counts and their own -log(n); typo missing on
+                every other row (the spread case);
+      long    — long_obs alone: FormatName's missing column separates ordinary names (-5) from TAB_STAR (-1000);
+      nolong  — name_obs an initial, long_obs missing: 0 for the crowd names among longs, -1000 for the others;
+      flat    — all three missing, 60 rows on one hub entity: the CRP prior over the entities named by an option;
+      tied    — pairs of entities with identical names;
+      new     — the row is its entity's only reference and observes a name of the domain that no entity holds
+                (a single name, two names equal ignoring case, or the initial of five unheld names with different n);
+      filler  — single-reference entities observed exactly; the filler names repeat.
+    The names domain holds mixed-case names, the ten crowd names, names that are options themselves, TAB_STAR and names
+    that are a short version of 1, 2 and 5 or more options.  The EMPTY NAME IS LEFT OUT: the lowering takes it, but the
+    AddTypos term on the same reference has no density for an empty clean value (add_typos.jl: NegativeBinomial(0, 0.9)
+    and log(0)), so no exact posterior exists for a row that observes typo.  FormatName's empty-name row of T is held
+    by the known answers and the restatement agreement of tests/test_tabulated_terms.py instead.
+    as_typos: the two tabulated terms declared as AddTypos on the same references (the routing contrast).
+    second_block: a second, independent block `b ~ B; w ~ AddTypos(b.z)` with a table of that many rows."""
+    from pclean_amd.model import AddTypos, ChooseUniformly, ExpandOnShortVersion, FormatName, LoweredModel, Model, Query
+    from pclean_amd.trace import Trace
+    rng = np.random.default_rng(seed)
+    ents, rows = [], []  # ents: name per latent row (None = dead); rows: (kind, entity, name_obs, long_obs, typo)
+
+    def ent(w):
+        ents.append(w)
+        return len(ents) - 1
+
+    longs = [TAB_CROWD_LONG] + list(TAB_CROWD_MORE) + list(TAB_CROWD_IN_LONGS)
+    taken = set(TAB_CROWD) | {TAB_STAR}
+    # ordinary names with 1, 2 or 5 long forms of their own; `own` = names that are options themselves
+    plain = _mixed_names(rng, 36, taken)
+    taken.update(plain)
+    forms = {}
+    for k, w in enumerate(plain):
+        forms[w] = []
+        while len(forms[w]) < (1, 2, 5)[k % 3]:
+            f = _insert(rng, w, int(rng.integers(1, 5)))
+            if f not in longs:
+                forms[w].append(f)
+                longs.append(f)
+    own = _mixed_names(rng, 10, taken)
+    taken.update(own)
+    longs += own
+    for w in own:
+        forms[w] = [w]
+    # crowd: every name on 1-3 entities with unequal reference counts, TAB_STAR on one
+    crowd_e = {}
+    for k, w in enumerate(TAB_CROWD + [TAB_STAR]):
+        crowd_e[w] = [ent(w) for _ in range(1 + k % 3)]
+    k = 0
+    # two initial rows per crowd entity (freeing one leaves the entity alive), a third on some; typo on every other entity's:
+    # the rows of an entity share one expected distribution, which gof pools
+    for w, es in crowd_e.items():
+        for e in es:
+            for j in range(2 + (k % 4 == 0)):
+                rows.append(("initial", e, "J." if (k + j) % 4 else "j.", TAB_CROWD_LONG, w if k % 2 else None))
+            k += 1
+    for k in range(20):
+        w = TAB_CROWD_IN_LONGS[k % 4]
+        e = crowd_e[w][k % len(crowd_e[w])]
+        rows.append(("nolong", e, "j." if k % 3 == 0 else "J.", None, w if k % 2 else None))
+    for k in range(10):  # long rows of the crowd: every crowd name, -5 - log(n) each, TAB_STAR at -1000
+        w = TAB_CROWD[k]
+        rows.append(("long", crowd_e[w][0], None, TAB_CROWD_LONG, None))
+    eq_e = {w: [ent(w), ent(w)] for w in own[:5]}
+    for k in range(20):
+        w = (own[:5] + TAB_CROWD_IN_LONGS)[k % 9]
+        es = eq_e.get(w) or crowd_e[w]
+        rows.append(("equal", es[k % len(es)], _swapped(w), None, None))
+    for k, w in enumerate(plain[:12]):  # long rows of ordinary names
+        e = ent(w)
+        rows += [("long", e, None, forms[w][j % len(forms[w])], None) for j in range(2)]
+    for k, w in enumerate(plain[12:18]):
+        e1, e2 = ent(w), ent(w)
+        f = forms[w]
+        rows += [("tied", e1, None, f[0], _typo(rng, w)), ("tied", e2, w.upper(), f[-1], w),
+                 ("tied", e1, w[0] + ".", f[0], None), ("tied", e2, w.lower(), f[-1], _typo(rng, w))]
+    hub = ent(own[5])
+    rows += [("flat", hub, None, None, None)] * 60
+    rows += [("equal", hub, _swapped(own[5]), None, None)] * 2  # (the hub outlives its flat rows being freed)
+    # names no entity holds: ten single ones, two pairs equal ignoring case, five with one initial
+    fresh = _mixed_names(rng, 10, taken)
+    taken.update(fresh)
+    for k, w in enumerate(fresh):
+        forms[w] = [_insert(rng, w, 2) for _ in range(1 + k % 2)]
+        longs += forms[w]
+    pairs = [("Quinn", "QUINN"), ("quade", "Quade")]
+    for a_, b_ in pairs:
+        forms[a_] = forms[b_] = [a_ + "xy"]
+        longs.append(a_ + "xy")
+    q_names = ["Quill", "quint", "QUIRE", "Quoin", "Quota"]
+    q_long = "QuillQuintQuireQuoinQuota"
+    longs += [q_long, "Quillon", "Quintet", "Quintal", "Quotas"]
+    pool = plain[18:] + _mixed_names(rng, 110, taken)  # filler names: about eight entities each at 1090 rows
+    taken.update(pool)
+    for w in pool:
+        if w not in forms:
+            forms[w] = [_insert(rng, w, 2)]
+            longs += forms[w]
+    assert len(set(longs)) == len(longs)
+    n_dead_at = set(range(len(ents) + 10, len(ents) + 10 + 7 * n_dead, 7)) if n_dead else set()
+    new_obs = ([(_swapped(w), forms[w][0], w if k % 2 else None) for k, w in enumerate(fresh)]
+               + [(a_.lower(), forms[a_][0], None) for a_, b_ in pairs] + [(b_, forms[a_][0], None) for a_, b_ in pairs]
+               + [("Q." if k % 2 else "q.", q_long, q_names[k % 5] if k >= 5 else None) for k in range(10)])
+    assert len(new_obs) == 24
+    for name_obs, long_obs, typo in new_obs:
+        while len(ents) in n_dead_at:
+            ents.append(None)
+        w = pool[len(ents) % len(pool)]
+        rows.append(("new", ent(w), name_obs, long_obs, typo))
+    assert n_table - len(ents) > 0
+    k = 0
+    while len(ents) < n_table:
+        if len(ents) in n_dead_at:
+            ents.append(None)
+            continue
+        w = pool[k % len(pool)]
+        k += 1
+        rows.append(("filler", ent(w), w, forms[w][0], w))
+    names = sorted({w for w in ents if w is not None} | set(plain) | set(own) | set(fresh) | set(q_names)
+                   | {x for p_ in pairs for x in p_})
+    m = Model()
+    a = m.add_class("A")
+    a.choice("x", ChooseUniformly(names))
+    bwords = None
+    if second_block:
+        bwords = _words(rng, 40, lo=18, hi=25, alphabet="qrstuvwxyz")
+        b = m.add_class("B")
+        b.choice("z", ChooseUniformly(bwords))
+    o = m.add_class("Obs")
+    with o.block():
+        o.fk("a", "A")
+        o.choice("name_obs", AddTypos("a.x") if as_typos else FormatName("a.x"))
+        o.choice("long_obs", AddTypos("a.x") if as_typos else ExpandOnShortVersion("a.x", longs))
+        o.choice("typo", AddTypos("a.x"))
+    bind = {"Name": ("a.x", "name_obs"), "Long": ("a.x", "long_obs"), "Typo": ("a.x", "typo")}
+    if second_block:
+        with o.block():
+            o.fk("b", "B")
+            o.choice("w", AddTypos("b.z"))
+        bind["W"] = ("b.z", "w")
+    q = Query(m, "Obs", bind)
+    n = len(rows)
+    dirty = {"Name": [r[2] for r in rows], "Long": [r[3] for r in rows], "Typo": [r[4] for r in rows]}
+    bcur = None
+    if second_block:  # B rows holding one of 40 long words; w the word or the word with one typo
+        bvals = [bwords[k % len(bwords)] for k in range(second_block)]
+        assert n >= second_block + 70
+        bcur = np.arange(n) % second_block  # every B row is referred to; the rows of tab_free_rows share theirs with a
+        free = _tab_free([r[0] for r in rows])  # row past the table's size, so that freeing them deletes no B row
+        bcur[second_block:second_block + len(free)] = bcur[free]
+        dirty["W"] = [bvals[k] if i % 3 else _typo(rng, bvals[k], "qrstuvwxyz") for i, k in enumerate(bcur)]
+    lw = LoweredModel(m, q, dirty)
+    obs = lw.encode_observations(dirty)
+    tr = Trace(lw, n, seed)
+    dom = lw.latent_dom[("A", "x")]
+    t = tr.tables["A"]
+    for k, w in enumerate(ents):
+        assert tr.insert_row("A", np.array([dom.index_of(w if w is not None else names[0])], np.int32)) == k
+    for i, r in enumerate(rows):
+        tr.cur[0, i] = r[1]
+        t.counts[r[1]] += 1
+    for k, w in enumerate(ents):
+        if w is None:
+            tr.delete_row("A", k)
+    assert t.n == n_table and int((~t.live[:t.n]).sum()) == len([w for w in ents if w is None])
+    if second_block:
+        bdom, tb = lw.latent_dom[("B", "z")], tr.tables["B"]
+        for k in range(second_block):
+            assert tr.insert_row("B", np.array([bdom.index_of(bvals[k])], np.int32)) == k
+        for i, k in enumerate(bcur):
+            tr.cur[1, i] = k
+        for k in range(second_block):
+            tb.counts[k] = int((bcur == k).sum())
+        assert (tb.counts[:second_block] > 0).all() and (tb.counts[bcur[free]] >= 2).all()
+    return dict(lw=lw, trace=tr, obs=obs, query=q, dirty=dirty, model=m, kind=np.array([r[0] for r in rows]),
+                names=names, longs=longs)
+
+
 # ---- draws of the product's sweeps as candidates ------------------------------------------------------------------
 class Encoder:
     """candidate <-> int code of one block: an existing key k is k, a new row with option j of its own choice is
@@ -558,6 +826,10 @@ SPREAD_SWEEPS = 2000   # sweeps of the spread-row case: a 0.1-nat shift moves p 
 SPREAD_P = 2
 PROGRAMS = {"generic": dict(n_table=300, seed=0, n_dead=0), "fast": dict(n_table=1090, seed=0, n_dead=5)}
 TWO_BLOCK = dict(n_table=1090, seed=1, two_blocks=True)
+PROGRAMS_TAB = {"generic": dict(n_table=300, seed=0, n_dead=0), "large": dict(n_table=1090, seed=0, n_dead=5)}
+TAB_PARTICLES = [(1, False), (2, False), (2, True), (9, False), (33, False), (64, False)]
+TAB_LATENT = [(2, False), (2, True), (9, False)]
+TAB_MIXED = dict(PROGRAMS_TAB["large"], second_block=1100)  # block 1's table: 1100 rows, the fast root path
 
 
 def two_block_rows(S):
@@ -617,13 +889,15 @@ def latent_exact(S, rc, live, ev_off, ev_rows, items):
     return out
 
 
-def latent_case(eng, S, rc, P, mh, n_sweeps, seed, every=3):
+def latent_case(eng, S, rc, P, mh, n_sweeps, seed, every=3, exact=None):
     """sweep_latent over every live row of A, n_sweeps times (sweep_idx 0..n_sweeps-1): the chosen particle 0 keeps
     the current value, any other draws from pi -> (1/P) d_cur + (1 - 1/P) pi under PG, MH_ACCEPT pi + ... under MH"""
     from pclean_amd.engine import InferenceConfig
     live, ev_off, ev_rows, ev_ctx, excl = latent_setup(S)
     items = np.arange(0, len(live), every)
-    exact = latent_exact(S, rc, live, ev_off, ev_rows, items)
+    if exact is None:  # (a caller with several cases over one frozen trace passes latent_exact's result for `items`)
+        exact = latent_exact(S, rc, live, ev_off, ev_rows, items)
+    assert len(exact) == len(items)
     root = S["lw"].latent_plans["A"]["roots"][0]
     cfg = InferenceConfig(1, P, use_mh_instead_of_pg=mh)
     D = np.empty((n_sweeps, len(items)), dtype=np.int64)
@@ -639,3 +913,31 @@ def latent_case(eng, S, rc, P, mh, n_sweeps, seed, every=3):
         e = mh_one_block(pi, cur) if mh else pg_one_block(pi, cur, P)
         res.append((int(t), e, tabulate(D[:, j].tolist())))
     return gof(res)
+
+
+def mixed_case(eng, S, rc, rows, P, n_sweeps, seed):
+    """n_sweeps sweeps of a program with two INDEPENDENT blocks over rows without a current referent in either; one
+    G-test per block against the block's own pi.  Returns ([gof of block 0, gof of block 1], max logml deviation)."""
+    from pclean_amd.engine import InferenceConfig
+    tr = S["trace"]
+    encs = [Encoder(S["lw"], tr, bi) for bi in (0, 1)]
+    cfg = InferenceConfig(1, P)
+    n = tr.cur.shape[1]
+    D = np.empty((2, n_sweeps, len(rows)), dtype=np.int64)
+    exact = [[rc.block_alone(int(i), bi) for i in rows] for bi in (0, 1)]
+    dev = 0.0
+    for s in range(n_sweeps):
+        choice, chosen, logml, new_rows = eng.sweep(tr, cfg, seed, s)
+        for bi in (0, 1):
+            D[bi, s] = encs[bi].codes(choice[bi], new_rows.get(bi), n)[rows]
+        if s == 0:
+            for j, i in enumerate(rows):
+                z = exact[0][j][1] + exact[1][j][1]
+                n_terms = sum(e.n_table + len(e.opt) + 1 for e in encs)
+                dev = max(dev, abs(float(logml[i]) - z) / logml_bound(n_terms, z))
+    out = []
+    for bi in (0, 1):
+        items = [(int(i), {encs[bi].code(k): v for k, v in exact[bi][j][0].items() if v > 0}, tabulate(D[bi, :, j].tolist()))
+                 for j, i in enumerate(rows)]
+        out.append(gof(items))
+    return out, dev

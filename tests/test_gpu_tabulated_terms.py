@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import posterior_exact as pe
 import tabulated_program as tp
 from pclean_amd import _lib
 from pclean_amd._lib import HipContext, PCleanHipError
@@ -230,6 +231,9 @@ def _restated_scores(S):
         out[nid] = sc
         lse[nid], got, _ = eng.hip.score_node(0, nid, rows, n_cand=len(opts), want_scores=True)
         out[("device", nid)] = got
+        for i in range(n):  # the leaf marginal the slot's new row takes from the device, against the restated scores
+            z = pe.log_marginal(dict(enumerate(sc[i].tolist())))
+            assert abs(float(lse[nid][i]) - z) <= pe.logml_bound(len(opts), z), (nid, i, float(lse[nid][i]), z)
     t = tr.tables["Person"]
     cols, counts = t.view()
     full, m1, scal = eng.hip.get_table_priors(lw.table_id["Person"], t.n)

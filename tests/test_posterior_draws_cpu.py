@@ -12,7 +12,13 @@ leg's cases (posterior_exact.PROGRAMS / TWO_BLOCK, S_GPU, SPREAD_SWEEPS): every 
 p < 1e-6 and exact samples must pass.  The pooled all-row cases catch the gross mutations (the dropped 1/P mass, an
 inverted MH acceptance, paired sweep indices); a 0.1-nat shift of a near candidate moves a probability p by about
 0.1 p (1 - p) and is caught by the spread-row case (SPREAD_SWEEPS draws of the rows that hold a near candidate),
-not by the all-row cases at S_GPU."""
+not by the all-row cases at S_GPU.
+
+The tabulated kind (FormatName, ExpandOnShortVersion) has no CPU oracle leg: neither oracle layer below the literal
+interpreter knows the two distributions.  Its part here states the conditions the device leg's inputs must meet
+(posterior_exact.tab_draw_program) and measures the power of tests/test_gpu_tabulated_draws.py's cases against four
+mistakes of a sweep: a skipped missing observation, two exchanged classes, a dropped -log(n), a class byte read one
+column off."""
 import numpy as np
 import pytest
 
@@ -175,3 +181,162 @@ def test_power_sweep_indices_identical(gpu_case):
     res = pe.gof(_items(rng, exact, exact, pe.S_GPU, pairs=True))
     print("two sweep indices with one draw:", pe.describe(res))
     assert res["p"] < 1e-6
+
+
+# ---- the tabulated kind (FormatName, ExpandOnShortVersion): conditions on the inputs and the power of the device leg ----
+import contextlib  # noqa: E402
+import math  # noqa: E402
+
+import tabulated_program as tp  # noqa: E402
+
+lit = pe.lit
+
+
+def _mutations(S):
+    """the four mistakes the device leg (tests/test_gpu_tabulated_draws.py) must be able to see, as replacements of the
+    literal interpreter's two densities: {name: (format_name_logpdf, expand_on_short_version_logpdf)}"""
+    f0, g0 = lit.format_name_logpdf, lit.expand_on_short_version_logpdf
+    EQUAL, INITIAL = math.log(0.9999), math.log(0.0001)
+    dom = S["lw"].latent_dom[("A", "x")]
+    strings = [dom.string(v) for v in range(len(dom))]
+    nxt = {w: strings[(v + 1) % len(strings)] for v, w in enumerate(strings)}  # the value one column further
+
+    def f_skip(o, name):
+        return 0.0 if o is None else f0(o, name)
+
+    def g_skip(o, short, options):
+        return 0.0 if o is None else g0(o, short, options)
+
+    def f_swap(o, name):
+        v = f0(o, name)
+        return v if o is None or name == "" or v == EQUAL else (-1000.0 if v == INITIAL else INITIAL)
+
+    def g_one(o, short, options):
+        v = g0(o, short, options)
+        return v if o is None or v == -1000.0 else -0.0
+
+    def f_next(o, name):  # class byte of (o, next value), density row of the value itself
+        if o is None or name == "":
+            return f0(o, name)
+        return f0(o, nxt[name]) if nxt[name] != "" else -1000.0
+
+    def g_next(o, short, options):
+        if o is None:
+            return g0(o, short, options)
+        if not lit._is_short_version(nxt[short], o):
+            return -1000.0
+        n = sum(1 for x in options if lit._is_short_version(short, x))
+        return -math.log(n) if n > 0 else -1000.0
+
+    return {"exact": (f0, g0), "a: missing observation skipped": (f_skip, g_skip), "b: classes 1 and 2 exchanged": (f_swap, g0),
+            "c: -log(n) dropped": (f0, g_one), "d: class byte one column off": (f_next, g_next)}
+
+
+@contextlib.contextmanager
+def _densities(f, g):
+    f0, g0 = lit.format_name_logpdf, lit.expand_on_short_version_logpdf
+    lit.format_name_logpdf, lit.expand_on_short_version_logpdf = f, g
+    try:
+        yield
+    finally:
+        lit.format_name_logpdf, lit.expand_on_short_version_logpdf = f0, g0
+
+
+def _tab_variant(name, f, g):
+    """(pi, current) per row of every case of the device leg, under the densities f, g"""
+    with _densities(f, g):
+        S = pe.tab_draw_program(**pe.PROGRAMS_TAB[name])
+        rc = pe.RowConditionals(S)
+        tr = S["trace"]
+        out = {"S": S, "rows": pe.check_rows(S)}
+        out["obs"] = [(rc.block0(int(i)), int(tr.cur[0, i])) for i in out["rows"]]
+        out["spread"] = [(rc.block0(int(i)), int(tr.cur[0, i])) for i in pe.tab_spread_rows(S)]
+        live, ev_off, ev_rows, ev_ctx, excl = pe.latent_setup(S)
+        out["latent"] = pe.latent_exact(S, rc, live, ev_off, ev_rows, np.arange(len(live)))
+        out["hub_evidence"] = int((ev_off[1:] - ev_off[:-1]).max())
+        F = pe.tab_draw_program(**pe.PROGRAMS_TAB[name])
+        free = pe.tab_free_rows(F)
+        pe.free_rows(F, free)
+        rcf = pe.RowConditionals(F)
+        out["free"] = [(rcf.block0(int(i)), None) for i in free]
+    return out
+
+
+@pytest.fixture(scope="module", params=list(pe.PROGRAMS_TAB))
+def tab_cases(request):
+    S = pe.tab_draw_program(**pe.PROGRAMS_TAB[request.param])
+    return request.param, {m: _tab_variant(request.param, f, g) for m, (f, g) in _mutations(S).items()}
+
+
+def _tab_closed_forms(v):
+    """{case name: ([closed-form output distribution per row], draws per row)} — the cases of the device leg"""
+    out = {}
+    for P, mh in pe.TAB_PARTICLES:
+        out[f"observed P{P}{'-MH' if mh else ''}"] = ([pe.mh_one_block(pi, s) if mh else pe.pg_one_block(pi, s, P)
+                                                       for (pi, z), s in v["obs"]], pe.S_GPU)
+    out["no referent P3"] = ([dict(pi) for (pi, z), s in v["free"]], pe.S_GPU)
+    out["spread rows"] = ([pe.pg_one_block(pi, s, pe.SPREAD_P) for (pi, z), s in v["spread"]], pe.SPREAD_SWEEPS)
+    for P, mh in pe.TAB_LATENT:
+        out[f"latent P{P}{'-MH' if mh else ''}"] = ([pe.mh_one_block(pi, c) if mh else pe.pg_one_block(pi, c, P)
+                                                     for pi, c in v["latent"]], pe.S_GPU)
+    return out
+
+
+def test_tab_program_conditions(tab_cases):
+    """conditions on the inputs of the device leg (not measurements): every checked row is carried by ordinary terms,
+    every class byte and both missing columns are scored with and without the AddTypos term, and little of a row's
+    expected mass sits in gof's pooled cell"""
+    name, variants = tab_cases
+    v = variants["exact"]
+    S = v["S"]
+    t = S["trace"].tables["A"]
+    kinds = S["kind"]
+    for k in ("equal", "initial", "long", "nolong", "tied", "new", "filler"):
+        assert (kinds == k).sum() >= 20, k
+    assert (kinds == "flat").sum() == 60 and v["hub_evidence"] > 60  # (more than a wavefront of missing observations)
+    if name == "large":
+        assert t.n >= 1024 and ((t.n + 15) & ~15) % 64 != 0 and not t.live[:t.n].all()
+    for (pi, z), s in v["obs"] + v["free"]:
+        assert z > -100.0
+    names, longs, d = S["names"], S["longs"], S["dirty"]
+    assert "" not in names and sum(w.startswith(("J", "j")) for w in names) >= 8 and any("*" in w for w in names)
+    assert set(names) & set(longs) and any(w != w.lower() and w != w.upper() for w in names)
+    n_of = {w: sum(tp.is_short_version(w, x) for x in longs) for w in names}
+    assert {1, 2} <= set(n_of.values()) and max(n_of.values()) >= 5
+    seen = set()
+    for i in v["rows"]:
+        typo = d["Typo"][i] is not None
+        for w in names:  # (every name is a candidate: through the entities that hold it or through the new row)
+            seen.add(("format", 3 if d["Name"][i] is None else tp.format_name_class(d["Name"][i], w), typo))
+            seen.add(("short", 3 if d["Long"][i] is None else tp.pair_class(tp.SHORT, d["Long"][i], w), typo))
+    assert seen == {("format", c, t_) for c in (0, 1, 2, 3) for t_ in (False, True)} | {("short", c, t_) for c in (0, 1, 3) for t_ in (False, True)}
+    for case, (exp, n) in _tab_closed_forms(v).items():
+        if case.startswith(("observed", "no referent")):
+            share = pe.pooled_mass(exp, n)
+            print(f"[{name}] {case}: at most {share:.3f} of a row's mass in the pooled cell")
+            assert share <= 0.25, case
+
+
+def test_tab_power_exact_samples_pass(tab_cases):
+    name, variants = tab_cases
+    rng = np.random.default_rng(11)
+    for case, (exp, n) in _tab_closed_forms(variants["exact"]).items():
+        res = pe.gof(_items(rng, exp, exp, n))
+        print(f"[{name}] {case}: {pe.describe(res)}")
+        assert res["p"] > pe.ALPHA, (case, pe.describe(res))
+
+
+@pytest.mark.parametrize("mutation", ["a", "b", "c", "d"])
+def test_tab_power_mutation_is_caught(tab_cases, mutation):
+    """each mutated sampler fails pe.ALPHA on at least one case of the device leg, at the device leg's number of sweeps"""
+    name, variants = tab_cases
+    (key,) = [k for k in variants if k.startswith(mutation + ":")]
+    exact, bad = _tab_closed_forms(variants["exact"]), _tab_closed_forms(variants[key])
+    rng = np.random.default_rng(12)
+    caught = []
+    for case in exact:
+        res = pe.gof(_items(rng, exact[case][0], bad[case][0], exact[case][1]))
+        if res["p"] < pe.ALPHA:
+            caught.append(case)
+            print(f"[{name}] {key} fails {case}: {pe.describe(res)}")
+    assert caught, f"{key} passes every case of the {name} program"

@@ -1,9 +1,17 @@
 """Tabulated likelihood terms (ExpandOnShortVersion, FormatName) on the host: the restatement's known answers, what the
-lowering emits for tests/tabulated_program.py, and every refusal of the lowering."""
+lowering emits for tests/tabulated_program.py, every refusal of the lowering, and the literal interpreter's two densities
+(oracle/literal.py, on strings) against known answers and against the table-shaped restatement."""
+import math
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import tabulated_program as tp
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import literal as lit  # noqa: E402
 from pclean_amd import _lib
 from pclean_amd.encode import StringPool
 from pclean_amd.engine import class_density_rows
@@ -149,3 +157,107 @@ def test_existing_terms_are_unchanged():
     lw = LoweredModel(m, Query(m, "Obs", {"Typo": ("p.name", "name_typo")}), {"Typo": ["Jim", "Amn"]})
     assert lw.class_pairs == {} and len(lw.pair_id) == 1
     assert lw.block_arrays(0)[0][1]["cacheable"] == 1
+
+
+# ---- the literal interpreter's densities (oracle/literal.py): strings in, float64 out -------------------------------------
+EQUAL, INITIAL, NEITHER = math.log(0.9999), math.log(0.0001), -1000.0
+
+
+def test_literal_format_name_known_answers():
+    f = lit.format_name_logpdf
+    assert f("JIM", "jim") == EQUAL and f("j.", "Jim") == INITIAL and f("Tim", "Jim") == NEITHER
+    # format_name.jl:49 — the initial form of the one-letter name "J" is "J."; the name "J." observed as "J" is neither
+    assert f("J.", "J") == INITIAL
+    assert f("J", "J.") == NEITHER
+    assert f("j.", "J.") == EQUAL  # (equality is asked first, format_name.jl:47)
+    # the empty name: every observation is impossible, the missing one certain (format_name.jl:35-36, 44-46)
+    assert f("", "") == NEITHER and f("x", "") == NEITHER and f(".", "") == NEITHER and f(None, "") == 0.0
+    # a name holding "*": impossible against a missing observation, an ordinary name against a present one
+    assert f(None, "a*b") == -1000.0 and f("A*B", "a*b") == EQUAL and f("a.", "a*b") == INITIAL and f("*.", "*") == INITIAL
+    assert f(None, "Jim") == -5.0
+    # character-by-character folding: U+0130 lowercases to two characters and stands for itself
+    assert f("\u0130x", "\u0130X") == EQUAL and f("i\u0307x", "\u0130x") == NEITHER
+    assert f("\u00c9mile", "\u00e9MILE") == EQUAL and f("\u00e9.", "\u00c9mile") == INITIAL
+    assert all(isinstance(f(o, n), float) for o, n in [("a", "a"), ("a.", "ab"), ("b", "a"), (None, "a"), (None, ""), ("a", "")])
+
+
+def test_literal_short_version_known_answers():
+    g = lit.expand_on_short_version_logpdf
+    opts = ["Sam", "Samuel", "Samantha", "Alan", "sal", "Bob"]
+    assert g("Bob", "zz", opts) == -1000.0 and g(None, "zz", opts) == -1000.0      # a short version of no option
+    assert g("Bob", "bb", opts) == -math.log(1) and g("Alan", "bb", opts) == -1000.0  # of one
+    assert g("Samuel", "sm", opts) == -math.log(3) == g("Samantha", "SM", opts)     # of several, ignoring case
+    assert g("Alan", "al", opts) == -math.log(3) and g("Bob", "al", opts) == -1000.0  # (Alan, sal, Samuel)
+    assert g("Sam", "Sam", opts) == -math.log(3)
+    # a missing observation: string membership of the value among the options, case and all (in(val, options))
+    assert g(None, "Sam", opts) == 0.0 and g(None, "sam", opts) == -1000.0 and g(None, "al", opts) == -1000.0
+    assert g("Bob", "", opts) == -math.log(6) and g(None, "", opts) == -1000.0      # the empty value fits every option
+    assert not lit._is_short_version("ab", "ba") and not lit._is_short_version("jimmy", "jim")
+    assert all(isinstance(g(o, v, opts), float) for o, v in [("Bob", "bb"), ("Bob", "zz"), (None, "Sam"), (None, "x")])
+
+
+def _some_strings(n, seed):
+    """strings of the kind test_gpu_tabulated_terms._strings makes (that module is GPU-marked: restated here): lengths
+    walking 0, 1, 2, 63, 64, 65, 300 over a small mixed-case alphabet, a few initial forms"""
+    rng = np.random.default_rng(seed)
+    alpha = "abAB.\u00c9\u00e9*"
+    out = []
+    for i in range(n):
+        L = [0, 1, 2, 63, 64, 65, 300][i % 7]
+        if i % 11 == 3:
+            out.append("abAB"[int(rng.integers(0, 4))] + ".")
+        else:
+            out.append("".join(alpha[int(rng.integers(0, len(alpha)))] for _ in range(L)))
+    return out
+
+
+def test_literal_densities_equal_the_table_restatement():
+    """two restatements written apart — oracle/literal.py on strings, tabulated_program on (T, class byte) — agree on
+    every (observed or missing, latent) pair, exactly"""
+    obs = sorted(set(_some_strings(230, 1)))
+    lat = _some_strings(240, 2)
+    rng = np.random.default_rng(3)
+    for j in range(0, len(lat), 4):  # class 0 of both rules, short versions, initials of latent strings, options as values
+        o = obs[int(rng.integers(0, len(obs)))]
+        lat[j] = (o.swapcase() if j % 8 == 0 else "".join(ch for ch in o if rng.random() < 0.5)) if j % 16 else o
+    lat = sorted(set(lat + [""]))
+    obs = sorted(set(obs + [v[0] + "." for v in lat[1:40]] + [""]))
+    assert len(obs) + len(lat) >= 300
+    for L in (0, 1, 2, 63, 64, 65, 300):
+        assert any(len(o) == L for o in obs) and any(len(v) == L for v in lat)
+    assert any(o != o.lower() and o != o.upper() for o in obs) and any(o.endswith(".") and len(o) == 2 for o in obs)
+    seen = {tp.SHORT: set(), tp.FORMAT: set()}
+    for rule in (tp.SHORT, tp.FORMAT):
+        options = obs if rule == tp.SHORT else None  # (the lowering requires an observed value to be an option)
+        T = tp.density_rows(rule, lat, options)
+        cls = tp.class_table(rule, obs, lat)
+        opts = tuple(obs)
+        for v, name in enumerate(lat):
+            got = lit.expand_on_short_version_logpdf(None, name, opts) if rule == tp.SHORT else lit.format_name_logpdf(None, name)
+            assert got == T[v, 3], (rule, None, name)
+            for u, o in enumerate(obs):
+                got = lit.expand_on_short_version_logpdf(o, name, opts) if rule == tp.SHORT else lit.format_name_logpdf(o, name)
+                assert got == T[v, cls[u, v]], (rule, o, name)
+                seen[rule].add(int(cls[u, v]))
+        seen[rule].update(("missing", float(x)) for x in T[:, 3])
+    assert {0, 1} <= seen[tp.SHORT] and {0, 1, 2} <= seen[tp.FORMAT]
+    assert {("missing", 0.0), ("missing", -1000.0)} <= seen[tp.SHORT]
+    assert {("missing", 0.0), ("missing", -1000.0), ("missing", -5.0)} <= seen[tp.FORMAT]
+
+
+def test_engine_density_rows_hold_the_reference_values():
+    """class_density_rows (what the engine uploads) against the literal densities on one value of every sort"""
+    names = ["", "a*b", "Jim", "J"]
+    T = class_density_rows(_lib.CLASS_FORMAT_NAME, names)
+    for v, name in enumerate(names):
+        seen = {0: name.upper(), 1: name[:1] + ".", 2: "zz"}
+        assert [T[v, c] for c in range(3)] == [lit.format_name_logpdf(seen[c], name) for c in range(3)] or name == ""
+        assert T[v, 3] == lit.format_name_logpdf(None, name)
+    assert list(T[0]) == [-1000.0, -1000.0, -1000.0, 0.0]
+    opts = ["Sam", "Samuel", "sal"]
+    vals = ["Sam", "sl", "zz"]
+    T = class_density_rows(_lib.CLASS_SHORT_VERSION, vals, opts, tp.short_counts(vals, opts))
+    assert T[0, 0] == lit.expand_on_short_version_logpdf("Samuel", "Sam", opts) == -math.log(2)
+    assert T[1, 0] == lit.expand_on_short_version_logpdf("sal", "sl", opts) == -math.log(2)
+    assert T[2, 0] == -1000.0 and (T[:, 1:3] == -1000.0).all()
+    assert [T[v, 3] for v in range(3)] == [lit.expand_on_short_version_logpdf(None, s, opts) for s in vals] == [0.0, -1000.0, -1000.0]
