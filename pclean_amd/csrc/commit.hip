@@ -14,9 +14,10 @@
 // phase clock of the commit kernel (PCLEAN_COMMIT_PROF=1 prints it): thread 0 stamps the constant-rate counter
 __device__ long long pcc_prof_t[64];
 __device__ int pcc_prof_n;
+__device__ int pcc_prof_wg;  // the workgroup (= plan of pcc_commit_mw_kernel) that stamps: PCLEAN_COMMIT_PROF_WG, default 0
 #define PCC_STAMP(name)                                                   \
   do {                                                                    \
-    if (tid == 0 && blockIdx.x == 0 && pcc_prof_n < 64) pcc_prof_t[pcc_prof_n++] = (long long)wall_clock64(); \
+    if (tid == 0 && (int)blockIdx.x == pcc_prof_wg && pcc_prof_n < 64) pcc_prof_t[pcc_prof_n++] = (long long)wall_clock64(); \
   } while (0)
 #define PCC_CUR_SEPARATE
 #include "commit_core.h"
@@ -72,6 +73,8 @@ struct CommitState {
   DevBuf<PccSums> d_sums;
   DevBuf<int> d_bar;   // arrival counter of pcc_commit_mw_kernel's barriers (monotone) ...
   int bar_count = 0;   // ... and its value when the next launch starts
+  PccBlock up_blocks[PCC_MAX_BLOCKS];  // what d_blocks holds, sweep_idx aside (pcc_prep_init_kernel writes that one) ...
+  int up_n = -1;                       // ... for so many plans; -1: nothing uploaded yet
   // several ranks (pclean_commit_device_dist): segment capacities (the same on every rank: from the window's size, then
   // from the last commit's global totals), the all-gather buffers, the gathered lists and the gathered-form blocks
   int cap_m[PCC_MAX_BLOCKS] = {0}, cap_k[PCC_MAX_BLOCKS] = {0};
@@ -133,28 +136,85 @@ void pclean_commit_table_reuploaded(pclean_ctx* ctx, int table_id) {
 }
 
 // ---- kernels --------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void pcc_commit_kernel(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks,
-                                                          int n_blocks, PccResult* res, int gathered) {
-  __shared__ int32_t part[1025];
-  if (threadIdx.x == 0) pcc_prof_n = 0;
-  if (threadIdx.x == 0 && !gathered) res->fallback_in = 0;  // (several ranks: pcc_merge_kernel wrote it; read by this thread)
-  if (threadIdx.x == 0)
-    for (int s = 0; s < n_slots; ++s) {
-      tb[s].state[PCC_ST_COLS_CHANGED] = 0;
-      tb[s].state[PCC_ST_CREATED] = 0;
-      tb[s].state[PCC_ST_DELETED] = 0;
-      tb[s].state[PCC_ST_NCHG] = 0;
+// what one thread does before a commit starts: the tables' per-commit words and the result's header
+__device__ void pcc_start(PccTable* tb, int n_slots, PccResult* res, int gathered) {
+  pcc_prof_n = 0;
+  if (!gathered) res->fallback_in = 0;  // (several ranks: pcc_merge_kernel wrote it; read by this thread)
+  for (int s = 0; s < n_slots; ++s) {
+    tb[s].state[PCC_ST_COLS_CHANGED] = 0;
+    tb[s].state[PCC_ST_CREATED] = 0;
+    tb[s].state[PCC_ST_DELETED] = 0;
+    tb[s].state[PCC_ST_NCHG] = 0;
+  }
+}
+
+// ---- phase A (pcc_prepare_block's four steps) as three chip-wide launches, grid.y = plan ------------------------------------
+// One workgroup walks the ~2 600 new-row records of a 1M-row sweep in three rounds per step, every round a chain of
+// dependent global-memory round trips (recpos -> record -> hash slot -> representative's record) its 16 waves cannot hide:
+// 88 us of the commit kernel's 190.  The steps touch scratch only and their records are independent (order-independent
+// atomics aside), so "all of step i before step i+1" is all they need, and a kernel boundary gives that.  Grids are sized
+// from host-known capacities (the record count stays on the device; threads beyond it do nothing) and exceed what is
+// co-resident: nothing in these kernels waits for another workgroup.  Whether the commit was refused before it started
+// (fallback_in) is fixed before the first of them; what they find themselves (PCC_FB_RECORDS, PCC_FB_DUMMY) stops no
+// step, exactly as in pcc_commit: the counts of a refused commit do not depend on timing.
+#define PCC_PREP_WG 256
+__global__ __launch_bounds__(PCC_PREP_WG) void pcc_prep_init_kernel(PccTable* tb, int n_slots, PccBlock* blocks, int n_blocks,
+                                                                    PccResult* res, int gathered, int sweep_idx, unsigned* sums,
+                                                                    int sums_words) {
+  const int tid = (int)(blockIdx.x * PCC_PREP_WG + threadIdx.x), nt = (int)(gridDim.x * PCC_PREP_WG), bi = (int)blockIdx.y;
+  const int refused = gathered ? res->fallback_in : 0;  // (one rank: thread 0 below is writing the word)
+  if (bi == 0 && tid == 0) {  // the only writer of these words in this launch
+    pcc_start(tb, n_slots, res, gathered);
+    pcc_reset_result(res);
+    for (int p = 0; p < n_blocks; ++p) {
+      blocks[p].sweep_idx = sweep_idx;  // (the one field that changes with every sweep: the blocks are not uploaded for it)
+      if (!refused) pcc_prepare_counts(blocks[p], p, res);
     }
-  pcc_commit(tb, n_slots, plans, blocks, n_blocks, res, part, (int)threadIdx.x, (int)blockDim.x);
+  }
+  if (bi == 0)  // the sums of pcc_refresh_kernel, which runs after the commit
+    for (int i = tid; i < sums_words; i += nt) sums[i] = 0u;
+  if (refused) return;
+  pcc_prepare_init(blocks[bi], tid, nt);
+}
+__global__ __launch_bounds__(PCC_PREP_WG) void pcc_prep_insert_kernel(const PccBlock* blocks, const PccResult* res) {
+  if (res->fallback_in) return;
+  pcc_prepare_insert(blocks[blockIdx.y], (int)(blockIdx.x * PCC_PREP_WG + threadIdx.x), (int)(gridDim.x * PCC_PREP_WG));
+}
+// steps 3 and 4 in one launch: the reuse step reads, of what step 3 wrote, only its own record's flags (same thread)
+__global__ __launch_bounds__(PCC_PREP_WG) void pcc_prep_classify_kernel(const PccTable* tb, const PccPlan* plans, const PccBlock* blocks,
+                                                                        PccResult* res) {
+  if (res->fallback_in) return;
+  const int tid = (int)(blockIdx.x * PCC_PREP_WG + threadIdx.x), nt = (int)(gridDim.x * PCC_PREP_WG), bi = (int)blockIdx.y;
+  pcc_prepare_classify(plans[bi], blocks[bi], bi, res, tid, nt);
+  pcc_prepare_reuse(tb, plans[bi], blocks[bi], res, tid, nt);
+}
+
+// prepared != 0: the launches above ran phase A (and pcc_start); what is left is pcc_commit's second half
+__global__ __launch_bounds__(1024) void pcc_commit_kernel(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks,
+                                                          int n_blocks, PccResult* res, int gathered, int prepared) {
+  __shared__ int32_t part[1025];
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  if (prepared) {
+    PCC_STAMP("start");
+    pcc_commit_apply(tb, n_slots, plans, blocks, n_blocks, res, part, tid, nt);
+    return;
+  }
+  if (tid == 0) pcc_start(tb, n_slots, res, gathered);
+  pcc_commit(tb, n_slots, plans, blocks, n_blocks, res, part, tid, nt);
 }
 
 // ---- one workgroup PER PLAN, when every plan's tables are its own (PccPlan::exclusive: hospital's Hospital / Measure slots,
-// every program of this image).  The one-workgroup kernel above walks the plans one after the other (1M rows: 90 us of
-// hashing the Measure slot's new-row records, then 65 us of reference counts + garbage collection of the Hospital plan,
-// then the Measure plan's creation and collection); their phases touch disjoint tables and disjoint scratch, so they run
-// side by side.  What they share — "is the commit refused?", decided before anything is modified — goes through a barrier
-// across the workgroups: a monotone device counter (never reset: the host passes the value it starts from), every
-// workgroup's thread 0 arrives and spins; the grid is one workgroup per plan (<= 16), always co-resident.
+// every program of this image).  The one-workgroup kernel above walks the plans one after the other (1M rows: 65 us of
+// reference counts + garbage collection of the Hospital plan, then the Measure plan's creation and collection); their
+// phases touch disjoint tables and disjoint scratch, so they run side by side.  What they share — "is the commit refused?",
+// decided before anything is modified — goes through a barrier across the workgroups: a monotone device counter (never
+// reset: the host passes the value it starts from), every workgroup's thread 0 arrives and spins; the grid is one
+// workgroup per plan (<= 16), always co-resident.
+// prepared != 0 (the default): phase A ran as the launches above, one barrier (after the capacity verdicts) is left.
+// prepared == 0 (PCLEAN_COMMIT_NARROW=1): phase A runs here, between a first barrier (the result's header is reset) and
+// that one.  The early exit after the first barrier reads fallback_in, which no workgroup writes after it: res->fallback
+// may already hold what a faster workgroup's phase A found, and a plan that skipped its own phase A for that would
+// report counts that depend on timing.
 __device__ void pcc_mw_barrier(int* ctr, int target) {
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -166,30 +226,25 @@ __device__ void pcc_mw_barrier(int* ctr, int target) {
   __syncthreads();
 }
 __global__ __launch_bounds__(1024) void pcc_commit_mw_kernel(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks,
-                                                             int n_blocks, PccResult* res, int gathered, int* bar, int bar0) {
+                                                             int n_blocks, PccResult* res, int gathered, int* bar, int bar0,
+                                                             int prepared) {
   __shared__ int32_t part[1025];
   const int tid = (int)threadIdx.x, nt = (int)blockDim.x, bi = (int)blockIdx.x;
-  if (bi == 0 && tid == 0) {  // what pcc_commit's first lines and the one-workgroup kernel's do
-    pcc_prof_n = 0;
-    if (!gathered) res->fallback_in = 0;
-    for (int s = 0; s < n_slots; ++s) {
-      tb[s].state[PCC_ST_COLS_CHANGED] = 0;
-      tb[s].state[PCC_ST_CREATED] = 0;
-      tb[s].state[PCC_ST_DELETED] = 0;
-      tb[s].state[PCC_ST_NCHG] = 0;
+  if (prepared) {
+    PCC_STAMP("start");
+  } else {
+    if (bi == 0 && tid == 0) {  // what pcc_commit's first lines and the one-workgroup kernel's do
+      pcc_start(tb, n_slots, res, gathered);
+      pcc_reset_result(res);
     }
-    res->fallback = res->fallback_in;
-    res->n_changed = 0;
-    for (int s = 0; s < PCC_MAX_SLOTS; ++s) res->alloc_upper[s] = 0;
-    for (int b = 0; b < PCC_MAX_BLOCKS; ++b) res->n_records[b] = res->n_distinct[b] = res->n_nested[b] = 0;
+    pcc_mw_barrier(bar, bar0 + n_blocks);
+    if (res->fallback_in) {  // (uniform: fixed before the barrier) — the second barrier's arrivals are still made: the host counts them
+      if (tid == 0) atomicAdd(bar, 1);
+      return;
+    }
+    pcc_prepare_block(tb, plans[bi], blocks[bi], bi, res, tid, nt);
+    __syncthreads();
   }
-  pcc_mw_barrier(bar, bar0 + n_blocks);
-  if (res->fallback) {  // (uniform: written before the barrier) — the second barrier's arrivals are still made: the host counts them
-    if (tid == 0) atomicAdd(bar, 1);
-    return;
-  }
-  pcc_prepare_block(tb, plans[bi], blocks[bi], bi, res, tid, nt);
-  __syncthreads();
   if (tid == 0) {  // the capacity of this plan's own tables (pcc_commit's check; every table has one user)
     const PccPlan& pl = plans[bi];
     for (int u = 0; u < pl.n_used; ++u) {
@@ -200,7 +255,7 @@ __global__ __launch_bounds__(1024) void pcc_commit_mw_kernel(PccTable* tb, int n
         atomicOr(&res->fallback, PCC_FB_CAPACITY);
     }
   }
-  pcc_mw_barrier(bar, bar0 + 2 * n_blocks);
+  pcc_mw_barrier(bar, bar0 + (prepared ? 1 : 2) * n_blocks);
   if (res->fallback) return;
   pcc_apply_block(tb, plans[bi], blocks[bi], bi, res, part, tid, nt);
 }
@@ -357,6 +412,7 @@ extern "C" int pclean_commit_enable(pclean_ctx* ctx, int32_t n_blocks, int32_t* 
     HIPCHK(ctx, hipHostMalloc((void**)&c->h_states, sizeof(int32_t) * PCC_MAX_SLOTS * PCC_ST_WORDS, hipHostMallocDefault));
   }
   c->tables_dirty = c->plans_dirty = true;
+  c->up_n = -1;
   c->enabled = true;
   *supported = 1;
   return PCLEAN_OK;
@@ -498,7 +554,8 @@ static int ensure_lut(pclean_ctx* ctx, CommitSlot& s, int64_t need) {
   return PCLEAN_OK;
 }
 
-static int launch_refresh(pclean_ctx* ctx, CommitState* c) {
+// zeroed: pcc_prep_init_kernel cleared the sums on its way
+static int launch_refresh(pclean_ctx* ctx, CommitState* c, bool zeroed = false) {
   PccRefreshAll ra{};
   int max_stride = 1;
   for (int si = 0; si < c->n_slots; ++si) {
@@ -507,7 +564,7 @@ static int launch_refresh(pclean_ctx* ctx, CommitState* c) {
     ra.t[si] = PccRefresh{t.counts.p, t.logc_full.p, t.logc_m1.p, s.lut.p, s.lut_n, t.n_rows};
     max_stride = std::max(max_stride, t.n_rows);
   }
-  { const int rcz = dev_zero(ctx, c->d_sums.p, sizeof(PccSums)); if (rcz) return rcz; }
+  if (!zeroed) { const int rcz = dev_zero(ctx, c->d_sums.p, sizeof(PccSums)); if (rcz) return rcz; }
   hipLaunchKernelGGL(pcc_refresh_kernel, dim3((max_stride + 255) / 256, c->n_slots), dim3(256), 0, ctx->stream, ra, c->d_res.p,
                      c->d_sums.p);
   {
@@ -599,7 +656,10 @@ static int commit_device_impl(pclean_ctx* ctx, int32_t n_blocks, uint32_t sweep_
     const Block& b = ctx->block[bi];
     BlockRun& r = s->run[bi];
     const PccPlan& pl = c->h_plans[p];
-    if (c->kcap[p] < 16384) c->kcap[p] = 16384;
+    // the scratch starts at 16384 records (PCLEAN_COMMIT_KCAP: another first capacity, e.g. a small one to see a sweep's
+    // records refused and the scratch regrown) and is doubled past what a commit needed
+    static const int kcap_min = getenv("PCLEAN_COMMIT_KCAP") ? std::max(1, atoi(getenv("PCLEAN_COMMIT_KCAP"))) : 16384;
+    if (c->kcap[p] < kcap_min) c->kcap[p] = kcap_min;
     const int kcap = c->kcap[p];
     int hsz = 1;
     while (hsz < 4 * kcap) hsz <<= 1;
@@ -634,7 +694,24 @@ static int commit_device_impl(pclean_ctx* ctx, int32_t n_blocks, uint32_t sweep_
     pb.newid = c->newid[p].p;
     pb.recpos = c->recpos[p].p;
   }
-  HIPCHK(ctx, hipMemcpyAsync(c->d_blocks.p, c->h_blocks, sizeof(PccBlock) * c->n_plans, hipMemcpyHostToDevice, ctx->stream));
+  // PCLEAN_COMMIT_NARROW=1 (and the one-workgroup kernel asked for by PCLEAN_COMMIT_ONE_WG=1): phase A inside the commit
+  // kernel, as before the wide launches
+  static const bool no_mw = getenv("PCLEAN_COMMIT_ONE_WG") != nullptr;
+  static const bool narrow = no_mw || getenv("PCLEAN_COMMIT_NARROW") != nullptr;
+  {
+    // the blocks change between sweeps of one window in sweep_idx alone, which pcc_prep_init_kernel takes as an argument:
+    // upload them only when something else did (another window, a sweep buffer that moved, more scratch)
+    bool same = !narrow && c->up_n == c->n_plans;
+    for (int p = 0; p < c->n_plans; ++p) {
+      PccBlock x = c->h_blocks[p];
+      x.sweep_idx = 0;
+      same = same && memcmp(&x, &c->up_blocks[p], sizeof x) == 0;
+      c->up_blocks[p] = x;
+    }
+    c->up_n = c->n_plans;
+    if (!same)
+      HIPCHK(ctx, hipMemcpyAsync(c->d_blocks.p, c->h_blocks, sizeof(PccBlock) * c->n_plans, hipMemcpyHostToDevice, ctx->stream));
+  }
   const PccBlock* commit_blocks = c->d_blocks.p;
   bool stats_reduced = false;
   int cur_rows = N;  // rows pcc_cur_kernel's grid is sized for
@@ -744,29 +821,52 @@ static int commit_device_impl(pclean_ctx* ctx, int32_t n_blocks, uint32_t sweep_
     for (int p = 0; p < c->n_plans; ++p) cur_rows = std::max<int64_t>(cur_rows, (int64_t)L.cap_m[p] * world);
   }
   // one workgroup per plan when no two plans share a table (pcc_commit_mw_kernel), else one workgroup for everything
-  static const bool no_mw = getenv("PCLEAN_COMMIT_ONE_WG") != nullptr;
   bool all_exclusive = c->n_plans > 1 && !no_mw;
   for (int p = 0; p < c->n_plans; ++p) all_exclusive = all_exclusive && c->h_plans[p].exclusive != 0;
+  static const bool prof = getenv("PCLEAN_COMMIT_PROF") != nullptr;
+  if (prof) {
+    const char* w = getenv("PCLEAN_COMMIT_PROF_WG");
+    const int wg = all_exclusive && w ? std::max(0, std::min(atoi(w), c->n_plans - 1)) : 0;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(pcc_prof_wg), &wg, sizeof wg);
+  }
+  if (!narrow) {  // phase A: three launches over the records of every plan (pcc_prep_*_kernel)
+    int kmax = 1, hmax = 1;
+    for (int p = 0; p < c->n_plans; ++p) {
+      kmax = std::max(kmax, c->kcap[p]);
+      int hsz = 1;
+      while (hsz < 4 * c->kcap[p]) hsz <<= 1;
+      hmax = std::max(hmax, hsz);
+    }
+    const dim3 g_rec((unsigned)((kmax + PCC_PREP_WG - 1) / PCC_PREP_WG), (unsigned)c->n_plans);
+    const dim3 g_init((unsigned)((std::max(kmax, hmax) + PCC_PREP_WG - 1) / PCC_PREP_WG), (unsigned)c->n_plans);
+    static_assert(sizeof(PccSums) % sizeof(unsigned) == 0, "pcc_prep_init_kernel clears the sums word by word");
+    hipLaunchKernelGGL(pcc_prep_init_kernel, g_init, dim3(PCC_PREP_WG), 0, ctx->stream, c->d_tables.p, c->n_slots,
+                       const_cast<PccBlock*>(commit_blocks), c->n_plans, c->d_res.p, dist ? 1 : 0, (int)sweep_idx,
+                       (unsigned*)c->d_sums.p, (int)(sizeof(PccSums) / sizeof(unsigned)));
+    hipLaunchKernelGGL(pcc_prep_insert_kernel, g_rec, dim3(PCC_PREP_WG), 0, ctx->stream, commit_blocks, c->d_res.p);
+    hipLaunchKernelGGL(pcc_prep_classify_kernel, g_rec, dim3(PCC_PREP_WG), 0, ctx->stream, c->d_tables.p, c->d_plans.p, commit_blocks,
+                       c->d_res.p);
+  }
   if (all_exclusive && !c->d_bar.p) {
     if (c->d_bar.alloc(16)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
     HIPCHK(ctx, hipMemsetAsync(c->d_bar.p, 0, 16 * sizeof(int), ctx->stream));
     c->bar_count = 0;
   }
   if (all_exclusive) {
-    if (c->bar_count > (1 << 30)) {  // (never in practice: 2 x plans per commit)
+    if (c->bar_count > (1 << 30)) {  // (never in practice: at most 2 x plans per commit)
       HIPCHK(ctx, hipMemsetAsync(c->d_bar.p, 0, 16 * sizeof(int), ctx->stream));
       c->bar_count = 0;
     }
     hipLaunchKernelGGL(pcc_commit_mw_kernel, dim3(c->n_plans), dim3(1024), 0, ctx->stream, c->d_tables.p, c->n_slots, c->d_plans.p,
-                       commit_blocks, c->n_plans, c->d_res.p, dist ? 1 : 0, c->d_bar.p, c->bar_count);
-    c->bar_count += 2 * c->n_plans;
+                       commit_blocks, c->n_plans, c->d_res.p, dist ? 1 : 0, c->d_bar.p, c->bar_count, narrow ? 0 : 1);
+    c->bar_count += (narrow ? 2 : 1) * c->n_plans;  // the barriers of this launch
   } else {
     hipLaunchKernelGGL(pcc_commit_kernel, dim3(1), dim3(1024), 0, ctx->stream, c->d_tables.p, c->n_slots, c->d_plans.p,
-                       commit_blocks, c->n_plans, c->d_res.p, dist ? 1 : 0);
+                       commit_blocks, c->n_plans, c->d_res.p, dist ? 1 : 0, narrow ? 0 : 1);
   }
   hipLaunchKernelGGL(pcc_cur_kernel, dim3(std::max(1, std::min(1024, (cur_rows + 255) / 256)), c->n_plans), dim3(256), 0, ctx->stream,
                      commit_blocks, c->d_res.p);
-  int rc = launch_refresh(ctx, c);
+  int rc = launch_refresh(ctx, c, !narrow);
   if (rc) return rc;
   rc = d2h_small(ctx, c->h_res, c->d_res.p, sizeof(PccResult));
   if (!rc) rc = d2h_small(ctx, c->h_states, c->d_states.p, sizeof(int32_t) * PCC_MAX_SLOTS * PCC_ST_WORDS);
@@ -778,7 +878,6 @@ static int commit_device_impl(pclean_ctx* ctx, int32_t n_blocks, uint32_t sweep_
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the ONE synchronisation of sweep + commit
   rc = pclean_sweep_finish_synced(ctx);
   if (rc) return rc;
-  static const bool prof = getenv("PCLEAN_COMMIT_PROF") != nullptr;
   if (prof) {
     long long t[64];
     int n = 0;

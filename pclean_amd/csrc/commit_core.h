@@ -9,9 +9,10 @@
 // list, the same counts as the host commit, bit for bit.
 //
 // ONE code path for two builds:
-//   * the GPU (commit.hip, PCC_DEVICE): one workgroup; every loop is strided over its threads, phases are
-//     separated by workgroup barriers, control flow is uniform (every branch condition is read from memory
-//     written before the preceding barrier);
+//   * the GPU (commit.hip, PCC_DEVICE): every loop is strided over (tid, nt), phases are separated by workgroup
+//     barriers — or, for the scratch-only steps of phase A, which also run as chip-wide launches, by kernel
+//     boundaries — and control flow is uniform (every branch condition is read from memory written before the
+//     preceding barrier);
 //   * the host harness of the CPU test-suite (tests/commit_host): tid = 0, nt = 1, barriers are no-ops.
 // Nothing here is a CPU fallback of the product: the product path only ever runs the GPU build.
 #pragma once
@@ -363,25 +364,41 @@ PCC_FN void pcc_mark_reuse(const PccTable* tb, const PccPlan& pl, const PccBlock
 }
 
 // ---- phase A of one block: group identical records, check what the commit would need; modifies scratch only -------
-PCC_FN void pcc_prepare_block(const PccTable* tb, const PccPlan& pl, const PccBlock& b, int bi, PccResult* res, int tid, int nt) {
-  const int k = b.counts2[1];
-  if (tid == 0) {
-    res->n_records[bi] = k;
-    res->n_distinct[bi] = 0;
-    res->n_nested[bi] = 0;
-  }
-  if (k > b.kcap) {
-    if (tid == 0) PCC_OR32(&res->fallback, PCC_FB_RECORDS);
-    return;
-  }
-  if (k == 0) return;
-  for (int j = tid; j < k; j += nt) b.recpos[j] = b.chosen_newpos ? b.chosen_newpos[b.new_list[j]] : j;
-  int hm = b.hmask < 63 ? b.hmask : 63;  // hash table of this sweep: the smallest power of two >= 4 k (at most the scratch's)
+// Four steps, each a (tid, nt)-strided loop over independent records (what they share goes through order-independent
+// atomics), each reading only what the step before it wrote: one workgroup runs them with barriers in between
+// (pcc_prepare_block), the GPU build also runs each as a chip-wide launch of its own (commit.hip: pcc_prep_*_kernel).
+// Every step decides for itself, from the device-side record count, whether the block has anything to prepare.
+
+// mask of this sweep's hash table: the smallest power of two >= 4 k (at most the scratch's), less one
+PCC_FN int32_t pcc_hash_mask(const PccBlock& b, int k) {
+  int hm = b.hmask < 63 ? b.hmask : 63;
   while (hm + 1 < 4 * k && hm < b.hmask) hm = 2 * hm + 1;
-  const uint32_t hmask = (uint32_t)hm;
+  return hm;
+}
+PCC_FN bool pcc_has_records(const PccBlock& b, int k) { return k > 0 && k <= b.kcap; }
+
+// step 1: the block's record count and the scratch check (ONE thread: the only writer of these words in this step) ...
+PCC_FN void pcc_prepare_counts(const PccBlock& b, int bi, PccResult* res) {
+  const int k = b.counts2[1];
+  res->n_records[bi] = k;
+  res->n_distinct[bi] = 0;
+  res->n_nested[bi] = 0;
+  if (k > b.kcap) PCC_OR32(&res->fallback, PCC_FB_RECORDS);
+}
+// ... the records' positions and an empty hash table
+PCC_FN void pcc_prepare_init(const PccBlock& b, int tid, int nt) {
+  const int k = b.counts2[1];
+  if (!pcc_has_records(b, k)) return;
+  for (int j = tid; j < k; j += nt) b.recpos[j] = b.chosen_newpos ? b.chosen_newpos[b.new_list[j]] : j;
+  const int hm = pcc_hash_mask(b, k);
   for (int i = tid; i <= hm; i += nt) b.ht[i] = -1;
-  PCC_BARRIER();
-  // insert: the slot of a class of identical records ends up holding its smallest record index
+}
+
+// step 2, insert: the slot of a class of identical records ends up holding its smallest record index
+PCC_FN void pcc_prepare_insert(const PccBlock& b, int tid, int nt) {
+  const int k = b.counts2[1];
+  if (!pcc_has_records(b, k)) return;
+  const uint32_t hmask = (uint32_t)pcc_hash_mask(b, k);
   for (int j = tid; j < k; j += nt) {
     const int32_t* v = pcc_record(b, j);
     uint32_t s = pcc_hash(b, v) & hmask;
@@ -398,7 +415,13 @@ PCC_FN void pcc_prepare_block(const PccTable* tb, const PccPlan& pl, const PccBl
       s = (s + 1) & hmask;
     }
   }
-  PCC_BARRIER();
+}
+
+// step 3, look-up and classify: rep, flags, what the first record of every class would create
+PCC_FN void pcc_prepare_classify(const PccPlan& pl, const PccBlock& b, int bi, PccResult* res, int tid, int nt) {
+  const int k = b.counts2[1];
+  if (!pcc_has_records(b, k)) return;
+  const uint32_t hmask = (uint32_t)pcc_hash_mask(b, k);
   for (int j = tid; j < k; j += nt) {
     const int32_t* v = pcc_record(b, j);
     uint32_t s = pcc_hash(b, v) & hmask;
@@ -431,13 +454,28 @@ PCC_FN void pcc_prepare_block(const PccTable* tb, const PccPlan& pl, const PccBl
     }
     b.flags[j] = fl;
   }
+}
+
+// step 4, reuse (a plan whose tables no other block touches): the root rows this block really creates are the first
+// records that do not keep their old referent
+PCC_FN void pcc_prepare_reuse(const PccTable* tb, const PccPlan& pl, const PccBlock& b, PccResult* res, int tid, int nt) {
+  const int k = b.counts2[1];
+  if (!pl.exclusive || !pcc_has_records(b, k)) return;
+  pcc_mark_reuse(tb, pl, b, k, true, tid, nt);  // (a record's flags and newid are its own thread's: no barrier needed in between)
+  for (int j = tid; j < k; j += nt)
+    if ((b.flags[j] & PCC_F_FIRST) && !(b.flags[j] & PCC_F_REUSE)) PCC_ADD32(&res->alloc_upper[pl.used_slot[0]], 1);
+}
+
+PCC_FN void pcc_prepare_block(const PccTable* tb, const PccPlan& pl, const PccBlock& b, int bi, PccResult* res, int tid, int nt) {
+  if (tid == 0) pcc_prepare_counts(b, bi, res);
+  pcc_prepare_init(b, tid, nt);
   PCC_BARRIER();
-  if (pl.exclusive) {  // the root rows this block really creates: first records that do not keep their old referent
-    pcc_mark_reuse(tb, pl, b, k, true, tid, nt);
-    for (int j = tid; j < k; j += nt)
-      if ((b.flags[j] & PCC_F_FIRST) && !(b.flags[j] & PCC_F_REUSE)) PCC_ADD32(&res->alloc_upper[pl.used_slot[0]], 1);
-    PCC_BARRIER();
-  }
+  pcc_prepare_insert(b, tid, nt);
+  PCC_BARRIER();
+  pcc_prepare_classify(pl, b, bi, res, tid, nt);
+  PCC_BARRIER();
+  pcc_prepare_reuse(tb, pl, b, res, tid, nt);
+  PCC_BARRIER();
 }
 
 // current referents of the rows that moved: the chosen existing referent, or the row created for the chosen proposal
@@ -679,22 +717,18 @@ PCC_FN void pcc_merge(const PccSegLayout& L, int p, int n_ranks, const int32_t* 
 }
 
 // ---- the whole commit ------------------------------------------------------------------------------------------------
-PCC_FN void pcc_commit(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks, int n_blocks, PccResult* res,
-                       int32_t* part, int tid, int nt) {
-  if (tid == 0) {
-    res->fallback = res->fallback_in;  // (what pcc_merge found wrong with the gathered lists; 0 on one rank)
-    res->n_changed = 0;
-    for (int s = 0; s < PCC_MAX_SLOTS; ++s) res->alloc_upper[s] = 0;
-    for (int bi = 0; bi < PCC_MAX_BLOCKS; ++bi) res->n_records[bi] = res->n_distinct[bi] = res->n_nested[bi] = 0;
-  }
-  PCC_BARRIER();
-  PCC_STAMP("start");
-  if (res->fallback) return;
-  for (int bi = 0; bi < n_blocks; ++bi) {
-    pcc_prepare_block(tb, plans[bi], blocks[bi], bi, res, tid, nt);
-    PCC_STAMP("prepare");
-  }
-  PCC_BARRIER();
+// what one thread does before anything else: the result's header (fallback_in: what pcc_merge found wrong with the gathered
+// lists; 0 on one rank).  The blocks' own entries are pcc_prepare_counts'.
+PCC_FN void pcc_reset_result(PccResult* res) {
+  res->fallback = res->fallback_in;
+  res->n_changed = 0;
+  for (int s = 0; s < PCC_MAX_SLOTS; ++s) res->alloc_upper[s] = 0;
+  for (int bi = 0; bi < PCC_MAX_BLOCKS; ++bi) res->n_records[bi] = res->n_distinct[bi] = res->n_nested[bi] = 0;
+}
+// the second half: every block is prepared (or the commit was refused before it started: then nothing was counted and
+// res->fallback says so) — the capacity verdict, then phase B
+PCC_FN void pcc_commit_apply(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks, int n_blocks, PccResult* res,
+                             int32_t* part, int tid, int nt) {
   if (tid == 0)
     for (int s = 0; s < n_slots; ++s) {
       const int a = res->alloc_upper[s];
@@ -706,6 +740,19 @@ PCC_FN void pcc_commit(PccTable* tb, int n_slots, const PccPlan* plans, const Pc
   PCC_BARRIER();
   if (res->fallback) return;
   for (int bi = 0; bi < n_blocks; ++bi) pcc_apply_block(tb, plans[bi], blocks[bi], bi, res, part, tid, nt);
+}
+PCC_FN void pcc_commit(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks, int n_blocks, PccResult* res,
+                       int32_t* part, int tid, int nt) {
+  if (tid == 0) pcc_reset_result(res);
+  PCC_BARRIER();
+  PCC_STAMP("start");
+  if (res->fallback) return;
+  for (int bi = 0; bi < n_blocks; ++bi) {
+    pcc_prepare_block(tb, plans[bi], blocks[bi], bi, res, tid, nt);
+    PCC_STAMP("prepare");
+  }
+  PCC_BARRIER();
+  pcc_commit_apply(tb, n_slots, plans, blocks, n_blocks, res, part, tid, nt);
 }
 
 // ---- host-side construction of a PccPlan from a block's plan arrays (shared by commit.hip and the test harness) ---
