@@ -246,6 +246,43 @@ function commit_pull_table(c, table, cap, n_cols)                               
         (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}), c.h, table, state, cols, counts, live, free, origin))
     state, cols, counts, live, free[1:state[2]], origin
 end
+# ---- cleaned table, accuracy counters and per-cell consensus on the device (csrc/recon.hip; what analysis.jl:15-88 reads off
+# the trace).  Bindings only: the lowering below does not build a reconstruction plan yet. -----------------------------------
+struct CReconCol; kind::Int32; block::Int32; table::Int32; col::Int32; block_b::Int32; table_b::Int32; col_b::Int32
+    fn_table::Int32; map_off::Int32; map_len::Int32; end                                                     # pclean_recon_col, 0-based ids
+recon_set_plan(c, cols::Vector{CReconCol}, id_map::Vector{Int32}) = GC.@preserve cols id_map check(c,
+    ccall((:pclean_recon_set_plan, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{CReconCol}, Int32, Ptr{Int32}), c.h, length(cols), cols, length(id_map), id_map))
+function recon_run(c, n_rows, n_cols)                                                                        # n_rows x n_cols pool ids (0-based, -1 none)
+    out = Matrix{Int32}(undef, n_rows, n_cols)
+    GC.@preserve out check(c, ccall((:pclean_recon_run, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}), c.h, out)); out
+end
+recon_set_truth(c, dirty::Matrix{Int32}, clean::Matrix{Int32}) = GC.@preserve dirty clean check(c,          # n_rows x n_cols each
+    ccall((:pclean_recon_set_truth, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c.h, dirty, clean))
+function recon_counts(c, n_cols, ring::Ptr{Cvoid}=C_NULL)                                                    # 5 x n_cols: errors, changed, cleaned, imputed, correctly imputed
+    out = Matrix{Int64}(undef, 5, n_cols)
+    GC.@preserve out check(c, ccall((:pclean_recon_counts, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}), c.h, ring, out)); out
+end
+function ring_create(c, keep)                                                                                # 4 * keep * n_cols * n_rows bytes of HBM; 1 <= keep <= 32
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(c, ccall((:pclean_ring_create, lib), Cint, (Ptr{Cvoid}, Int32, Ref{Ptr{Cvoid}}), c.h, keep, r)); r[]
+end
+ring_destroy(ring::Ptr{Cvoid}) = ccall((:pclean_ring_destroy, lib), Cint, (Ptr{Cvoid},), ring)
+function ring_info(ring::Ptr{Cvoid})                                                                         # keep, n_cols, n_rows, adds
+    out = zeros(Int64, 4); ccall((:pclean_ring_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), ring, out); out
+end
+ring_add(c, ring::Ptr{Cvoid}) = check(c, ccall((:pclean_ring_add, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.h, ring))
+function ring_consensus(c, ring::Ptr{Cvoid})                                                                 # (mode, support), n_rows x n_cols each
+    info = ring_info(ring); mode = Matrix{Int32}(undef, info[3], info[2]); support = similar(mode)
+    GC.@preserve mode support check(c, ccall((:pclean_ring_consensus, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}),
+                                             c.h, ring, mode, support)); mode, support
+end
+ring_remap(c, ring::Ptr{Cvoid}, old_to_new::Vector{Int32}) = GC.@preserve old_to_new check(c,
+    ccall((:pclean_ring_remap, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}), c.h, ring, length(old_to_new), old_to_new))
+function cell_mode(c, snapshots::Matrix{Int32})                                                              # n_cells x n_snapshots, oldest first
+    m, s = size(snapshots); mode = Vector{Int32}(undef, m); support = Vector{Int32}(undef, m)
+    GC.@preserve snapshots mode support check(c, ccall((:pclean_cell_mode, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), c.h, s, m, snapshots, mode, support)); mode, support
+end
 # stable argsort of small ids on the device (0-based permutation; the sort behind evidence_csr at 10^6 rows)
 function argsort_ids(c, ids::Vector{Int32}, id_max)
     out = Vector{Int32}(undef, length(ids))

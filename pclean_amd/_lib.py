@@ -84,6 +84,16 @@ class CommitSummary(C.Structure):
 
 COMMIT_FB_RECORDS, COMMIT_FB_DUMMY, COMMIT_FB_CAPACITY = 1, 2, 4
 
+
+class ReconCol(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("block", C.c_int32), ("table", C.c_int32), ("col", C.c_int32),
+                ("block_b", C.c_int32), ("table_b", C.c_int32), ("col_b", C.c_int32), ("fn_table", C.c_int32),
+                ("map_off", C.c_int32), ("map_len", C.c_int32)]
+
+
+RECON_PATH, RECON_FN = 0, 1
+RING_MAX_KEEP = 32  # PCLEAN_RING_MAX_KEEP
+
 TERM_DTYPE = np.dtype([("obs_col", "<i4"), ("cand_col", "<i4"), ("pair_table", "<i4"), ("dens_kind", "<i4"),
                        ("max_typos", "<i4"), ("ctx_slot", "<i4"), ("fn_table", "<i4"), ("ctx_mode", "<i4")])
 NODE_DTYPE = np.dtype([("kind", "<i4"), ("table", "<i4"), ("term_begin", "<i4"), ("n_terms", "<i4"),
@@ -724,6 +734,84 @@ class HipContext:
         check(self.h, self.lib.pclean_stats_device_ptr(self.h, C.c_int32(table_id), C.byref(ptr), C.byref(n)),
               "pclean_stats_device_ptr")
         return ptr.value, n.value
+
+    # -- cleaned table, accuracy counters, per-cell consensus (csrc/recon.hip) ---------------------------------------
+    def recon_set_plan(self, cols, id_map):
+        """cols: list of ReconCol; id_map: the columns' value id -> pool id maps, concatenated"""
+        arr = (ReconCol * max(len(cols), 1))(*cols)
+        id_map = np.ascontiguousarray(id_map, dtype=np.int32)
+        check(self.h, self.lib.pclean_recon_set_plan(self.h, C.c_int32(len(cols)), arr, C.c_int32(len(id_map)),
+                                                     _p(id_map, C.c_int32) if len(id_map) else None), "pclean_recon_set_plan")
+
+    def recon_run(self, n_cols, n_rows, fetch=True):
+        """the plan's columns from the device-resident state: int32 [n_cols][n_rows] (None with fetch=False: the result
+        stays on the device for recon_counts)"""
+        out = np.empty((n_cols, n_rows), dtype=np.int32) if fetch else None
+        check(self.h, self.lib.pclean_recon_run(self.h, _p(out, C.c_int32)), "pclean_recon_run")
+        return out
+
+    def recon_set_truth(self, dirty_ids, clean_ids):
+        d = np.ascontiguousarray(dirty_ids, dtype=np.int32)
+        c = np.ascontiguousarray(clean_ids, dtype=np.int32)
+        assert d.shape == c.shape and d.ndim == 2
+        check(self.h, self.lib.pclean_recon_set_truth(self.h, _p(d, C.c_int32), _p(c, C.c_int32)), "pclean_recon_set_truth")
+
+    def recon_counts(self, n_cols, ring=None):
+        """int64 [n_cols][5] counters of the last recon_run (ring None) or of the ring's last consensus"""
+        out = np.zeros((n_cols, 5), dtype=np.int64)
+        check(self.h, self.lib.pclean_recon_counts(self.h, ring, _p(out, C.c_int64)), "pclean_recon_counts")
+        return out
+
+    def ring_create(self, keep):
+        if not 1 <= int(keep) <= RING_MAX_KEEP:
+            raise ValueError(f"keep must be in 1..{RING_MAX_KEEP}, got {keep}")
+        ring = C.c_void_p()
+        check(self.h, self.lib.pclean_ring_create(self.h, C.c_int32(int(keep)), C.byref(ring)), "pclean_ring_create")
+        return ring
+
+    def ring_destroy(self, ring):
+        if ring:
+            self.lib.pclean_ring_destroy(ring)
+
+    def ring_info(self, ring):
+        """(keep, n_cols, n_rows, adds)"""
+        out = np.zeros(4, dtype=np.int64)
+        rc = self.lib.pclean_ring_info(ring, _p(out, C.c_int64))
+        if rc != 0:
+            raise PCleanHipError(f"pclean_ring_info failed with status {rc}")
+        return tuple(int(v) for v in out)
+
+    def ring_add(self, ring):
+        check(self.h, self.lib.pclean_ring_add(self.h, ring), "pclean_ring_add")
+
+    def ring_consensus(self, ring, fetch=True):
+        """(mode, support) int32 [n_cols][n_rows] over the kept snapshots ((None, None) with fetch=False)"""
+        keep, n_cols, n_rows, _ = self.ring_info(ring)
+        mode = np.empty((n_cols, n_rows), dtype=np.int32) if fetch else None
+        sup = np.empty((n_cols, n_rows), dtype=np.int32) if fetch else None
+        check(self.h, self.lib.pclean_ring_consensus(self.h, ring, _p(mode, C.c_int32), _p(sup, C.c_int32)),
+              "pclean_ring_consensus")
+        return mode, sup
+
+    def ring_remap(self, ring, old_to_new):
+        m = np.ascontiguousarray(old_to_new, dtype=np.int32)
+        check(self.h, self.lib.pclean_ring_remap(self.h, ring, C.c_int32(len(m)), _p(m, C.c_int32) if len(m) else None),
+              "pclean_ring_remap")
+
+    def cell_mode(self, snapshots):
+        """The consensus kernel on snapshots int32 [S][M] (oldest first, 1 <= S <= 32): (mode[M], support[M]) — per cell
+        the most frequent value and the number of snapshots holding it; ties go to the value seen most recently."""
+        snaps = np.ascontiguousarray(snapshots, dtype=np.int32)
+        if snaps.ndim != 2:
+            raise ValueError("snapshots must be [S][M]")
+        s, m = snaps.shape
+        if not 1 <= s <= RING_MAX_KEEP:
+            raise ValueError(f"between 1 and {RING_MAX_KEEP} snapshots, got {s}")
+        mode = np.empty(m, dtype=np.int32)
+        sup = np.empty(m, dtype=np.int32)
+        check(self.h, self.lib.pclean_cell_mode(self.h, C.c_int32(s), C.c_int64(m), _p(snaps, C.c_int32), _p(mode, C.c_int32),
+                                                _p(sup, C.c_int32)), "pclean_cell_mode")
+        return mode, sup
 
     def get_root_stats(self):
         r = RootStats()

@@ -7,20 +7,24 @@ columns, imputations for missing dirty cells; F1 = harmonic mean.
 import numpy as np
 
 
-def reconstructed_pool_ids(lowered, trace, row_slice=None):
-    """{query column: pool id of the value PClean currently believes, per local row}."""
+def reconstructed_pool_ids(lowered, trace, row_slice=None, columns=None):
+    """{query column: pool id of the value PClean currently believes, per local row}.  columns: only those (default all)."""
     lw = lowered
     m, q = lw.model, lw.query
     ocls = m.classes[q.cls]
     fk_block = {blk["root_fk"]: bi for bi, blk in enumerate(lw.blocks) if not blk.get("score")}
     out = {}
     for col, ref in q.cleanmap.items():
+        if columns is not None and col not in columns:
+            continue
         own = ocls.attr(ref) if "." not in ref else None
         if own is not None and own.kind == "choice":  # own discrete choice (e.g. br): option -> string
             bi = next(iter(lw.locals))
             li = lw.locals[bi].index(ref)
             dom = lw.latent_dom[(q.cls, ref)]
-            out[col] = dom.id_array()[np.maximum(trace.locals[bi][:, li], 0)]
+            # (own choices are host-owned even while device commits are ahead of the trace's other arrays: no pull)
+            loc = getattr(trace, "_locals", None) or trace.locals
+            out[col] = dom.id_array()[np.maximum(loc[bi][:, li], 0)]
             continue
         gi = None
         if own is not None and own.kind == "julia":  # a queried numeric column is reported through its own Gaussian term
@@ -66,14 +70,24 @@ def _pool_ids(index, values, unknown, missing):
     return table[codes]  # code -1 (None) selects the last entry
 
 
-def accuracy_counts(lowered, trace, dirty, clean):
-    """The five counters of evaluate_accuracy for the rows held by `trace`."""
+def accuracy_counts(lowered, trace, dirty, clean, skip=()):
+    """The five counters of evaluate_accuracy for the rows held by `trace`.  skip: columns left out altogether (somebody
+    else counts them: tally.CellTally, on the device)."""
     lw = lowered
-    ours = reconstructed_pool_ids(lw, trace)
-    n = trace.cur.shape[1]
+    ours = reconstructed_pool_ids(lw, trace, columns=None if not skip else
+                                  [c for c in lw.query.cleanmap if c not in skip])
+    cur = getattr(trace, "_cur", None)  # (the shape only: no pull of a trace the device is ahead of)
+    n = (trace.cur if cur is None else cur).shape[1]
+    return counts_given(lw, ours, n, dirty, clean, skip)
+
+
+def counts_given(lowered, ours, n, dirty, clean, skip=()):
+    """The five counters for a cleaned table given as `ours` (what reconstructed_pool_ids returns: pool ids per string
+    column, ("numeric", values) per numeric one) over the first n rows; columns of `skip` are left out altogether."""
+    lw = lowered
     errors = changed = cleaned = imputed = imputed_ok = 0
     for col in clean:
-        if col not in dirty:
+        if col not in dirty or col in skip:
             continue
         d = np.asarray(dirty[col][:n], dtype=object)
         c = np.asarray(clean[col][:n], dtype=object)
@@ -137,6 +151,24 @@ def reconstructed_table(lowered, trace, dirty):
     return out
 
 
+def consensus_table(lowered, tally, dirty):
+    """The cleaned table from the per-cell consensus of `tally` (tally.CellTally) instead of the last sample: every queried
+    string column holds its most frequent value over the kept samples and is followed by `<column>__support`, the number
+    of kept samples that agree with it (of tally.n_kept).  Numeric queried columns are not tallied: like the columns that
+    are not queried they are copied from `dirty`."""
+    ids, support = tally.consensus()
+    n = len(next(iter(ids.values()))) if ids else 0
+    strings = lowered.pool.strings
+    out = {}
+    for col, vals in dirty.items():
+        if col not in ids:
+            out[col] = list(vals[:n]) if ids else list(vals)
+            continue
+        out[col] = [strings[i] if i >= 0 else None for i in ids[col]]
+        out[col + "__support"] = [int(v) for v in support[col]]
+    return out
+
+
 def latent_table(lowered, trace, cname):
     """One inferred latent table (save_tables, analysis.jl:8-13): row id + the value of every own attribute and
     reference slot of the class (flattened copies of referents' values are left out, as the reference does
@@ -156,8 +188,9 @@ def latent_table(lowered, trace, cname):
     return out
 
 
-def save_results(directory, name, lowered, trace, dirty, timestamp=True):
-    """save_results (analysis.jl:15-33): reconstructed_<class>.csv + inferred_<class>.csv per latent class."""
+def save_results(directory, name, lowered, trace, dirty, timestamp=True, tally=None):
+    """save_results (analysis.jl:15-33): reconstructed_<class>.csv + inferred_<class>.csv per latent class; with a
+    tally (tally.CellTally) also consensus_<class>.csv (consensus_table)."""
     import datetime
     import os
 
@@ -166,6 +199,9 @@ def save_results(directory, name, lowered, trace, dirty, timestamp=True):
     os.makedirs(d, exist_ok=True)
     pd.DataFrame(reconstructed_table(lowered, trace, dirty)).to_csv(
         os.path.join(d, f"reconstructed_{lowered.query.cls}.csv"), index=False)
+    if tally is not None:
+        pd.DataFrame(consensus_table(lowered, tally, dirty)).to_csv(
+            os.path.join(d, f"consensus_{lowered.query.cls}.csv"), index=False)
     for cname in trace.tables:
         pd.DataFrame(latent_table(lowered, trace, cname)).to_csv(os.path.join(d, f"inferred_{cname}.csv"), index=False)
     return d

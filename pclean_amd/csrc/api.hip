@@ -39,6 +39,7 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
   (void)pclean_comm_destroy(ctx);
   pclean_commit_state_free(ctx);
   pclean_sweep_state_free(ctx);
+  pclean_recon_state_free(ctx);
   ctx->stage.release();
   ctx->ustage.release();
   ctx->stats_pack.release();

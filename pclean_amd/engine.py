@@ -100,6 +100,7 @@ class Engine:
         self._uploaded_shape = {}
         self._last_upload = {}
         self._dc = None  # state of the device-resident commit (enable_device_commit)
+        self.reloads = 0  # how often reload() replaced the context (what lives in a context, e.g. tally.CellTally's plan, follows)
         self._upload_static()
         if row_offset:
             _lib.check(self.hip.h, self.hip.lib.pclean_set_row_offset(self.hip.h, _lib.C.c_int64(row_offset)),
@@ -138,6 +139,7 @@ class Engine:
         if getattr(self, "_comm", None) is not None:
             self.init_device_comm(self._comm)
         self._dc = None  # (a fresh context: the device-resident commit is set up again on demand)
+        self.reloads += 1
 
     def sample_prior_strings(self, dist, n, seed, stream):
         """n draws of random(StringPrior) (string_prior.jl:28-40: length uniform on [min, max], bigram letters) or
@@ -601,6 +603,21 @@ class Engine:
             for a in lw.model.classes[cname].attrs:
                 if a.kind == "choice" and isinstance(a.dist, ChooseProportionally) and a.dist.param == pname:
                     state.counts = np.bincount(t.cols[lw.colidx[cname][a.name], rows], minlength=len(state.counts)).astype(np.int64)
+
+    def make_device_current(self, trace):
+        """The latent tables and the observed rows' referents of `trace` as the device holds them are its current state
+        afterwards: nothing to do while device commits are ahead of the host arrays (no pull), else whatever moved since
+        the last upload goes up (upload_trace / set_cur) — what a kernel reading the device-resident state needs
+        (tally.CellTally)."""
+        if trace._dev is self:
+            return
+        if trace._dev is not None:
+            raise _lib.PCleanHipError("the trace is ahead on another engine")
+        self.upload_trace(trace)
+        if self._dc is not None:
+            self._sync_cur(trace)
+        else:
+            self.hip.set_cur(trace._cur)
 
     def sweep_moved(self):
         """{block: (rows relative to the swept window, new referent)} of the last sweep, rows ascending."""

@@ -653,13 +653,16 @@ def initialize_trace(engine, trace, config, seed, max_batch=256, comm=None, merg
     return trace
 
 
-def run_inference(engine, trace, config, seed, verbose=False, comm=None, max_sub_batches=32, batch_rows=None):
+def run_inference(engine, trace, config, seed, verbose=False, comm=None, max_sub_batches=32, batch_rows=None, tally=None,
+                  tally_from=0):
     """run_inference! (inference.jl:83-88): config.num_iters sweeps over all classes.  `comm` shards
     every class sweep over the ranks of a torch.distributed job (one process per GPU).  A class sweep is
     cut into sub-batches between which the class's parameters are resampled (`sub_batches`): at most
     max_sub_batches per class, so tables with n / rejuv_frequency <= max_sub_batches follow the reference's
     cadence exactly; batch_rows=1 is the reference's sequential schedule (sub_batches).  use_lo_sweeps is, as in the reference, only read by instrumented_inference.jl (out of
-    scope): pgibbs_sweep! sweeps the latent classes regardless of it."""
+    scope): pgibbs_sweep! sweeps the latent classes regardless of it.  tally (tally.CellTally): the cleaned table after
+    every iteration it >= tally_from is added to its ring of kept samples (on the device, where the sweeps leave the state);
+    the trace is only read."""
     lw = engine.lw
     if hasattr(engine, "prepare") and not getattr(engine, "_prepared", False):
         with _timed("prepare"):
@@ -677,4 +680,7 @@ def run_inference(engine, trace, config, seed, verbose=False, comm=None, max_sub
             if verbose:
                 print(f"iteration {it + 1}/{config.num_iters} {cname}: {ch} changes", flush=True)
                 trace.check_consistency()
+        if tally is not None and it >= tally_from:
+            with _timed("tally"):
+                tally.add(trace)
     return trace

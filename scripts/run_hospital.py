@@ -1,4 +1,6 @@
-"""experiments/hospital/run.jl on the HIP path: initialize_trace + run_inference! + evaluate_accuracy."""
+"""experiments/hospital/run.jl on the HIP path: initialize_trace + run_inference! + evaluate_accuracy.
+`--consensus K` keeps the cleaned table of the last K iterations on the device (pclean_amd.tally.CellTally) and prints the
+F1 of their per-cell consensus next to the last sample's."""
 import os
 import sys
 import time
@@ -14,7 +16,7 @@ from pclean_amd.model import LoweredModel
 from pclean_amd.trace import Trace
 
 
-def main(particles=2, mh=True, iters=1, seed=0, shuffle=True):
+def main(particles=2, mh=True, iters=1, seed=0, shuffle=True, consensus=0):
     dirty, clean = ex.hospital_data()
     if shuffle:  # random row order for the batched initialisation (experiments.shuffle_rows)
         (dirty, clean), _ = ex.shuffle_rows([dirty, clean], seed)
@@ -33,9 +35,19 @@ def main(particles=2, mh=True, iters=1, seed=0, shuffle=True):
     print('after init:', {c: (t.n, t.n_live) for c, t in tr.tables.items()}, flush=True)
     t1 = time.time()
     acc0 = evaluate_accuracy(lw, tr, dirty, clean)
-    run_inference(eng, tr, cfg, seed, verbose=True)
+    tally = None
+    if consensus:
+        from pclean_amd.tally import CellTally
+        tally = CellTally(eng, tr, keep=consensus)
+    run_inference(eng, tr, cfg, seed, verbose=True, tally=tally, tally_from=max(0, iters - consensus))
     t2 = time.time()
     acc = evaluate_accuracy(lw, tr, dirty, clean)
+    if tally is not None:
+        cacc = tally.consensus_accuracy(dirty, clean)
+        print(f"last-sample F1 {acc['f1']:.4f}; consensus F1 over the last {tally.n_kept} iterations {cacc['f1']:.4f}")
+        print("consensus:", cacc)
+        acc = dict(acc, consensus=cacc)
+        tally.close()
     print("tables:", {c: (t.n, t.n_live) for c, t in tr.tables.items()})
     print(f"init {t1 - t0:.2f}s  F1 after init {acc0['f1']:.4f}; inference {t2 - t1:.2f}s")
     print(acc)
@@ -45,5 +57,10 @@ def main(particles=2, mh=True, iters=1, seed=0, shuffle=True):
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(particles=int(a[0]) if a else 2, mh=(a[1] == "mh") if len(a) > 1 else True, iters=int(a[2]) if len(a) > 2 else 1,
+    k = 0
+    if "--consensus" in a:  # --consensus K: iterations kept for the per-cell consensus (at most 32)
+        i = a.index("--consensus")
+        k = int(a[i + 1])
+        del a[i:i + 2]
+    main(consensus=k, particles=int(a[0]) if a else 2, mh=(a[1] == "mh") if len(a) > 1 else True, iters=int(a[2]) if len(a) > 2 else 1,
          shuffle="sorted" not in a)
