@@ -125,6 +125,16 @@ function sweep_latent!(c, cfg, seed, sweep_idx, block, roots::Vector{Int32}, key
         c.h, cc, seed, sweep_idx, block, length(roots), roots, n, keys, ev_off, ev_rows, ctxp, excl, chosen, vals))
     chosen, vals
 end
+# opt-in: latent sweeps weigh the particles whose served option lists chose (or stand for) the ProposalDummyValue
+# (block_proposal.jl:49-60; include/pclean_hip.h: which roots are served and what excl then carries for them)
+set_latent_dummy_correction(c, on::Bool) = check(c, ccall((:pclean_set_latent_dummy_correction, lib), Cint, (Ptr{Cvoid}, Cint), c.h, on ? 1 : 0))
+function get_latent_weights(c)                       # w[particle, item] of the last corrected latent sweep (parity checks)
+    n = Ref{Int32}(0); P = Ref{Int32}(0)
+    check(c, ccall((:pclean_get_latent_weights, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Int32}, Ref{Int32}), c.h, C_NULL, n, P))
+    w = zeros(Float64, P[], n[])
+    isempty(w) || GC.@preserve w check(c, ccall((:pclean_get_latent_weights, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Int32}, Ref{Int32}), c.h, w, n, P))
+    w
+end
 # per-candidate scores of ONE plan node of a latent plan against evidence sets (parity checks: what the generated proposal
 # of proposal_compiler.jl:306-350 accumulates for every candidate); scores[:, i] over the node's candidates (+ new row)
 function score_node_ev(c, block, node, keys::Vector{Int32}, ev_off::Vector{Int32}, ev_rows::Vector{Int32},

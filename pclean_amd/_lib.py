@@ -590,6 +590,21 @@ class HipContext:
             "pclean_sweep_latent")
         return chosen, vals
 
+    def set_latent_dummy_correction(self, on):
+        """pclean_set_latent_dummy_correction: latent sweeps weigh chosen ProposalDummyValues (off by default)"""
+        check(self.h, self.lib.pclean_set_latent_dummy_correction(self.h, C.c_int(int(bool(on)))),
+              "pclean_set_latent_dummy_correction")
+
+    def get_latent_weights(self):
+        """pclean_get_latent_weights: log-weight corrections [n_items][P] of the last corrected latent sweep (parity checks)"""
+        n, P = C.c_int32(0), C.c_int32(0)
+        check(self.h, self.lib.pclean_get_latent_weights(self.h, None, C.byref(n), C.byref(P)), "pclean_get_latent_weights")
+        w = np.zeros((n.value, P.value), dtype=np.float64)
+        if w.size:
+            check(self.h, self.lib.pclean_get_latent_weights(self.h, _p(w, C.c_double), C.byref(n), C.byref(P)),
+                  "pclean_get_latent_weights")
+        return w
+
     # -- C-level RCCL exchange (for hosts without torch.distributed; the Python host uses parallel.Comm) --
     def comm_unique_id(self):
         buf = (C.c_ubyte * 128)()

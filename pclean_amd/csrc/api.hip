@@ -43,6 +43,9 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
   ctx->stage.release();
   ctx->ustage.release();
   ctx->stats_pack.release();
+  ctx->lat_w.release();
+  ctx->lat_dp.release();
+  ctx->lat_flag.release();
   ctx->sym.release();
   ctx->off.release();
   ctx->obs.release();
@@ -82,6 +85,24 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
 }
 
 extern "C" const char* pclean_last_error(const pclean_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+
+extern "C" int pclean_set_latent_dummy_correction(pclean_ctx* ctx, int on) {
+  if (!ctx || on < 0 || on > 1) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_latent_dummy_correction: bad arguments");
+  ctx->latent_dummy = on != 0;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_get_latent_weights(pclean_ctx* ctx, double* w_out, int32_t* n_items, int32_t* P) {
+  if (!ctx || !n_items || !P) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_get_latent_weights: bad arguments");
+  *n_items = ctx->lat_w_items;
+  *P = ctx->lat_w_P;
+  const size_t n = (size_t)ctx->lat_w_items * ctx->lat_w_P;
+  if (!w_out || n == 0) return PCLEAN_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpyAsync(w_out, ctx->lat_w.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PCLEAN_OK;
+}
 
 // ---------------------------------------------------------------------------
 extern "C" int pclean_load_strings(pclean_ctx* ctx, int32_t n_strings, const uint16_t* sym, const int64_t* off) {

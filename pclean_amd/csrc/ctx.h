@@ -249,6 +249,14 @@ struct pclean_ctx {
   int32_t ev_res_n = 0;         // rows held (0: nothing resident)
   bool ev_res_has_ctx = false;
   bool defer_outputs = false;   // pclean_set_sweep_mode bit 0
+  // pclean_set_latent_dummy_correction: latent sweeps weigh the particles whose served option lists chose (or hold a value
+  // that stands for) the ProposalDummyValue (latent.hip); lat_w = the log-weight corrections [lat_w_items][lat_w_P] of the
+  // last such sweep (pclean_get_latent_weights), lat_dp / lat_flag = its distance matrices and "string too long" mark
+  bool latent_dummy = false;
+  DevBuf<double> lat_w;
+  int32_t lat_w_items = 0, lat_w_P = 0;
+  DevBuf<int16_t> lat_dp;
+  DevBuf<unsigned int> lat_flag;
   void* commit_state = nullptr;  // owned by commit.hip
   HostStage stage;               // page-locked staging of caller arrays (table uploads, latent-sweep inputs / outputs)
   HostStage ustage;              // ... of the row unions of CandTable::delta_log (asked for in the middle of a sweep call,

@@ -526,6 +526,348 @@ extern "C" int pclean_argsort_ids(pclean_ctx* ctx, int32_t n, const int32_t* ids
   return PCLEAN_OK;
 }
 
+// ---- weights of chosen ProposalDummyValues in latent sweeps (pclean_set_latent_dummy_correction) ------------------------
+// block_proposal.jl:49-60 for a latent row: a particle whose option list took the ProposalDummyValue of a StringPrior draws
+// the string (propose_non_enumerable!) and re-scores the observations below the choice on it; a retained particle whose
+// value is no atom of the proposal stands for the dummy and is weighed the same way with the string it holds.  The
+// enumeration scored the dummy option with its mass and the PLACEHOLDER's likelihood, so the particle's log-weight moves by
+//     c = -logp[dummy option] + sum over terms, over the distinct observed values o of the item (ensure_agg: with counts)
+//         cnt(o) * (logdensity(o | string) - logdensity(o | placeholder))
+// A SLOT is (item t, particle p, served root li) with such a particle; slot index = (t * P + p) * n_leaves + li.
+#define LDC_MAX_LEAVES 8
+#define LDC_MAX_TERMS 2
+#define LDC_ARENA_CELLS ((size_t)32 << 20)  // int16 cells of distance matrices per launch (64 MB); PCLEAN_LATENT_DUMMY_ARENA
+struct LdcTermDev {
+  const uint8_t* pair;
+  const uint16_t* lat_len;
+  const int32_t* obs_ids;
+  int32_t n_lat, elem_bytes, max_typos, dist_mode;
+};
+struct LdcLeafDev {
+  int32_t node, dummy_val, dummy_k, n_opt, min_len, max_len, n_terms, n_lat_min;
+  const int32_t* opt_vals;
+  const double* opt_logp;
+  const int32_t* draws;  // [n_items][P] option drawn by particle p (particle 0's is not looked at)
+  const int32_t* excl;   // [n_items] value id a retained particle holds in place of the dummy, -1: it holds an atom
+  const AggDev* agg;     // [n_terms] aggregated evidence of the node's terms
+  LdcTermDev t[LDC_MAX_TERMS];
+};
+struct LdcPackDev {
+  int32_t n_leaves, site_block, P, n_items;
+  LdcLeafDev leaf[LDC_MAX_LEAVES];
+  const uint16_t* sym;
+  const int64_t* off;
+  const double* lm_init;
+  const double* lm_trans;
+  const uint16_t* letter_sym;
+  const double* nb;
+  const double* logl;
+  int32_t nb_stride, max_obs_len;  // max_obs_len: longest observed string the lanes' matrices were sized for
+  int16_t* dp;                     // arena: lane_cells cells per lane, 64 lanes per slot of the launch
+  int64_t lane_cells;
+  unsigned int* too_long;          // set when an observed string is longer than that
+};
+__global__ void ldc_flag_kernel(LdcPackDev pk, size_t n, int32_t* __restrict__ flag) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  const int li = (int)(q % pk.n_leaves);
+  const size_t tp = q / pk.n_leaves;
+  const int p = (int)(tp % pk.P), t = (int)(tp / pk.P);
+  const LdcLeafDev& lf = pk.leaf[li];
+  bool hit;
+  if (p == 0) {
+    const int v = lf.excl[t];
+    hit = v >= 0 && v < lf.n_lat_min;
+  } else {
+    const int k = lf.draws[tp];
+    hit = k >= 0 && k < lf.n_opt && lf.opt_vals[k] == lf.dummy_val;
+  }
+  flag[q] = hit ? PCLEAN_CHOICE_NEW : 0;
+}
+// One wavefront per slot (four slots per workgroup): lane 0 draws the slot's string into LDS, the lanes stride over the
+// item's distinct observed values, each with a distance matrix of its own in the arena; the lanes' fp64 partial sums are
+// added in lane order.
+__global__ __launch_bounds__(256) void latent_dummy_correction_kernel(int j0, int n_slots, const int32_t* __restrict__ slots,
+                                                                      LdcPackDev pk, const int32_t* __restrict__ keys,
+                                                                      uint64_t seed, uint32_t sweep,
+                                                                      double* __restrict__ corr) {
+  __shared__ uint16_t s_str[4][DUMMY_MAX_LEN + 1];
+  __shared__ int s_len[4];
+  __shared__ double s_part[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int jl = blockIdx.x * 4 + wave;  // slot of this launch's slice [j0, j0 + n_slots)
+  const bool live = jl < n_slots;
+  int li = 0, p = 0, t = 0;
+  if (live) {
+    const int q = slots[j0 + jl];
+    li = q % pk.n_leaves;
+    const int tp = q / pk.n_leaves;
+    p = tp % pk.P;
+    t = tp / pk.P;
+  }
+  const LdcLeafDev& lf = pk.leaf[li];
+  if (live && p > 0 && lane == 0) {
+    const uint64_t key = pclean_dummy_seed(seed, PCLEAN_SITE_NODE(pk.site_block, lf.node), (uint32_t)p, sweep);
+    s_len[wave] = dummy_draw_string(key, (uint32_t)keys[t], lf.min_len, lf.max_len, pk.lm_init, pk.lm_trans, pk.letter_sym,
+                                    s_str[wave]);
+  }
+  __syncthreads();
+  double part = 0.0;
+  if (live) {
+    const int v0 = p == 0 ? lf.excl[t] : -1;  // retained particle: the value it holds (both densities are table lookups)
+    const int L = p > 0 ? s_len[wave] : 0;
+    int16_t* H = pk.dp + ((size_t)jl * 64 + lane) * pk.lane_cells;
+    for (int ti = 0; ti < lf.n_terms; ++ti) {
+      const LdcTermDev& tm = lf.t[ti];
+      const AggDev ag = lf.agg[ti];
+      const int r1 = ag.end ? ag.end[t] : ag.off[t + 1];
+      for (int r = ag.off[t] + lane; r < r1; r += 64) {
+        const int o = (int)(ag.key[r] & 0xffffffull) - 1;
+        if (o < 0) continue;  // a missing observation
+        int d, Lv;
+        if (p > 0) {
+          const int sid = tm.obs_ids[o];
+          const uint16_t* os = pk.sym + pk.off[sid];
+          const int ol = (int)(pk.off[sid + 1] - pk.off[sid]);
+          if (ol > pk.max_obs_len) {
+            pk.too_long[0] = 1u;
+            continue;
+          }
+          d = dummy_distance(tm.dist_mode, os, ol, s_str[wave], L, H);
+          Lv = L;
+        } else {
+          const size_t pi = (size_t)o * tm.n_lat + v0;
+          d = tm.elem_bytes == 1 ? (int)tm.pair[pi] : (int)((const uint16_t*)tm.pair)[pi];
+          Lv = tm.lat_len[v0];
+        }
+        double l;
+        if (tm.max_typos >= 0 && d > tm.max_typos) {
+          l = -1e5;
+        } else {
+          d = min(d, pk.nb_stride - 1);
+          l = pk.nb[(size_t)((Lv + 4) / 5) * pk.nb_stride + d];
+          l -= pk.logl[Lv] * (double)d;
+          l -= 1.629048269010741 * (double)d;
+        }
+        const size_t pi = (size_t)o * tm.n_lat + lf.dummy_val;
+        const int dph = tm.elem_bytes == 1 ? (int)tm.pair[pi] : (int)((const uint16_t*)tm.pair)[pi];
+        double lph;
+        if (tm.max_typos >= 0 && dph > tm.max_typos) {
+          lph = -1e5;
+        } else {
+          const int Lp = tm.lat_len[lf.dummy_val];
+          lph = pk.nb[(size_t)((Lp + 4) / 5) * pk.nb_stride + dph];
+          lph -= pk.logl[Lp] * (double)dph;
+          lph -= 1.629048269010741 * (double)dph;
+        }
+        part += (double)ag.cnt[r] * (l - lph);
+      }
+    }
+  }
+  s_part[wave][lane] = part;
+  __syncthreads();
+  if (live && lane == 0) {
+    double c = -lf.opt_logp[lf.dummy_k];
+    for (int q = 0; q < 64; ++q) c += s_part[wave][q];
+    corr[j0 + jl] = c;
+  }
+}
+// wl[t * P + p] = the corrections of the slots of (t, p) in root order, 0 where it has none
+__global__ void ldc_weights_kernel(size_t n_tp, int n_leaves, const int32_t* __restrict__ pos, const double* __restrict__ corr,
+                                   double* __restrict__ wl) {
+  const size_t tp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tp >= n_tp) return;
+  double w = 0.0;
+  for (int li = 0; li < n_leaves; ++li) {
+    const int j = pos[tp * n_leaves + li];
+    if (j >= 0) w += corr[j];
+  }
+  wl[tp] = w;
+}
+// an item whose weights are all exactly 0 keeps the choice of latent_choice_kernel
+__global__ void ldc_merge_choice_kernel(int n_items, int P, const double* __restrict__ wl, const int32_t* __restrict__ weighted,
+                                        int32_t* __restrict__ chosen) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_items) return;
+  bool any = false;
+  for (int p = 0; p < P; ++p) any |= wl[(size_t)t * P + p] != 0.0;
+  if (any) chosen[t] = weighted[t];
+}
+// vals[origin[j]][node] = the draw of item origin[j]'s chosen particle
+__global__ void ldc_pick_draw_kernel(int n, int P, const int32_t* __restrict__ origin, const int32_t* __restrict__ particle,
+                                     const int32_t* __restrict__ draws, int n_nodes, int node, int32_t* __restrict__ vals) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) vals[(size_t)origin[j] * n_nodes + node] = draws[(size_t)origin[j] * P + particle[j]];
+}
+
+// The dummy of the option list of node `nid` of a latent plan: latent plans carry no dummy specification of their own; the
+// node of an observed-class block on the same option table does.
+static bool ldc_find_dummy(pclean_ctx* ctx, int table, int32_t* dummy_value, int32_t* dummy_spec) {
+  for (int bi = 0; bi < PCLEAN_MAX_BLOCKS; ++bi) {
+    const Block& ob = ctx->block[bi];
+    if (!ob.valid || ob.is_score) continue;
+    for (const pclean_node& n : ob.nodes)
+      if (n.kind == PCLEAN_NODE_LEAF && n.table == table && n.dummy_value != 0) {
+        *dummy_value = n.dummy_value;
+        *dummy_spec = n.dummy_spec;
+        return true;
+      }
+  }
+  return false;
+}
+// Is root node `nid` of latent plan b served (pclean_hip.h: pclean_set_latent_dummy_correction)?  Fills the host-known part
+// of its description.
+static bool ldc_served(pclean_ctx* ctx, const Block& b, int nid, LdcLeafDev* out, int* max_obs_len) {
+  const pclean_node& n = b.nodes[nid];
+  if (n.kind != PCLEAN_NODE_LEAF || n.n_terms < 1 || n.n_terms > LDC_MAX_TERMS) return false;
+  if (nid < (int)b.node_gauss.size() && b.node_gauss[nid] >= 0) return false;
+  const CandTable& t = ctx->cand[n.table];
+  if (!t.valid || !t.is_options || t.n_cols != 1) return false;
+  int32_t dval = n.dummy_value, dspec = n.dummy_spec;
+  if (dval == 0 && !ldc_find_dummy(ctx, n.table, &dval, &dspec)) return false;
+  if ((dspec & 0xff) != PCLEAN_DUMMY_STRING_PRIOR) return false;
+  LdcLeafDev lf{};
+  lf.node = nid;
+  lf.dummy_val = dval - 1;
+  lf.dummy_k = -1;
+  for (size_t k = 0; k < t.h_vals.size(); ++k)
+    if (t.h_vals[k] == lf.dummy_val) lf.dummy_k = (int)k;
+  if (lf.dummy_k < 0 || (int)t.h_vals.size() != t.n_rows) return false;
+  lf.n_opt = t.n_rows;
+  lf.min_len = (dspec >> 8) & 0xff;
+  lf.max_len = (dspec >> 16) & 0xff;
+  lf.opt_vals = t.cols.p;
+  lf.opt_logp = t.logc_full.p;
+  lf.n_lat_min = INT32_MAX;
+  for (int ti = 0; ti < n.n_terms; ++ti) {
+    const pclean_term& tm = b.terms[n.term_begin + ti];
+    if (tm.dens_kind != PCLEAN_DENS_ADD_TYPOS || tm.ctx_slot >= 0 || tm.cand_col != 0) return false;
+    const PairTable& pt = ctx->pair[tm.pair_table];
+    if (!pt.valid || !pt.obs_ids.p || lf.dummy_val >= pt.n_lat) return false;
+    LdcTermDev& td = lf.t[lf.n_terms++];
+    td.pair = pt.d.p;
+    td.lat_len = pt.lat_len.p;
+    td.obs_ids = pt.obs_ids.p;
+    td.n_lat = pt.n_lat;
+    td.elem_bytes = pt.elem_bytes;
+    td.max_typos = tm.max_typos;
+    td.dist_mode = pt.dist_mode;
+    lf.n_lat_min = std::min(lf.n_lat_min, pt.n_lat);
+    if (max_obs_len) *max_obs_len = std::max(*max_obs_len, pt.max_obs_len);
+  }
+  if (out) *out = lf;
+  return true;
+}
+
+// Steps (a)-(d) of a latent sweep with pclean_set_latent_dummy_correction on (data-driven proposals): draws[r] = the
+// [n_items][P] draws of served root r, ctx->lat_w = the log-weight corrections, chosen = the particle picked from them where
+// they are not all 0.  One count read-back (how many slots).
+static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_idx, int block_id, int n_roots,
+                                const int32_t* roots, int n_items, int P, int use_mh, const int32_t* d_keys,
+                                const int32_t* d_off, const int32_t* d_evr, const int32_t* d_evc, const int32_t* d_excl,
+                                int32_t* d_chosen, std::vector<const int32_t*>& draws, bool* flag_used) {
+  SweepState* s = st(ctx);
+  Block& b = ctx->block[block_id];
+  const size_t NP = (size_t)n_items * P;
+  if (ctx->lat_w.alloc(NP)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  ctx->lat_w_items = n_items;
+  ctx->lat_w_P = P;
+  HIPCHK(ctx, hipMemsetAsync(ctx->lat_w.p, 0, NP * sizeof(double), ctx->stream));
+  if (P < 2) return PCLEAN_OK;
+  LdcPackDev pk{};
+  std::vector<int> served;
+  for (int r = 0; r < n_roots && pk.n_leaves < LDC_MAX_LEAVES; ++r)
+    if (ldc_served(ctx, b, roots[r], &pk.leaf[pk.n_leaves], &pk.max_obs_len)) {
+      served.push_back(r);
+      ++pk.n_leaves;
+    }
+  if (served.empty()) return PCLEAN_OK;
+  if (!ctx->lm_valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "latent dummy correction: pclean_set_lm_tables first");
+  if (pk.max_obs_len > DUMMY_MAX_LEN)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "latent dummy correction: observed strings longer than %d symbols below a "
+                                                 "dummy-bearing choice", DUMMY_MAX_LEN);
+  const int NL = pk.n_leaves;
+  if (NP * NL >= ((size_t)1 << 31)) return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "latent dummy correction: too many particles in one call");
+  ProfScope ps(ctx, "latent_dummy_weights");
+  // (a) every particle's draw of the served option lists: particle ids 0 .. P - 1 at the node's own site
+  ItemList ilall{n_items, nullptr, nullptr, nullptr, nullptr, d_off, d_off + 1, d_evr, d_evc, d_keys};
+  int max_len = 0;
+  for (int i = 0; i < NL; ++i) {
+    LdcLeafDev& lf = pk.leaf[i];
+    int32_t* dr = scratch<int32_t>(ctx, NP);
+    if (!dr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    int rc = eval_node(ctx, block_id, lf.node, ilall, nullptr, seed, sweep_idx, P, nullptr, dr, nullptr, nullptr, false);
+    if (rc) return rc;
+    const AggDev* agg = nullptr;
+    rc = ensure_agg(ctx, block_id, lf.node, ilall, &agg);
+    if (rc) return rc;
+    lf.draws = dr;
+    lf.excl = d_excl + (size_t)served[i] * n_items;
+    lf.agg = agg;
+    draws[served[i]] = dr;
+    max_len = std::max(max_len, lf.max_len);
+  }
+  pk.site_block = block_id;
+  pk.P = P;
+  pk.n_items = n_items;
+  pk.sym = ctx->sym.p;
+  pk.off = ctx->off.p;
+  pk.lm_init = ctx->lm_init.p;
+  pk.lm_trans = ctx->lm_trans.p;
+  pk.letter_sym = ctx->letter_sym.p;
+  pk.nb = ctx->nb.p;
+  pk.logl = ctx->logl.p;
+  pk.nb_stride = ctx->max_d + 1;
+  // (b) the slots that need a correction
+  const size_t NQ = NP * NL;
+  int32_t* flag = scratch<int32_t>(ctx, NQ);
+  int32_t* slots = scratch<int32_t>(ctx, NQ);
+  int32_t* pos = scratch<int32_t>(ctx, NQ);
+  if (!flag || !slots || !pos) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(ldc_flag_kernel, grid1(NQ), dim3(256), 0, ctx->stream, pk, NQ, flag);
+  HIPCHK(ctx, hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), ctx->stream));
+  hipLaunchKernelGGL(compact_new_kernel, grid1(NQ), dim3(256), 0, ctx->stream, NQ, flag, 0, s->counter.p, nullptr, nullptr);
+  unsigned int n_slots = 0;
+  PCLEAN_READ_COUNT(ctx, s->counter.p, &n_slots);
+  static const bool dbg = getenv("PCLEAN_DEBUG_DUMMY") != nullptr;
+  if (dbg) fprintf(stderr, "[pclean] latent block %d: %u dummy slots among %zu (row, particle, choice)\n", block_id, n_slots, NQ);
+  if (n_slots == 0) return PCLEAN_OK;
+  if (n_slots > NQ) return pclean_fail(ctx, PCLEAN_ERR_STATE, "latent dummy correction: slot count out of range");
+  HIPCHK(ctx, hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), ctx->stream));
+  hipLaunchKernelGGL(compact_new_kernel, grid1(NQ), dim3(256), 0, ctx->stream, NQ, flag, 1, s->counter.p, slots, pos);
+  // (c) their corrections, in slices whose distance matrices (one per lane) fit the arena
+  const char* ae = getenv("PCLEAN_LATENT_DUMMY_ARENA");  // int16 cells (tests: a launch cut into several slices)
+  const size_t arena = ae && atoll(ae) > 0 ? (size_t)atoll(ae) : LDC_ARENA_CELLS;
+  pk.lane_cells = (int64_t)(pk.max_obs_len + 2) * (max_len + 2);
+  const size_t slot_cells = (size_t)pk.lane_cells * 64;
+  const int per_launch = (int)std::min<size_t>(std::max<size_t>(arena / slot_cells, 1), n_slots);
+  double* corr = scratch<double>(ctx, n_slots);
+  if (!corr || ctx->lat_dp.alloc((size_t)per_launch * slot_cells) || ctx->lat_flag.alloc(1))
+    return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemsetAsync(ctx->lat_flag.p, 0, sizeof(unsigned int), ctx->stream));
+  pk.dp = ctx->lat_dp.p;
+  pk.too_long = ctx->lat_flag.p;
+  {
+    ProfScope pk_scope(ctx, "latent_dummy_correction_kernel");
+    for (unsigned int j0 = 0; j0 < n_slots; j0 += (unsigned int)per_launch) {
+      const int cnt = (int)std::min<unsigned int>((unsigned int)per_launch, n_slots - j0);
+      hipLaunchKernelGGL(latent_dummy_correction_kernel, dim3((cnt + 3) / 4), dim3(256), 0, ctx->stream, (int)j0, cnt, slots,
+                         pk, d_keys, seed, sweep_idx, corr);
+    }
+  }
+  hipLaunchKernelGGL(ldc_weights_kernel, grid1(NP), dim3(256), 0, ctx->stream, NP, NL, pos, corr, ctx->lat_w.p);
+  // (d) the particle, from the weights
+  int32_t* weighted = scratch<int32_t>(ctx, n_items);
+  if (!weighted) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  DISPATCH_PMAX(P, hipLaunchKernelGGL(latent_prior_choice_kernel<PMAX>, grid1(n_items), dim3(256), 0, ctx->stream, n_items, P,
+                                      use_mh, ctx->lat_w.p, d_keys, seed, sweep_idx, (uint32_t)block_id, weighted));
+  hipLaunchKernelGGL(ldc_merge_choice_kernel, grid1(n_items), dim3(256), 0, ctx->stream, n_items, P, ctx->lat_w.p, weighted,
+                     d_chosen);
+  HIPCHK(ctx, hipGetLastError());
+  *flag_used = true;  // (the "string too long" mark rides on the call's last synchronisation)
+  return PCLEAN_OK;
+}
+
 // res_rows / res_ctx: the items' evidence rows (and per-row ctx values) already on the device (pclean_sweep_latent_resident);
 // the host arrays ev_rows / ev_ctx are not looked at then (has_ctx says whether the plan's terms read per-row ctx values)
 static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, uint64_t seed, uint32_t sweep_idx,
@@ -577,7 +919,7 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
   const size_t b_keys = (size_t)n_items * 4, b_off = ((size_t)n_items + 1) * 4, b_evr = res_rows ? 0 : (size_t)n_ev * 4,
                b_evc = (ev_ctx && n_ev) ? (size_t)n_ev * PCLEAN_MAX_CTX * 4 : 0, b_excl = (size_t)n_roots * n_items * 4,
                b_vals = (size_t)n_items * nn * 4;
-  if (ctx->stage.grow(2 * b_keys + b_off + b_evr + b_evc + b_excl + b_vals + 8 * 256))
+  if (ctx->stage.grow(2 * b_keys + b_off + b_evr + b_evc + b_excl + b_vals + 10 * 256))
     return pclean_fail(ctx, PCLEAN_ERR_HIP, "page-locked staging alloc failed");
   ctx->stage.rewind();
   auto stage_up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
@@ -593,6 +935,7 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
   HIPCHK(ctx, stage_up(d_excl, excl, b_excl));
   int32_t* h_chosen = (int32_t*)ctx->stage.take(b_keys);
   int32_t* h_vals = (int32_t*)ctx->stage.take(b_vals);
+  unsigned int* h_ldc_flag = (unsigned int*)ctx->stage.take(sizeof(unsigned int));
   int32_t* d_iop = scratch<int32_t>(ctx, std::max(n_ev, 1));
   if (!d_iop) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
   if (n_ev) hipLaunchKernelGGL(item_of_pos_kernel, grid1(n_ev), dim3(256), 0, ctx->stream, n_ev, n_items, d_off, d_iop);
@@ -709,6 +1052,15 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
                      sweep_idx, (uint32_t)block_id, d_chosen);
   hipLaunchKernelGGL(fill_i32_kernel, grid1((size_t)n_items * nn), dim3(256), 0, ctx->stream, d_vals,
                      (size_t)n_items * nn, -2);
+  // pclean_set_latent_dummy_correction: the served option lists draw for every particle first, the particles that took (or
+  // stand for) a dummy are weighed, and the choice above is replaced where a weight differs from 0
+  std::vector<const int32_t*> served_draws(n_roots, nullptr);  // per root: its [n_items][P] draws, null: not served
+  bool ldc_flag_used = false;
+  if (ctx->latent_dummy) {
+    const int rcl = latent_dummy_weights(ctx, seed, sweep_idx, block_id, n_roots, roots, n_items, P, use_mh, d_keys, d_off,
+                                         d_evr, d_evc, d_excl, d_chosen, served_draws, &ldc_flag_used);
+    if (rcl) return rcl;
+  }
   // rows that take a fresh particle
   hipLaunchKernelGGL(mark_positive_kernel, grid1(n_items), dim3(256), 0, ctx->stream, n_items, d_chosen, d_flag);
   HIPCHK(ctx, hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), ctx->stream));
@@ -788,6 +1140,11 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
         const int K = side_streams(ctx), n_fk_side = fk_first ? std::min((int)fk_roots.size(), std::max(K - 1, 0)) : 0;
         const int rcs = sf.use(K > n_fk_side ? n_fk_side + (int)oi % (K - n_fk_side) : (int)oi);
         if (rcs) return rcs;
+        if (served_draws[r]) {  // (drawn for every particle before the choice: latent_dummy_weights)
+          hipLaunchKernelGGL(ldc_pick_draw_kernel, grid1(cnt), dim3(256), 0, ctx->stream, (int)cnt, P, org, part, served_draws[r],
+                             nn, root, d_vals);
+          continue;
+        }
         int32_t* draws = scratch<int32_t>(ctx, cnt);
         if (!draws) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
         int rc = eval_node(ctx, block_id, root, il, nullptr, seed, sweep_idx, 1, nullptr, draws, nullptr, nullptr, false);
@@ -833,6 +1190,7 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
   }
   HIPCHK(ctx, hipMemcpyAsync(h_chosen, d_chosen, b_keys, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(h_vals, d_vals, b_vals, hipMemcpyDeviceToHost, ctx->stream));
+  if (ldc_flag_used) HIPCHK(ctx, hipMemcpyAsync(h_ldc_flag, ctx->lat_flag.p, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
   {
     int rcq = queue_over_copy(ctx);  // the sync-free re-runs' counts ride on the call's one synchronisation
     if (!rcq) rcq = d2h_flush(ctx);
@@ -841,6 +1199,9 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
   PCLEAN_SYNC(ctx);
   memcpy(chosen, h_chosen, b_keys);
   memcpy(vals, h_vals, b_vals);
+  if (ldc_flag_used && *h_ldc_flag)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "latent dummy correction: an observed string is longer than its pair table "
+                                                 "announced");
   apply_over_stats(ctx);
   s->lat_agg.clear();
   if (s->prof_on) prof_collect(ctx);

@@ -626,18 +626,56 @@ class Engine:
                     for bi, blk in enumerate(self.lw.blocks) if not blk.get("score")}
         return {bi: self.hip.get_moved(bi) for bi, blk in enumerate(self.lw.blocks) if not blk.get("score")}
 
-    def sweep_latent(self, trace, cname, config, seed, sweep_idx, live, ev_off, ev_rows, ev_ctx, excl, ev_begin=None):
+    def latent_dummy_served(self, cname):
+        """Attributes of latent class cname whose chosen ProposalDummyValues a latent sweep with dummy_correction=True
+        weighs (pclean_set_latent_dummy_correction): the class's own choices (leaf roots of its plan) with an unkeyed
+        StringPrior whose evidence terms are all plain AddTypos terms (no JuliaNode context, not tabulated, no Gaussian
+        term on the node).  Everything else — TimePrior choices, keyed priors, reference slots — is swept as with the
+        flag off."""
+        lw = self.lw
+        pl = lw.latent_plans.get(cname)
+        if pl is None:
+            return []
+        out = []
+        for r, root in enumerate(pl["roots"]):
+            node = pl["nodes"][root]
+            if node[0] != _lib.NODE_LEAF:
+                continue
+            attr = pl["root_attr"][r]
+            d = lw.model.classes[cname].attr(attr).dist
+            if not isinstance(d, StringPrior) or getattr(d, "keyed_by", None):
+                continue
+            terms = pl["terms"][node[2]:node[2] + node[3]]
+            if not 1 <= len(terms) <= 2 or (pl["block_id"], root) in getattr(lw, "gauss", {}):
+                continue
+            typo_pairs = {pid for pid, _, _ in lw.pair_id.values()}  # (AddTypos tables: built on the device from the strings)
+            if all(t[3] == _lib.DENS_ADD_TYPOS and t[5] < 0 and t[2] in typo_pairs for t in terms):
+                out.append(attr)
+        return out
+
+    def sweep_latent(self, trace, cname, config, seed, sweep_idx, live, ev_off, ev_rows, ev_ctx, excl, ev_begin=None,
+                     dummy_correction=False):
         """Rejuvenation of the latent rows `live` of class cname against their evidence sets
         (pclean_sweep_latent).  Returns (chosen particle, sampled node values) per latent row.  ev_begin (with ev_rows
-        None): the rows' evidence starts at that position of the evidence build_evidence_device left on the device."""
+        None): the rows' evidence starts at that position of the evidence build_evidence_device left on the device.
+        dummy_correction: the particles of the served choices (latent_dummy_served) that chose, or stand for, the
+        ProposalDummyValue are weighed as block_proposal.jl:49-60 does (excl then names the drawn strings that rows
+        hold: inference.latent_current_choices); latent_weights() returns the corrections afterwards."""
         pl = self.lw.latent_plans[cname]
         cfg = config.as_c() if isinstance(config, InferenceConfig) else config
         self.hip.set_active_rows(0, -1)
+        if dummy_correction or getattr(self, "_latent_dummy_on", False):  # (a reload makes a fresh context: set per call)
+            self.hip.set_latent_dummy_correction(dummy_correction)
+            self._latent_dummy_on = bool(dummy_correction)
         if ev_begin is not None:
             return self.hip.sweep_latent_resident(cfg, seed, sweep_idx, pl["block_id"], pl["roots"], live, ev_off, ev_begin,
                                                   excl, len(pl["nodes"]))
         return self.hip.sweep_latent(cfg, seed, sweep_idx, pl["block_id"], pl["roots"], live, ev_off, ev_rows, ev_ctx,
                                      excl, len(pl["nodes"]))
+
+    def latent_weights(self):
+        """log-weight corrections [rows][particles] of the last sweep_latent(..., dummy_correction=True) (parity checks)"""
+        return self.hip.get_latent_weights()
 
     def build_evidence_device(self, trace, cname):
         """inference.build_evidence on the device (pclean_build_evidence): returns (live, ev_off, None, None) with the ordered

@@ -188,7 +188,16 @@ def _count_dummy_cases(lw, trace, todo, obs):
 
 
 def _leaf_node_of(lw, bi, cname, aname):
-    """node id of the option list of attribute cname.aname in observed-class block bi (None if it has none)"""
+    """node id of the option list of attribute cname.aname in observed-class block bi (None if it has none); bi beyond the
+    observed class's blocks: the plan of latent class cname, whose own choice aname is a root"""
+    if bi >= len(lw.blocks):
+        pl = lw.latent_plans.get(cname)
+        if pl is None or pl["block_id"] != bi:
+            return None
+        for r, root in enumerate(pl["roots"]):
+            if pl["nodes"][root][0] == 1 and pl["root_attr"][r] == aname:
+                return root
+        return None
     for nid, info in enumerate(lw.blocks[bi]["node_info"]):
         if info["kind"] == "leaf" and info["cls"] == cname and info["attr"] == aname:
             return nid
@@ -238,13 +247,16 @@ def resample_dummies(engine, trace, seed, stamp):
         strings = engine.sample_prior_strings(d, len(rows), seed, stream)
         if isinstance(d, StringPrior) and hasattr(engine, "sample_prior_strings_at"):
             # rows created by an observed-class sweep: the string the sweep already drew for the creating particle's
-            # weight (private stream pclean_dummy_seed(seed, site of the option list, particle, sweep) at the creating row)
+            # weight (private stream pclean_dummy_seed(seed, site of the option list, particle, sweep) at the creating row);
+            # rows whose own choice took the dummy in a latent sweep with dummy_correction: the same, at the latent row
             seeds, elems, where = [], [], []
             for i, r in enumerate(rows):
                 org = trace.row_origin.get((cname, int(r)))
                 if org is None:
                     continue
                 row_o, particle, sweep_idx, bi = org
+                if bi >= len(lw.blocks) and an not in engine.latent_dummy_served(cname):
+                    continue  # (recorded by a latent sweep with dummy_correction: only the served choices were weighed)
                 node = _leaf_node_of(lw, bi, cname, an)
                 if node is None:
                     continue
@@ -323,10 +335,13 @@ def _materialise_latent(lw, trace, pl, node, vals):
     return trace.insert_row(cname, values)
 
 
-def commit_latent(lw, trace, cname, live, chosen, vals):
+def commit_latent(lw, trace, cname, live, chosen, vals, dummy_origin=None):
     """Apply a latent-class sweep: rows whose chosen particle is fresh take the sampled values
     (run_smc! tail, row_inference.jl:169-185, for a latent row).  Array operations over all changed rows;
-    only proposals of a brand-new referent are built one by one."""
+    only proposals of a brand-new referent are built one by one.  dummy_origin = (served attributes, sweep_idx) of a
+    sweep with dummy_correction: a committed row whose served choice took the ProposalDummyValue is recorded in
+    trace.row_origin as (key = the row, chosen particle, sweep_idx, the plan's block id) — the draw stream of the string
+    its weight was computed with, which resample_dummies then gives it."""
     pl = lw.latent_plans[cname]
     t = trace.tables[cname]
     idx = np.flatnonzero(np.asarray(chosen) > 0)
@@ -334,6 +349,20 @@ def commit_latent(lw, trace, cname, live, chosen, vals):
         return 0
     h = np.asarray(live, dtype=np.int64)[idx]
     vals = np.asarray(vals)
+    if dummy_origin is not None and dummy_origin[0]:
+        served, sweep_idx = dummy_origin
+        took = np.zeros(len(idx), dtype=bool)
+        for r, root in enumerate(pl["roots"]):
+            attr = pl["root_attr"][r]
+            if attr in served:
+                dummy = lw.latent_dom[(cname, attr)].get(lw.model.classes[cname].attr(attr).dist.dummy_value())
+                took |= lw.option_values[(cname, attr)][vals[idx, root]] == dummy
+        particles = np.asarray(chosen)[idx]
+        for k in range(len(idx)):  # (a row that holds no dummy needs no origin: an older record is dropped)
+            if took[k]:
+                trace.set_row_origin(cname, int(h[k]), int(h[k]), int(particles[k]), int(sweep_idx), int(pl["block_id"]))
+            else:
+                trace.set_row_origin(cname, int(h[k]), None)
     fks, props = trace._class_plan(cname)
     for j, state in props:  # own-choice sufficient statistics: take the old values out ...
         np.subtract.at(state.counts, t.cols[j, h], 1)
@@ -397,11 +426,14 @@ def _crosses_rejuv(b0, b1, config):
     return b1 // rf != b0 // rf
 
 
-def latent_current_choices(lw, trace, cname, rows, config):
+def latent_current_choices(lw, trace, cname, rows, config, dummy_served=()):
     """excl argument of pclean_sweep_latent for latent rows `rows` of class cname: per sub-plan root the row's current
     referent (reference slots; -1 for choices).  With use_dd_proposals = false the retained particle must also name the
     current OPTION of every choice: the index of the row's value in the proposal's options — a value that is no option
-    (a string drawn for a chosen dummy) counts as the ProposalDummyValue, as in block_proposal.jl:49-52."""
+    (a string drawn for a chosen dummy) counts as the ProposalDummyValue, as in block_proposal.jl:49-52.
+    dummy_served (data-driven proposals with dummy_correction: Engine.latent_dummy_served): for these choices the entry
+    is the latent-domain id of the row's current value when that value is no option (a string drawn earlier, which the
+    retained particle holds in place of the dummy), else -1."""
     pl = lw.latent_plans[cname]
     t = trace.tables[cname]
     excl = np.full((len(pl["roots"]), len(rows)), -1, dtype=np.int32)
@@ -409,7 +441,11 @@ def latent_current_choices(lw, trace, cname, rows, config):
         col = lw.colidx[cname][pl["root_attr"][r]]
         if pl["nodes"][root][0] == 0:
             excl[r] = t.cols[col, rows]
-        elif not getattr(config, "use_dd_proposals", True):
+        elif getattr(config, "use_dd_proposals", True):
+            if pl["root_attr"][r] in dummy_served:
+                cur = t.cols[col, rows]
+                excl[r] = np.where(np.isin(cur, lw.option_values[(cname, pl["root_attr"][r])]), -1, cur)
+        else:
             opts = lw.option_values[(cname, pl["root_attr"][r])]
             index = np.full(len(lw.latent_dom[(cname, pl["root_attr"][r])]) + 1, -1, dtype=np.int32)
             index[opts[::-1]] = np.arange(len(opts) - 1, -1, -1)  # first option holding each value
@@ -423,13 +459,20 @@ def latent_current_choices(lw, trace, cname, rows, config):
 
 
 def latent_sweep(engine, trace, cname, config, seed, sweep_idx, comm=None, max_sub_batches=32, verbose=False,
-                 batch_rows=None):
+                 batch_rows=None, dummy_correction=False):
     """One rejuvenation sweep of latent class cname.  With several ranks the live latent rows are
     block-partitioned: a rank scores its rows against their complete evidence sets (observations and
     trace are replicated), then (chosen particle, sampled values) are all-gathered and every rank
-    applies the same commit — no floating-point reduction, identical result for any rank count."""
+    applies the same commit — no floating-point reduction, identical result for any rank count.
+    dummy_correction (one process, data-driven proposals): the class's served choices (Engine.latent_dummy_served) weigh
+    a particle that chose, or stands for, the ProposalDummyValue as block_proposal.jl:49-60 does, and a committed row
+    gets exactly the string its weight was computed with."""
     comm = comm or Comm()
+    if dummy_correction and comm.world > 1:
+        raise NotImplementedError("latent sweeps with dummy_correction run in one process")
     lw = engine.lw
+    served = list(engine.latent_dummy_served(cname)) if dummy_correction and config.use_dd_proposals else []
+    extra = dict(dummy_correction=True) if dummy_correction else {}
     pl = lw.latent_plans[cname]
     from ._lib import _ctx_cols
     dev_sort = getattr(getattr(engine, "hip", None), "argsort_ids", None) if not os.environ.get("PCLEAN_HOST_ARGSORT") else None
@@ -467,7 +510,7 @@ def latent_sweep(engine, trace, cname, config, seed, sweep_idx, comm=None, max_s
             resample_class_parameters(trace, cname)
             if verbose and (b0 // max(config.reporting_frequency, 1)) != ((b0 - 1) // max(config.reporting_frequency, 1)):
                 print(f"{cname}: Cleaning row {b0} of {len(live)}", flush=True)
-        excl = latent_current_choices(lw, trace, cname, live[b0:b1], config)
+        excl = latent_current_choices(lw, trace, cname, live[b0:b1], config, served)
         with _timed(f"latent/{cname}/upload"):
             engine.upload_trace(trace)
         lo, hi = shard_bounds(b1 - b0, comm.rank, comm.world)
@@ -480,17 +523,17 @@ def latent_sweep(engine, trace, cname, config, seed, sweep_idx, comm=None, max_s
                 if ev_rows is None:  # (resident evidence)
                     chosen, vals = engine.sweep_latent(trace, cname, config, seed, sweep_idx, live[lo:hi],
                                                        ev_off[lo:hi + 1] - e0, None, None,
-                                                       np.ascontiguousarray(excl[:, lo - b0:hi - b0]), ev_begin=e0)
+                                                       np.ascontiguousarray(excl[:, lo - b0:hi - b0]), ev_begin=e0, **extra)
                 else:
                     chosen, vals = engine.sweep_latent(trace, cname, config, seed, sweep_idx, live[lo:hi],
                                                        ev_off[lo:hi + 1] - e0, ev_rows[e0:e1],
                                                        None if ev_ctx is None else ev_ctx[e0:e1],
-                                                       np.ascontiguousarray(excl[:, lo - b0:hi - b0]))
+                                                       np.ascontiguousarray(excl[:, lo - b0:hi - b0]), **extra)
         if comm.world > 1:
             chosen = comm.allgather_varlen_i32(chosen)
             vals = comm.allgather_varlen_i32(vals).reshape(-1, len(pl["nodes"]))
         with _timed(f"latent/{cname}/commit"):
-            changed += commit_latent(lw, trace, cname, live[b0:b1], chosen, vals)
+            changed += commit_latent(lw, trace, cname, live[b0:b1], chosen, vals, (served, sweep_idx) if served else None)
             if _after_commit(engine, trace, seed):
                 pl = lw.latent_plans[cname]  # (the lowered model was rebuilt in place)
                 # placeholders became drawn strings: per-evidence-row ctx values may have held a dummy's id
@@ -654,7 +697,7 @@ def initialize_trace(engine, trace, config, seed, max_batch=256, comm=None, merg
 
 
 def run_inference(engine, trace, config, seed, verbose=False, comm=None, max_sub_batches=32, batch_rows=None, tally=None,
-                  tally_from=0):
+                  tally_from=0, latent_dummy_correction=False):
     """run_inference! (inference.jl:83-88): config.num_iters sweeps over all classes.  `comm` shards
     every class sweep over the ranks of a torch.distributed job (one process per GPU).  A class sweep is
     cut into sub-batches between which the class's parameters are resampled (`sub_batches`): at most
@@ -662,8 +705,11 @@ def run_inference(engine, trace, config, seed, verbose=False, comm=None, max_sub
     cadence exactly; batch_rows=1 is the reference's sequential schedule (sub_batches).  use_lo_sweeps is, as in the reference, only read by instrumented_inference.jl (out of
     scope): pgibbs_sweep! sweeps the latent classes regardless of it.  tally (tally.CellTally): the cleaned table after
     every iteration it >= tally_from is added to its ring of kept samples (on the device, where the sweeps leave the state);
-    the trace is only read."""
+    the trace is only read.  latent_dummy_correction: the latent sweeps weigh chosen ProposalDummyValues
+    (latent_sweep(..., dummy_correction=True); one process)."""
     lw = engine.lw
+    if latent_dummy_correction and comm is not None and comm.world > 1:
+        raise NotImplementedError("latent_dummy_correction runs in one process")
     if hasattr(engine, "prepare") and not getattr(engine, "_prepared", False):
         with _timed("prepare"):
             engine.prepare(trace, comm)  # (one-time: compact tables and caches of every class, device-resident commit)
@@ -672,7 +718,8 @@ def run_inference(engine, trace, config, seed, verbose=False, comm=None, max_sub
             print(f"Iteration {it + 1}/{config.num_iters}", flush=True)
         for cname in lw.model.class_order:
             if cname in lw.latent_plans:
-                ch = latent_sweep(engine, trace, cname, config, seed, it, comm, max_sub_batches, verbose, batch_rows)
+                ch = latent_sweep(engine, trace, cname, config, seed, it, comm, max_sub_batches, verbose, batch_rows,
+                                  **(dict(dummy_correction=True) if latent_dummy_correction else {}))
             elif cname == lw.query.cls:
                 ch = observed_sweep(engine, trace, config, seed, it, comm, max_sub_batches, verbose, batch_rows)
             else:

@@ -336,6 +336,15 @@ class Trace:
             self.row_origin.pop((cname, int(r)), None)
         return r
 
+    def set_row_origin(self, cname, row, key, particle=0, sweep_idx=0, block_id=0):
+        """row_origin of an EXISTING row whose own choice took a ProposalDummyValue in a latent sweep that weighed it
+        (inference.commit_latent): (RNG key of the row in that sweep, chosen particle, sweep_idx, block id of the class's
+        plan) — what names the private stream of the drawn string; key None drops the record."""
+        if key is None:
+            self.row_origin.pop((cname, int(row)), None)
+        else:
+            self.row_origin[(cname, int(row))] = (int(key), int(particle), int(sweep_idx), int(block_id))
+
     def delete_row(self, cname, r):
         """unrefer_to_row! tail (dependency_tracking.jl:189-201): drop the row, release its referents."""
         t = self.tables[cname]

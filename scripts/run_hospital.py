@@ -16,7 +16,7 @@ from pclean_amd.model import LoweredModel
 from pclean_amd.trace import Trace
 
 
-def main(particles=2, mh=True, iters=1, seed=0, shuffle=True, consensus=0):
+def main(particles=2, mh=True, iters=1, seed=0, shuffle=True, consensus=0, latent_dummy_correction=False):
     dirty, clean = ex.hospital_data()
     if shuffle:  # random row order for the batched initialisation (experiments.shuffle_rows)
         (dirty, clean), _ = ex.shuffle_rows([dirty, clean], seed)
@@ -39,7 +39,11 @@ def main(particles=2, mh=True, iters=1, seed=0, shuffle=True, consensus=0):
     if consensus:
         from pclean_amd.tally import CellTally
         tally = CellTally(eng, tr, keep=consensus)
-    run_inference(eng, tr, cfg, seed, verbose=True, tally=tally, tally_from=max(0, iters - consensus))
+    if latent_dummy_correction:
+        print("latent sweeps weigh chosen dummy values of:",
+              {c: eng.latent_dummy_served(c) for c in lw.latent_plans if eng.latent_dummy_served(c)}, flush=True)
+    run_inference(eng, tr, cfg, seed, verbose=True, tally=tally, tally_from=max(0, iters - consensus),
+                  latent_dummy_correction=latent_dummy_correction)
     t2 = time.time()
     acc = evaluate_accuracy(lw, tr, dirty, clean)
     if tally is not None:
@@ -62,5 +66,8 @@ if __name__ == "__main__":
         i = a.index("--consensus")
         k = int(a[i + 1])
         del a[i:i + 2]
-    main(consensus=k, particles=int(a[0]) if a else 2, mh=(a[1] == "mh") if len(a) > 1 else True, iters=int(a[2]) if len(a) > 2 else 1,
+    ldc = "--latent-dummy-correction" in a  # latent sweeps weigh chosen ProposalDummyValues (block_proposal.jl:49-60)
+    if ldc:
+        a.remove("--latent-dummy-correction")
+    main(consensus=k, latent_dummy_correction=ldc, particles=int(a[0]) if a else 2, mh=(a[1] == "mh") if len(a) > 1 else True, iters=int(a[2]) if len(a) > 2 else 1,
          shuffle="sorted" not in a)
