@@ -202,6 +202,20 @@ class HipContext:
                                                      C.c_int32(table.shape[1]), _p(table, C.c_uint8)),
               "pclean_set_pair_table")
 
+    def set_pair_strings(self, table_id, obs_ids, lat_ids):
+        """pool strings behind a host-computed 0/1 "same string" table (after set_pair_table)"""
+        obs_ids = np.ascontiguousarray(obs_ids, dtype=np.int32)
+        lat_ids = np.ascontiguousarray(lat_ids, dtype=np.int32)
+        check(self.h, self.lib.pclean_set_pair_strings(self.h, C.c_int32(table_id), C.c_int32(len(obs_ids)),
+                                                       _p(obs_ids, C.c_int32), C.c_int32(len(lat_ids)),
+                                                       _p(lat_ids, C.c_int32)), "pclean_set_pair_strings")
+
+    def set_time_symbols(self, sym16):
+        """pool symbols of 0 .. 9 : ' ' a p . m (0xFFFF: not in the pool): what a rendered TimePrior draw is made of"""
+        sym16 = np.ascontiguousarray(sym16, dtype=np.uint16)
+        assert sym16.size == 16
+        check(self.h, self.lib.pclean_set_time_symbols(self.h, _p(sym16, C.c_uint16)), "pclean_set_time_symbols")
+
     # -- tabulated likelihood terms (DENS_TABULATED) ----------------------------
     def set_fold_table(self, fold):
         fold = np.ascontiguousarray(fold, dtype=np.uint16)
@@ -444,6 +458,16 @@ class HipContext:
                                                         _p(out, C.c_int32)), "pclean_random_time_prior")
         return out
 
+    def random_time_prior_at(self, seeds, elems):
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        elems = np.ascontiguousarray(elems, dtype=np.uint32)
+        assert seeds.shape == elems.shape
+        out = np.zeros((len(seeds), 3), dtype=np.int32)
+        check(self.h, self.lib.pclean_random_time_prior_at(self.h, C.c_int32(len(seeds)), _p(seeds, C.c_uint64),
+                                                           _p(elems, C.c_uint32), _p(out, C.c_int32)),
+              "pclean_random_time_prior_at")
+        return out
+
     def table_shape(self, table_id):
         """(rows, columns) of a candidate table as the library holds it (a latent table uploaded with spare capacity
         for the device-resident commit has more rows than the trace's table)"""
@@ -594,6 +618,13 @@ class HipContext:
         """pclean_set_latent_dummy_correction: latent sweeps weigh chosen ProposalDummyValues (off by default)"""
         check(self.h, self.lib.pclean_set_latent_dummy_correction(self.h, C.c_int(int(bool(on)))),
               "pclean_set_latent_dummy_correction")
+
+    def set_latent_dummy_options(self, dummy_k):
+        """pclean_set_latent_dummy_options: int32 [n_roots][n_items], the dummy option of every row's key in the option table
+        of every keyed root (-1: not keyed / no options), for the next sweep_latent call alone"""
+        dummy_k = np.ascontiguousarray(dummy_k, dtype=np.int32)
+        check(self.h, self.lib.pclean_set_latent_dummy_options(self.h, C.c_int32(dummy_k.shape[0]), C.c_int32(dummy_k.shape[1]),
+                                                               _p(dummy_k, C.c_int32)), "pclean_set_latent_dummy_options")
 
     def get_latent_weights(self):
         """pclean_get_latent_weights: log-weight corrections [n_items][P] of the last corrected latent sweep (parity checks)"""

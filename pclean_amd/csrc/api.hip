@@ -46,6 +46,8 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
   ctx->lat_w.release();
   ctx->lat_dp.release();
   ctx->lat_flag.release();
+  ctx->lat_dk.release();
+  ctx->time_sym.release();
   ctx->sym.release();
   ctx->off.release();
   ctx->obs.release();
@@ -57,6 +59,8 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
     p.d.release();
     p.lat_len.release();
     p.obs_ids.release();
+    p.same_obs_ids.release();
+    p.same_lat_ids.release();
     p.cls.release();
   }
   ctx->fold.release();
@@ -89,6 +93,30 @@ extern "C" const char* pclean_last_error(const pclean_ctx* ctx) { return ctx ? c
 extern "C" int pclean_set_latent_dummy_correction(pclean_ctx* ctx, int on) {
   if (!ctx || on < 0 || on > 1) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_latent_dummy_correction: bad arguments");
   ctx->latent_dummy = on != 0;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_set_latent_dummy_options(pclean_ctx* ctx, int32_t n_roots, int32_t n_items, const int32_t* dummy_k) {
+  if (!ctx || n_roots <= 0 || n_items < 0 || (n_items > 0 && !dummy_k))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_latent_dummy_options: bad arguments");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ctx->lat_dk_valid = false;
+  const size_t n = (size_t)n_roots * n_items;
+  (void)hipStreamSynchronize(ctx->stream);  // (no kernel reads the previous call's values any more)
+  if (ctx->lat_dk.alloc(std::max<size_t>(n, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  if (n) HIPCHK(ctx, hipMemcpy(ctx->lat_dk.p, dummy_k, n * sizeof(int32_t), hipMemcpyHostToDevice));
+  ctx->lat_dk_roots = n_roots;
+  ctx->lat_dk_items = n_items;
+  ctx->lat_dk_valid = true;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_set_time_symbols(pclean_ctx* ctx, const uint16_t* sym16) {
+  if (!ctx || !sym16) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_time_symbols: bad arguments");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->time_sym.alloc(16)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemcpy(ctx->time_sym.p, sym16, 16 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  ctx->time_sym_valid = true;
   return PCLEAN_OK;
 }
 
@@ -416,6 +444,8 @@ extern "C" int pclean_set_pair_table(pclean_ctx* ctx, int32_t table_id, int32_t 
   pt.n_lat = n_lat;
   pt.elem_bytes = 1;
   pt.max_lat_len = pt.max_obs_len = 0;
+  pt.same_obs_ids.release();
+  pt.same_lat_ids.release();
   int rc = pclean_ensure_density(ctx, 64);
   if (rc) return rc;
   if (pt.d.alloc((size_t)n_obs * n_lat) || pt.lat_len.alloc(n_lat))
@@ -424,6 +454,25 @@ extern "C" int pclean_set_pair_table(pclean_ctx* ctx, int32_t table_id, int32_t 
   HIPCHK(ctx, hipMemset(pt.lat_len.p, 0, n_lat * sizeof(uint16_t)));
   pt.valid = true;
   pt.version = ++g_pclean_version;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_set_pair_strings(pclean_ctx* ctx, int32_t table_id, int32_t n_obs, const int32_t* obs_ids, int32_t n_lat,
+                                       const int32_t* lat_ids) {
+  if (!ctx || table_id < 0 || table_id >= PCLEAN_MAX_TABLES || n_obs <= 0 || n_lat <= 0 || !obs_ids || !lat_ids)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_pair_strings: bad arguments");
+  PairTable& pt = ctx->pair[table_id];
+  if (!pt.valid || pt.n_obs != n_obs || pt.n_lat != n_lat)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_pair_strings: pair table %d is not a %d x %d table", table_id, n_obs, n_lat);
+  if (ctx->n_strings == 0) return pclean_fail(ctx, PCLEAN_ERR_STATE, "load strings first");
+  int max_la = 0, max_lb = 0;
+  int rc = check_string_ids(ctx, n_obs, obs_ids, "obs", &max_la);
+  if (!rc) rc = check_string_ids(ctx, n_lat, lat_ids, "lat", &max_lb);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (pt.same_obs_ids.alloc(n_obs) || pt.same_lat_ids.alloc(n_lat)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemcpy(pt.same_obs_ids.p, obs_ids, (size_t)n_obs * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(pt.same_lat_ids.p, lat_ids, (size_t)n_lat * sizeof(int32_t), hipMemcpyHostToDevice));
   return PCLEAN_OK;
 }
 

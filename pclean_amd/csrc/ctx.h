@@ -86,6 +86,8 @@ struct PairTable {
   int32_t dist_mode = PCLEAN_DIST_DL;  // flavour the table was built with (dummy_dev.h scores drawn strings with it)
   int32_t max_lat_len = 0, max_obs_len = 0;
   double mean_lat_len = 0.0;  // AddTypos tables built on the device: mean length of the latent strings
+  DevBuf<int32_t> same_obs_ids, same_lat_ids;  // host-set 0/1 "same string" tables: pool string of every observed / latent
+                                               // value (pclean_set_pair_strings; forgotten by pclean_set_pair_table)
   DevBuf<double> cls;         // [n_lat][4] class densities of a PCLEAN_DENS_TABULATED term (pclean_set_class_density)
   bool cls_valid = false;     // ... uploaded since the table was last built
 };
@@ -257,6 +259,13 @@ struct pclean_ctx {
   int32_t lat_w_items = 0, lat_w_P = 0;
   DevBuf<int16_t> lat_dp;
   DevBuf<unsigned int> lat_flag;
+  // ... its keyed roots: lat_dk[r * lat_dk_items + t] = the dummy option of row t's key in root r's option table, for the next
+  // pclean_sweep_latent call alone (pclean_set_latent_dummy_options); time_sym = the pool symbols of a rendered TimePrior draw
+  DevBuf<int32_t> lat_dk;
+  int32_t lat_dk_roots = 0, lat_dk_items = 0;
+  bool lat_dk_valid = false;
+  DevBuf<uint16_t> time_sym;
+  bool time_sym_valid = false;
   void* commit_state = nullptr;  // owned by commit.hip
   HostStage stage;               // page-locked staging of caller arrays (table uploads, latent-sweep inputs / outputs)
   HostStage ustage;              // ... of the row unions of CandTable::delta_log (asked for in the middle of a sweep call,

@@ -81,3 +81,40 @@ __device__ inline int dummy_distance(int dist_mode, const uint16_t* a, int la, c
   }
   return H[(la + 1) * W + (lb + 1)];
 }
+
+#define DUMMY_TIME_LEN 10  // "12:59 a.m."
+
+// random(TimePrior) of (key, row) (time_prior.jl:21-23; random_time_prior_at_kernel's three draws, stream 0) rendered
+// "{h}:{m} a.m." / "{h}:{m} p.m." (minutes not zero-padded: sampling.random_time_prior) as pool symbols into
+// out[0 .. len), returns len.  tsym: the symbols of 0 .. 9 : ' ' a p . m (pclean_set_time_symbols; 0xFFFF: not in the
+// pool — the time then equals no pool string)
+__device__ inline int dummy_draw_time(uint64_t key, uint32_t row, const uint16_t* tsym, uint16_t* out) {
+  const uint32_t site = PCLEAN_SITE_RANDOM(PCLEAN_RANDOM_TIME_PRIOR);
+  const int h = 1 + (int)pclean_mulhi64(pclean_rand64(key, row, site, 0u, 0u), (uint64_t)12);
+  const int m = 1 + (int)pclean_mulhi64(pclean_rand64(key, row, site, 1u, 0u), (uint64_t)60);
+  const bool am = (pclean_rand64(key, row, site, 2u, 0u) >> 63) != 0;
+  int n = 0;
+  if (h >= 10) out[n++] = tsym[h / 10];
+  out[n++] = tsym[h % 10];
+  out[n++] = tsym[10];
+  if (m >= 10) out[n++] = tsym[m / 10];
+  out[n++] = tsym[m % 10];
+  out[n++] = tsym[11];
+  out[n++] = tsym[am ? 12 : 13];
+  out[n++] = tsym[14];
+  out[n++] = tsym[15];
+  out[n++] = tsym[14];
+  return n;
+}
+
+// is pool string a[0 .. la) the string s[0 .. ls) (ls <= DUMMY_TIME_LEN)?  Every symbol is read (at a clamped index) before
+// any is compared: one level of loads
+__device__ inline bool dummy_same_string(const uint16_t* a, int la, const uint16_t* s, int ls) {
+  bool same = la == ls;
+  uint16_t x[DUMMY_TIME_LEN];
+#pragma unroll
+  for (int k = 0; k < DUMMY_TIME_LEN; ++k) x[k] = la > 0 ? a[min(k, la - 1)] : (uint16_t)0;  // (an empty string: nothing to read)
+#pragma unroll
+  for (int k = 0; k < DUMMY_TIME_LEN; ++k) same = same && (k >= ls || x[k] == s[k]);
+  return same;
+}

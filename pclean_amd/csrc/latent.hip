@@ -540,16 +540,24 @@ extern "C" int pclean_argsort_ids(pclean_ctx* ctx, int32_t n, const int32_t* ids
 struct LdcTermDev {
   const uint8_t* pair;
   const uint16_t* lat_len;
-  const int32_t* obs_ids;
+  const int32_t* obs_ids;  // pool string of every observed value
+  const int32_t* lat_ids;  // MaybeSwap terms: pool string of every latent value
+  const int32_t* nopt;     // MaybeSwap terms: [n_opt] number of options of the option's key (the column max_typos names)
   int32_t n_lat, elem_bytes, max_typos, dist_mode;
+  int32_t term, n_obs;     // term: the term's place among the node's terms (its aggregated evidence)
 };
+#define LDC_KIND_STRING 0  // StringPrior under plain AddTypos terms
+#define LDC_KIND_TIME 1    // TimePrior under MaybeSwap terms
 struct LdcLeafDev {
   int32_t node, dummy_val, dummy_k, n_opt, min_len, max_len, n_terms, n_lat_min;
+  int32_t kind, pad;
   const int32_t* opt_vals;
   const double* opt_logp;
   const int32_t* draws;  // [n_items][P] option drawn by particle p (particle 0's is not looked at)
   const int32_t* excl;   // [n_items] value id a retained particle holds in place of the dummy, -1: it holds an atom
-  const AggDev* agg;     // [n_terms] aggregated evidence of the node's terms
+  const AggDev* agg;     // [the node's terms] aggregated evidence
+  const int32_t* row_dk;   // keyed option table: [n_items] the dummy option of the row's key (-1: none); null: dummy_k
+  const int32_t* opt_key;  // keyed option table: [n_opt] the key an option is listed under
   LdcTermDev t[LDC_MAX_TERMS];
 };
 struct LdcPackDev {
@@ -566,8 +574,21 @@ struct LdcPackDev {
   int16_t* dp;                     // arena: lane_cells cells per lane, 64 lanes per slot of the launch
   int64_t lane_cells;
   unsigned int* too_long;          // set when an observed string is longer than that
+  // time leaves: log1p(-p) / log(p) of the probability table, log(n), the symbols of a rendered time
+  const double* prob_same;
+  const double* prob_diff;
+  const double* logn;
+  const uint16_t* time_sym;
+  int32_t n_prob, pad;
 };
-__global__ void ldc_flag_kernel(LdcPackDev pk, size_t n, int32_t* __restrict__ flag) {
+// the dummy option of row t's key in the leaf's option table, -1: none
+__device__ __forceinline__ int ldc_row_dummy(const LdcLeafDev& lf, int t) {
+  const int dk = lf.row_dk ? lf.row_dk[t] : lf.dummy_k;
+  return (dk >= 0 && dk < lf.n_opt && lf.opt_vals[dk] == lf.dummy_val) ? dk : -1;
+}
+// flag_s / flag_t (a call that serves time leaves; else null): the same marks by leaf kind
+__global__ void ldc_flag_kernel(LdcPackDev pk, size_t n, int32_t* __restrict__ flag, int32_t* __restrict__ flag_s,
+                                int32_t* __restrict__ flag_t) {
   const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= n) return;
   const int li = (int)(q % pk.n_leaves);
@@ -582,7 +603,12 @@ __global__ void ldc_flag_kernel(LdcPackDev pk, size_t n, int32_t* __restrict__ f
     const int k = lf.draws[tp];
     hit = k >= 0 && k < lf.n_opt && lf.opt_vals[k] == lf.dummy_val;
   }
+  hit = hit && ldc_row_dummy(lf, t) >= 0;
   flag[q] = hit ? PCLEAN_CHOICE_NEW : 0;
+  if (flag_s) {
+    flag_s[q] = (hit && lf.kind == LDC_KIND_STRING) ? PCLEAN_CHOICE_NEW : 0;
+    flag_t[q] = (hit && lf.kind == LDC_KIND_TIME) ? PCLEAN_CHOICE_NEW : 0;
+  }
 }
 // One wavefront per slot (four slots per workgroup): lane 0 draws the slot's string into LDS, the lanes stride over the
 // item's distinct observed values, each with a distance matrix of its own in the arena; the lanes' fp64 partial sums are
@@ -590,13 +616,15 @@ __global__ void ldc_flag_kernel(LdcPackDev pk, size_t n, int32_t* __restrict__ f
 __global__ __launch_bounds__(256) void latent_dummy_correction_kernel(int j0, int n_slots, const int32_t* __restrict__ slots,
                                                                       LdcPackDev pk, const int32_t* __restrict__ keys,
                                                                       uint64_t seed, uint32_t sweep,
-                                                                      double* __restrict__ corr) {
+                                                                      double* __restrict__ corr,
+                                                                      const unsigned int* __restrict__ n_dev) {
   __shared__ uint16_t s_str[4][DUMMY_MAX_LEN + 1];
   __shared__ int s_len[4];
   __shared__ double s_part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int jl = blockIdx.x * 4 + wave;  // slot of this launch's slice [j0, j0 + n_slots)
-  const bool live = jl < n_slots;
+  // (n_dev: the list's length where only the device knows it — a call that also holds time slots; n_slots bounds it)
+  const bool live = jl < n_slots && (!n_dev || (unsigned int)(j0 + jl) < n_dev[0]);
   int li = 0, p = 0, t = 0;
   if (live) {
     const int q = slots[j0 + jl];
@@ -619,7 +647,7 @@ __global__ __launch_bounds__(256) void latent_dummy_correction_kernel(int j0, in
     int16_t* H = pk.dp + ((size_t)jl * 64 + lane) * pk.lane_cells;
     for (int ti = 0; ti < lf.n_terms; ++ti) {
       const LdcTermDev& tm = lf.t[ti];
-      const AggDev ag = lf.agg[ti];
+      const AggDev ag = lf.agg[tm.term];
       const int r1 = ag.end ? ag.end[t] : ag.off[t + 1];
       for (int r = ag.off[t] + lane; r < r1; r += 64) {
         const int o = (int)(ag.key[r] & 0xffffffull) - 1;
@@ -667,13 +695,102 @@ __global__ __launch_bounds__(256) void latent_dummy_correction_kernel(int j0, in
   s_part[wave][lane] = part;
   __syncthreads();
   if (live && lane == 0) {
-    double c = -lf.opt_logp[lf.dummy_k];
+    double c = -lf.opt_logp[max(ldc_row_dummy(lf, t), 0)];  // (a slot's row has one: ldc_flag_kernel)
     for (int q = 0; q < 64; ++q) c += s_part[wave][q];
     corr[j0 + jl] = c;
   }
 }
-// wl[t * P + p] = the corrections of the slots of (t, p) in root order, 0 where it has none
+// The same for the slots of TimePrior leaves (LDC_KIND_TIME), whose terms are MaybeSwap terms (maybe_swap.jl:13-28) on 0/1
+// "same string" tables: lane 0 draws and renders the slot's time into LDS, the lanes stride over the option table for "is it
+// one of the key's own atoms" (by pool symbols) and then over the item's distinct (ctx value, observed value) pairs — no
+// distance matrix, no arena.  Entry j of the list writes corr[j]; n_dev[0] = the list's length (n_max bounds it).
+__global__ __launch_bounds__(256) void latent_dummy_time_kernel(int n_max, const unsigned int* __restrict__ n_dev,
+                                                                const int32_t* __restrict__ slots, LdcPackDev pk,
+                                                                const int32_t* __restrict__ keys, uint64_t seed, uint32_t sweep,
+                                                                double* __restrict__ corr) {
+  __shared__ uint16_t s_str[4][DUMMY_TIME_LEN];
+  __shared__ int s_len[4];
+  __shared__ int s_isopt[4];
+  __shared__ double s_part[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = blockIdx.x * 4 + wave;
+  const bool live = j < n_max && (unsigned int)j < n_dev[0];
+  int li = 0, p = 0, t = 0;
+  if (live) {
+    const int q = slots[j];
+    li = q % pk.n_leaves;
+    const int tp = q / pk.n_leaves;
+    p = tp % pk.P;
+    t = tp / pk.P;
+  }
+  const LdcLeafDev& lf = pk.leaf[li];
+  if (lane == 0) {
+    s_isopt[wave] = 0;
+    s_len[wave] = 0;
+    if (live && p > 0) {
+      const uint64_t key = pclean_dummy_seed(seed, PCLEAN_SITE_NODE(pk.site_block, lf.node), (uint32_t)p, sweep);
+      s_len[wave] = dummy_draw_time(key, (uint32_t)keys[t], pk.time_sym, s_str[wave]);
+    }
+  }
+  __syncthreads();
+  const int dk = live ? max(ldc_row_dummy(lf, t), 0) : 0;  // (a slot's row has one: ldc_flag_kernel)
+  const int L = s_len[wave];
+  if (live && p > 0) {  // a drawn time that is one of the key's own atoms is that option
+    const LdcTermDev& t0 = lf.t[0];
+    const int kk = lf.opt_key[dk];
+    bool mine = false;
+    for (int k = lane; k < lf.n_opt; k += 64) {
+      const int kv = lf.opt_vals[k], kkey = lf.opt_key[k];
+      const int sid = t0.lat_ids[min(max(kv, 0), t0.n_lat - 1)];
+      const int64_t b = pk.off[sid];
+      const int la = (int)(pk.off[sid + 1] - b);
+      const bool same = dummy_same_string(pk.sym + b, la, s_str[wave], L);
+      mine = mine || (same && kkey == kk && kv != lf.dummy_val && kv >= 0 && kv < t0.n_lat);
+    }
+    if (mine) s_isopt[wave] = 1;
+  }
+  __syncthreads();
+  double part = 0.0;
+  if (live) {
+    const bool isopt = s_isopt[wave] != 0;
+    const int v0 = p == 0 ? lf.excl[t] : 0;  // retained particle: the value it holds (both densities are table lookups)
+    for (int ti = 0; ti < lf.n_terms; ++ti) {
+      const LdcTermDev& tm = lf.t[ti];
+      const AggDev ag = lf.agg[tm.term];
+      const double logn = pk.logn[min(max(tm.nopt[dk], 0), 4095)];
+      const int r1 = ag.end ? ag.end[t] : ag.off[t + 1];
+      for (int r = ag.off[t] + lane; r < r1; r += 64) {
+        // (the loads of a level issued together, each on a safe index; what must not count is selected away)
+        const uint64_t key = ag.key[r];
+        const int cn = ag.cnt[r];
+        const int o = (int)(key & 0xffffffull) - 1;
+        const int ec = min((int)((key >> 24) & 0xffffull), pk.n_prob - 1);
+        const int os = min(max(o, 0), tm.n_obs - 1);
+        const int dph = (int)tm.pair[(size_t)os * tm.n_lat + lf.dummy_val];
+        const int dv0 = (int)tm.pair[(size_t)os * tm.n_lat + v0];
+        const int sid = tm.obs_ids[os];
+        const double ps = pk.prob_same[ec], pd = pk.prob_diff[ec] - logn;
+        const int64_t b = pk.off[sid];
+        const int la = (int)(pk.off[sid + 1] - b);
+        const bool same = p > 0 ? dummy_same_string(pk.sym + b, la, s_str[wave], L) : dv0 == 0;
+        const double lph = o < 0 ? -1000.0 : (dph == 0 ? ps : pd);
+        const double lv = o < 0 ? (isopt ? 0.0 : -1000.0) : (same ? ps : pd);
+        part += (double)cn * (lv - lph);
+      }
+    }
+  }
+  s_part[wave][lane] = part;
+  __syncthreads();
+  if (live && lane == 0) {
+    double c = -lf.opt_logp[dk];
+    for (int q = 0; q < 64; ++q) c += s_part[wave][q];
+    corr[j] = c;
+  }
+}
+// wl[t * P + p] = the corrections of the slots of (t, p) in root order, 0 where it has none (pos_t / corr_t: the time slots'
+// list of a call that serves time leaves, else null)
 __global__ void ldc_weights_kernel(size_t n_tp, int n_leaves, const int32_t* __restrict__ pos, const double* __restrict__ corr,
+                                   const int32_t* __restrict__ pos_t, const double* __restrict__ corr_t,
                                    double* __restrict__ wl) {
   const size_t tp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tp >= n_tp) return;
@@ -681,6 +798,10 @@ __global__ void ldc_weights_kernel(size_t n_tp, int n_leaves, const int32_t* __r
   for (int li = 0; li < n_leaves; ++li) {
     const int j = pos[tp * n_leaves + li];
     if (j >= 0) w += corr[j];
+    if (pos_t) {
+      const int jt = pos_t[tp * n_leaves + li];
+      if (jt >= 0) w += corr_t[jt];
+    }
   }
   wl[tp] = w;
 }
@@ -716,45 +837,80 @@ static bool ldc_find_dummy(pclean_ctx* ctx, int table, int32_t* dummy_value, int
   return false;
 }
 // Is root node `nid` of latent plan b served (pclean_hip.h: pclean_set_latent_dummy_correction)?  Fills the host-known part
-// of its description.
-static bool ldc_served(pclean_ctx* ctx, const Block& b, int nid, LdcLeafDev* out, int* max_obs_len) {
+// of its description.  row_dk: the rows' dummy options of this root (device, pclean_set_latent_dummy_options), null: none
+// were given — a keyed option table is not served then.
+static bool ldc_served(pclean_ctx* ctx, const Block& b, int nid, const int32_t* row_dk, LdcLeafDev* out, int* max_obs_len) {
   const pclean_node& n = b.nodes[nid];
-  if (n.kind != PCLEAN_NODE_LEAF || n.n_terms < 1 || n.n_terms > LDC_MAX_TERMS) return false;
+  if (n.kind != PCLEAN_NODE_LEAF || n.n_terms < 1 || n.n_terms > LDC_MAX_TERMS + 1) return false;
   if (nid < (int)b.node_gauss.size() && b.node_gauss[nid] >= 0) return false;
   const CandTable& t = ctx->cand[n.table];
-  if (!t.valid || !t.is_options || t.n_cols != 1) return false;
+  if (!t.valid || !t.is_options || t.n_cols < 1) return false;
+  const bool keyed = t.n_cols > 1;
+  if (keyed && !row_dk) return false;
   int32_t dval = n.dummy_value, dspec = n.dummy_spec;
   if (dval == 0 && !ldc_find_dummy(ctx, n.table, &dval, &dspec)) return false;
-  if ((dspec & 0xff) != PCLEAN_DUMMY_STRING_PRIOR) return false;
+  const int dkind = dspec & 0xff;
+  if (dkind != PCLEAN_DUMMY_STRING_PRIOR && dkind != PCLEAN_DUMMY_TIME_PRIOR) return false;
   LdcLeafDev lf{};
   lf.node = nid;
+  lf.kind = dkind == PCLEAN_DUMMY_TIME_PRIOR ? LDC_KIND_TIME : LDC_KIND_STRING;
+  if (lf.kind == LDC_KIND_TIME && (!keyed || !ctx->time_sym_valid || ctx->n_prob <= 0 || !ctx->logn.p)) return false;
   lf.dummy_val = dval - 1;
   lf.dummy_k = -1;
-  for (size_t k = 0; k < t.h_vals.size(); ++k)
-    if (t.h_vals[k] == lf.dummy_val) lf.dummy_k = (int)k;
-  if (lf.dummy_k < 0 || (int)t.h_vals.size() != t.n_rows) return false;
+  if ((int)t.h_vals.size() != t.n_rows) return false;
+  if (keyed) {  // (every key has a dummy option of its own: the rows say which)
+    lf.row_dk = row_dk;
+    lf.opt_key = t.cols.p + (size_t)t.n_rows;
+  } else {
+    for (size_t k = 0; k < t.h_vals.size(); ++k)
+      if (t.h_vals[k] == lf.dummy_val) lf.dummy_k = (int)k;
+    if (lf.dummy_k < 0) return false;
+  }
   lf.n_opt = t.n_rows;
   lf.min_len = (dspec >> 8) & 0xff;
   lf.max_len = (dspec >> 16) & 0xff;
   lf.opt_vals = t.cols.p;
   lf.opt_logp = t.logc_full.p;
   lf.n_lat_min = INT32_MAX;
+  int n_key_terms = 0;
   for (int ti = 0; ti < n.n_terms; ++ti) {
     const pclean_term& tm = b.terms[n.term_begin + ti];
-    if (tm.dens_kind != PCLEAN_DENS_ADD_TYPOS || tm.ctx_slot >= 0 || tm.cand_col != 0) return false;
+    if (keyed && tm.dens_kind == PCLEAN_DENS_EQUAL && tm.cand_col == 1 && tm.ctx_slot < 0) {
+      // the directly observed key: the dummy option of the row's key and the value it stands for score alike
+      if (++n_key_terms > 1) return false;
+      continue;
+    }
+    if (lf.n_terms >= LDC_MAX_TERMS || tm.cand_col != 0) return false;
+    if (tm.pair_table < 0 || tm.pair_table >= PCLEAN_MAX_TABLES) return false;
     const PairTable& pt = ctx->pair[tm.pair_table];
-    if (!pt.valid || !pt.obs_ids.p || lf.dummy_val >= pt.n_lat) return false;
-    LdcTermDev& td = lf.t[lf.n_terms++];
+    if (!pt.valid || lf.dummy_val >= pt.n_lat) return false;
+    LdcTermDev& td = lf.t[lf.n_terms];
+    td.term = ti;
     td.pair = pt.d.p;
     td.lat_len = pt.lat_len.p;
-    td.obs_ids = pt.obs_ids.p;
     td.n_lat = pt.n_lat;
+    td.n_obs = pt.n_obs;
     td.elem_bytes = pt.elem_bytes;
     td.max_typos = tm.max_typos;
     td.dist_mode = pt.dist_mode;
+    if (lf.kind == LDC_KIND_TIME) {
+      // MaybeSwap on a 0/1 table whose strings are known; the evidence row's ctx value is its probability-table entry
+      if (tm.dens_kind != PCLEAN_DENS_MAYBE_SWAP || tm.ctx_slot < 0 || tm.ctx_mode != 1 || tm.max_typos < 1 ||
+          tm.max_typos >= t.n_cols || pt.elem_bytes != 1 || pt.n_obs < 1 || !pt.same_obs_ids.p || !pt.same_lat_ids.p ||
+          tm.fn_table < 0 || lf.dummy_val < tm.fn_table)
+        return false;
+      td.obs_ids = pt.same_obs_ids.p;
+      td.lat_ids = pt.same_lat_ids.p;
+      td.nopt = t.cols.p + (size_t)tm.max_typos * t.n_rows;
+    } else {
+      if (tm.dens_kind != PCLEAN_DENS_ADD_TYPOS || tm.ctx_slot >= 0 || !pt.obs_ids.p) return false;
+      td.obs_ids = pt.obs_ids.p;
+      if (max_obs_len) *max_obs_len = std::max(*max_obs_len, pt.max_obs_len);
+    }
+    ++lf.n_terms;
     lf.n_lat_min = std::min(lf.n_lat_min, pt.n_lat);
-    if (max_obs_len) *max_obs_len = std::max(*max_obs_len, pt.max_obs_len);
   }
+  if (lf.n_terms < 1 || (keyed && n_key_terms != 1)) return false;
   if (out) *out = lf;
   return true;
 }
@@ -765,7 +921,7 @@ static bool ldc_served(pclean_ctx* ctx, const Block& b, int nid, LdcLeafDev* out
 static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_idx, int block_id, int n_roots,
                                 const int32_t* roots, int n_items, int P, int use_mh, const int32_t* d_keys,
                                 const int32_t* d_off, const int32_t* d_evr, const int32_t* d_evc, const int32_t* d_excl,
-                                int32_t* d_chosen, std::vector<const int32_t*>& draws, bool* flag_used) {
+                                int32_t* d_chosen, std::vector<const int32_t*>& draws, bool* flag_used, bool have_dk) {
   SweepState* s = st(ctx);
   Block& b = ctx->block[block_id];
   const size_t NP = (size_t)n_items * P;
@@ -776,13 +932,16 @@ static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_i
   if (P < 2) return PCLEAN_OK;
   LdcPackDev pk{};
   std::vector<int> served;
+  int n_string = 0, n_time = 0;
   for (int r = 0; r < n_roots && pk.n_leaves < LDC_MAX_LEAVES; ++r)
-    if (ldc_served(ctx, b, roots[r], &pk.leaf[pk.n_leaves], &pk.max_obs_len)) {
+    if (ldc_served(ctx, b, roots[r], have_dk ? ctx->lat_dk.p + (size_t)r * n_items : nullptr, &pk.leaf[pk.n_leaves],
+                   &pk.max_obs_len)) {
       served.push_back(r);
+      ++(pk.leaf[pk.n_leaves].kind == LDC_KIND_TIME ? n_time : n_string);
       ++pk.n_leaves;
     }
   if (served.empty()) return PCLEAN_OK;
-  if (!ctx->lm_valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "latent dummy correction: pclean_set_lm_tables first");
+  if (n_string && !ctx->lm_valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "latent dummy correction: pclean_set_lm_tables first");
   if (pk.max_obs_len > DUMMY_MAX_LEN)
     return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "latent dummy correction: observed strings longer than %d symbols below a "
                                                  "dummy-bearing choice", DUMMY_MAX_LEN);
@@ -805,7 +964,7 @@ static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_i
     lf.excl = d_excl + (size_t)served[i] * n_items;
     lf.agg = agg;
     draws[served[i]] = dr;
-    max_len = std::max(max_len, lf.max_len);
+    if (lf.kind == LDC_KIND_STRING) max_len = std::max(max_len, lf.max_len);
   }
   pk.site_block = block_id;
   pk.P = P;
@@ -818,13 +977,27 @@ static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_i
   pk.nb = ctx->nb.p;
   pk.logl = ctx->logl.p;
   pk.nb_stride = ctx->max_d + 1;
-  // (b) the slots that need a correction
+  pk.prob_same = ctx->prob_same.p;
+  pk.prob_diff = ctx->prob_diff.p;
+  pk.logn = ctx->logn.p;
+  pk.time_sym = ctx->time_sym.p;
+  pk.n_prob = ctx->n_prob;
+  // (b) the slots that need a correction; with time leaves among the served ones also by leaf kind: a list each, whose
+  // lengths stay on the device (the one count the host reads is their sum)
   const size_t NQ = NP * NL;
   int32_t* flag = scratch<int32_t>(ctx, NQ);
   int32_t* slots = scratch<int32_t>(ctx, NQ);
   int32_t* pos = scratch<int32_t>(ctx, NQ);
+  int32_t *flag_s = nullptr, *flag_t = nullptr, *slots_t = nullptr, *pos_t = nullptr;
+  if (n_time) {
+    flag_s = scratch<int32_t>(ctx, NQ);
+    flag_t = scratch<int32_t>(ctx, NQ);
+    slots_t = scratch<int32_t>(ctx, NQ);
+    pos_t = scratch<int32_t>(ctx, NQ);
+    if (!flag_s || !flag_t || !slots_t || !pos_t) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  }
   if (!flag || !slots || !pos) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-  hipLaunchKernelGGL(ldc_flag_kernel, grid1(NQ), dim3(256), 0, ctx->stream, pk, NQ, flag);
+  hipLaunchKernelGGL(ldc_flag_kernel, grid1(NQ), dim3(256), 0, ctx->stream, pk, NQ, flag, flag_s, flag_t);
   HIPCHK(ctx, hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), ctx->stream));
   hipLaunchKernelGGL(compact_new_kernel, grid1(NQ), dim3(256), 0, ctx->stream, NQ, flag, 0, s->counter.p, nullptr, nullptr);
   unsigned int n_slots = 0;
@@ -833,29 +1006,43 @@ static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_i
   if (dbg) fprintf(stderr, "[pclean] latent block %d: %u dummy slots among %zu (row, particle, choice)\n", block_id, n_slots, NQ);
   if (n_slots == 0) return PCLEAN_OK;
   if (n_slots > NQ) return pclean_fail(ctx, PCLEAN_ERR_STATE, "latent dummy correction: slot count out of range");
-  HIPCHK(ctx, hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), ctx->stream));
-  hipLaunchKernelGGL(compact_new_kernel, grid1(NQ), dim3(256), 0, ctx->stream, NQ, flag, 1, s->counter.p, slots, pos);
-  // (c) their corrections, in slices whose distance matrices (one per lane) fit the arena
-  const char* ae = getenv("PCLEAN_LATENT_DUMMY_ARENA");  // int16 cells (tests: a launch cut into several slices)
-  const size_t arena = ae && atoll(ae) > 0 ? (size_t)atoll(ae) : LDC_ARENA_CELLS;
-  pk.lane_cells = (int64_t)(pk.max_obs_len + 2) * (max_len + 2);
-  const size_t slot_cells = (size_t)pk.lane_cells * 64;
-  const int per_launch = (int)std::min<size_t>(std::max<size_t>(arena / slot_cells, 1), n_slots);
+  // (s->counter: 4 words — [0] the string slots' list, or every slot's in a call without time leaves; [1] the time slots')
+  HIPCHK(ctx, hipMemsetAsync(s->counter.p, 0, 2 * sizeof(unsigned int), ctx->stream));
+  hipLaunchKernelGGL(compact_new_kernel, grid1(NQ), dim3(256), 0, ctx->stream, NQ, n_time ? flag_s : flag, 1, s->counter.p, slots,
+                     pos);
+  if (n_time)
+    hipLaunchKernelGGL(compact_new_kernel, grid1(NQ), dim3(256), 0, ctx->stream, NQ, flag_t, 1, s->counter.p + 1, slots_t, pos_t);
+  const unsigned int* n_dev_s = n_time ? s->counter.p : nullptr;
   double* corr = scratch<double>(ctx, n_slots);
-  if (!corr || ctx->lat_dp.alloc((size_t)per_launch * slot_cells) || ctx->lat_flag.alloc(1))
-    return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-  HIPCHK(ctx, hipMemsetAsync(ctx->lat_flag.p, 0, sizeof(unsigned int), ctx->stream));
-  pk.dp = ctx->lat_dp.p;
-  pk.too_long = ctx->lat_flag.p;
-  {
+  double* corr_t = n_time ? scratch<double>(ctx, n_slots) : nullptr;
+  if (!corr || (n_time && !corr_t)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  // (c) their corrections: the string slots in slices whose distance matrices (one per lane) fit the arena ...
+  if (n_string) {
+    const char* ae = getenv("PCLEAN_LATENT_DUMMY_ARENA");  // int16 cells (tests: a launch cut into several slices)
+    const size_t arena = ae && atoll(ae) > 0 ? (size_t)atoll(ae) : LDC_ARENA_CELLS;
+    pk.lane_cells = (int64_t)(pk.max_obs_len + 2) * (max_len + 2);
+    const size_t slot_cells = (size_t)pk.lane_cells * 64;
+    const int per_launch = (int)std::min<size_t>(std::max<size_t>(arena / slot_cells, 1), n_slots);
+    if (ctx->lat_dp.alloc((size_t)per_launch * slot_cells) || ctx->lat_flag.alloc(1))
+      return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+    HIPCHK(ctx, hipMemsetAsync(ctx->lat_flag.p, 0, sizeof(unsigned int), ctx->stream));
+    pk.dp = ctx->lat_dp.p;
+    pk.too_long = ctx->lat_flag.p;
     ProfScope pk_scope(ctx, "latent_dummy_correction_kernel");
     for (unsigned int j0 = 0; j0 < n_slots; j0 += (unsigned int)per_launch) {
       const int cnt = (int)std::min<unsigned int>((unsigned int)per_launch, n_slots - j0);
       hipLaunchKernelGGL(latent_dummy_correction_kernel, dim3((cnt + 3) / 4), dim3(256), 0, ctx->stream, (int)j0, cnt, slots,
-                         pk, d_keys, seed, sweep_idx, corr);
+                         pk, d_keys, seed, sweep_idx, corr, n_dev_s);
     }
+    *flag_used = true;  // (the "string too long" mark rides on the call's last synchronisation)
   }
-  hipLaunchKernelGGL(ldc_weights_kernel, grid1(NP), dim3(256), 0, ctx->stream, NP, NL, pos, corr, ctx->lat_w.p);
+  // ... the time slots in one launch (no matrices: the arena neither holds nor cuts them)
+  if (n_time) {
+    ProfScope pk_scope(ctx, "latent_dummy_time_kernel");
+    hipLaunchKernelGGL(latent_dummy_time_kernel, dim3((n_slots + 3) / 4), dim3(256), 0, ctx->stream, (int)n_slots,
+                       s->counter.p + 1, slots_t, pk, d_keys, seed, sweep_idx, corr_t);
+  }
+  hipLaunchKernelGGL(ldc_weights_kernel, grid1(NP), dim3(256), 0, ctx->stream, NP, NL, pos, corr, pos_t, corr_t, ctx->lat_w.p);
   // (d) the particle, from the weights
   int32_t* weighted = scratch<int32_t>(ctx, n_items);
   if (!weighted) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
@@ -864,7 +1051,6 @@ static int latent_dummy_weights(pclean_ctx* ctx, uint64_t seed, uint32_t sweep_i
   hipLaunchKernelGGL(ldc_merge_choice_kernel, grid1(n_items), dim3(256), 0, ctx->stream, n_items, P, ctx->lat_w.p, weighted,
                      d_chosen);
   HIPCHK(ctx, hipGetLastError());
-  *flag_used = true;  // (the "string too long" mark rides on the call's last synchronisation)
   return PCLEAN_OK;
 }
 
@@ -882,6 +1068,9 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
     const int rcp = prior_mode_supported(ctx, ctx->block[block_id], "pclean_sweep_latent");
     if (rcp) return rcp;
   }
+  // (the rows' dummy options of keyed roots are those of this call alone: pclean_set_latent_dummy_options)
+  const bool have_dk = ctx->lat_dk_valid && ctx->lat_dk_roots == n_roots && ctx->lat_dk_items == n_items;
+  ctx->lat_dk_valid = false;
   if (n_items == 0) return PCLEAN_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Block& b = ctx->block[block_id];
@@ -1058,7 +1247,7 @@ static int sweep_latent_impl(pclean_ctx* ctx, const pclean_infer_config* cfg, ui
   bool ldc_flag_used = false;
   if (ctx->latent_dummy) {
     const int rcl = latent_dummy_weights(ctx, seed, sweep_idx, block_id, n_roots, roots, n_items, P, use_mh, d_keys, d_off,
-                                         d_evr, d_evc, d_excl, d_chosen, served_draws, &ldc_flag_used);
+                                         d_evr, d_evc, d_excl, d_chosen, served_draws, &ldc_flag_used, have_dk);
     if (rcl) return rcl;
   }
   // rows that take a fresh particle

@@ -182,6 +182,18 @@ __global__ void random_time_prior_kernel(int n, uint64_t seed, uint32_t stream, 
   out[3 * i + 2] = (int32_t)(d.next() >> 63);
 }
 
+// the same with a private (key, counter row) per element, stream 0 (the time a chosen ProposalDummyValue of a TimePrior
+// stands for: dummy_dev.h's dummy_draw_time makes the same three draws)
+__global__ void random_time_prior_at_kernel(int n, const uint64_t* __restrict__ seeds, const uint32_t* __restrict__ elems,
+                                            int32_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Draws d{seeds[i], elems[i], PCLEAN_SITE_RANDOM(PCLEAN_RANDOM_TIME_PRIOR), 0u, 0};
+  out[3 * i] = 1 + (int32_t)d.below(12);
+  out[3 * i + 1] = 1 + (int32_t)d.below(60);
+  out[3 * i + 2] = (int32_t)(d.next() >> 63);
+}
+
 // Host staging: copy inputs up, run, copy outputs down.  These samplers are not on the sweep's
 // critical path (they run when a proposal picks a dummy value or a node is unobserved), so they
 // use plain synchronous transfers.
@@ -340,5 +352,23 @@ extern "C" int pclean_random_time_prior(pclean_ctx* ctx, int32_t n, uint64_t see
   hipLaunchKernelGGL(random_time_prior_kernel, grid_for(n), dim3(256), 0, ctx->stream, n, seed, stream, d_out.p);
   TRY(down(ctx, out, d_out, (size_t)n * 3));
   d_out.release();
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_random_time_prior_at(pclean_ctx* ctx, int32_t n, const uint64_t* seeds, const uint32_t* elems,
+                                           int32_t* out) {
+  if (!ctx || n < 0 || (n > 0 && (!out || !seeds || !elems)))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_random_time_prior_at: bad arguments");
+  if (n == 0) return PCLEAN_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DevBuf<uint64_t> d_seeds;
+  DevBuf<uint32_t> d_elems;
+  DevBuf<int32_t> d_out;
+  TRY(up(ctx, d_seeds, seeds, (size_t)n));
+  TRY(up(ctx, d_elems, elems, (size_t)n));
+  if (d_out.alloc((size_t)n * 3)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  hipLaunchKernelGGL(random_time_prior_at_kernel, grid_for(n), dim3(256), 0, ctx->stream, n, d_seeds.p, d_elems.p, d_out.p);
+  TRY(down(ctx, out, d_out, (size_t)n * 3));
+  d_seeds.release(); d_elems.release(); d_out.release();
   return PCLEAN_OK;
 }

@@ -66,6 +66,8 @@ def lw_locals(lw):
 
 
 def _logsumexp(x):
+    if len(x) == 0:  # (a key without atoms: all of the mass is its dummy's)
+        return -np.inf
     m = np.max(x)
     if not np.isfinite(m):
         return m
@@ -100,6 +102,7 @@ class Engine:
         self._uploaded_shape = {}
         self._last_upload = {}
         self._dc = None  # state of the device-resident commit (enable_device_commit)
+        self.latent_dummy_keyed = False  # latent_dummy_served: keyed choices too (inference.latent_sweep turns it on)
         self.reloads = 0  # how often reload() replaced the context (what lives in a context, e.g. tally.CellTally's plan, follows)
         self._upload_static()
         if row_offset:
@@ -153,6 +156,8 @@ class Engine:
         """random(StringPrior) with the private streams the sweep used for the weights of the particles that chose the
         dummy (pclean_dummy_seed keys, global observed rows): the strings those particles' new rows hold."""
         from . import sampling
+        if isinstance(dist, TimePrior):  # (the times a latent sweep with dummy_correction weighed: element = the latent row)
+            return sampling.random_time_prior_at(self.hip, seeds, elems)
         return sampling.random_string_prior_at(self.hip, seeds, elems, dist.min_len, dist.max_len)
 
     # -- static data ----------------------------------------------------------
@@ -184,8 +189,10 @@ class Engine:
             hip.set_fn_table(fid, fn)
         for key, (pid, n) in lw.eq_pairs.items():  # equality constraints: 0 on the diagonal, 1 elsewhere
             hip.set_pair_table(pid, (1 - np.eye(n, dtype=np.uint8)))
-        for pid in lw.same_pairs:  # MaybeSwap: 0 iff the observed string is the latent value
+        for pid, (odom, vdom) in lw.same_pairs.items():  # MaybeSwap: 0 iff the observed string is the latent value
             hip.set_pair_table(pid, lw.same_pair_table(pid))
+            hip.set_pair_strings(pid, odom.id_array(), vdom.id_array())  # (a drawn time is compared with the strings)
+        hip.set_time_symbols([lw.pool.symbol_of(ch) for ch in "0123456789: ap.m"])
         self._upload_class_tables()
         if getattr(lw, "xnum", None) is not None and lw.xnum.shape[0]:
             hip.load_numeric_columns(lw.xnum)
@@ -628,11 +635,19 @@ class Engine:
 
     def latent_dummy_served(self, cname):
         """Attributes of latent class cname whose chosen ProposalDummyValues a latent sweep with dummy_correction=True
-        weighs (pclean_set_latent_dummy_correction): the class's own choices (leaf roots of its plan) with an unkeyed
-        StringPrior whose evidence terms are all plain AddTypos terms (no JuliaNode context, not tabulated, no Gaussian
-        term on the node).  Everything else — TimePrior choices, keyed priors, reference slots — is swept as with the
-        flag off."""
+        weighs (pclean_set_latent_dummy_correction): the class's own choices (leaf roots of its plan) with
+          * a StringPrior, keyed or not, whose evidence terms are all plain AddTypos terms (no JuliaNode context, not
+            tabulated), or
+          * a TimePrior whose evidence terms are all MaybeSwap terms (the error probability looked up per evidence row),
+        one or two such terms, no Gaussian term on the node; a keyed choice carries the equality term of its directly
+        observed key besides.  Everything else — reference slots among it — is swept as with the flag off.
+        KEYED choices (every TimePrior is one) are served only while `latent_dummy_keyed` is on: serving them takes the
+        per-row dummy options (latent_dummy_options) and an `excl` that goes by the row's key, which inference.latent_sweep
+        and run_inference supply — they turn the switch on — and a caller of the bare sweep_latent written before keyed
+        choices were served does not: with the switch off (the default) such a caller gets the answers and the sweeps it
+        always got."""
         lw = self.lw
+        keyed_on = bool(getattr(self, "latent_dummy_keyed", False))
         pl = lw.latent_plans.get(cname)
         if pl is None:
             return []
@@ -643,14 +658,50 @@ class Engine:
                 continue
             attr = pl["root_attr"][r]
             d = lw.model.classes[cname].attr(attr).dist
-            if not isinstance(d, StringPrior) or getattr(d, "keyed_by", None):
+            if not isinstance(d, (StringPrior, TimePrior)):
                 continue
             terms = pl["terms"][node[2]:node[2] + node[3]]
+            if getattr(d, "keyed_by", None):
+                if not keyed_on:
+                    continue
+                key_terms = [t for t in terms if t[3] == _lib.DENS_EQUAL and t[1] == 1 and t[5] < 0]
+                if len(key_terms) != 1:
+                    continue
+                terms = [t for t in terms if t is not key_terms[0]]
             if not 1 <= len(terms) <= 2 or (pl["block_id"], root) in getattr(lw, "gauss", {}):
                 continue
+            if isinstance(d, TimePrior):
+                if all(t[3] == _lib.DENS_MAYBE_SWAP and t[5] >= 0 and t[7] == 1 and t[1] == 0 and t[2] in lw.same_pairs
+                       for t in terms):
+                    out.append(attr)
+                continue
             typo_pairs = {pid for pid, _, _ in lw.pair_id.values()}  # (AddTypos tables: built on the device from the strings)
-            if all(t[3] == _lib.DENS_ADD_TYPOS and t[5] < 0 and t[2] in typo_pairs for t in terms):
+            if all(t[3] == _lib.DENS_ADD_TYPOS and t[5] < 0 and t[1] == 0 and t[2] in typo_pairs for t in terms):
                 out.append(attr)
+        return out
+
+    def latent_dummy_options(self, trace, cname, rows):
+        """pclean_set_latent_dummy_options for latent rows `rows` of class cname: per root of the class's plan the index of
+        the dummy option of the row's key in the root's option table — the served keyed choices (latent_dummy_served); -1
+        everywhere else and for a key without options.  None when the class serves no keyed choice."""
+        lw = self.lw
+        pl = lw.latent_plans[cname]
+        served = self.latent_dummy_served(cname)
+        t = trace.tables[cname]
+        out = None
+        for r, attr in enumerate(pl["root_attr"]):
+            d = lw.model.classes[cname].attr(attr).dist if attr in served else None
+            if d is None or not getattr(d, "keyed_by", None):
+                continue
+            if out is None:
+                out = np.full((len(pl["roots"]), len(rows)), -1, dtype=np.int32)
+            vals, keys = lw.option_values[(cname, attr)], lw.option_keycol[(cname, attr)]
+            dummy = lw.latent_dom[(cname, attr)].get(d.dummy_value())
+            rowkey = t.cols[lw.colidx[cname][d.keyed_by], rows]
+            lut = np.full(max(int(keys.max()), int(rowkey.max()) if len(rowkey) else 0) + 1, -1, dtype=np.int32)
+            at = np.flatnonzero(vals == dummy)
+            lut[keys[at]] = at
+            out[r] = lut[rowkey]
         return out
 
     def sweep_latent(self, trace, cname, config, seed, sweep_idx, live, ev_off, ev_rows, ev_ctx, excl, ev_begin=None,
@@ -667,6 +718,10 @@ class Engine:
         if dummy_correction or getattr(self, "_latent_dummy_on", False):  # (a reload makes a fresh context: set per call)
             self.hip.set_latent_dummy_correction(dummy_correction)
             self._latent_dummy_on = bool(dummy_correction)
+        if dummy_correction:  # (keyed choices: which option is the dummy of each row's key)
+            dk = self.latent_dummy_options(trace, cname, np.asarray(live))
+            if dk is not None:
+                self.hip.set_latent_dummy_options(dk)
         if ev_begin is not None:
             return self.hip.sweep_latent_resident(cfg, seed, sweep_idx, pl["block_id"], pl["roots"], live, ev_off, ev_begin,
                                                   excl, len(pl["nodes"]))

@@ -245,7 +245,7 @@ def resample_dummies(engine, trace, seed, stamp):
     drawn = []
     for cname, j, an, d, rows, stream in todo:
         strings = engine.sample_prior_strings(d, len(rows), seed, stream)
-        if isinstance(d, StringPrior) and hasattr(engine, "sample_prior_strings_at"):
+        if isinstance(d, (StringPrior, TimePrior)) and hasattr(engine, "sample_prior_strings_at"):
             # rows created by an observed-class sweep: the string the sweep already drew for the creating particle's
             # weight (private stream pclean_dummy_seed(seed, site of the option list, particle, sweep) at the creating row);
             # rows whose own choice took the dummy in a latent sweep with dummy_correction: the same, at the latent row
@@ -257,6 +257,8 @@ def resample_dummies(engine, trace, seed, stamp):
                 row_o, particle, sweep_idx, bi = org
                 if bi >= len(lw.blocks) and an not in engine.latent_dummy_served(cname):
                     continue  # (recorded by a latent sweep with dummy_correction: only the served choices were weighed)
+                if bi < len(lw.blocks) and isinstance(d, TimePrior):
+                    continue  # (the observed-class sweeps weigh no drawn time: the stream draw above stays)
                 node = _leaf_node_of(lw, bi, cname, an)
                 if node is None:
                     continue
@@ -432,8 +434,8 @@ def latent_current_choices(lw, trace, cname, rows, config, dummy_served=()):
     current OPTION of every choice: the index of the row's value in the proposal's options — a value that is no option
     (a string drawn for a chosen dummy) counts as the ProposalDummyValue, as in block_proposal.jl:49-52.
     dummy_served (data-driven proposals with dummy_correction: Engine.latent_dummy_served): for these choices the entry
-    is the latent-domain id of the row's current value when that value is no option (a string drawn earlier, which the
-    retained particle holds in place of the dummy), else -1."""
+    is the latent-domain id of the row's current value when that value is no option — of the row's own key, for a keyed
+    choice — (a string or time drawn earlier, which the retained particle holds in place of the dummy), else -1."""
     pl = lw.latent_plans[cname]
     t = trace.tables[cname]
     excl = np.full((len(pl["roots"]), len(rows)), -1, dtype=np.int32)
@@ -444,7 +446,16 @@ def latent_current_choices(lw, trace, cname, rows, config, dummy_served=()):
         elif getattr(config, "use_dd_proposals", True):
             if pl["root_attr"][r] in dummy_served:
                 cur = t.cols[col, rows]
-                excl[r] = np.where(np.isin(cur, lw.option_values[(cname, pl["root_attr"][r])]), -1, cur)
+                opts = lw.option_values[(cname, pl["root_attr"][r])]
+                keyed_by = getattr(lw.model.classes[cname].attr(pl["root_attr"][r]).dist, "keyed_by", None)
+                if keyed_by:  # an option of the row's OWN key: a value listed under another key alone is none
+                    okeys = lw.option_keycol[(cname, pl["root_attr"][r])].astype(np.int64)
+                    rkeys = t.cols[lw.colidx[cname][keyed_by], rows].astype(np.int64)
+                    m = int(max(opts.max(), cur.max() if len(cur) else 0)) + 1
+                    is_option = np.isin(rkeys * m + cur, okeys * m + opts)
+                else:
+                    is_option = np.isin(cur, opts)
+                excl[r] = np.where(is_option, -1, cur)
         else:
             opts = lw.option_values[(cname, pl["root_attr"][r])]
             index = np.full(len(lw.latent_dom[(cname, pl["root_attr"][r])]) + 1, -1, dtype=np.int32)
@@ -471,6 +482,8 @@ def latent_sweep(engine, trace, cname, config, seed, sweep_idx, comm=None, max_s
     if dummy_correction and comm.world > 1:
         raise NotImplementedError("latent sweeps with dummy_correction run in one process")
     lw = engine.lw
+    if dummy_correction:  # (this sweep fills excl by the rows' keys and the engine names their dummy options: keyed choices too)
+        engine.latent_dummy_keyed = True
     served = list(engine.latent_dummy_served(cname)) if dummy_correction and config.use_dd_proposals else []
     extra = dict(dummy_correction=True) if dummy_correction else {}
     pl = lw.latent_plans[cname]

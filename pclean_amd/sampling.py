@@ -77,3 +77,9 @@ def random_maybe_swap(hip, vals, options, probs, seed=0, stream=0):
 def random_time_prior(hip, n, seed=0, stream=0):
     hm = hip.random_time_prior(n, seed, stream)
     return [f"{h}:{m} {'a.m.' if am else 'p.m.'}" for h, m, am in hm]
+
+
+def random_time_prior_at(hip, seeds, elems):
+    """random(TimePrior) with a private stream per element (seeds[i], elems[i]), stream 0."""
+    hm = hip.random_time_prior_at(seeds, elems)
+    return [f"{h}:{m} {'a.m.' if am else 'p.m.'}" for h, m, am in hm]
