@@ -737,6 +737,8 @@ extern "C" int pclean_set_options(pclean_ctx* ctx, int32_t table_id, int32_t n_o
   t.is_options = true;
   t.n_rows = n_options;
   t.n_cols = 1;
+  t.grid_outer_col = -1;
+  t.grid_inner = 0;
   if (t.cols.alloc(n_options) || t.logc_full.alloc(n_options))
     return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
   // the candidate-compact byte tables of the wave kernel depend on the option VALUES only: keep their version when
@@ -783,6 +785,21 @@ extern "C" int pclean_set_options_cols(pclean_ctx* ctx, int32_t table_id, int32_
   t.cols_version = t.version;
   if (t.cols.alloc((size_t)n_options * n_cols)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
   HIPCHK(ctx, hipMemcpy(t.cols.p, cols, (size_t)n_options * n_cols * sizeof(int32_t), hipMemcpyHostToDevice));
+  // a full grid over the two value columns (enum_kernels.hip: enum_product_kernel evaluates a term once per factor value)
+  if (n_cols == 2 && n_options >= 4)
+    for (int oc = 0; oc < 2 && t.grid_outer_col < 0; ++oc) {
+      const int32_t* outer = cols + (size_t)oc * n_options;
+      const int32_t* inner = cols + (size_t)(1 - oc) * n_options;
+      int nb = 1;
+      while (nb < n_options && outer[nb] == outer[0]) ++nb;
+      if (nb < 2 || nb >= n_options || n_options % nb) continue;
+      bool ok = true;
+      for (int k = 0; k < n_options && ok; ++k) ok = outer[k] == outer[(k / nb) * nb] && inner[k] == inner[k % nb];
+      if (ok) {
+        t.grid_outer_col = oc;
+        t.grid_inner = nb;
+      }
+    }
   return PCLEAN_OK;
 }
 

@@ -623,8 +623,10 @@ static int commit_device_impl(pclean_ctx* ctx, int32_t n_blocks, uint32_t sweep_
     for (size_t i = 0; i < b.nodes.size(); ++i)
       if (b.nodes[i].kind == PCLEAN_NODE_LEAF) {
         const int32_t* ov = ctx->cand[b.nodes[i].table].cols.p;
-        if (pl.opt_vals[i] != ov) {
+        const int32_t os = ctx->cand[b.nodes[i].table].n_rows;
+        if (pl.opt_vals[i] != ov || pl.opt_stride[i] != os) {
           pl.opt_vals[i] = ov;
+          pl.opt_stride[i] = os;
           c->plans_dirty = true;
         }
       }

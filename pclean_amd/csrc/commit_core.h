@@ -72,6 +72,7 @@ static inline int32_t pcc_cas32_host(int32_t* p, int32_t cmp, int32_t v) {
 #define PCC_FB_RECORDS 1   // more new-row records than the scratch holds
 #define PCC_FB_DUMMY 2     // a created row would hold a ProposalDummyValue (the host draws its value, block_proposal.jl:58-60)
 #define PCC_FB_CAPACITY 4  // a table would outgrow its device capacity
+#define PCC_FB_PLAN 8      // a new row's column comes from value column > 0 of a leaf whose plan entry has no opt_stride
 
 struct PccTable {
   int32_t* cols;        // [n_cols][stride] column-major flattened rows
@@ -102,7 +103,9 @@ struct PccPlan {  // static description of one block's enumeration plan (include
   int32_t node_used[PCC_MAX_NODES];      // FK nodes: index into used_slot
   int32_t fk_post[PCC_MAX_NODES];        // FK nodes in creation order: a node after all its descendants, the root last
   int32_t used_slot[PCC_MAX_SLOTS];      // distinct table slots of the FK nodes; used_slot[0] = the root's
-  const int32_t* opt_vals[PCC_MAX_NODES];  // leaves: option index -> latent value id
+  const int32_t* opt_vals[PCC_MAX_NODES];  // leaves: option index -> latent value id, column-major [value columns][opt_stride]
+  int32_t opt_stride[PCC_MAX_NODES];     // leaves: options of the table (0: not set — fine for one value column; a colmap entry
+                                         // naming another column of such a leaf refuses the commit, PCC_FB_PLAN)
   const int32_t* colmap;                 // pairs (child node, child column), see pclean_node::colmap_begin
 };
 
@@ -252,7 +255,8 @@ PCC_FN uint64_t pcc_new_nodes(const PccPlan& pl, const int32_t* v, int32_t* row)
 PCC_FN int32_t pcc_col_value(const PccTable* tb, const PccPlan& pl, const int32_t* v, const int32_t* row, int f, int c) {
   const int cn = pl.colmap[2 * (pl.cmb[f] + c)], cc = pl.colmap[2 * (pl.cmb[f] + c) + 1];
   if (cn >= 0) {
-    if (pl.kind[cn] == 1) return pl.opt_vals[cn][v[cn]];
+    // a leaf with several value columns (a product leaf: the index's value, the choice's value) gives column cc of the option
+    if (pl.kind[cn] == 1) return pl.opt_vals[cn][(size_t)cc * pl.opt_stride[cn] + v[cn]];
     const PccTable& tc = tb[pl.slot[cn]];
     return tc.cols[(size_t)cc * tc.stride + row[cn]];
   }
@@ -730,6 +734,17 @@ PCC_FN void pcc_reset_result(PccResult* res) {
 PCC_FN void pcc_commit_apply(PccTable* tb, int n_slots, const PccPlan* plans, const PccBlock* blocks, int n_blocks, PccResult* res,
                              int32_t* part, int tid, int nt) {
   if (tid == 0)
+    for (int bi = 0; bi < n_blocks; ++bi) {  // (a caller that built the plan and forgot the strides of a multi-column leaf)
+      const PccPlan& pl = plans[bi];
+      for (int p = 0; p < pl.n_fk_nodes; ++p) {
+        const int f = pl.fk_post[p];
+        for (int c = 0; c < tb[pl.slot[f]].n_cols; ++c) {
+          const int cn = pl.colmap[2 * (pl.cmb[f] + c)], cc = pl.colmap[2 * (pl.cmb[f] + c) + 1];
+          if (cn >= 0 && pl.kind[cn] == 1 && cc != 0 && pl.opt_stride[cn] == 0) res->fallback |= PCC_FB_PLAN;
+        }
+      }
+    }
+  if (tid == 0)
     for (int s = 0; s < n_slots; ++s) {
       const int a = res->alloc_upper[s];
       if (a == 0) continue;
@@ -785,6 +800,7 @@ static inline int pcc_build_plan(const PccNodeIn* nodes, int n_nodes, const int3
     pl.slot[i] = -1;
     pl.node_used[i] = -1;
     pl.opt_vals[i] = nullptr;
+    pl.opt_stride[i] = 0;
     if (nodes[i].kind == 1 && nodes[i].dummy_value != 0) pl.track = 1;
     if (nodes[i].kind == 0) {
       const int s = slot_of_table[nodes[i].table];

@@ -98,6 +98,10 @@ struct CandTable {
   uint64_t cols_version = 0;  // re-upload of the value columns
   bool is_options = false;
   int32_t n_rows = 0, n_cols = 0;
+  // option tables whose first two value columns form a full grid (a product leaf: option a * |B| + b holds (a, b); or the
+  // keyed form of an indexed parameter: option key * |B| + b holds (b, key)): the column that holds k / grid_inner,
+  // -1: no grid (pclean_set_options_cols looks at the values it uploads)
+  int32_t grid_outer_col = -1, grid_inner = 0;
   // rows [n_used, n_rows) have never held a row (the spare capacity of the device-resident commit: count 0, weight
   // exactly 0): a scan need not look at them.  0: unknown (every row may be in use)
   int32_t n_used = 0;

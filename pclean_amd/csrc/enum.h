@@ -239,9 +239,21 @@ int pclean_update_compact(pclean_ctx* ctx, const uint8_t* pair, int n_obs, int n
 int pclean_build_priors(pclean_ctx* ctx, const int64_t* counts, const double* logc_full, int n_cand, int kpad,
                         double logden_e, double logden_n, double* prior_e, double* prior_n, uint16_t* alive);
 
+// Product leaf (an option table that is a full grid over two value columns, ctx.h: CandTable::grid_outer_col): which factor
+// every term reads and where its cached values start in LDS.  pclean_product_plan returns false when the launch takes the
+// generic kernels: no grid, PCLEAN_NO_PRODUCT_LEAF, evidence sets, a ctx slot / MaybeSwap / Gaussian term, or cached term
+// values (plus, for a grouped launch, the prefix array) beyond the LDS of a workgroup.
+struct ProductDev {
+  int32_t n_outer, n_inner, total, lds_prefix;  // total: cached doubles; lds_prefix: 1 = the fixed-point prefix lives in LDS too
+  int32_t inner[PCLEAN_MAX_TERMS];              // 1: the term reads the inner factor (k % n_inner), 0: the outer (k / n_inner)
+  int32_t off[PCLEAN_MAX_TERMS];
+};
+// t: the node's own candidate table (the caller knows it from the plan: pclean_node::table)
+bool pclean_product_plan(const CandTable& t, const NodeDev& nd, const ItemsDev& it, ProductDev* pr);
+// product: the plan pclean_product_plan made for THIS launch (null: the generic kernels)
 int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, const ChildrenDev& ch, uint64_t seed,
                        uint32_t sweep, uint32_t site, int n_draws, double* lse_out, double* scores_out,
-                       int32_t* draws_out, double* scores_tmp = nullptr);
+                       int32_t* draws_out, double* scores_tmp = nullptr, const ProductDev* product = nullptr);
 // doubles of scratch (scores_tmp) with which the launch above computes its scores one candidate per thread first; 0: not used
 size_t pclean_enum_split_scores(const NodeDev& nd, const ItemsDev& it);
 // cacheable option lists: per-observed-value (maximum, total, coarse prefix) and draws through them (enum_kernels.hip)

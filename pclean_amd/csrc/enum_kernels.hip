@@ -1466,6 +1466,234 @@ int pclean_launch_prior_terms_ev(pclean_ctx* ctx, int n_items, int P, int n_node
   return PCLEAN_OK;
 }
 
+// ---- product leaves: an option list that is a full grid over two factors (ProductDev, enum.h) ---------------------------
+// Every term of such a leaf reads ONE of the two factors, so its density takes n_outer or n_inner values per item, not
+// n_outer x n_inner.  One workgroup per item (or group of items):
+//   1  each term once per value of the factor it reads — candidate_score()'s rules: a tabulated term scores a missing
+//      observation, the others skip it — the doubles into LDS; the gathers of a term's values are independent and in flight
+//      together
+//   2  the grid: s_k = prior_k, then += the cached value of every term in plan order — the same doubles in the same order as
+//      candidate_score(), so maximum, fixed-point weights, total, log-marginal and draws are the generic kernels', bit for bit
+//   3  LDSP: weights and their inclusive prefix in LDS, every (member item, draw) by binary search (enum_node_kernel's
+//      phases 3-5); else the scores are recomputed from the cached values per pass (enum_node_big_kernel's passes B, C)
+template <int BT, bool LDSP>
+__global__ __launch_bounds__(BT) void enum_product_kernel(const NodeDev nd, const DensDev dn, const ItemsDev it, const ProductDev pr,
+                                                           uint64_t seed, uint32_t sweep, uint32_t site, int n_draws,
+                                                           int item_base, double* __restrict__ lse_out,
+                                                           double* __restrict__ scores_out, int32_t* __restrict__ draws_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  int g = blockIdx.x + item_base;
+  if (it.sel) {
+    if ((unsigned int)g >= *it.sel_n) return;
+    g = it.sel[g];
+  }
+  const int m_lo = it.grp_off ? it.grp_off[g] : g, m_hi = it.grp_off ? it.grp_off[g + 1] : g + 1;
+  const int t = it.grp_off ? it.members[m_lo] : g;
+  const int to = it.out_pos ? it.out_pos[t] : t;
+  const int n = nd.n_cand;
+  double* red = (double*)smem;               // [16]
+  uint64_t* wsum = (uint64_t*)(red + 16);    // [16]
+  double* tv = (double*)(wsum + 16);         // [pr.total] cached term values
+  uint64_t* u = (uint64_t*)(tv + pr.total);  // [n] (LDSP)
+  const ItemView v = item_view(nd, it, t);
+  const int n_inner = pr.n_inner;
+
+  // ---- 1: the terms, once per factor value ------------------------------------------------------------------------
+  unsigned int skip = 0;
+  for (int ti = 0; ti < nd.n_terms; ++ti) {
+    const TermDev& tm = nd.terms[ti];
+    const int o = tm.obs_col[v.row];
+    const bool tab = tm.dens_kind == PCLEAN_DENS_TABULATED;
+    if (!tab && o < 0) {  // explicitly missing observation: the term adds nothing
+      skip |= 1u << ti;
+      continue;
+    }
+    const int nf = pr.inner[ti] ? n_inner : pr.n_outer;
+    const size_t stride = pr.inner[ti] ? 1 : (size_t)n_inner;
+    double* dst = tv + pr.off[ti];
+    for (int j = tid; j < nf; j += BT) {
+      const int val = tm.cand_col[(size_t)j * stride];
+      double x;
+      if (tab) {
+        x = tabulated_density(tm, o, val);
+      } else {
+        const size_t idx = (size_t)o * tm.n_lat + val;
+        const int d = tm.elem_bytes == 1 ? (int)tm.pair[idx] : (int)((const uint16_t*)tm.pair)[idx];
+        x = term_density(tm, dn, d, val);
+      }
+      dst[j] = x;
+    }
+  }
+  __syncthreads();
+  auto score = [&](int k) -> double {
+    const int a = k / n_inner, b = k - a * n_inner;
+    double sk = nd.logc_full[k];
+    for (int ti = 0; ti < nd.n_terms; ++ti)
+      if (!((skip >> ti) & 1u)) sk += tv[pr.off[ti] + (pr.inner[ti] ? b : a)];
+    return sk;
+  };
+
+  // ---- 2: maximum ---------------------------------------------------------------------------------------------------
+  double lmax = -__builtin_inf();
+  for (int k = tid; k < n; k += BT) {
+    const double sk = score(k);
+    if (scores_out) scores_out[(size_t)to * n + k] = sk;
+    lmax = fmax(lmax, sk);
+  }
+  lmax = wave_max(lmax);
+  if (lane == 0) red[wave] = lmax;
+  __syncthreads();
+  double m = red[0];
+  for (int w = 1; w < BT / 64; ++w) m = fmax(m, red[w]);
+
+  const int chunk = (n + BT - 1) / BT;
+  const int lo = min(tid * chunk, n), hi = min(lo + chunk, n);
+  if (LDSP) {
+    // ---- 3 (LDS): weights, chunk sums, inclusive prefix in place, draws of every member item -------------------------
+    for (int k = tid; k < n; k += BT) u[k] = (m == -__builtin_inf()) ? 0ull : pclean_fixw(score(k) - m);
+    __syncthreads();
+    uint64_t part = 0;
+    for (int k = lo; k < hi; ++k) part += u[k];
+    uint64_t U;
+    const uint64_t pre = block_excl_scan<BT / 64>(part, wsum, &U);
+    {
+      uint64_t run = pre;
+      for (int k = lo; k < hi; ++k) {
+        run += u[k];
+        u[k] = run;
+      }
+    }
+    __syncthreads();
+    const double lse = pclean_lse_from_fix(m, U);
+    const int nd_eff = n_draws > 0 ? n_draws : 1;
+    const int n_out = (m_hi - m_lo) * nd_eff;
+    const int draw_is = it.draw_is ? it.draw_is : n_draws, draw_ds = it.draw_ds ? it.draw_ds : 1;
+    for (int q = tid; q < n_out; q += BT) {
+      const int mi = m_lo + q / nd_eff, j = q % nd_eff;
+      const int tm_ = it.grp_off ? it.members[mi] : t;
+      const int tom = it.out_pos ? it.out_pos[tm_] : tm_;
+      if (j == 0 && lse_out) lse_out[tom] = lse;
+      if (n_draws <= 0) continue;
+      int32_t res = n - 1;
+      if (U != 0) {
+        const int row_m = it.row ? it.row[tm_] : tm_;
+        const uint32_t rng_row = it.rng_row ? (uint32_t)it.rng_row[tm_] : (uint32_t)((int64_t)row_m + it.row_offset);
+        const uint32_t pid = it.particle ? (uint32_t)it.particle[tm_] : (uint32_t)j;
+        const uint64_t x = pclean_mulhi64(pclean_rand64(seed, rng_row, site, pid, sweep), U);
+        int a = 0, b = n - 1;
+        while (a < b) {
+          const int mid = (a + b) >> 1;
+          if (u[mid] > x)
+            b = mid;
+          else
+            a = mid + 1;
+        }
+        res = a;
+      }
+      draws_out[(size_t)tom * draw_is + (size_t)j * draw_ds] = res;
+    }
+  } else {
+    // ---- 3 (grid beyond LDS, never grouped): chunk sums and draws from recomputed scores -----------------------------
+    uint64_t part = 0;
+    if (m != -__builtin_inf())
+      for (int k = lo; k < hi; ++k) part += pclean_fixw(score(k) - m);
+    uint64_t U;
+    const uint64_t pre = block_excl_scan<BT / 64>(part, wsum, &U);
+    if (tid == 0 && lse_out) lse_out[to] = pclean_lse_from_fix(m, U);
+    if (n_draws > 0) {
+      const uint32_t rng_row = it.rng_row ? (uint32_t)it.rng_row[t] : (uint32_t)((int64_t)v.row + it.row_offset);
+      for (int j = 0; j < n_draws; ++j) {
+        const uint32_t pid = it.particle ? (uint32_t)it.particle[t] : (uint32_t)j;
+        int32_t* dst = draws_out + (size_t)to * (it.draw_is ? it.draw_is : n_draws) + (size_t)j * (it.draw_ds ? it.draw_ds : 1);
+        if (U == 0) {
+          if (tid == 0) *dst = n - 1;
+          continue;
+        }
+        const uint64_t x = pclean_mulhi64(pclean_rand64(seed, rng_row, site, pid, sweep), U);
+        if (x >= pre && x < pre + part) {
+          uint64_t acc = pre;
+          int k = lo;
+          for (; k < hi; ++k) {
+            acc += pclean_fixw(score(k) - m);
+            if (acc > x) break;
+          }
+          *dst = k;
+        }
+      }
+    }
+  }
+}
+
+#define PRODUCT_LDS_MAX ((size_t)160 * 1024)
+
+bool pclean_product_plan(const CandTable& table, const NodeDev& nd, const ItemsDev& it, ProductDev* pr) {
+  static const bool off = getenv("PCLEAN_NO_PRODUCT_LEAF") != nullptr;
+  if (off || nd.kind != PCLEAN_NODE_LEAF || it.ev_lo || nd.g.on || nd.n_terms < 1 || nd.n_terms > PCLEAN_MAX_TERMS) return false;
+  const CandTable* t = &table;
+  if (!t->valid || !t->is_options || t->logc_full.p != nd.logc_full || t->grid_outer_col < 0 || t->n_cols != 2 ||
+      t->n_rows != nd.n_cand || t->grid_inner < 1)
+    return false;
+  pr->n_inner = t->grid_inner;
+  pr->n_outer = t->n_rows / t->grid_inner;
+  pr->total = 0;
+  for (int ti = 0; ti < nd.n_terms; ++ti) {
+    const TermDev& tm = nd.terms[ti];
+    if (tm.ctx_slot >= 0 || tm.dens_kind == PCLEAN_DENS_MAYBE_SWAP) return false;
+    int col = -1;
+    for (int c = 0; c < 2; ++c)
+      if (tm.cand_col == t->cols.p + (size_t)c * t->n_rows) col = c;
+    if (col < 0) return false;
+    pr->inner[ti] = col != t->grid_outer_col;
+    pr->off[ti] = pr->total;
+    pr->total += pr->inner[ti] ? pr->n_inner : pr->n_outer;
+  }
+  const size_t small = (size_t)(32 + pr->total) * 8, full = small + (size_t)nd.n_cand * 8;
+  if (full <= PRODUCT_LDS_MAX)
+    pr->lds_prefix = 1;
+  else if (small <= PRODUCT_LDS_MAX && !it.grp_off)
+    pr->lds_prefix = 0;
+  else
+    return false;  // the cached term values do not fit the LDS of a workgroup
+  return true;
+}
+
+static int pclean_launch_product(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, const ProductDev& pr, uint64_t seed,
+                                 uint32_t sweep, uint32_t site, int n_draws, double* lse_out, double* scores_out,
+                                 int32_t* draws_out) {
+  DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
+  static bool attr_set = false;
+  if (!attr_set) {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_product_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRODUCT_LDS_MAX));
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_product_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRODUCT_LDS_MAX));
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_product_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRODUCT_LDS_MAX));
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_product_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRODUCT_LDS_MAX));
+    attr_set = true;
+  }
+  const size_t lds = (size_t)(32 + pr.total) * 8 + (pr.lds_prefix ? (size_t)nd.n_cand * 8 : 0);
+  // (as the generic launches: workgroups of 1024 threads when the launch cannot fill the chip with workgroups of 256)
+  const bool wide = nd.n_cand >= 4096 && (it.n <= 1024 || (it.sel && it.n <= 16384) || (lds > 20 * 1024 && it.n <= 65536));
+  const int kMaxBlocks = 4 * 1024 * 1024;
+  for (int base = 0; base < it.n; base += kMaxBlocks) {
+    const dim3 grid(std::min(kMaxBlocks, it.n - base));
+    if (wide && pr.lds_prefix)
+      hipLaunchKernelGGL((enum_product_kernel<1024, true>), grid, dim3(1024), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
+                         base, lse_out, scores_out, draws_out);
+    else if (wide)
+      hipLaunchKernelGGL((enum_product_kernel<1024, false>), grid, dim3(1024), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
+                         base, lse_out, scores_out, draws_out);
+    else if (pr.lds_prefix)
+      hipLaunchKernelGGL((enum_product_kernel<256, true>), grid, dim3(256), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
+                         base, lse_out, scores_out, draws_out);
+    else
+      hipLaunchKernelGGL((enum_product_kernel<256, false>), grid, dim3(256), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
+                         base, lse_out, scores_out, draws_out);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return PCLEAN_OK;
+}
+
 // rows of the split launch's score scratch: every item of a direct launch within 256 MB, and of an indirect one (its
 // device-side list is usually a few per cent of the items) at most 64 — later workgroups compute their scores themselves
 static int pclean_enum_split_slots(const ItemsDev& it, int nc) {
@@ -1489,8 +1717,9 @@ size_t pclean_enum_split_scores(const NodeDev& nd, const ItemsDev& it) {
 
 int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, const ChildrenDev& ch, uint64_t seed,
                        uint32_t sweep, uint32_t site, int n_draws, double* lse_out, double* scores_out,
-                       int32_t* draws_out, double* scores_tmp) {
+                       int32_t* draws_out, double* scores_tmp, const ProductDev* product) {
   if (it.n <= 0) return PCLEAN_OK;
+  if (product) return pclean_launch_product(ctx, nd, it, *product, seed, sweep, site, n_draws, lse_out, scores_out, draws_out);
   const int nc = nd.n_cand + (nd.kind == PCLEAN_NODE_FK ? 1 : 0);
   const size_t lds = (size_t)((nc + 1) & ~1) * 8 + (16 + 64) * 8;
   DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};

@@ -1022,14 +1022,17 @@ int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, co
     }
   }
   if (!fast && !fast_ev) {
-    ProfScope ps(ctx, n.kind == PCLEAN_NODE_FK ? "enum_fk_generic" : "enum_leaf_generic");
+    ProductDev prd;
+    const bool product = pclean_product_plan(ctx->cand[n.table], nd, it, &prd);  // (the phase name says which path a leaf took)
+    ProfScope ps(ctx, n.kind == PCLEAN_NODE_FK ? "enum_fk_generic" : (product ? "enum_leaf_product" : "enum_leaf_generic"));
     if (time_it) (void)hipEventRecord(s->ev0, ctx->stream);
     double* sc_tmp = nullptr;  // (few items with evidence sets and long lists: the scores one candidate per thread first)
-    if (!scores_out) {
+    if (!scores_out && !product) {
       const size_t sc_n = pclean_enum_split_scores(nd, it);
       if (sc_n && !(sc_tmp = scratch<double>(ctx, sc_n))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
     }
-    rc = pclean_launch_enum(ctx, nd, it, ch, seed, sweep, site, n_draws, lse_out, scores_out, draws_out, sc_tmp);
+    rc = pclean_launch_enum(ctx, nd, it, ch, seed, sweep, site, n_draws, lse_out, scores_out, draws_out, sc_tmp,
+                            product ? &prd : nullptr);
     if (time_it) (void)hipEventRecord(s->ev1, ctx->stream);
     return rc;
   }

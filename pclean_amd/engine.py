@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from ._lib import HipContext, InferConfig
 from .encode import lm_log_tables
-from .model import ChooseProportionally, ChooseUniformly, StringPrior, TimePrior, Unmodeled
+from .model import ChooseProportionally, ChooseUniformly, NumberCodePrior, StringPrior, TimePrior, Unmodeled, number_code
 
 # time_prior.jl:10 — atoms matching this pattern score -log(1440), everything else -Inf
 _TIME_RE = re.compile(r"^[0-9]?[0-9]:[0-9][0-9] [ap]\.m\.$")
@@ -59,6 +59,17 @@ def class_density_rows(rule, strings, options=None, counts=None):
                 T[v, 0], T[v, 1] = np.log(0.9999), np.log(0.0001)
             T[v, 3] = 0.0 if s == "" else (-1000.0 if "*" in s else -5.0)
     return T
+
+
+def number_code_logp(codes):
+    """logdensity(NumberCodePrior(), code) = -log(code) of the observed code strings (number_code_prior.jl:10-14), float64"""
+    vals = []
+    for s in codes:
+        v = number_code(s)
+        if v is None:
+            raise ValueError(f"NumberCodePrior: value {s!r} is not a decimal integer >= 1")
+        vals.append(float(v))
+    return -np.log(np.array(vals, dtype=np.float64))
 
 
 def lw_locals(lw):
@@ -215,7 +226,9 @@ class Engine:
                 self.option_logp[(cname, aname)] = logp
                 hip.set_options_cols(tid, np.stack([vals, keys, lw.option_ncol[(cname, aname)]]), logp)
                 continue
-            if d is None or isinstance(d, Unmodeled) or not isinstance(d, (StringPrior, ChooseUniformly, ChooseProportionally)):
+            if isinstance(d, NumberCodePrior):  # (never among the observed class's own choices: the lowering refuses that)
+                logp = number_code_logp([dom.string(v) for v in range(len(dom))])
+            elif d is None or isinstance(d, Unmodeled) or not isinstance(d, (StringPrior, ChooseUniformly, ChooseProportionally)):
                 if cname == lw.query.cls:
                     continue  # own choices of the observed class are enumerated as locals, not as leaves
                 logp = np.zeros(len(dom))  # Unmodeled: logdensity 0 (unmodeled.jl:7-10)
@@ -334,12 +347,26 @@ class Engine:
             d = m.classes[cname].attr(aname).dist
             if isinstance(d, ChooseProportionally):
                 with np.errstate(divide="ignore"):
-                    logp = np.log(trace.params[(cname, d.param)].value)  # logprobs(), utils.jl:33-36
+                    # logprobs(), utils.jl:33-36; an IndexedProportionsParameter: log theta_key[option], key-major as the options
+                    logp = np.log(trace.params[(cname, d.param)].value)
+                    ix = getattr(lw, "indexed", {}).get((cname, aname), ("", ""))
+                    if ix[0] == "product":  # joint prior log pA(a) + log theta_a[b], added in that order
+                        da = m.classes[cname].attr(ix[1]).dist
+                        la = (np.log(trace.params[(cname, da.param)].value) if isinstance(da, ChooseProportionally)
+                              else np.full(len(da.options), -np.log(len(da.options))))
+                        logp = la[:, None] + logp
+                    logp = logp.reshape(-1)
                 self.option_logp[(cname, aname)] = logp
                 prev = last.get(("options", cname, aname))
                 if prev is not None and np.array_equal(prev, logp):
                     continue
-                hip.set_options(lw.option_id[(cname, aname)], lw.option_values[(cname, aname)], logp)
+                if (cname, aname) in getattr(lw, "option_cols", {}):
+                    hip.set_options_cols(lw.option_id[(cname, aname)], lw.option_cols[(cname, aname)], logp)
+                elif (cname, aname) in getattr(lw, "indexed", {}):
+                    hip.set_options_cols(lw.option_id[(cname, aname)], np.stack([lw.option_values[(cname, aname)],
+                                                                                 lw.option_keycol[(cname, aname)]]), logp)
+                else:
+                    hip.set_options(lw.option_id[(cname, aname)], lw.option_values[(cname, aname)], logp)
                 last[("options", cname, aname)] = logp.copy()
         if lw.prob_spec is not None:
             pt = trace.prob_table()
@@ -374,6 +401,14 @@ class Engine:
         for bi in self.lw.locals:
             self.hip.set_cur_locals(bi, loc[bi])
 
+    def _refuse_prior_product(self, cfg, who, infos):
+        """use_dd_proposals = false on a plan holding a product leaf: the prior proposal would have to sample the index and
+        then the choice from theta[index]; the option table holds their joint prior only.  Refused HERE, by the Python
+        driver: the C ABI has no mark for such a leaf"""
+        if not cfg.use_dd_proposals and any("product" in info for info in infos):
+            raise _lib.PCleanHipError(f"{who}: a product leaf (an indexed ChooseProportionally enumerated jointly with its "
+                                      "index) under use_dd_proposals = false (prior proposals) is not supported")
+
     def sweep(self, trace, config, seed, sweep_idx, lo=0, hi=None, reuse_buffers=False, light=False):
         """One batched sweep over the observed rows [lo, hi) of the trace (default: all of them).
         Returns (choice, chosen_particle, logml, new_rows), all indexed relative to lo.  reuse_buffers:
@@ -382,6 +417,7 @@ class Engine:
         light: no per-row outputs are copied back (choice / chosen / logml are None); the commit reads the
         moved rows (sweep_moved) and the new-row records only."""
         cfg = config.as_c() if isinstance(config, InferenceConfig) else config
+        self._refuse_prior_product(cfg, "Engine.sweep", [i for blk in self.lw.blocks for i in blk["node_info"]])
         hi = trace.cur.shape[1] if hi is None else hi
         if hi <= lo:  # a rank may own no row of a small batch
             for bi in self.lw.locals:
@@ -488,6 +524,7 @@ class Engine:
         the trace is marked as behind the device and pulls the state when something reads it (Trace._sync)."""
         dc = self._dc
         cfg = config.as_c() if isinstance(config, InferenceConfig) else config
+        self._refuse_prior_product(cfg, "Engine.sweep_commit_device", [i for blk in self.lw.blocks for i in blk["node_info"]])
         hi = trace._cur.shape[1] if hi is None else hi
         if trace._dev is None:  # the host arrays are current: the device gets whatever moved since the last upload
             self.upload_trace(trace)
@@ -605,11 +642,9 @@ class Engine:
             trace._cur[...] = self.hip.get_cur(*trace._cur.shape)
         dc["cur_version"] = (id(trace), trace._cur_version)
         for (cname, pname), state in trace._params.items():  # own-choice sufficient statistics (check_consistency's identity)
-            t = trace._tables[cname]
-            rows = np.flatnonzero(t.live[:t.n])
             for a in lw.model.classes[cname].attrs:
                 if a.kind == "choice" and isinstance(a.dist, ChooseProportionally) and a.dist.param == pname:
-                    state.counts = np.bincount(t.cols[lw.colidx[cname][a.name], rows], minlength=len(state.counts)).astype(np.int64)
+                    state.counts = trace.recount(cname, a.name)
 
     def make_device_current(self, trace):
         """The latent tables and the observed rows' referents of `trace` as the device holds them are its current state
@@ -657,6 +692,8 @@ class Engine:
             if node[0] != _lib.NODE_LEAF:
                 continue
             attr = pl["root_attr"][r]
+            if isinstance(attr, tuple):  # a product leaf: neither choice has a dummy
+                continue
             d = lw.model.classes[cname].attr(attr).dist
             if not isinstance(d, (StringPrior, TimePrior)):
                 continue
@@ -714,6 +751,7 @@ class Engine:
         hold: inference.latent_current_choices); latent_weights() returns the corrections afterwards."""
         pl = self.lw.latent_plans[cname]
         cfg = config.as_c() if isinstance(config, InferenceConfig) else config
+        self._refuse_prior_product(cfg, "Engine.sweep_latent", pl["node_info"])
         self.hip.set_active_rows(0, -1)
         if dummy_correction or getattr(self, "_latent_dummy_on", False):  # (a reload makes a fresh context: set per call)
             self.hip.set_latent_dummy_correction(dummy_correction)

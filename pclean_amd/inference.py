@@ -18,7 +18,7 @@ import numpy as np
 
 from .model import ChooseProportionally
 from .parallel import Comm, exchange_and_commit, shard_bounds
-from .trace import CHOICE_NEW
+from .trace import CHOICE_NEW, prop_cells
 
 
 # ---------------------------------------------------------------------------
@@ -324,7 +324,7 @@ def _materialise_latent(lw, trace, pl, node, vals):
         if cn < 0:
             continue
         if nodes[cn][0] == 1:
-            values[j] = lw.option_values[(info[cn]["cls"], info[cn]["attr"])][vals[cn]]
+            values[j] = lw.option_column(info[cn]["cls"], info[cn]["attr"], cc)[vals[cn]]
         else:
             r = child_row(cn)  # may create the child row (and grow its table) first
             values[j] = trace.tables[info[cn]["cls"]].cols[cc, r]
@@ -366,15 +366,25 @@ def commit_latent(lw, trace, cname, live, chosen, vals, dummy_origin=None):
             else:
                 trace.set_row_origin(cname, int(h[k]), None)
     fks, props = trace._class_plan(cname)
-    for j, state in props:  # own-choice sufficient statistics: take the old values out ...
-        np.subtract.at(state.counts, t.cols[j, h], 1)
+    for prop in props:  # own-choice sufficient statistics: take the old values out ...
+        np.subtract.at(prop[2].counts.reshape(-1), prop_cells(t, prop, h), 1)
     changed = 0
     released = []  # (class, rows) referents to release AFTER every new reference has been counted:
     # another row of this batch may have joined a referent that this row leaves (batched schedule)
     for r, root in enumerate(pl["roots"]):
         attr = pl["root_attr"][r]
-        j = lw.colidx[cname][attr]
         v = vals[idx, root]
+        if isinstance(attr, tuple):  # a product leaf: the option names both values
+            for cc, an in enumerate(attr):
+                j = lw.colidx[cname][an]
+                new = lw.option_column(cname, attr[1], cc)[v]
+                moved = new != t.cols[j, h]
+                if moved.any():
+                    t.cols[j, h[moved]] = new[moved]
+                    t.cols_dirty = True
+                    changed += int(moved.sum())
+            continue
+        j = lw.colidx[cname][attr]
         old = t.cols[j, h].copy()
         if pl["nodes"][root][0] == 1:  # leaf: option index -> latent value
             new = lw.option_values[(cname, attr)][v]
@@ -391,8 +401,8 @@ def commit_latent(lw, trace, cname, live, chosen, vals, dummy_origin=None):
             t.cols[j, h[moved]] = new[moved]
             t.cols_dirty = True
             changed += int(moved.sum())
-    for j, state in props:  # ... and put the new ones in
-        np.add.at(state.counts, t.cols[j, h], 1)
+    for prop in props:  # ... and put the new ones in
+        np.add.at(prop[2].counts.reshape(-1), prop_cells(t, prop, h), 1)
     for tgt_cls, old in released:
         np.subtract.at(trace.tables[tgt_cls].counts, old, 1)
     for tgt_cls, old in released:
@@ -440,6 +450,8 @@ def latent_current_choices(lw, trace, cname, rows, config, dummy_served=()):
     t = trace.tables[cname]
     excl = np.full((len(pl["roots"]), len(rows)), -1, dtype=np.int32)
     for r, root in enumerate(pl["roots"]):
+        if isinstance(pl["root_attr"][r], tuple):  # a product leaf: no dummy, and prior proposals are refused (Engine)
+            continue
         col = lw.colidx[cname][pl["root_attr"][r]]
         if pl["nodes"][root][0] == 0:
             excl[r] = t.cols[col, rows]
@@ -458,6 +470,11 @@ def latent_current_choices(lw, trace, cname, rows, config, dummy_served=()):
                 excl[r] = np.where(is_option, -1, cur)
         else:
             opts = lw.option_values[(cname, pl["root_attr"][r])]
+            ix = getattr(lw, "indexed", {}).get((cname, pl["root_attr"][r]))
+            if ix is not None:  # options (value, key), key-major: the row's value under the row's own key
+                nb = len(lw.model.classes[cname].attr(pl["root_attr"][r]).dist.options)
+                excl[r] = t.cols[lw.colidx[cname][ix[1]], rows] * nb + t.cols[col, rows]
+                continue
             index = np.full(len(lw.latent_dom[(cname, pl["root_attr"][r])]) + 1, -1, dtype=np.int32)
             index[opts[::-1]] = np.arange(len(opts) - 1, -1, -1)  # first option holding each value
             cur = index[t.cols[col, rows]]

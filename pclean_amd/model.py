@@ -45,10 +45,12 @@ class ChooseUniformly:
 
 
 class ChooseProportionally:
-    """choose_proportionally.jl: ChooseProportionally(options, probs::ProportionsParameter)."""
+    """choose_proportionally.jl: ChooseProportionally(options, probs::ProportionsParameter).  With `index` the
+    parameter is an IndexedProportionsParameter read at the value of attribute `index` of the same class
+    (`probs[key]`, dsl/builder.jl:195-201): one probability vector per value of that attribute."""
 
-    def __init__(self, options, param):
-        self.options, self.param = list(options), param
+    def __init__(self, options, param, index=None):
+        self.options, self.param, self.index = list(options), param, index
 
 
 class AddTypos:
@@ -118,6 +120,19 @@ class Unmodeled:
     """unmodeled.jl: logdensity 0, no proposal; must be observed."""
 
 
+class NumberCodePrior:
+    """number_code_prior.jl:10-14: logdensity -log(code) of an observed integer code, no proposal; must be observed.
+    The values are the observed strings, each a decimal integer >= 1 (so that no density is positive)."""
+
+
+def number_code(s):
+    """the integer a NumberCodePrior value stands for, None when the string is no decimal integer >= 1"""
+    if not isinstance(s, str) or not s.isascii() or not s.isdigit():
+        return None
+    v = int(s)
+    return v if v >= 1 else None
+
+
 class Transformation:
     """transformed_gaussian.jl:5-9 — forward, backward, |g'|."""
 
@@ -158,6 +173,14 @@ class IndexedLookup:
 
 class ProportionsParameter:
     """choose_proportionally.jl:31-74 (Dirichlet prior, default concentration 1.0)."""
+
+    def __init__(self, concentration=1.0):
+        self.concentration = float(concentration)
+
+
+class IndexedProportionsParameter:
+    """`@learned x::Dict{K, ProportionsParameter{c}}` (dsl/syntax.jl:139-144, distributions.jl:45-61): one Dirichlet
+    vector per key, all with the same concentration."""
 
     def __init__(self, concentration=1.0):
         self.concentration = float(concentration)
@@ -327,6 +350,7 @@ class LoweredModel:
         self.latent_ev_prob = {}    # latent class -> scoring block whose error-prob index feeds the evidence ctx
         self.latent_plans = {}
         self._build_domains(dirty_columns)
+        self._resolve_indexed()
         self._build_layouts()
         self._build_blocks()
         self._build_latent_plans()
@@ -391,14 +415,109 @@ class LoweredModel:
                     key = (cn, la.name)
                 if key not in self.latent_dom:  # e.g. Unmodeled: its values are whatever is observed
                     vals = [v for v in dirty_columns[col] if v is not None]
+                    if isinstance(getattr(m.classes[key[0]].attr(key[1]), "dist", None), NumberCodePrior):
+                        for v in vals:
+                            if number_code(v) is None:
+                                raise ValueError(f"{col}: value {v!r} is not a decimal integer >= 1 (NumberCodePrior of "
+                                                 f"{key[0]}.{key[1]})")
                     self.latent_dom[key] = Domain(self.pool, list(dict.fromkeys(vals)))
                 self.obs_dom[dirty] = self.latent_dom[key]
                 self.direct_obs[dirty] = key
             self.obs_index[dirty] = len(self.obs_cols)
             self.obs_cols.append(dirty)
+        for cname in m.class_order:  # (number_code_prior.jl:1: "for _observed_ number codes")
+            for a in m.classes[cname].attrs:
+                if a.kind == "choice" and isinstance(a.dist, NumberCodePrior):
+                    if cname == self.query.cls:
+                        raise NotImplementedError(f"{cname}.{a.name}: NumberCodePrior among the observed class's own choices "
+                                                  "is not lowered")
+                    if (cname, a.name) not in self.direct_obs.values():
+                        raise ValueError(f"{cname}.{a.name}: a NumberCodePrior value must be observed directly")
         self.query_columns = {dirty: col for col, dirty in self.query.obsmap.items()}
         self._never_missing = {dirty for col, dirty in self.query.obsmap.items()
                                if all(v is not None for v in dirty_columns[col])}
+
+    def _resolve_indexed(self):
+        """ChooseProportionally(options, param, index=attr): how each indexed choice is lowered.  self.indexed maps
+        (class, dependent attribute) -> ("keyed", index attribute): the index is observed directly (e.g. Unmodeled) and the
+        choice is lowered as keyed StringPrior atoms are — options (value, key) for every key of the index's domain, the
+        equality term on the observed key; or -> ("product", index attribute): the index is a sibling ChooseProportionally /
+        ChooseUniformly choice declared before it in the same block, and the two become ONE leaf over the |A| x |B| joint
+        options (proposal_compiler.jl:55-129 enumerates them jointly).  Everything else is refused by name."""
+        m = self.model
+        self.indexed = {}
+        self.product_index = {}  # (class, index attribute) -> its dependent: the two are enumerated as one product leaf
+        for cname in m.class_order:
+            cls = m.classes[cname]
+            seen = {}
+            for a in cls.attrs:
+                if a.kind != "choice" or not isinstance(a.dist, ChooseProportionally):
+                    continue
+                prior = cls.attr(a.dist.param).prior
+                ix = a.dist.index
+                who = f"{cname}.{a.name}"
+                if ix is None:
+                    if isinstance(prior, IndexedProportionsParameter):
+                        raise ValueError(f"{who}: the IndexedProportionsParameter {a.dist.param} needs index=...")
+                    continue
+                if not isinstance(prior, IndexedProportionsParameter):
+                    raise ValueError(f"{who}: index={ix!r} needs an IndexedProportionsParameter, {a.dist.param} is none")
+                if "." in ix:
+                    raise NotImplementedError(f"{who}: an index reached through a reference ({ix}) is not lowered")
+                ia = cls.attr(ix)
+                if ia.kind == "julia":
+                    raise NotImplementedError(f"{who}: a JuliaNode index ({ix}) is not lowered")
+                if ia.kind != "choice":
+                    raise NotImplementedError(f"{who}: the index {ix} is a reference slot, not a value")
+                if cname == self.query.cls:
+                    raise NotImplementedError(f"{who}: an indexed choice among the observed class's own choices is not lowered "
+                                              "(those are enumerated with the Gaussian observations)")
+                if isinstance(ia.dist, ChooseProportionally) and ia.dist.index is not None:
+                    raise NotImplementedError(f"{who}: the index {ix} is itself indexed")
+                if ix in seen:
+                    raise NotImplementedError(f"{who}: {ix} already indexes {seen[ix]}; two dependents on one index are not "
+                                              "lowered")
+                seen[ix] = a.name
+                blk_of = {n: k for k, names in enumerate(cls.blocks) for n in names}
+                if blk_of[ix] != blk_of[a.name]:
+                    raise NotImplementedError(f"{who}: the index {ix} is declared in another block")
+                if [x.name for x in cls.attrs].index(ix) > [x.name for x in cls.attrs].index(a.name):
+                    raise NotImplementedError(f"{who}: the index {ix} must be declared before the choice")
+                if isinstance(ia.dist, (ChooseProportionally, ChooseUniformly)):
+                    # the product leaf stands at the dependent's place: nothing declared between the two may read the index
+                    names = [x.name for x in cls.attrs]
+                    for mid in cls.attrs[names.index(ix) + 1:names.index(a.name)]:
+                        reads = list(getattr(mid, "args", ())) if mid.kind == "julia" else [
+                            getattr(getattr(mid, "dist", None), f, None) for f in ("keyed_by", "index", "ref", "mean", "unit", "val", "key")]
+                        if ix in reads:
+                            raise NotImplementedError(f"{who}: {mid.name}, declared between the index {ix} and the choice, reads "
+                                                      "the index; declare it after the choice")
+                    na, nb = len(ia.dist.options), len(a.dist.options)
+                    if na * nb > 2 ** 31 - 1:
+                        raise NotImplementedError(f"{who}: the product with {ix} has {na} x {nb} options, more than 2^31 - 1")
+                    if (cname, ix) not in self.latent_dom:
+                        raise NotImplementedError(f"{who}: the options of the index {ix} are not strings")
+                    self.indexed[(cname, a.name)] = ("product", ix)
+                    self.product_index[(cname, ix)] = a.name
+                    continue
+                if (cname, ix) not in self.direct_obs.values():
+                    raise NotImplementedError(f"{who}: the index {ix} is neither a sibling ChooseProportionally / "
+                                              "ChooseUniformly choice nor observed directly")
+                # a row whose key is not observed would enumerate the options of every key while its key leaf is drawn on its
+                # own: the new row could hold a (key, value) pair never scored under theta[key] and count it for that key
+                for obsname, k in self.direct_obs.items():
+                    if k == (cname, ix) and obsname not in self._never_missing:
+                        raise NotImplementedError(f"{who}: the index {ix} is observed through {obsname}, which has missing "
+                                                  "values; the keyed form needs the key of every row")
+                self.indexed[(cname, a.name)] = ("keyed", ix)
+
+    def keyed_index(self, cname, aname):
+        """attribute whose (directly observed) value selects the options of choice aname: StringPrior / TimePrior atoms
+        `keyed_by` it, or the key of an IndexedProportionsParameter; None for an ordinary choice"""
+        d = self.model.classes[cname].attr(aname).dist if cname in self.model.classes else None
+        if (isinstance(d, StringPrior) and d.keyed_by) or isinstance(d, TimePrior):
+            return d.keyed_by
+        return self.indexed.get((cname, aname), (None, None))[1]
 
     def gauss_backward(self, rows, unit_idx, g=0):
         """unit.backward(x) of the g-th Gaussian observation of `rows` under the Transformation options unit_idx (one per
@@ -471,6 +590,7 @@ class LoweredModel:
         self.option_values = {}
         self.option_keycol = {}
         self.option_ncol = {}
+        self.option_cols = {}  # (class, attr) of a product leaf -> [2][options] value columns (index's value, own value)
         for (cname, aname), dom in self.latent_dom.items():
             self.option_id[(cname, aname)] = self._next_table
             self._next_table += 1
@@ -497,6 +617,22 @@ class LoweredModel:
                     # column 2: number of atoms of the option's key group (MaybeSwap's length(options))
                     nk = {kdom.get(k): len(atoms) for k, atoms in d.atoms.items()}
                     self.option_ncol[(cname, aname)] = np.array([nk[k] for k in keys], dtype=np.int32)
+                elif self.indexed.get((cname, aname), ("", ""))[0] == "product":
+                    # option a * |B| + b; two value columns: the index's value, the choice's value
+                    na, nb = len(self.latent_dom[(cname, self.indexed[(cname, aname)][1])]), len(d.options)
+                    self.option_cols[(cname, aname)] = np.stack([np.repeat(np.arange(na, dtype=np.int32), nb),
+                                                                 np.tile(np.arange(nb, dtype=np.int32), na)])
+                    self.option_values[(cname, aname)] = self.option_cols[(cname, aname)][1]
+                elif (cname, aname) in self.indexed:
+                    # options = for every key of the index's domain, in domain order: every option; column 1 = key index
+                    nk, nb = len(self.latent_dom[(cname, self.indexed[(cname, aname)][1])]), len(d.options)
+                    self.option_values[(cname, aname)] = np.tile(np.arange(nb, dtype=np.int32), nk)
+                    self.option_keycol[(cname, aname)] = np.repeat(np.arange(nk, dtype=np.int32), nb)
+
+    def option_column(self, cname, aname, cc=0):
+        """latent value per option of leaf (cname, aname) for column cc of a new row's colmap entry (a product leaf has two)"""
+        cols = self.option_cols.get((cname, aname))
+        return self.option_values[(cname, aname)] if cols is None else cols[cc]
 
     # -- plans --------------------------------------------------------------
     def _obs_terms_of_block(self, ocls, names):
@@ -710,23 +846,29 @@ class LoweredModel:
                 for c in self.layout[a.target]:
                     colsrc[a.name + "." + c.name] = (cid, self.colidx[a.target][c.name])
             elif a.kind == "choice":
-                sub = [t for t in terms if t["path"] == a.name]
+                if (cname, a.name) in self.product_index:
+                    continue  # enumerated jointly with its dependent: column 0 of that leaf
+                prod = self.indexed.get((cname, a.name), ("", ""))
+                prod = prod[1] if prod[0] == "product" else None
+                # (a product leaf: the terms of the index read value column 0, those of the choice column 1, declaration order)
+                sub = [t for t in terms if t["path"] == a.name or (prod is not None and t["path"] == prod)]
                 cid = len(blk["nodes"])
                 ltb = len(blk["terms"])
                 for t in sub:
-                    self._emit_term(blk, t, 0)
+                    self._emit_term(blk, t, 1 if prod is not None and t["path"] == a.name else 0)
                 n_leaf_terms = len(sub)
-                if (isinstance(a.dist, StringPrior) and a.dist.keyed_by) or isinstance(a.dist, TimePrior):
+                keyed_by = self.keyed_index(cname, a.name) if prod is None else None
+                if keyed_by:
                     # atoms belong to the key they were listed under: the option's key must equal the
                     # (directly observed) key of this row
-                    kt = [t for t in terms if t["path"] == a.dist.keyed_by and t.get("dens") == _lib.DENS_EQUAL]
+                    kt = [t for t in terms if t["path"] == keyed_by and t.get("dens") == _lib.DENS_EQUAL]
                     if len(kt) != 1:
                         raise NotImplementedError("keyed atoms need their key attribute observed directly")
                     self._emit_term(blk, kt[0], 1)
                     n_leaf_terms += 1
                 # (the per-observed-value cache has no slot for the missing observation a tabulated term scores)
                 cacheable = int(n_leaf_terms == 1 and len(sub) == 1 and sub[0]["ctx"] is None
-                                and sub[0].get("dens") != _lib.DENS_TABULATED)
+                                and sub[0].get("dens") != _lib.DENS_TABULATED and prod is None)
                 # the ProposalDummyValue of the proposal (string_prior.jl:16-26, time_prior.jl:15-19): which latent
                 # value is the placeholder and what random(dist) samples when the dummy is chosen
                 dval, dspec = 0, 0
@@ -744,6 +886,9 @@ class LoweredModel:
                 blk["node_info"].append(dict(kind="leaf", cls=cname, attr=a.name, path=prefix + a.name))
                 kids.append(cid)
                 colsrc[a.name] = (cid, 0)
+                if prod is not None:
+                    blk["node_info"][-1]["product"] = (prod, a.name)
+                    colsrc[prod], colsrc[a.name] = (cid, 0), (cid, 1)
         cb = len(blk["children"])
         blk["children"].extend(kids)
         cmb = len(blk["colmap"]) // 2
@@ -1017,7 +1162,8 @@ class LoweredModel:
                     plan["roots"].append(self._copy_subtree(blk, child, plan, -1, bi))
                     ci = blk["node_info"][child]
                     # attribute of T this root re-proposes
-                    plan["root_attr"].append(ci["attr"] if ci["kind"] == "leaf" else ci["path"].split(".")[-1])
+                    # (a product leaf writes two attributes: the pair)
+                    plan["root_attr"].append(ci.get("product", ci["attr"]) if ci["kind"] == "leaf" else ci["path"].split(".")[-1])
                 self.latent_plans[cname] = plan
                 next_block += 1
 

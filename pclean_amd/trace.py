@@ -28,6 +28,32 @@ class ProportionsState:
         self.value = rng.dirichlet(self.alpha + self.counts)
 
 
+class IndexedProportionsState:
+    """IndexedParameter of ProportionsParameters (distributions.jl:45-61, choose_proportionally.jl:36-74): one
+    Dirichlet-categorical vector per key of the index's domain, value / counts [key][option].  The vectors are drawn
+    eagerly, in domain order; the reference draws a key's vector when the key is first read (distributions.jl:50-55):
+    the same distribution, another order of the generator's stream."""
+
+    def __init__(self, n_keys, n_options, concentration, rng):
+        self.alpha = np.full(n_options, concentration, dtype=np.float64)
+        self.counts = np.zeros((n_keys, n_options), dtype=np.int64)
+        self.value = np.empty((n_keys, n_options), dtype=np.float64)
+        for k in range(n_keys):
+            self.value[k] = rng.dirichlet(self.alpha)
+
+    def resample(self, rng):  # resample_value! of every key's parameter (distributions.jl:57-61), in domain order
+        for k in range(len(self.value)):
+            self.value[k] = rng.dirichlet(self.alpha + self.counts[k])
+
+
+def prop_cells(t, prop, rows):
+    """cells of a conjugate choice's flattened counts that rows `rows` of table t fall in; prop = (column, key column
+    or -1, parameter state) as Trace._class_plan lists them: the option, or key * n_options + option"""
+    j, kj, state = prop
+    v = t.cols[j, rows]
+    return v if kj < 0 else t.cols[kj, rows].astype(np.int64) * state.counts.shape[1] + v
+
+
 class MeanTableState:
     """IndexedParameter of MeanParameters (add_noise.jl:15-82, distributions.jl:45-55), dense over
     the index tuple; values are initialised eagerly from the prior (the reference does it lazily)."""
@@ -200,6 +226,11 @@ class Trace:
             for a in m.classes[cname].attrs:
                 if a.kind == "choice" and isinstance(a.dist, ChooseProportionally):
                     prior = m.classes[cname].attr(a.dist.param).prior
+                    ix = getattr(lowered, "indexed", {}).get((cname, a.name))
+                    if ix is not None:  # one vector per key of the index's domain
+                        self.params[(cname, a.dist.param)] = IndexedProportionsState(
+                            len(lowered.latent_dom[(cname, ix[1])]), len(a.dist.options), prior.concentration, self.rng)
+                        continue
                     self.params[(cname, a.dist.param)] = ProportionsState(len(a.dist.options), prior.concentration,
                                                                          self.rng)
         self._class_plans, self._node_plans = {}, {}
@@ -299,12 +330,15 @@ class Trace:
 
     # -- own-choice sufficient statistics (update_sufficient_statistics!, dependency_tracking.jl:6-21)
     def _class_plan(self, cname):
-        """(direct reference-slot columns [(col, target class)], conjugate choices [(col, parameter state)])."""
+        """(direct reference-slot columns [(col, target class)], conjugate choices [(col, key column or -1, parameter
+        state)]: prop_cells)."""
         p = self._class_plans.get(cname)
         if p is None:
             lw = self.lw
             fks = [(j, c.target) for j, c in enumerate(lw.layout[cname]) if c.kind == "fk" and "." not in c.name]
-            props = [(lw.colidx[cname][a.name], self.params[(cname, a.dist.param)])
+            ixd = getattr(lw, "indexed", {})
+            props = [(lw.colidx[cname][a.name], lw.colidx[cname][ixd[(cname, a.name)][1]] if (cname, a.name) in ixd else -1,
+                      self.params[(cname, a.dist.param)])
                      for a in lw.model.classes[cname].attrs
                      if a.kind == "choice" and isinstance(a.dist, ChooseProportionally)]
             p = self._class_plans[cname] = (fks, props)
@@ -312,8 +346,8 @@ class Trace:
 
     def _own_choice_stats(self, cname, row, sign):
         t = self.tables[cname]
-        for j, state in self._class_plan(cname)[1]:
-            state.counts[t.cols[j, row]] += sign
+        for prop in self._class_plan(cname)[1]:
+            prop[2].counts.reshape(-1)[prop_cells(t, prop, row)] += sign
 
     def _dedup_key(self, cname, values):
         return (cname,) + tuple(int(v) for v in values)
@@ -375,8 +409,8 @@ class Trace:
         fks, props = self._class_plan(cname)
         for j, target in fks:
             np.add.at(self.tables[target].counts, values[:, j], 1)
-        for j, state in props:
-            np.add.at(state.counts, values[:, j], 1)
+        for prop in props:
+            np.add.at(prop[2].counts.reshape(-1), prop_cells(t, prop, ids), 1)
         self._bulk_ids = ids
         return ids
 
@@ -389,8 +423,8 @@ class Trace:
         t = self.tables[cname]
         assert np.all(t.counts[ids] == 0) and np.all(t.live[ids])
         fks, props = self._class_plan(cname)
-        for j, state in props:
-            np.subtract.at(state.counts, t.cols[j, ids], 1)
+        for prop in props:
+            np.subtract.at(prop[2].counts.reshape(-1), prop_cells(t, prop, ids), 1)
         t.live[ids] = False
         t.free.extend(ids.tolist())
         for j, target in fks:
@@ -477,7 +511,7 @@ class Trace:
                 cn, cc = blk["colmap"][2 * (cmb + j)], blk["colmap"][2 * (cmb + j) + 1]
                 if cn >= 0:
                     if nodes[cn][0] == 1:  # leaf: option index -> latent value
-                        leaves.append((j, cn, self.lw.option_values[(info[cn]["cls"], info[cn]["attr"])]))
+                        leaves.append((j, cn, self.lw.option_column(info[cn]["cls"], info[cn]["attr"], cc)))
                     else:
                         copies.append((j, cn, info[cn]["cls"], cc))
                 if c.kind == "fk" and "." not in c.name:
@@ -571,8 +605,18 @@ class Trace:
             live = np.nonzero(t.live[:t.n])[0]
             for a in lw.model.classes[cname].attrs:
                 if a.kind == "choice" and isinstance(a.dist, ChooseProportionally) and a.dist.param == pname:
-                    got = np.bincount(t.cols[lw.colidx[cname][a.name], live], minlength=len(p.counts))
-                    assert np.array_equal(got, p.counts), f"{cname}.{pname}: Dirichlet counts out of sync"
+                    assert np.array_equal(self.recount(cname, a.name), p.counts), f"{cname}.{pname}: Dirichlet counts out of sync"
+
+    def recount(self, cname, aname):
+        """Dirichlet counts of the ChooseProportionally choice cname.aname from the live rows of its table: [option], or
+        [key][option] under an IndexedProportionsParameter"""
+        lw = self.lw
+        t = self.tables[cname]
+        live = np.nonzero(t.live[:t.n])[0]
+        state = self.params[(cname, lw.model.classes[cname].attr(aname).dist.param)]
+        ix = getattr(lw, "indexed", {}).get((cname, aname))
+        prop = (lw.colidx[cname][aname], lw.colidx[cname][ix[1]] if ix is not None else -1, state)
+        return np.bincount(prop_cells(t, prop, live), minlength=state.counts.size).astype(np.int64).reshape(state.counts.shape)
 
     def commit_batch(self, begin, count, choice, new_rows, dedup=False, sweep_idx=0):
         """Commit a batch of observed rows [begin, begin+count) (initialize_trace: rows had no
