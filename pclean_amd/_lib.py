@@ -299,6 +299,15 @@ class HipContext:
     def force_generic(self, on):
         check(self.h, self.lib.pclean_debug_force_generic(self.h, C.c_int32(int(on))), "pclean_debug_force_generic")
 
+    ENUM_LAUNCH_SLOTS = tuple(f"{k}_{bt}{ev}" for k in ("lds", "big") for bt in (256, 1024) for ev in ("", "_ev")) + (
+        "scores", "scores_ev", "product_256_lds", "product_256", "product_1024_lds", "product_1024")
+
+    def enum_launches(self, reset=False):
+        """kernel launches of the generic enumeration per instantiation since the last reset, by ENUM_LAUNCH_SLOTS name"""
+        out = np.zeros(len(self.ENUM_LAUNCH_SLOTS), dtype=np.int64)
+        check(self.h, self.lib.pclean_debug_enum_launches(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_enum_launches")
+        return dict(zip(self.ENUM_LAUNCH_SLOTS, out.tolist()))
+
     def set_table(self, table_id, cols, counts, strength, discount, n_cols=None):
         """cols None (with n_cols given) keeps the columns uploaded before and refreshes the counts only."""
         counts = np.ascontiguousarray(counts, dtype=np.int64)

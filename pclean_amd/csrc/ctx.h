@@ -280,6 +280,10 @@ struct pclean_ctx {
   bool prior_mode = false;     // sweep.hip / latent.hip: the running sweep proposes from the priors (use_dd_proposals = false)
   bool force_generic = false;  // debug: never take the compact-table root kernel
   bool no_item_agg = false;    // debug: aggregate evidence with the global sort + run-length encoding only
+  // debug (pclean_debug_enum_launches): kernel launches of pclean_launch_enum per instantiation, counted on the host.
+  // [0..8) enum_node_kernel / enum_node_big_kernel: 4 * big + 2 * (BT == 1024) + EV; [8..10) enum_scores_kernel<EV>;
+  // [10..14) enum_product_kernel: 10 + 2 * (BT == 1024) + !LDSP
+  int64_t enum_launches[PCLEAN_ENUM_LAUNCH_SLOTS] = {};
   void* sweep_state = nullptr;  // owned by sweep.hip
   void* rccl_comm = nullptr;    // ncclComm_t of pclean_comm_init (comm.hip)
   void* recon_state = nullptr;  // owned by recon.hip

@@ -1677,18 +1677,23 @@ static int pclean_launch_product(pclean_ctx* ctx, const NodeDev& nd, const Items
   const int kMaxBlocks = 4 * 1024 * 1024;
   for (int base = 0; base < it.n; base += kMaxBlocks) {
     const dim3 grid(std::min(kMaxBlocks, it.n - base));
-    if (wide && pr.lds_prefix)
+    if (wide && pr.lds_prefix) {
+      ++ctx->enum_launches[12];
       hipLaunchKernelGGL((enum_product_kernel<1024, true>), grid, dim3(1024), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
                          base, lse_out, scores_out, draws_out);
-    else if (wide)
+    } else if (wide) {
+      ++ctx->enum_launches[13];
       hipLaunchKernelGGL((enum_product_kernel<1024, false>), grid, dim3(1024), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
                          base, lse_out, scores_out, draws_out);
-    else if (pr.lds_prefix)
+    } else if (pr.lds_prefix) {
+      ++ctx->enum_launches[10];
       hipLaunchKernelGGL((enum_product_kernel<256, true>), grid, dim3(256), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
                          base, lse_out, scores_out, draws_out);
-    else
+    } else {
+      ++ctx->enum_launches[11];
       hipLaunchKernelGGL((enum_product_kernel<256, false>), grid, dim3(256), lds, ctx->stream, nd, dn, it, pr, seed, sweep, site, n_draws,
                          base, lse_out, scores_out, draws_out);
+    }
   }
   HIPCHK(ctx, hipGetLastError());
   return PCLEAN_OK;
@@ -1745,28 +1750,37 @@ int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, c
       int slot_cap = 0;
       if (scores_tmp && !it.grp_off && !scores_out) {  // ... and the scores first, one candidate per thread (enum_scores_kernel)
         slot_cap = pclean_enum_split_slots(it, nc);
-        if (it.ev_lo)
+        if (it.ev_lo) {
+          ++ctx->enum_launches[9];
           hipLaunchKernelGGL((enum_scores_kernel<true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
-        else
+        } else {
+          ++ctx->enum_launches[8];
           hipLaunchKernelGGL((enum_scores_kernel<false>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
+        }
         scores_in = scores_tmp;
       }
-      if (it.ev_lo)
+      if (it.ev_lo) {
+        ++ctx->enum_launches[7];
         hipLaunchKernelGGL((enum_node_big_kernel<1024, true>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                          n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
-      else
+      } else {
+        ++ctx->enum_launches[6];
         hipLaunchKernelGGL((enum_node_big_kernel<1024, false>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                          n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
+      }
     } else {
       for (int base = 0; base < it.n; base += kMaxBlocks)
-        if (it.ev_lo)
+        if (it.ev_lo) {
+          ++ctx->enum_launches[5];
           hipLaunchKernelGGL((enum_node_big_kernel<256, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
                            dn, it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
-        else
+        } else {
+          ++ctx->enum_launches[4];
           hipLaunchKernelGGL((enum_node_big_kernel<256, false>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
                            dn, it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
+        }
     }
   } else {
     static bool attr_set = false;
@@ -1783,28 +1797,37 @@ int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, c
       int slot_cap = 0;
       if (scores_tmp && !it.grp_off && !scores_out) {
         slot_cap = pclean_enum_split_slots(it, nc);
-        if (it.ev_lo)
+        if (it.ev_lo) {
+          ++ctx->enum_launches[9];
           hipLaunchKernelGGL((enum_scores_kernel<true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
-        else
+        } else {
+          ++ctx->enum_launches[8];
           hipLaunchKernelGGL((enum_scores_kernel<false>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
+        }
         scores_in = scores_tmp;
       }
-      if (it.ev_lo)
+      if (it.ev_lo) {
+        ++ctx->enum_launches[3];
         hipLaunchKernelGGL((enum_node_kernel<1024, true>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                            n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
-      else
+      } else {
+        ++ctx->enum_launches[2];
         hipLaunchKernelGGL((enum_node_kernel<1024, false>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                            n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
+      }
     } else {
       for (int base = 0; base < it.n; base += kMaxBlocks)
-        if (it.ev_lo)
+        if (it.ev_lo) {
+          ++ctx->enum_launches[1];
           hipLaunchKernelGGL((enum_node_kernel<256, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
                              it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
-        else
+        } else {
+          ++ctx->enum_launches[0];
           hipLaunchKernelGGL((enum_node_kernel<256, false>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
                              it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
+        }
     }
   }
   HIPCHK(ctx, hipGetLastError());

@@ -1306,6 +1306,13 @@ extern "C" int pclean_debug_force_generic(pclean_ctx* ctx, int32_t on) {
   return PCLEAN_OK;
 }
 
+extern "C" int pclean_debug_enum_launches(pclean_ctx* ctx, int64_t* out, int32_t reset) {
+  if (!ctx) return PCLEAN_ERR_ARG;
+  if (out) memcpy(out, ctx->enum_launches, sizeof(ctx->enum_launches));
+  if (reset) memset(ctx->enum_launches, 0, sizeof(ctx->enum_launches));
+  return PCLEAN_OK;
+}
+
 extern "C" int pclean_set_row_offset(pclean_ctx* ctx, int64_t row_offset) {
   if (!ctx || row_offset < 0) return pclean_fail(ctx, PCLEAN_ERR_ARG, "bad row offset");
   st(ctx)->row_offset = row_offset;
