@@ -91,7 +91,7 @@ class ReconCol(C.Structure):
                 ("map_off", C.c_int32), ("map_len", C.c_int32)]
 
 
-RECON_PATH, RECON_FN = 0, 1
+RECON_PATH, RECON_FN, RECON_OWN, RECON_NUM = 0, 1, 2, 3  # PCLEAN_RECON_*
 RING_MAX_KEEP = 32  # PCLEAN_RING_MAX_KEEP
 
 TERM_DTYPE = np.dtype([("obs_col", "<i4"), ("cand_col", "<i4"), ("pair_table", "<i4"), ("dens_kind", "<i4"),
@@ -815,6 +815,34 @@ class HipContext:
         """int64 [n_cols][5] counters of the last recon_run (ring None) or of the ring's last consensus"""
         out = np.zeros((n_cols, 5), dtype=np.int64)
         check(self.h, self.lib.pclean_recon_counts(self.h, ring, _p(out, C.c_int64)), "pclean_recon_counts")
+        return out
+
+    def recon_set_locals(self, block, locals_):
+        """own choices of every observed row for `block`, int32 [n_rows][2]: what the plan's OWN / NUM columns read"""
+        loc = np.ascontiguousarray(locals_, dtype=np.int32)
+        assert loc.ndim == 2 and loc.shape[1] == 2
+        check(self.h, self.lib.pclean_recon_set_locals(self.h, C.c_int32(int(block)), C.c_int32(loc.shape[0]), _p(loc, C.c_int32)),
+              "pclean_recon_set_locals")
+
+    def recon_values(self, n_numeric, n_rows, ring=None, fetch=True):
+        """float64 [n_numeric][n_rows]: the plan's NUM columns as numbers, from the last recon_run (ring None) or from the
+        ring's last consensus"""
+        out = np.empty((n_numeric, n_rows), dtype=np.float64) if fetch else None
+        check(self.h, self.lib.pclean_recon_values(self.h, ring, _p(out, C.c_double)), "pclean_recon_values")
+        return out
+
+    def recon_set_truth_num(self, dirty, clean):
+        d = np.ascontiguousarray(dirty, dtype=np.float64)
+        c = np.ascontiguousarray(clean, dtype=np.float64)
+        assert d.shape == c.shape and d.ndim == 2
+        check(self.h, self.lib.pclean_recon_set_truth_num(self.h, _p(d, C.c_double), _p(c, C.c_double)),
+              "pclean_recon_set_truth_num")
+
+    def recon_counts_up_to(self, n_cols, n_up_to, ring=None):
+        """int64 [n_cols][6] = the five counters over the first n_up_to rows + `missing` (evaluate_accuracy_up_to)"""
+        out = np.zeros((n_cols, 6), dtype=np.int64)
+        check(self.h, self.lib.pclean_recon_counts_up_to(self.h, ring, C.c_int32(int(n_up_to)), _p(out, C.c_int64)),
+              "pclean_recon_counts_up_to")
         return out
 
     def ring_create(self, keep):

@@ -1,4 +1,4 @@
-"""evaluate_accuracy (src/analysis.jl:36-88) over the flat trace, vectorised.
+"""evaluate_accuracy and evaluate_accuracy_up_to (src/analysis.jl:36-143) over the flat trace, vectorised.
 
 Counts follow the reference exactly: `errors` over every column common to the
 dirty and clean tables (queried or not), `changed` / `cleaned` over queried
@@ -84,8 +84,20 @@ def accuracy_counts(lowered, trace, dirty, clean, skip=()):
 def counts_given(lowered, ours, n, dirty, clean, skip=()):
     """The five counters for a cleaned table given as `ours` (what reconstructed_pool_ids returns: pool ids per string
     column, ("numeric", values) per numeric one) over the first n rows; columns of `skip` are left out altogether."""
+    return _counts_up_to(lowered, ours, n, dirty, clean, n, skip)[:5]
+
+
+def counts_given_up_to(lowered, ours, n, dirty, clean, n_up_to, skip=()):
+    """counts_given when only the first n_up_to of the n rows have been cleaned (evaluate_accuracy_up_to,
+    analysis.jl:90-143): six counters [errors, changed, cleaned, imputed, imputed_ok, missing].  Rows >= n_up_to add to
+    `errors` and `missing` only; `missing` = every missing dirty cell of a queried column whose clean cell is present."""
+    return _counts_up_to(lowered, ours, n, dirty, clean, n_up_to, skip)
+
+
+def _counts_up_to(lowered, ours, n, dirty, clean, n_up_to, skip=()):
     lw = lowered
-    errors = changed = cleaned = imputed = imputed_ok = 0
+    errors = changed = cleaned = imputed = imputed_ok = missing = 0
+    done = np.arange(n) < n_up_to  # rows the cleaned table holds (`ours !== nothing`)
     for col in clean:
         if col not in dirty or col in skip:
             continue
@@ -102,22 +114,24 @@ def counts_given(lowered, ours, n, dirty, clean, skip=()):
             cn = np.array([np.nan if v is None else float(v) for v in c])
             errors -= int(np.sum(ne & ~dmiss))
             errors += int(np.sum((dn != cn) & ~dmiss))
-            ch = (~dmiss) & (o != dn)
+            ch = done & (~dmiss) & (o != dn)
             changed += int(np.sum(ch))
             cleaned += int(np.sum(ch & (o == cn)))
-            imputed += int(np.sum(dmiss & ~np.isnan(cn)))  # analysis.jl:52-60 counts numeric imputations too
-            imputed_ok += int(np.sum(dmiss & (o == cn)))
+            imputed += int(np.sum(done & dmiss & ~np.isnan(cn)))  # analysis.jl:52-60 counts numeric imputations too
+            imputed_ok += int(np.sum(done & dmiss & (o == cn)))
+            missing += int(np.sum(dmiss & ~np.isnan(cn)))
             continue
         d_id = _pool_ids(lw.pool.index, d, -3, -4)
         c_id = _pool_ids(lw.pool.index, c, -5, -6)
         o = ours[col]
         cmiss = c_id == -6
-        imputed += int(np.sum(dmiss & ~cmiss))
-        imputed_ok += int(np.sum(dmiss & ~cmiss & (o == c_id)))
-        ch = (~dmiss) & (o != d_id)
+        imputed += int(np.sum(done & dmiss & ~cmiss))
+        imputed_ok += int(np.sum(done & dmiss & ~cmiss & (o == c_id)))
+        missing += int(np.sum(dmiss & ~cmiss))
+        ch = done & (~dmiss) & (o != d_id)
         changed += int(np.sum(ch))
         cleaned += int(np.sum(ch & (o == c_id)))
-    return np.array([errors, changed, cleaned, imputed, imputed_ok], dtype=np.int64)
+    return np.array([errors, changed, cleaned, imputed, imputed_ok, missing], dtype=np.int64)
 
 
 def f1_from_counts(cnt):
@@ -134,6 +148,39 @@ def evaluate_accuracy(lowered, trace, dirty, clean):
     return f1_from_counts(accuracy_counts(lowered, trace, dirty, clean))
 
 
+def f1_from_counts_up_to(cnt):
+    """The fields evaluate_accuracy_up_to returns (analysis.jl:137-142) from its six counters: recall is taken over
+    errors + missing — every missing cell, cleaned yet or not — while `imputed` counts the cleaned rows' only."""
+    errors, changed, cleaned, imputed, imputed_ok, missing = [float(x) for x in cnt]
+    num = cleaned + imputed_ok
+    precision = num / (changed + imputed) if (changed + imputed) > 0 else float("nan")
+    recall = num / (errors + missing) if (errors + missing) > 0 else float("nan")
+    f1 = 2.0 / (1 / precision + 1 / recall) if num > 0 else 0.0
+    return dict(f1=f1, errors=int(errors), changed=int(changed), cleaned=int(cleaned), precision=precision,
+                recall=recall, imputed=int(imputed), correctly_imputed=int(imputed_ok))
+
+
+def accuracy_counts_up_to(lowered, trace, dirty, clean, n, skip=()):
+    """The six counters of evaluate_accuracy_up_to for the rows held by `trace` when only the first n have been cleaned
+    (n beyond the trace's rows: all of them)."""
+    lw = lowered
+    ours = reconstructed_pool_ids(lw, trace, columns=None if not skip else
+                                  [c for c in lw.query.cleanmap if c not in skip])
+    cur = getattr(trace, "_cur", None)  # (the shape only, as accuracy_counts)
+    rows = (trace.cur if cur is None else cur).shape[1]
+    return counts_given_up_to(lw, ours, rows, dirty, clean, n, skip)
+
+
+def evaluate_accuracy_up_to(lowered, trace, dirty, clean, n):
+    """evaluate_accuracy_up_to(dirty, clean, table, query, N) (analysis.jl:90-143): the accuracy when only the first n rows
+    have been cleaned — the "F1 against rows processed" curve of the initialisation."""
+    return f1_from_counts_up_to(accuracy_counts_up_to(lowered, trace, dirty, clean, n))
+
+
+def _render_numbers(values):
+    return [None if np.isnan(v) else (int(v) if float(v).is_integer() else float(v)) for v in values]
+
+
 def reconstructed_table(lowered, trace, dirty):
     """The cleaned table: every queried column replaced by what PClean believes, the others copied
     (the DataFrame save_results writes, analysis.jl:21-30).  Values come back as strings / numbers."""
@@ -145,7 +192,7 @@ def reconstructed_table(lowered, trace, dirty):
         if col not in ours:
             out[col] = list(vals[:n])
         elif isinstance(ours[col], tuple):
-            out[col] = [None if np.isnan(v) else (int(v) if float(v).is_integer() else float(v)) for v in ours[col][1]]
+            out[col] = _render_numbers(ours[col][1])
         else:
             out[col] = [lw.pool.strings[i] if i >= 0 else None for i in ours[col]]
     return out
@@ -154,17 +201,19 @@ def reconstructed_table(lowered, trace, dirty):
 def consensus_table(lowered, tally, dirty):
     """The cleaned table from the per-cell consensus of `tally` (tally.CellTally) instead of the last sample: every queried
     string column holds its most frequent value over the kept samples and is followed by `<column>__support`, the number
-    of kept samples that agree with it (of tally.n_kept).  Numeric queried columns are not tallied: like the columns that
-    are not queried they are copied from `dirty`."""
+    of kept samples that agree with it (of tally.n_kept).  A tally made with own=True serves the numeric queried columns
+    too (the number under the most frequent Transformation option, rendered as reconstructed_table renders it, and its
+    support); without it they are not tallied: like the columns that are not queried they are copied from `dirty`."""
     ids, support = tally.consensus()
-    n = len(next(iter(ids.values()))) if ids else 0
+    n = len(support[next(iter(support))]) if ids else 0
     strings = lowered.pool.strings
     out = {}
     for col, vals in dirty.items():
         if col not in ids:
             out[col] = list(vals[:n]) if ids else list(vals)
             continue
-        out[col] = [strings[i] if i >= 0 else None for i in ids[col]]
+        out[col] = (_render_numbers(ids[col][1]) if isinstance(ids[col], tuple)
+                    else [strings[i] if i >= 0 else None for i in ids[col]])
         out[col + "__support"] = [int(v) for v in support[col]]
     return out
 

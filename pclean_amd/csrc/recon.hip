@@ -1,7 +1,10 @@
 // The cleaned table where the sweeps leave their state: reconstruction of the queried columns from the device-resident
 // referents and latent tables, the five counters of evaluate_accuracy (analysis.jl:36-88), a ring of the last
 // reconstructions and its per-cell consensus (most frequent value + support).  Everything here streams [columns][rows]
-// int32 arrays; nothing touches the sweep, commit or enumeration state.
+// int32 arrays; nothing touches the sweep, commit or enumeration state.  Own enumerated choices of the observed class and
+// numeric columns reported through a Gaussian term are two further column kinds (PCLEAN_RECON_OWN / _NUM): they read a copy
+// of the rows' own choices that this state owns, a numeric column's cells are Transformation option indices and its fp64
+// values are materialised by a second small kernel; the counters take a row bound (evaluate_accuracy_up_to).
 #include <algorithm>
 
 #include "ctx.h"
@@ -16,13 +19,21 @@ struct ReconState {
   bool out_valid = false;
   DevBuf<int32_t> dirty, clean;  // [n_cols][n_rows] pool ids of the dirty / clean table (pclean_recon_set_truth)
   bool truth_valid = false;
-  DevBuf<unsigned long long> counts;  // [n_cols][5]
+  DevBuf<unsigned long long> counts;  // [n_cols][6]
+  // own enumerated choices of the observed rows per block, [n_rows][2] (pclean_recon_set_locals): what OWN / NUM columns read
+  DevBuf<int32_t> locals[PCLEAN_MAX_BLOCKS];
+  int32_t locals_rows[PCLEAN_MAX_BLOCKS] = {};
+  std::vector<int32_t> num_cols;   // plan positions of the NUM columns
+  DevBuf<double> vals;             // [n_numeric][n_rows]: the last pclean_recon_values
+  DevBuf<double> dirty_num, clean_num;  // [n_numeric][n_rows] (pclean_recon_set_truth_num)
+  bool truth_num_valid = false;
 };
 
 struct pclean_ring {
   int device = 0;
   int32_t keep = 0, n_cols = 0, n_rows = 0;
   int64_t adds = 0;
+  std::vector<char> is_num;       // per column: its cells are option indices of a NUM column (pclean_ring_remap skips them)
   DevBuf<int32_t> data;           // [keep][n_cols][n_rows]
   DevBuf<int32_t> mode, support;  // [n_cols][n_rows]: the last pclean_ring_consensus
   bool consensus_valid = false;
@@ -41,6 +52,10 @@ void pclean_recon_state_free(pclean_ctx* ctx) {
   r->dirty.release();
   r->clean.release();
   r->counts.release();
+  for (auto& l : r->locals) l.release();
+  r->vals.release();
+  r->dirty_num.release();
+  r->clean_num.release();
   delete r;
   ctx->recon_state = nullptr;
 }
@@ -58,6 +73,8 @@ struct ReconColDev {
   const int32_t* fn;     // [fn_na][fn_nb]
   const int32_t* map;    // value id -> pool id
   int32_t rows_a, rows_b, fn_na, fn_nb, map_len, kind;
+  // OWN / NUM: cur_a = the block's own choices [n_rows][2] (null: a term without a Transformation, option 0),
+  // rows_a = which of the two
 };
 struct ReconArgs {
   int32_t n_cols;
@@ -73,6 +90,11 @@ __global__ __launch_bounds__(256) void recon_kernel(int n_rows, ReconArgs a, int
   int k = -1;
   for (int c = 0; c < a.n_cols; ++c) {
     const ReconColDev& d = a.c[c];
+    if (d.kind == PCLEAN_RECON_OWN || d.kind == PCLEAN_RECON_NUM) {
+      const int32_t l = d.cur_a ? max(d.cur_a[(size_t)row * 2 + d.rows_a], 0) : 0;
+      out[(size_t)c * n_rows + row] = d.kind == PCLEAN_RECON_NUM ? l : (l < d.map_len ? d.map[l] : -1);
+      continue;
+    }
     if (d.cur_a != held) {
       k = d.cur_a[row];
       held = d.cur_a;
@@ -92,12 +114,64 @@ __global__ __launch_bounds__(256) void recon_kernel(int n_rows, ReconArgs a, int
   }
 }
 
+// The Gaussian term a NUM column names (block, node = q.table, position on the node = q.col) as it is loaded now; null:
+// none, or one whose Transformation is not picked by an own choice of the block.
+static const pclean_gauss* recon_gauss_of(const pclean_ctx* ctx, const pclean_recon_col& q) {
+  if (q.block < 0 || q.block >= PCLEAN_MAX_BLOCKS || q.table < 0 || q.col < 0) return nullptr;
+  const Block& b = ctx->block[q.block];
+  if (!b.valid || (size_t)q.table >= b.node_gauss.size() || b.node_gauss[q.table] < 0) return nullptr;
+  int32_t gi = b.node_gauss[q.table];
+  if (q.col > 0) {
+    if ((size_t)q.table >= b.node_gauss_more.size() || (size_t)(q.col - 1) >= b.node_gauss_more[q.table].size()) return nullptr;
+    gi = b.node_gauss_more[q.table][q.col - 1];
+  }
+  if (gi < 0 || (size_t)gi >= b.gauss.size()) return nullptr;
+  const pclean_gauss* g = &b.gauss[gi];
+  if (g->transform_src_kind == PCLEAN_GSRC_LOCAL ? (g->transform_src < 0 || g->transform_src > 1) : g->transform_src_kind != -1)
+    return nullptr;
+  return g;
+}
+
+// Values of one NUM column: the option index of every row -> rint(backward_u(x)).  One multiply, then round-half-even
+// (no addition follows the product: nothing to contract), as np.round(x * t_scale[u]) on the host.
+struct NumColDev {
+  const double* x;      // the term's numeric column
+  const double* tx[4];  // per option: the derived column holding backward_u(x) (non-linear), null: x * scale[u]
+  double scale[4];
+  int32_t n_opt;
+};
+__global__ __launch_bounds__(256) void recon_values_kernel(int n_rows, NumColDev d, const int32_t* __restrict__ idx,
+                                                           double* __restrict__ out) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  const int32_t u = idx[row];
+  double v = __longlong_as_double(0x7ff8000000000000LL);
+  if (u >= 0 && u < d.n_opt) {
+    const double* t = u == 0 ? d.tx[0] : u == 1 ? d.tx[1] : u == 2 ? d.tx[2] : d.tx[3];
+    const double s = u == 0 ? d.scale[0] : u == 1 ? d.scale[1] : u == 2 ? d.scale[2] : d.scale[3];
+    v = rint(t ? t[row] : d.x[row] * s);
+  }
+  out[row] = v;
+}
+
 extern "C" int pclean_recon_set_plan(pclean_ctx* ctx, int32_t n_cols, const pclean_recon_col* cols, int32_t n_map,
                                      const int32_t* id_map) {
   if (!ctx || n_cols < 0 || (n_cols > 0 && !cols) || n_map < 0 || (n_map > 0 && !id_map))
     return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_set_plan: bad arguments");
   for (int c = 0; c < n_cols; ++c) {
     const pclean_recon_col& q = cols[c];
+    if (q.kind == PCLEAN_RECON_OWN) {
+      if (q.block < 0 || q.block >= PCLEAN_MAX_BLOCKS || (q.col != 0 && q.col != 1) || q.map_off < 0 || q.map_len < 0 ||
+          (int64_t)q.map_off + q.map_len > n_map)
+        return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_set_plan: bad column %d (an own choice is 0 or 1)", c);
+      continue;
+    }
+    if (q.kind == PCLEAN_RECON_NUM) {
+      if (!recon_gauss_of(ctx, q))
+        return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_set_plan: bad column %d (block %d, node %d holds no Gaussian term %d "
+                                                "whose Transformation an own choice picks)", c, q.block, q.table, q.col);
+      continue;
+    }
     const bool fn = q.kind == PCLEAN_RECON_FN;
     if ((q.kind != PCLEAN_RECON_PATH && !fn) || q.block < 0 || q.block >= PCLEAN_MAX_BLOCKS || q.table < 0 ||
         q.table >= PCLEAN_MAX_TABLES || q.col < 0 || q.map_off < 0 || q.map_len < 0 || (int64_t)q.map_off + q.map_len > n_map ||
@@ -108,8 +182,11 @@ extern "C" int pclean_recon_set_plan(pclean_ctx* ctx, int32_t n_cols, const pcle
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ReconState* r = rst(ctx);
-  r->out_valid = r->truth_valid = false;
+  r->out_valid = r->truth_valid = r->truth_num_valid = false;
   r->cols.assign(cols, cols + n_cols);
+  r->num_cols.clear();
+  for (int c = 0; c < n_cols; ++c)
+    if (cols[c].kind == PCLEAN_RECON_NUM) r->num_cols.push_back(c);
   if (r->id_map.alloc((size_t)std::max(n_map, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
   if (n_map) HIPCHK(ctx, hipMemcpy(r->id_map.p, id_map, (size_t)n_map * 4, hipMemcpyHostToDevice));
   r->n_map = n_map;
@@ -128,6 +205,27 @@ static int recon_launch(pclean_ctx* ctx, ReconState* r, int32_t* out) {
     for (int c = 0; c < a.n_cols; ++c) {
       const pclean_recon_col& q = r->cols[c0 + c];
       ReconColDev& d = a.c[c];
+      if (q.kind == PCLEAN_RECON_OWN || q.kind == PCLEAN_RECON_NUM) {
+        int32_t li = q.col;
+        if (q.kind == PCLEAN_RECON_NUM) {
+          const pclean_gauss* g = recon_gauss_of(ctx, q);
+          if (!g) return pclean_fail(ctx, PCLEAN_ERR_STATE, "reconstruction: column %d names a Gaussian term that is not loaded", c0 + c);
+          li = g->transform_src_kind == PCLEAN_GSRC_LOCAL ? g->transform_src : -1;
+        }
+        d.kind = q.kind;
+        d.cur_a = nullptr;
+        d.rows_a = 0;
+        if (li >= 0) {
+          if (!r->locals[q.block].p || r->locals_rows[q.block] != ctx->n_rows)
+            return pclean_fail(ctx, PCLEAN_ERR_STATE, "reconstruction: column %d needs the own choices of block %d "
+                                                      "(pclean_recon_set_locals)", c0 + c, q.block);
+          d.cur_a = r->locals[q.block].p;
+          d.rows_a = li;
+        }
+        d.map = q.kind == PCLEAN_RECON_OWN ? r->id_map.p + q.map_off : nullptr;
+        d.map_len = q.kind == PCLEAN_RECON_OWN ? q.map_len : 0;
+        continue;
+      }
       const CandTable& ta = ctx->cand[q.table];
       if (q.block >= ctx->dev_cur_blocks || !ta.valid || ta.is_options || q.col >= ta.n_cols || !ta.cols.p)
         return pclean_fail(ctx, PCLEAN_ERR_STATE, "reconstruction: column %d names a block / table that is not loaded", c0 + c);
@@ -172,37 +270,143 @@ extern "C" int pclean_recon_run(pclean_ctx* ctx, int32_t* out) {
   return PCLEAN_OK;
 }
 
-// ---- accuracy counters ------------------------------------------------------------------------------------------------
-// blockIdx.y = column; per thread five integer sums over its rows, per workgroup one 64-bit atomic per counter
-__global__ __launch_bounds__(256) void recon_counts_kernel(int n_rows, const int32_t* __restrict__ ours,
-                                                           const int32_t* __restrict__ dirty, const int32_t* __restrict__ clean,
-                                                           unsigned long long* __restrict__ counts) {
-  const size_t base = (size_t)blockIdx.y * n_rows;
-  unsigned int s[5] = {0, 0, 0, 0, 0};
-  for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += gridDim.x * blockDim.x) {
-    const int32_t o = ours[base + row], d = dirty[base + row], c = clean[base + row];
-    const bool dmiss = d == -4, cmiss = c == -6;
-    const bool ch = !dmiss && o != d;
-    s[0] += (!dmiss && d != c);
-    s[1] += ch;
-    s[2] += (ch && o == c);
-    s[3] += (dmiss && !cmiss);
-    s[4] += (dmiss && !cmiss && o == c);
+extern "C" int pclean_recon_set_locals(pclean_ctx* ctx, int32_t block, int32_t n_rows, const int32_t* locals) {
+  if (!ctx || block < 0 || block >= PCLEAN_MAX_BLOCKS || !locals || n_rows <= 0)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_set_locals: bad arguments");
+  if (n_rows != ctx->n_rows)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_set_locals: %d rows, the context holds %d", n_rows, ctx->n_rows);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  ReconState* r = rst(ctx);
+  r->locals_rows[block] = 0;
+  r->out_valid = false;
+  if (r->locals[block].alloc((size_t)n_rows * 2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemcpy(r->locals[block].p, locals, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+  r->locals_rows[block] = n_rows;
+  return PCLEAN_OK;
+}
+
+// option indices of the source (the last reconstruction or a ring's consensus), or null with the error set
+static const int32_t* recon_source(pclean_ctx* ctx, ReconState* r, const pclean_ring* ring, const char* who) {
+  if (ring) {
+    if (!ring->consensus_valid || ring->n_cols != (int32_t)r->cols.size() || ring->n_rows != ctx->n_rows || ring->device != ctx->device) {
+      pclean_fail(ctx, PCLEAN_ERR_STATE, "%s: the ring holds no consensus of this plan's shape", who);
+      return nullptr;
+    }
+    return ring->mode.p;
   }
-  __shared__ unsigned int part[4][5];
+  if (!r->out_valid) {
+    pclean_fail(ctx, PCLEAN_ERR_STATE, "%s: no reconstruction (pclean_recon_run)", who);
+    return nullptr;
+  }
+  return r->out.p;
+}
+
+// the NUM columns' values of `ours` [n_cols][n_rows] into r->vals [n_numeric][n_rows] (queued on the stream)
+static int recon_values_launch(pclean_ctx* ctx, ReconState* r, const int32_t* ours) {
+  const size_t n = (size_t)ctx->n_rows;
+  if (r->vals.alloc(std::max<size_t>(r->num_cols.size() * n, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  for (size_t k = 0; k < r->num_cols.size(); ++k) {
+    const int c = r->num_cols[k];
+    const pclean_gauss* g = recon_gauss_of(ctx, r->cols[c]);
+    if (!g) return pclean_fail(ctx, PCLEAN_ERR_STATE, "reconstruction: column %d names a Gaussian term that is not loaded", c);
+    if (!ctx->xnum.p || g->x_col < 0 || g->x_col >= ctx->n_xcols || ctx->xnum.n < (size_t)ctx->n_xcols * n)
+      return pclean_fail(ctx, PCLEAN_ERR_STATE, "reconstruction: column %d reads a numeric column that is not loaded", c);
+    NumColDev d{};
+    d.x = ctx->xnum.p + (size_t)g->x_col * n;
+    d.n_opt = g->transform_src_kind == PCLEAN_GSRC_LOCAL ? std::min(std::max(g->local_n[g->transform_src], 0), 4) : 1;
+    for (int u = 0; u < 4; ++u) {
+      d.scale[u] = g->t_scale[u];
+      d.tx[u] = nullptr;
+      if (g->t_x_col[u] >= 0) {
+        if (g->t_x_col[u] >= ctx->n_xcols)
+          return pclean_fail(ctx, PCLEAN_ERR_STATE, "reconstruction: column %d reads a numeric column that is not loaded", c);
+        d.tx[u] = ctx->xnum.p + (size_t)g->t_x_col[u] * n;
+      }
+    }
+    hipLaunchKernelGGL(recon_values_kernel, recon_grid(n), dim3(256), 0, ctx->stream, ctx->n_rows, d, ours + (size_t)c * n,
+                       r->vals.p + k * n);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_recon_values(pclean_ctx* ctx, const pclean_ring* ring, double* out) {
+  if (!ctx) return PCLEAN_ERR_ARG;
+  ReconState* r = rst(ctx);
+  if (r->num_cols.empty() || ctx->n_rows <= 0)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_recon_values: the plan has no numeric column");
+  const int32_t* ours = recon_source(ctx, r, ring, "pclean_recon_values");
+  if (!ours) return PCLEAN_ERR_STATE;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int rc = recon_values_launch(ctx, r, ours);
+  if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (out) HIPCHK(ctx, hipMemcpy(out, r->vals.p, r->num_cols.size() * (size_t)ctx->n_rows * 8, hipMemcpyDeviceToHost));
+  return PCLEAN_OK;
+}
+
+// ---- accuracy counters ------------------------------------------------------------------------------------------------
+// per thread six integer sums over its rows, per workgroup one 64-bit atomic per counter: {errors, changed, cleaned,
+// imputed, correctly imputed, missing}.  Rows >= n_up_to have not been cleaned (analysis.jl:99, `ours === nothing`): they
+// add to errors and missing only.
+__device__ __forceinline__ void recon_counts_reduce(const unsigned int (&s)[6], unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int part[4][6];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int q = 0; q < 5; ++q) {
+  for (int q = 0; q < 6; ++q) {
     unsigned int v = s[q];
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     if (lane == 0) part[wave][q] = v;
   }
   __syncthreads();
-  if (threadIdx.x < 5) {
+  if (threadIdx.x < 6) {
     const unsigned long long v = (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] +
                                  part[3][threadIdx.x];
-    if (v) atomicAdd(&counts[(size_t)blockIdx.y * 5 + threadIdx.x], v);
+    if (v) atomicAdd(&counts[threadIdx.x], v);
   }
+}
+
+// blockIdx.y = column
+__global__ __launch_bounds__(256) void recon_counts_kernel(int n_rows, int n_up_to, const int32_t* __restrict__ ours,
+                                                           const int32_t* __restrict__ dirty, const int32_t* __restrict__ clean,
+                                                           unsigned long long* __restrict__ counts) {
+  const size_t base = (size_t)blockIdx.y * n_rows;
+  unsigned int s[6] = {0, 0, 0, 0, 0, 0};
+  for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += gridDim.x * blockDim.x) {
+    const int32_t o = ours[base + row], d = dirty[base + row], c = clean[base + row];
+    const bool in = row < n_up_to;
+    const bool dmiss = d == -4, cmiss = c == -6;
+    const bool ch = in && !dmiss && o != d;
+    s[0] += (!dmiss && d != c);
+    s[1] += ch;
+    s[2] += (ch && o == c);
+    s[3] += (in && dmiss && !cmiss);
+    s[4] += (in && dmiss && !cmiss && o == c);
+    s[5] += (dmiss && !cmiss);
+  }
+  recon_counts_reduce(s, counts + (size_t)blockIdx.y * 6);
+}
+
+// one NUM column: the rules of the host's numeric branch on fp64 values, dmiss = the dirty value is NaN; comparisons as
+// IEEE has them (NaN equals nothing, differs from everything)
+__global__ __launch_bounds__(256) void recon_counts_num_kernel(int n_rows, int n_up_to, const double* __restrict__ ours,
+                                                               const double* __restrict__ dirty, const double* __restrict__ clean,
+                                                               unsigned long long* __restrict__ counts) {
+  unsigned int s[6] = {0, 0, 0, 0, 0, 0};
+  for (int row = blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += gridDim.x * blockDim.x) {
+    const double o = ours[row], d = dirty[row], c = clean[row];
+    const bool in = row < n_up_to;
+    const bool dmiss = d != d, cmiss = c != c;
+    const bool ch = in && !dmiss && o != d;
+    s[0] += (!dmiss && d != c);
+    s[1] += ch;
+    s[2] += (ch && o == c);
+    s[3] += (in && dmiss && !cmiss);
+    s[4] += (in && dmiss && o == c);
+    s[5] += (dmiss && !cmiss);
+  }
+  recon_counts_reduce(s, counts);
 }
 
 extern "C" int pclean_recon_set_truth(pclean_ctx* ctx, const int32_t* dirty, const int32_t* clean) {
@@ -221,29 +425,72 @@ extern "C" int pclean_recon_set_truth(pclean_ctx* ctx, const int32_t* dirty, con
   return PCLEAN_OK;
 }
 
+extern "C" int pclean_recon_set_truth_num(pclean_ctx* ctx, const double* dirty, const double* clean) {
+  if (!ctx || !dirty || !clean) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_set_truth_num: bad arguments");
+  ReconState* r = rst(ctx);
+  if (r->num_cols.empty() || ctx->n_rows <= 0)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_recon_set_truth_num: the plan has no numeric column, or no observed rows");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t cells = r->num_cols.size() * (size_t)ctx->n_rows;
+  r->truth_num_valid = false;
+  if (r->dirty_num.alloc(cells) || r->clean_num.alloc(cells)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemcpy(r->dirty_num.p, dirty, cells * 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(r->clean_num.p, clean, cells * 8, hipMemcpyHostToDevice));
+  r->truth_num_valid = true;
+  return PCLEAN_OK;
+}
+
+// six counters per column into r->counts (device) over the first n_up_to cleaned rows; a NUM column's int32 counters are
+// replaced by those of its fp64 values
+static int recon_counts_run(pclean_ctx* ctx, const pclean_ring* ring, int32_t n_up_to, const char* who) {
+  ReconState* r = rst(ctx);
+  if (!r->truth_valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "%s: no dirty / clean columns (pclean_recon_set_truth)", who);
+  if (!r->num_cols.empty() && !r->truth_num_valid)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "%s: no dirty / clean values of the numeric columns (pclean_recon_set_truth_num)", who);
+  const int n_cols = (int)r->cols.size();
+  const int32_t* ours = recon_source(ctx, r, ring, who);
+  if (!ours) return PCLEAN_ERR_STATE;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (r->counts.alloc((size_t)n_cols * 6)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipMemsetAsync(r->counts.p, 0, (size_t)n_cols * 6 * 8, ctx->stream));
+  const size_t n = (size_t)ctx->n_rows;
+  const unsigned gx = (unsigned)std::min<size_t>(std::max<size_t>((n + 255) / 256, 1), 1024);
+  hipLaunchKernelGGL(recon_counts_kernel, dim3(gx, (unsigned)n_cols), dim3(256), 0, ctx->stream, ctx->n_rows, n_up_to, ours,
+                     r->dirty.p, r->clean.p, r->counts.p);
+  HIPCHK(ctx, hipGetLastError());
+  if (!r->num_cols.empty()) {
+    const int rc = recon_values_launch(ctx, r, ours);
+    if (rc) return rc;
+    for (size_t k = 0; k < r->num_cols.size(); ++k) {
+      unsigned long long* cnt = r->counts.p + (size_t)r->num_cols[k] * 6;
+      HIPCHK(ctx, hipMemsetAsync(cnt, 0, 6 * 8, ctx->stream));
+      hipLaunchKernelGGL(recon_counts_num_kernel, dim3(gx), dim3(256), 0, ctx->stream, ctx->n_rows, n_up_to, r->vals.p + k * n,
+                         r->dirty_num.p + k * n, r->clean_num.p + k * n, cnt);
+    }
+    HIPCHK(ctx, hipGetLastError());
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PCLEAN_OK;
+}
+
 extern "C" int pclean_recon_counts(pclean_ctx* ctx, const pclean_ring* ring, int64_t* out) {
   if (!ctx || !out) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_counts: bad arguments");
+  const int rc = recon_counts_run(ctx, ring, ctx->n_rows, "pclean_recon_counts");
+  if (rc) return rc;
   ReconState* r = rst(ctx);
-  if (!r->truth_valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_recon_counts: no dirty / clean columns (pclean_recon_set_truth)");
-  const int n_cols = (int)r->cols.size();
-  const int32_t* ours = nullptr;
-  if (ring) {
-    if (!ring->consensus_valid || ring->n_cols != n_cols || ring->n_rows != ctx->n_rows || ring->device != ctx->device)
-      return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_recon_counts: the ring holds no consensus of this plan's shape");
-    ours = ring->mode.p;
-  } else {
-    if (!r->out_valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_recon_counts: no reconstruction (pclean_recon_run)");
-    ours = r->out.p;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (r->counts.alloc((size_t)n_cols * 5)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-  HIPCHK(ctx, hipMemsetAsync(r->counts.p, 0, (size_t)n_cols * 5 * 8, ctx->stream));
-  const unsigned gx = (unsigned)std::min<size_t>(std::max<size_t>(((size_t)ctx->n_rows + 255) / 256, 1), 1024);
-  hipLaunchKernelGGL(recon_counts_kernel, dim3(gx, (unsigned)n_cols), dim3(256), 0, ctx->stream, ctx->n_rows, ours, r->dirty.p,
-                     r->clean.p, r->counts.p);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipMemcpy(out, r->counts.p, (size_t)n_cols * 5 * 8, hipMemcpyDeviceToHost));
+  std::vector<int64_t> six(r->cols.size() * 6);  // [n_cols][6] on the device -> the first five of every column
+  HIPCHK(ctx, hipMemcpy(six.data(), r->counts.p, six.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < r->cols.size(); ++c) std::copy(six.begin() + c * 6, six.begin() + c * 6 + 5, out + c * 5);
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_recon_counts_up_to(pclean_ctx* ctx, const pclean_ring* ring, int32_t n_up_to, int64_t* out) {
+  if (!ctx || !out || n_up_to < 0) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_recon_counts_up_to: bad arguments");
+  const int rc = recon_counts_run(ctx, ring, n_up_to, "pclean_recon_counts_up_to");
+  if (rc) return rc;
+  ReconState* r = rst(ctx);
+  HIPCHK(ctx, hipMemcpy(out, r->counts.p, r->cols.size() * 6 * 8, hipMemcpyDeviceToHost));
   return PCLEAN_OK;
 }
 
@@ -338,6 +585,8 @@ extern "C" int pclean_ring_create(pclean_ctx* ctx, int32_t keep, pclean_ring** o
   g->keep = keep;
   g->n_cols = (int32_t)r->cols.size();
   g->n_rows = ctx->n_rows;
+  g->is_num.assign(r->cols.size(), 0);
+  for (int32_t c : r->num_cols) g->is_num[c] = 1;
   const size_t cells = (size_t)g->n_cols * g->n_rows;
   if (g->data.alloc(cells * keep) || g->mode.alloc(cells) || g->support.alloc(cells)) {
     g->data.release();
@@ -431,7 +680,17 @@ extern "C" int pclean_ring_remap(pclean_ctx* ctx, pclean_ring* ring, int32_t n_o
   if (e == hipSuccess) {
     const size_t n = (size_t)ring->n_cols * ring->n_rows * (size_t)std::min<int64_t>(ring->adds, ring->keep);
     // (before the ring has wrapped its kept snapshots are slots [0, adds))
-    if (n) hipLaunchKernelGGL(ring_remap_kernel, stream_grid(n), dim3(256), 0, ctx->stream, n, ring->data.p, n_old, map.p);
+    const bool any_num = std::find(ring->is_num.begin(), ring->is_num.end(), (char)1) != ring->is_num.end();
+    if (n && !any_num)
+      hipLaunchKernelGGL(ring_remap_kernel, stream_grid(n), dim3(256), 0, ctx->stream, n, ring->data.p, n_old, map.p);
+    else if (n) {  // column by column in every kept slot; the option indices of NUM columns stay
+      const size_t rows = (size_t)ring->n_rows, slots = n / ((size_t)ring->n_cols * rows);
+      for (size_t s = 0; s < slots; ++s)
+        for (int32_t c = 0; c < ring->n_cols; ++c)
+          if (!ring->is_num[c])
+            hipLaunchKernelGGL(ring_remap_kernel, stream_grid(rows), dim3(256), 0, ctx->stream, rows,
+                               ring->data.p + (s * ring->n_cols + c) * rows, n_old, map.p);
+    }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }

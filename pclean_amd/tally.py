@@ -4,7 +4,9 @@
 a pull of every latent table.  `CellTally` serves the same columns from the device-resident referents and tables
 (csrc/recon.hip): the reconstruction, the five counters of evaluate_accuracy (analysis.jl:36-88), a ring of the last
 `keep` reconstructions and, per cell, the most frequent kept value with its support — one posterior sample is a noisy
-point estimate, and the sampler visits many states per run.
+point estimate, and the sampler visits many states per run.  With own=True the observed class's own enumerated choices
+and its numeric columns (reported through a Gaussian term) are served from the device as well, and `accuracy_up_to` gives
+evaluate_accuracy_up_to (analysis.jl:90-143) from the same counter kernels with a row bound.
 """
 import collections
 
@@ -33,15 +35,20 @@ class ReconPlan:
     """Which queried columns the device reconstructs and how (pclean_recon_set_plan).
     columns: their names in plan order (the columns of one block follow each other, function-table columns last);
     cols / id_map: the C descriptors; host_strings: queried string columns that stay on the host (own enumerated choices,
-    JuliaNodes without a function table); numeric: queried numeric columns (reported through a Gaussian term)."""
+    JuliaNodes without a function table); numeric: queried numeric columns (reported through a Gaussian term).
+    own=True also plans the own enumerated choices of the observed class (kind "own": the option's pool id, from the own
+    choices CellTally uploads) and the numeric columns (kind "num": the cell is the Transformation option the row holds,
+    its value round(backward_u(x)) is materialised on the device) — after the path and function-table columns, in that
+    order; `device_numeric` names the latter, and host_strings keeps only JuliaNodes without a function table."""
 
-    def __init__(self, lowered):
+    def __init__(self, lowered, own=False):
         lw = lowered
+        self.own = bool(own)
         m, q = lw.model, lw.query
         ocls = m.classes[q.cls]
         fk_block = {blk["root_fk"]: bi for bi, blk in enumerate(lw.blocks) if not blk.get("score")}
-        paths, fns = [], []
-        self.host_strings, self.numeric = [], []
+        paths, fns, owns, nums = [], [], [], []
+        self.host_strings, self.numeric, self.device_numeric = [], [], []
         for col, ref in q.cleanmap.items():
             if "." in ref:
                 head, rest = ref.split(".", 1)
@@ -53,7 +60,17 @@ class ReconPlan:
                 continue
             own = ocls.attr(ref)
             if own.kind == "julia" and any(sp["gauss_attr"] == q.obsmap[col] for sp in lw.gauss_specs):
-                self.numeric.append(col)
+                if self.own:  # term g of the block sits on its root node (0), in declaration order
+                    g = next(g for g, sp in enumerate(lw.gauss_specs) if sp["gauss_attr"] == q.obsmap[col])
+                    nums.append((col, dict(kind=_lib.RECON_NUM, block=lw.gauss_block, table=0, col=g), np.zeros(0, np.int32)))
+                    self.device_numeric.append(col)
+                else:
+                    self.numeric.append(col)
+                continue
+            if self.own and own.kind == "choice":
+                bi = next(iter(lw.locals))
+                owns.append((col, dict(kind=_lib.RECON_OWN, block=bi, table=-1, col=lw.locals[bi].index(ref)),
+                             lw.latent_dom[(q.cls, ref)].id_array()))
                 continue
             ft = self._fn_table_of(lw, own, fk_block) if own.kind == "julia" else None
             if ft is None:
@@ -62,7 +79,7 @@ class ReconPlan:
                 fns.append((col, ft[0], ft[1]))
         paths.sort(key=lambda p: p[0])  # (stable: one block's columns together, in query order)
         self.columns, self.cols, maps, off = [], [], [], 0
-        for col, desc, idmap in [(p[1], p[2], p[3]) for p in paths] + fns:
+        for col, desc, idmap in [(p[1], p[2], p[3]) for p in paths] + fns + owns + nums:
             idmap = np.ascontiguousarray(idmap, dtype=np.int32)
             rc = _lib.ReconCol(block_b=-1, table_b=-1, col_b=-1, fn_table=-1)
             for k, v in desc.items():
@@ -73,7 +90,12 @@ class ReconPlan:
             self.columns.append(col)
             self.cols.append(rc)
         self.id_map = np.concatenate(maps) if maps else np.zeros(0, dtype=np.int32)
-        self.kinds = {c: ("fn" if rc.kind == _lib.RECON_FN else "path") for c, rc in zip(self.columns, self.cols)}
+        names = {_lib.RECON_PATH: "path", _lib.RECON_FN: "fn", _lib.RECON_OWN: "own", _lib.RECON_NUM: "num"}
+        self.kinds = {c: names[rc.kind] for c, rc in zip(self.columns, self.cols)}
+        # blocks whose own choices the device needs: every OWN column's, and a NUM column's unless its term has no Transformation
+        self.local_blocks = sorted({rc.block for rc in self.cols if rc.kind == _lib.RECON_OWN} |
+                                   {rc.block for rc in self.cols if rc.kind == _lib.RECON_NUM
+                                    and lw.gauss_specs[rc.col]["t_local"] is not None})
 
     @staticmethod
     def _fn_table_of(lw, j, fk_block):
@@ -120,30 +142,59 @@ class CellTally:
 
     The kept values are string pool ids.  When the lowered model is rebuilt (LoweredModel.relower, after strings were
     drawn for chosen dummy values) the pool is rebuilt too: after every Engine.reload the tally uploads its plan again and,
-    unless the old pool's strings are a prefix of the new one's, translates the kept snapshots to the new ids."""
+    unless the old pool's strings are a prefix of the new one's, translates the kept snapshots to the new ids.
 
-    def __init__(self, engine, trace, keep=16):
+    own=True (opt-in; without it plan, columns and answers are what they always were): the own enumerated choices of the
+    observed class and the numeric columns reported through a Gaussian term are served from the device too
+    (ReconPlan(lowered, own=True)).  The own choices are host-owned and always current (the engine writes them into the
+    trace after every sweep, also while device commits are ahead): the tally uploads them — 8 bytes per row — into a
+    buffer of the reconstruction state whenever they changed since its last upload; no Engine.pull.  A numeric column's
+    kept cells are Transformation option indices: its consensus is the number under the most frequent option."""
+
+    def __init__(self, engine, trace, keep=16, own=False):
         keep = int(keep)
         if not 1 <= keep <= _lib.RING_MAX_KEEP:
             raise ValueError(f"keep must be in 1..{_lib.RING_MAX_KEEP}, got {keep}")
-        self.engine, self.lw, self.keep = engine, engine.lw, keep
+        self.engine, self.lw, self.keep, self.own = engine, engine.lw, keep, bool(own)
         self.n_rows = int(trace._cur.shape[1])
         if engine.obs.shape[1] != self.n_rows or engine.row_offset:
             raise ValueError("CellTally needs an engine that holds every observed row of the trace")
         self._ring = None
         self._host_ring = collections.deque(maxlen=keep)  # {column: pool ids} of the host-only string columns
         self._adds = 0
+        import weakref
+        self._trace = weakref.ref(trace)  # (a numeric column's plan needs the Gaussian terms loaded: _upload_plan)
         self._install()
 
     # -- plan / pool bookkeeping --------------------------------------------------------------------------------------
     def _install(self):
-        self.plan = ReconPlan(self.lw)
+        self.plan = ReconPlan(self.lw, own=True) if self.own else ReconPlan(self.lw)
         self.columns = list(self.plan.columns)
+        self._num = [self.columns.index(c) for c in self.plan.device_numeric]  # plan positions of the numeric columns
         if self.columns:
-            self.engine.hip.recon_set_plan(self.plan.cols, self.plan.id_map)
-            self.engine.hip._recon_truth = None  # (a context's dirty / clean ids go with its plan; tallies of one engine share them)
+            self._upload_plan()
         self._hip, self._reloads = self.engine.hip, self.engine.reloads
         self._pool = self.lw.pool  # (relower makes a new pool object: this one keeps the ids the kept snapshots hold)
+
+    def _upload_plan(self):
+        hip = self.engine.hip
+        if self._num and getattr(self.engine, "_gauss_pending", False):
+            # the library checks a numeric column against its Gaussian term, which a fresh context gets with the first
+            # upload of a trace (it needs the mean tables)
+            tr = self._trace()
+            if tr is None or tr._dev is not None:
+                raise _lib.PCleanHipError("CellTally(own=True): the engine has not loaded the Gaussian terms yet and the trace "
+                                          "that would bring them is gone or ahead on a device")
+            self.engine.upload_trace(tr)
+        hip.recon_set_plan(self.plan.cols, self.plan.id_map)
+        hip._recon_truth = None  # (a context's dirty / clean ids go with its plan; tallies of one engine share them)
+        hip._recon_own = self.own
+
+    def _ensure_plan(self):
+        """tallies of one engine share its context's plan: put this one's back when a tally of the other kind (own or
+        not) uploaded its own since"""
+        if self.columns and getattr(self.engine.hip, "_recon_own", self.own) != self.own:
+            self._upload_plan()
 
     def _refresh(self):
         """after an Engine.reload: the plan goes into the fresh context, kept snapshots follow the pool's ids"""
@@ -165,9 +216,19 @@ class CellTally:
         if trace._cur.shape[1] != self.n_rows:
             raise ValueError("the trace holds another number of rows than the tally was made for")
         self._refresh()
+        self._ensure_plan()
         self.engine.make_device_current(trace)
+        if self.plan.local_blocks:
+            hip = self.engine.hip
+            sent = hip.__dict__.setdefault("_recon_locals", {})
+            for bi in self.plan.local_blocks:
+                loc = trace._locals[bi]  # (host-owned and current even while device commits are ahead: no pull)
+                if bi not in sent or not np.array_equal(sent[bi], loc):
+                    hip.recon_set_locals(bi, loc)
+                    sent[bi] = np.array(loc, dtype=np.int32, copy=True)
 
     def _ensure_truth(self, dirty, clean):
+        self._ensure_plan()
         have = getattr(self.engine.hip, "_recon_truth", None)
         if have is not None and have[0] is dirty and have[1] is clean:
             return
@@ -176,10 +237,20 @@ class CellTally:
         c = np.full((len(self.columns), n), -6, dtype=np.int32)
         counted = np.zeros(len(self.columns), dtype=bool)
         for i, col in enumerate(self.columns):
-            if col in dirty and col in clean:
+            if col in dirty and col in clean and i not in self._num:
                 d[i], c[i] = truth_ids(index, dirty[col][:n], clean[col][:n])
                 counted[i] = True
         self.engine.hip.recon_set_truth(d, c)
+        if self._num:  # numeric columns are counted from numbers, NaN = a missing cell
+            dn = np.full((len(self._num), n), np.nan)
+            cn = np.full((len(self._num), n), np.nan)
+            for k, i in enumerate(self._num):
+                col = self.columns[i]
+                if col in dirty and col in clean:
+                    dn[k] = [np.nan if v is None else float(v) for v in dirty[col][:n]]
+                    cn[k] = [np.nan if v is None else float(v) for v in clean[col][:n]]
+                    counted[i] = True
+            self.engine.hip.recon_set_truth_num(dn, cn)
         self.engine.hip._recon_truth = (dirty, clean, counted)
 
     def close(self):
@@ -197,20 +268,34 @@ class CellTally:
     def reconstruct(self, trace):
         """{column: int32[n] pool ids} of `.columns`: analysis.reconstructed_pool_ids computed on the device, from the
         device-resident state when device commits are ahead of the host arrays (no pull), else after uploading what moved.
-        A row without a referent in a column's block holds -1."""
+        A row without a referent in a column's block holds -1.  A numeric column (own=True) comes as the host gives it:
+        ("numeric", float64[n]), bit for bit np.round(lowered.gauss_backward(...))."""
         if not self.columns:
             return {}
         self._current(trace)
         out = self.engine.hip.recon_run(len(self.columns), self.n_rows)
-        return {col: out[i] for i, col in enumerate(self.columns)}
+        got = {col: out[i] for i, col in enumerate(self.columns)}
+        self._put_values(got, None)
+        return got
 
-    def _device_counts(self, ring=None):
-        per_col = self.engine.hip.recon_counts(len(self.columns), ring)
+    def _put_values(self, into, ring):
+        if self._num:
+            vals = self.engine.hip.recon_values(len(self._num), self.n_rows, ring)
+            for k, i in enumerate(self._num):
+                into[self.columns[i]] = ("numeric", vals[k])
+
+    def _device_counts(self, ring=None, n_up_to=None):
+        if n_up_to is None:
+            per_col = self.engine.hip.recon_counts(len(self.columns), ring)
+        else:
+            per_col = self.engine.hip.recon_counts_up_to(len(self.columns), n_up_to, ring)
         return per_col[self.engine.hip._recon_truth[2]].sum(axis=0).astype(np.int64)
 
     def accuracy_counts(self, trace, dirty, clean):
         """analysis.accuracy_counts(lowered, trace, dirty, clean): `.columns` are reconstructed and counted on the device
-        (dirty / clean ids are uploaded once per pair of tables), the remaining columns by the host code, and added."""
+        (dirty / clean ids are uploaded once per pair of tables), the remaining columns by the host code, and added.
+        With own=True the host is left with the columns that are not queried and JuliaNodes without a function table:
+        for a program without such nodes nothing reads the trace."""
         total = np.zeros(5, dtype=np.int64)
         if self.columns:
             self._current(trace)
@@ -218,6 +303,22 @@ class CellTally:
             self.engine.hip.recon_run(len(self.columns), self.n_rows, fetch=False)
             total += self._device_counts()
         return total + analysis.accuracy_counts(self.lw, trace, dirty, clean, skip=set(self.columns))
+
+    def accuracy_counts_up_to(self, trace, dirty, clean, n):
+        """analysis.accuracy_counts_up_to(lowered, trace, dirty, clean, n): six counters, the same counter kernels with a
+        row bound (`.columns` on the device, the rest on the host)."""
+        n = max(0, min(int(n), self.n_rows))
+        total = np.zeros(6, dtype=np.int64)
+        if self.columns:
+            self._current(trace)
+            self._ensure_truth(dirty, clean)
+            self.engine.hip.recon_run(len(self.columns), self.n_rows, fetch=False)
+            total += self._device_counts(n_up_to=n)
+        return total + analysis.accuracy_counts_up_to(self.lw, trace, dirty, clean, n, skip=set(self.columns))
+
+    def accuracy_up_to(self, trace, dirty, clean, n):
+        """analysis.evaluate_accuracy_up_to(lowered, trace, dirty, clean, n) with the device's counters"""
+        return analysis.f1_from_counts_up_to(self.accuracy_counts_up_to(trace, dirty, clean, n))
 
     # -- kept samples -------------------------------------------------------------------------------------------------
     @property
@@ -246,22 +347,27 @@ class CellTally:
     def consensus(self):
         """(ids, support): per queried STRING column the most frequent pool id of every cell over the `n_kept` kept samples
         and the number of kept samples holding it; ties go to the value seen most recently.  Host-only string columns
-        are tallied from host snapshots with the same rule.  Numeric queried columns are left out: a mode of real-valued
-        draws says little, and they are not on the device."""
+        are tallied from host snapshots with the same rule.  Numeric queried columns are left out — unless the tally was
+        made with own=True: then a numeric column comes as ("numeric", float64 values), the number under the Transformation
+        option most of the kept samples hold (a mode of the discrete choice, not of real-valued draws), with that option's
+        support."""
         if not self._adds:
             raise ValueError("nothing kept yet: CellTally.add first")
         self._refresh()
         ids, support = self._host_consensus()
         if self.columns:
+            self._ensure_plan()
             mode, sup = self.engine.hip.ring_consensus(self._ring)
             for i, col in enumerate(self.columns):
                 ids[col], support[col] = mode[i], sup[i]
+            self._put_values(ids, self._ring)
         order = [c for c in self.lw.query.cleanmap if c in ids]
         return {c: ids[c] for c in order}, {c: support[c] for c in order}
 
     def consensus_accuracy(self, dirty, clean):
         """evaluate_accuracy of the consensus table, with the same counters (the device's for `.columns`).  Numeric queried
-        columns are not tallied: they stand at their dirty values (nothing changed, nothing imputed correctly)."""
+        columns are counted from their consensus values by a tally made with own=True; otherwise they are not tallied and
+        stand at their dirty values (nothing changed, nothing imputed correctly)."""
         if not self._adds:
             raise ValueError("nothing kept yet: CellTally.add first")
         self._refresh()

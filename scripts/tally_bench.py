@@ -6,6 +6,11 @@ Kernel figures are host-clock times of calls that end in a stream synchronisatio
 bytes are what the algorithm has to move, computed from the shapes.  Writes profiles/tally_bench.json.
 
     python scripts/tally_bench.py [--rows N] [--keep K] [--out FILE]
+
+`--program rents` times the shipped rents program instead (all of its rows unless --rows says otherwise): accuracy_counts
+and add + consensus once through the mixed path (CellTally(eng, tr): three columns on the device, room types and the rent
+on the host, reading the trace) and once with own=True (all five on the device).  The own=True calls run with Engine.pull
+made to raise, and both paths' counters must equal the host's.  Writes profiles/tally_bench_rents.json.
 """
 import argparse
 import json
@@ -21,16 +26,117 @@ import numpy as np
 HBM_PEAK = 8.0e12  # bytes/s, MI355X specification
 
 
+def main_rents(args):
+    from pclean_amd import analysis
+    from pclean_amd import experiments as ex
+    from pclean_amd import inference as inf
+    from pclean_amd.engine import Engine, InferenceConfig
+    from pclean_amd.model import LoweredModel
+    from pclean_amd.tally import CellTally
+    from pclean_amd.trace import Trace
+
+    dirty, clean = ex.rents_data()
+    (dirty, clean), _ = ex.shuffle_rows([dirty, clean], 0)
+    if args.rows:
+        dirty = {c: v[:args.rows] for c, v in dirty.items()}
+        clean = {c: v[:args.rows] for c, v in clean.items()}
+    m = ex.rents_model(dirty)
+    lw = LoweredModel(m, ex.rents_query(m), dirty)
+    obs = lw.encode_observations(dirty)
+    n = obs.shape[1]
+    eng = Engine(lw, obs)
+    cfg = InferenceConfig(1, 2, use_mh_instead_of_pg=True, rejuv_frequency=500)
+    tr = Trace(lw, n, 0)
+    inf.initialize_trace(eng, tr, cfg, 0, max_batch=2048)
+    inf.run_inference(eng, tr, cfg, 0)
+    sweep = [0]
+
+    def advance():
+        sweep[0] += 1
+        inf.observed_sweep(eng, tr, cfg, 0, sweep[0])
+
+    pulls = [0]
+    real_pull = Engine.pull
+
+    def counting_pull(self, trace):
+        pulls[0] += 1
+        return real_pull(self, trace)
+
+    def refusing_pull(self, trace):
+        raise AssertionError("Engine.pull called on the own=True path")
+
+    def timed(fn, own):
+        """a tally call alone sees the counted / refused Engine.pull: the sweeps between the calls pull as they always do
+        (rents' parameter moves read the trace)"""
+        Engine.pull = refusing_pull if own else counting_pull
+        try:
+            t0 = time.perf_counter()
+            out = fn()
+            return out, 1e3 * (time.perf_counter() - t0)
+        finally:
+            Engine.pull = real_pull
+
+    res = {"program": "rents", "rows": n, "queried_columns": len(lw.query.cleanmap), "keep": args.keep, "calls": args.calls,
+           "note": "milliseconds, median of `calls` calls after one warm-up; an observed-class sweep before every call"}
+    for own in (False, True):
+        tally = CellTally(eng, tr, keep=args.keep, own=own)
+        pulls[0] = 0
+        cnt_ms, both = [], []
+        for i in range(args.calls + 1):
+            advance()
+            dev_counts, d = timed(lambda: tally.accuracy_counts(tr, dirty, clean), own)
+            if i:
+                cnt_ms.append(d)
+        for _ in range(args.keep):
+            advance()
+            timed(lambda: tally.add(tr), own)
+        for i in range(args.calls + 1):
+            advance()
+            _, a = timed(lambda: tally.add(tr), own)
+            _, f = timed(tally.consensus, own)
+            if i:
+                both.append(a + f)
+        advance()
+        dev_counts, _ = timed(lambda: tally.accuracy_counts(tr, dirty, clean), own)
+        cacc, _ = timed(lambda: tally.consensus_accuracy(dirty, clean), own)
+        n_pulls = pulls[0]
+        same = bool(np.array_equal(dev_counts, analysis.accuracy_counts(lw, tr, dirty, clean)))
+        if not same:
+            raise SystemExit(f"[tally_bench] own={own}: the tally's counters differ from analysis.accuracy_counts")
+        res["own" if own else "mixed"] = {"columns_on_device": len(tally.columns), "equals_host_counts": same,
+                                          "pulls": n_pulls, "accuracy_counts_ms": statistics.median(cnt_ms),
+                                          "add_plus_consensus_ms": statistics.median(both), "n_kept": tally.n_kept,
+                                          "f1_consensus": cacc["f1"]}
+        print(f"[tally_bench] rents own={own}: {res['own' if own else 'mixed']}", file=sys.stderr, flush=True)
+        tally.close()
+    res["f1_last_sample"] = analysis.evaluate_accuracy(lw, tr, dirty, clean)["f1"]
+    eng.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--program", choices=["hospital", "rents"], default="hospital")
+    ap.add_argument("--rows", type=int, default=None)
     ap.add_argument("--hospitals", type=int, default=10_000)
     ap.add_argument("--particles", type=int, default=20)
     ap.add_argument("--seed", type=int, default=20250926)
     ap.add_argument("--keep", type=int, default=16)
     ap.add_argument("--calls", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tally_bench.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "tally_bench.json" if args.program == "hospital" else "tally_bench_rents.json")
+    if args.program == "rents":
+        res = main_rents(args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(json.dumps(res))
+        return
+    if args.rows is None:
+        args.rows = 1_000_000
 
     import bench
     from pclean_amd import _lib, analysis
