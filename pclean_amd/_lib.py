@@ -308,6 +308,16 @@ class HipContext:
         check(self.h, self.lib.pclean_debug_enum_launches(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_enum_launches")
         return dict(zip(self.ENUM_LAUNCH_SLOTS, out.tolist()))
 
+    ROOT_LAUNCH_SLOTS = ("wave_2", "wave_4", "wave_8", "wave_12", "wave_16", "settle", "worklist_pack", "lazy",
+                         "overflow_lds", "resolved_draws")
+
+    def root_launches(self, reset=False):
+        """what the compact-table root launch and its overflow re-run launched since the last reset, by ROOT_LAUNCH_SLOTS
+        name (counted on the host)"""
+        out = np.zeros(len(self.ROOT_LAUNCH_SLOTS), dtype=np.int64)
+        check(self.h, self.lib.pclean_debug_root_launches(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_root_launches")
+        return dict(zip(self.ROOT_LAUNCH_SLOTS, out.tolist()))
+
     def set_table(self, table_id, cols, counts, strength, discount, n_cols=None):
         """cols None (with n_cols given) keeps the columns uploaded before and refreshes the counts only."""
         counts = np.ascontiguousarray(counts, dtype=np.int64)

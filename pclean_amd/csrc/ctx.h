@@ -284,6 +284,10 @@ struct pclean_ctx {
   // [0..8) enum_node_kernel / enum_node_big_kernel: 4 * big + 2 * (BT == 1024) + EV; [8..10) enum_scores_kernel<EV>;
   // [10..14) enum_product_kernel: 10 + 2 * (BT == 1024) + !LDSP
   int64_t enum_launches[PCLEAN_ENUM_LAUNCH_SLOTS] = {};
+  // debug (pclean_debug_root_launches): what pclean_launch_root_fast / pclean_launch_overflow_fast launched, counted on the
+  // host.  [0..5) fk_root_wave_kernel<2|4|8|12|16>, 5 group_settle_kernel, 6 worklist_pack_kernel, 7 a scan launch that was
+  // given the lazy-draw lists, 8 overflow_lds_kernel, 9 resolved_draws_kernel
+  int64_t root_launches[PCLEAN_ROOT_LAUNCH_SLOTS] = {};
   void* sweep_state = nullptr;  // owned by sweep.hip
   void* rccl_comm = nullptr;    // ncclComm_t of pclean_comm_init (comm.hip)
   void* recon_state = nullptr;  // owned by recon.hip

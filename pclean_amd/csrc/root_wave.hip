@@ -1781,6 +1781,7 @@ int pclean_launch_overflow_fast(pclean_ctx* ctx, const FastRootDev& fr, const It
   const int grid = over_list ? std::min(it.n, 256) : it.n;
   hipLaunchKernelGGL(overflow_lds_kernel, dim3(grid), dim3(OVF_T), lds, ctx->stream, fr, it, ch, seed, sweep, site, n_draws,
                      lse_out, draws_out, over_list, over_count);
+  ++ctx->root_launches[8];
   HIPCHK(ctx, hipGetLastError());
   return 1;
 }
@@ -1905,13 +1906,18 @@ int pclean_launch_root_fast(pclean_ctx* ctx, const FastRootDev& fr, const ItemsD
     hipLaunchKernelGGL(group_settle_kernel, dim3(n_wg), dim3(256), 0, ctx->stream, sa, ws, it.n, n_draws, desc_scratch, g_m, g_U,
                        draws_out, scan_stats, use_worklist ? seg_list : nullptr, chunk_ctr, seg_cap, lazy ? extra->lz_ns : nullptr,
                        lazy ? extra->lz_k : nullptr, lazy ? extra->lz_p : nullptr, lazy ? extra->eager_rows : nullptr);
-    if (use_worklist)
+    ++ctx->root_launches[5];
+    if (use_worklist) {
       hipLaunchKernelGGL(worklist_pack_kernel, dim3(1), dim3(1024), 0, ctx->stream, seg_list, seg_cap, chunk_ctr, worklist, wl_stat);
+      ++ctx->root_launches[6];
+    }
   }
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(64 * wpg), 0, ctx->stream, fr, wi, seed, sweep, site, n_draws, it.n, chunk, desc_scratch,
                      chunk_ctr, g_m, g_U, draws_out, overflow_flag, overflow_count, overflow_list, scan_stats,
                      use_worklist ? worklist : nullptr, lazy ? extra->lz_k : nullptr, lazy ? extra->lz_p : nullptr,
                      lazy ? extra->lz_ns : nullptr, lazy ? extra->eager_rows : nullptr, no_dense ? 0 : 1);
+  ++ctx->root_launches[variant == 2 ? 0 : variant == 4 ? 1 : variant == 8 ? 2 : variant == 12 ? 3 : 4];
+  if (lazy) ++ctx->root_launches[7];
 #ifdef WAVE_PHASE_CLOCK
   if (it.n > 100000) {
     unsigned long long h[16];
@@ -1933,6 +1939,7 @@ int pclean_launch_root_fast(pclean_ctx* ctx, const FastRootDev& fr, const ItemsD
     hipLaunchKernelGGL(resolved_draws_kernel, dim3((n_mem_all + 255) / 256), dim3(256), 0, ctx->stream, n_mem_all, it.n,
                        it.grp_off, it.members, it.out_pos, g_res, n_draws, it.draw_is ? it.draw_is : n_draws,
                        it.draw_ds ? it.draw_ds : 1, draws_out);
+    ++ctx->root_launches[9];
   }
   if (lse_out && it.grp_off && it.grp_uid && n_items > 0)
     hipLaunchKernelGGL(member_lse_kernel, dim3((n_items + 255) / 256), dim3(256), 0, ctx->stream, n_items, it.grp_uid, it.members,

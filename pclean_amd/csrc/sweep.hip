@@ -1313,6 +1313,13 @@ extern "C" int pclean_debug_enum_launches(pclean_ctx* ctx, int64_t* out, int32_t
   return PCLEAN_OK;
 }
 
+extern "C" int pclean_debug_root_launches(pclean_ctx* ctx, int64_t* out, int32_t reset) {
+  if (!ctx) return PCLEAN_ERR_ARG;
+  if (out) memcpy(out, ctx->root_launches, sizeof(ctx->root_launches));
+  if (reset) memset(ctx->root_launches, 0, sizeof(ctx->root_launches));
+  return PCLEAN_OK;
+}
+
 extern "C" int pclean_set_row_offset(pclean_ctx* ctx, int64_t row_offset) {
   if (!ctx || row_offset < 0) return pclean_fail(ctx, PCLEAN_ERR_ARG, "bad row offset");
   st(ctx)->row_offset = row_offset;
