@@ -17,8 +17,9 @@ MAX_GAUSS = 4  # PCLEAN_MAX_GAUSS
 EV_MAX_STEPS = 4  # PCLEAN_EV_MAX_STEPS
 CHOICE_NEW = -1
 DIST_OSA, DIST_DL = 0, 1
-DENS_ADD_TYPOS, DENS_EQUAL, DENS_MAYBE_SWAP, DENS_TABULATED = 0, 1, 2, 3
-CLASS_SHORT_VERSION, CLASS_FORMAT_NAME = 0, 1
+DENS_ADD_TYPOS, DENS_EQUAL, DENS_MAYBE_SWAP, DENS_TABULATED, DENS_NAME3 = 0, 1, 2, 3, 4
+CLASS_SHORT_VERSION, CLASS_FORMAT_NAME, CLASS_NAME_PREFIX, CLASS_NAME_SUFFIX = 0, 1, 2, 3
+NAME3_CAND, NAME3_OBS = 0, 1  # PCLEAN_NAME3_*: where a name3 term takes a value from
 NODE_FK, NODE_LEAF = 0, 1
 DUMMY_STRING_PRIOR, DUMMY_TIME_PRIOR = 1, 2
 
@@ -516,6 +517,21 @@ class HipContext:
             C.c_int32(len(terms)), terms.ctypes.data_as(C.c_void_p), C.c_int32(len(children)),
             _p(children, C.c_int32), C.c_int32(len(colmap)), _p(colmap, C.c_int32), C.c_int32(len(csb)),
             _p(csb, C.c_int32), _p(csc, C.c_int32)), "pclean_load_block")
+
+    def set_term_name3(self, block_id, term_id, src_kind, src_col, suffix_table, obs_ids, first_ids, mid_ids, last_ids,
+                       log_three, log_two):
+        """what term `term_id` (DENS_NAME3) of a loaded block reads besides its Term: per name (first, middle, last) the
+        source (NAME3_CAND: candidate column, NAME3_OBS: observed column), the suffix table, the pool strings of the four
+        domains and the two constants (pclean_set_term_name3)"""
+        src_kind = np.ascontiguousarray(src_kind, dtype=np.int32)
+        src_col = np.ascontiguousarray(src_col, dtype=np.int32)
+        assert src_kind.size == 3 and src_col.size == 3
+        ids = [np.ascontiguousarray(a, dtype=np.int32) for a in (obs_ids, first_ids, mid_ids, last_ids)]
+        check(self.h, self.lib.pclean_set_term_name3(
+            self.h, C.c_int32(block_id), C.c_int32(term_id), _p(src_kind, C.c_int32), _p(src_col, C.c_int32),
+            C.c_int32(suffix_table), C.c_int32(len(ids[0])), _p(ids[0], C.c_int32), C.c_int32(len(ids[1])),
+            _p(ids[1], C.c_int32), C.c_int32(len(ids[2])), _p(ids[2], C.c_int32), C.c_int32(len(ids[3])),
+            _p(ids[3], C.c_int32), C.c_double(log_three), C.c_double(log_two)), "pclean_set_term_name3")
 
     # -- enumeration / sweep ---------------------------------------------------
     def score_node(self, block_id, node_id, rows, ctxv=None, excl=None, snew=None, seed=0, sweep=0, n_draws=0,

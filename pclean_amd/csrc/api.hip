@@ -82,6 +82,7 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
     for (auto& l : b.leaf_U) l.release();
     for (auto& l : b.leaf_coarse) l.release();
     for (auto& l : b.leaf_udummy) l.release();
+    for (Name3Term& n3 : b.name3) n3.release();
   }
   (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -314,7 +315,8 @@ static int check_string_ids(pclean_ctx* ctx, int n, const int32_t* ids, const ch
 extern "C" int pclean_build_class_table(pclean_ctx* ctx, int32_t table_id, int32_t n_obs, const int32_t* obs_ids,
                                         int32_t n_lat, const int32_t* lat_ids, int32_t rule, int32_t dot_symbol) {
   if (!ctx || table_id < 0 || table_id >= PCLEAN_MAX_TABLES || n_obs < 0 || n_lat <= 0 || (n_obs > 0 && !obs_ids) || !lat_ids ||
-      (rule != PCLEAN_CLASS_SHORT_VERSION && rule != PCLEAN_CLASS_FORMAT_NAME))
+      (rule != PCLEAN_CLASS_SHORT_VERSION && rule != PCLEAN_CLASS_FORMAT_NAME && rule != PCLEAN_CLASS_NAME_PREFIX &&
+       rule != PCLEAN_CLASS_NAME_SUFFIX))
     return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_build_class_table: bad arguments");
   if (ctx->n_strings == 0) return pclean_fail(ctx, PCLEAN_ERR_STATE, "load strings first");
   if (ctx->n_fold < ctx->n_symbols)
@@ -382,6 +384,100 @@ extern "C" int pclean_set_class_density(pclean_ctx* ctx, int32_t table_id, int32
   HIPCHK(ctx, hipMemcpy(pt.cls.p, dens, (size_t)n_lat * 4 * sizeof(double), hipMemcpyHostToDevice));
   pt.cls_valid = true;
   pt.version = ++g_pclean_version;
+  return PCLEAN_OK;
+}
+
+// start and length of the pool strings ids[0 .. n) on the device (lo may be null: lengths only)
+static int upload_string_spans(pclean_ctx* ctx, int n, const int32_t* ids, DevBuf<int64_t>* lo, DevBuf<int32_t>& len) {
+  std::vector<int64_t> hlo((size_t)std::max(n, 1), 0);
+  std::vector<int32_t> hlen((size_t)std::max(n, 1), 0);
+  for (int i = 0; i < n; ++i) {
+    hlo[i] = ctx->h_off[ids[i]];
+    hlen[i] = (int32_t)(ctx->h_off[ids[i] + 1] - ctx->h_off[ids[i]]);
+  }
+  if ((lo && lo->alloc(hlo.size())) || len.alloc(hlen.size())) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  if (lo) HIPCHK(ctx, hipMemcpy(lo->p, hlo.data(), hlo.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipMemcpy(len.p, hlen.data(), hlen.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return PCLEAN_OK;
+}
+
+// The three-name FormatName term (PCLEAN_DENS_NAME3): the term's sources, its suffix table and the string spans the
+// survivor compare of enum_kernels.hip (name3_middle_matches) walks.  Checked here once, resolved to device pointers per
+// launch (eval.hip: build_node_dev).
+extern "C" int pclean_set_term_name3(pclean_ctx* ctx, int32_t block_id, int32_t term_id, const int32_t* src_kind,
+                                     const int32_t* src_col, int32_t suffix_table, int32_t n_obs, const int32_t* obs_ids,
+                                     int32_t n_first, const int32_t* first_ids, int32_t n_mid, const int32_t* mid_ids,
+                                     int32_t n_last, const int32_t* last_ids, double log_three, double log_two) {
+  if (!ctx || block_id < 0 || block_id >= PCLEAN_MAX_BLOCKS || !src_kind || !src_col || suffix_table < 0 ||
+      suffix_table >= PCLEAN_MAX_TABLES || n_obs < 0 || (n_obs > 0 && !obs_ids) || n_first <= 0 || !first_ids || n_mid <= 0 ||
+      !mid_ids || n_last <= 0 || !last_ids)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: bad arguments");
+  Block& b = ctx->block[block_id];
+  if (!b.valid || b.is_score) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_set_term_name3: block %d not loaded", block_id);
+  if (term_id < 0 || term_id >= (int)b.terms.size() || b.terms[term_id].dens_kind != PCLEAN_DENS_NAME3)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: term %d of block %d is not a name3 term", term_id, block_id);
+  const pclean_term& tm = b.terms[term_id];
+  if (tm.ctx_slot >= 0) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: name3 term %d with a ctx slot", term_id);
+  if (!(log_three <= 0.0) || !(log_two <= 0.0))  // (NaN fails too; the gate of the new-row branch relies on terms <= 0)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: the two constants must be log-probabilities <= 0");
+  const PairTable& pp = ctx->pair[tm.pair_table];
+  const PairTable& ps = ctx->pair[suffix_table];
+  if (!pp.valid || !ps.valid || pp.elem_bytes != 1 || ps.elem_bytes != 1)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_set_term_name3: name3 term %d needs its prefix table %d and suffix table %d "
+                                              "built as byte tables (pclean_build_class_table)", term_id, tm.pair_table, suffix_table);
+  if (pp.n_obs != n_obs || ps.n_obs != n_obs || pp.n_lat != n_first || ps.n_lat != n_last)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: name3 term %d: the tables are [%d][%d] and [%d][%d], the "
+                                            "domains %d x %d and %d x %d", term_id, pp.n_obs, pp.n_lat, ps.n_obs, ps.n_lat, n_obs,
+                       n_first, n_obs, n_last);
+  int n_owner_cols = -1;  // columns of the candidate table of the node that owns the term
+  for (const pclean_node& nd : b.nodes)
+    if (term_id >= nd.term_begin && term_id < nd.term_begin + nd.n_terms && ctx->cand[nd.table].valid)
+      n_owner_cols = ctx->cand[nd.table].n_cols;
+  for (int j = 0; j < 3; ++j) {
+    if (src_kind[j] != PCLEAN_NAME3_CAND && src_kind[j] != PCLEAN_NAME3_OBS)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: name3 term %d: source kind %d", term_id, src_kind[j]);
+    const int lim = src_kind[j] == PCLEAN_NAME3_OBS ? ctx->n_cols : n_owner_cols;
+    if (src_col[j] < 0 || (lim >= 0 && src_col[j] >= lim))  // (a table set later is checked per launch)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: name3 term %d: source column %d out of range", term_id,
+                         src_col[j]);
+  }
+  if (src_kind[0] == PCLEAN_NAME3_CAND && src_col[0] != tm.cand_col)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_set_term_name3: name3 term %d: the first name's column is the term's cand_col",
+                       term_id);
+  int ml = 0;
+  int rc = check_string_ids(ctx, n_obs, obs_ids, "obs", &ml);
+  if (!rc) rc = check_string_ids(ctx, n_first, first_ids, "first name", &ml);
+  if (!rc) rc = check_string_ids(ctx, n_mid, mid_ids, "middle name", &ml);
+  if (!rc) rc = check_string_ids(ctx, n_last, last_ids, "last name", &ml);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  (void)hipStreamSynchronize(ctx->stream);
+  Name3Term* n3 = nullptr;
+  for (Name3Term& x : b.name3)
+    if (x.term == term_id) n3 = &x;
+  if (!n3) {
+    b.name3.emplace_back();
+    n3 = &b.name3.back();
+  }
+  n3->term = -1;  // (valid only once everything below is in place)
+  rc = upload_string_spans(ctx, n_obs, obs_ids, &n3->obs_lo, n3->obs_len);
+  if (!rc) rc = upload_string_spans(ctx, n_first, first_ids, nullptr, n3->first_len);
+  if (!rc) rc = upload_string_spans(ctx, n_mid, mid_ids, &n3->mid_lo, n3->mid_len);
+  if (!rc) rc = upload_string_spans(ctx, n_last, last_ids, nullptr, n3->last_len);
+  if (rc) return rc;
+  for (int j = 0; j < 3; ++j) {
+    n3->src_kind[j] = src_kind[j];
+    n3->src_col[j] = src_col[j];
+  }
+  n3->suffix_table = suffix_table;
+  n3->n_obs = n_obs;
+  n3->n_first = n_first;
+  n3->n_mid = n_mid;
+  n3->n_last = n_last;
+  n3->log_three = log_three;
+  n3->log_two = log_two;
+  n3->term = term_id;
+  b.version = ++g_pclean_version;
   return PCLEAN_OK;
 }
 
@@ -1033,6 +1129,9 @@ extern "C" int pclean_load_block(pclean_ctx* ctx, int32_t block_id, int32_t n_no
     if (tm.dens_kind == PCLEAN_DENS_TABULATED && tm.ctx_slot >= 0)
       return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_load_block: tabulated term %d with a ctx slot (a tabulated likelihood of "
                                               "a JuliaNode value) is not supported", i);
+    if (tm.dens_kind == PCLEAN_DENS_NAME3 && tm.ctx_slot >= 0)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_load_block: name3 term %d with a ctx slot (FormatName(first, middle, last) "
+                                              "of a JuliaNode value) is not supported", i);
     if (tm.pair_table < 0 || tm.pair_table >= PCLEAN_MAX_TABLES || tm.ctx_slot >= n_ctx ||
         (tm.ctx_slot >= 0 && (tm.fn_table < 0 || tm.fn_table >= PCLEAN_MAX_TABLES)))
       return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_load_block: term %d malformed", i);
@@ -1043,7 +1142,8 @@ extern "C" int pclean_load_block(pclean_ctx* ctx, int32_t block_id, int32_t n_no
   for (pclean_node& nd : b.nodes)
     if (nd.kind == PCLEAN_NODE_LEAF && nd.cacheable)
       for (int i = 0; i < nd.n_terms; ++i)
-        if (terms[nd.term_begin + i].dens_kind == PCLEAN_DENS_TABULATED) nd.cacheable = 0;
+        if (terms[nd.term_begin + i].dens_kind == PCLEAN_DENS_TABULATED || terms[nd.term_begin + i].dens_kind == PCLEAN_DENS_NAME3)
+          nd.cacheable = 0;  // (a name3 term reads more of the row than one observed column)
   b.children.assign(children, children + n_children);
   b.colmap.assign(colmap, colmap + n_colmap);
   b.n_ctx = n_ctx;
@@ -1075,6 +1175,9 @@ extern "C" int pclean_load_block(pclean_ctx* ctx, int32_t block_id, int32_t n_no
       const int rcd = pclean_ensure_density(ctx, (nodes[i].dummy_spec >> 16) & 0xff);
       if (rcd) return rcd;
     }
+  if (!b.name3.empty()) (void)hipStreamSynchronize(ctx->stream);  // (no kernel reads the old name3 arrays any more)
+  for (Name3Term& n3 : b.name3) n3.release();
+  b.name3.clear();
   b.gauss.clear();
   b.node_gauss.assign(n_nodes, -1);
   b.node_gauss_more.assign(n_nodes, {});

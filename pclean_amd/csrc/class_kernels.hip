@@ -8,6 +8,8 @@
 // pieces of CLS_PIECE symbols, so strings of any length take the same path; every lane walks the piece with its own
 // two-pointer state (O(length of the observed string) per pair) and reads its latent string's next symbol only when its
 // pointer advances.
+// The rules PCLEAN_CLASS_NAME_PREFIX / _SUFFIX (the byte tables of the three-name FormatName term) take the same kernel:
+// a lane's walk is decided at the first mismatch and reads its latent string only at the positions the affix covers.
 // short_count_kernel — the same walk against the option strings; a lane sums over its workgroup's options in a register
 // and adds the partial count with one integer atomic per latent value (sums of integers: order independent).
 #include <algorithm>
@@ -28,6 +30,7 @@ __device__ __forceinline__ int pair_class(const uint16_t* __restrict__ sym, cons
   const uint16_t first = (live && s > 0) ? fold[sym[slo]] : (uint16_t)0;
   ShortWalk w{0, first};
   bool eq = true, init = false;
+  bool affix = name_affix_start(s, l);  // (the two name rules: dotf is the folded separator)
   for (int p0 = 0; p0 < l; p0 += CLS_PIECE) {
     const int np = min(CLS_PIECE, l - p0);
     __syncthreads();  // (the previous piece, or the previous string, is consumed)
@@ -37,6 +40,14 @@ __device__ __forceinline__ int pair_class(const uint16_t* __restrict__ sym, cons
     if (RULE == PCLEAN_CLASS_SHORT_VERSION) {
       if (w.a >= s) continue;  // (matched: nothing left to look for)
       for (int b = 0; b < np; ++b) short_walk_step(w, s, s_long[b], [&](int a) { return fold[sym[slo + a]]; });
+    } else if (RULE == PCLEAN_CLASS_NAME_PREFIX) {
+      if (!affix || p0 > s) continue;  // (decided, or past the separator)
+      for (int b = 0; b < np; ++b)
+        affix = name_prefix_step(affix, p0 + b, s, s_long[b], dotf, [&](int a) { return fold[sym[slo + a]]; });
+    } else if (RULE == PCLEAN_CLASS_NAME_SUFFIX) {
+      if (!affix || p0 + np <= l - s - 1) continue;  // (decided, or the piece ends before the separator)
+      for (int b = 0; b < np; ++b)
+        affix = name_suffix_step(affix, p0 + b, s, l, s_long[b], dotf, [&](int a) { return fold[sym[slo + a]]; });
     } else {
       if (p0 == 0 && l == 2 && s >= 1) init = s_long[0] == first && s_long[1] == dotf;
       const int nb = min(np, s - p0);  // (symbols of the piece that the name has a counterpart for)
@@ -44,6 +55,7 @@ __device__ __forceinline__ int pair_class(const uint16_t* __restrict__ sym, cons
     }
   }
   if (RULE == PCLEAN_CLASS_SHORT_VERSION) return short_walk_class(w, s);
+  if (RULE == PCLEAN_CLASS_NAME_PREFIX || RULE == PCLEAN_CLASS_NAME_SUFFIX) return affix ? 1 : 0;
   return format_name_class_of(eq, init, s, l);
 }
 
@@ -120,6 +132,12 @@ int pclean_launch_class_table(pclean_ctx* ctx, PairTable& pt, const int32_t* d_o
   for_chunks(pt.n_obs, [&](int begin, int gy) {
     if (rule == PCLEAN_CLASS_SHORT_VERSION)
       hipLaunchKernelGGL(class_table_kernel<PCLEAN_CLASS_SHORT_VERSION>, dim3(gx, gy), dim3(CLS_T), 0, ctx->stream, ctx->sym.p,
+                         ctx->off.p, ctx->fold.p, d_obs_ids, d_lat_ids, begin, pt.n_obs, pt.n_lat, dotf, pt.d.p);
+    else if (rule == PCLEAN_CLASS_NAME_PREFIX)
+      hipLaunchKernelGGL(class_table_kernel<PCLEAN_CLASS_NAME_PREFIX>, dim3(gx, gy), dim3(CLS_T), 0, ctx->stream, ctx->sym.p,
+                         ctx->off.p, ctx->fold.p, d_obs_ids, d_lat_ids, begin, pt.n_obs, pt.n_lat, dotf, pt.d.p);
+    else if (rule == PCLEAN_CLASS_NAME_SUFFIX)
+      hipLaunchKernelGGL(class_table_kernel<PCLEAN_CLASS_NAME_SUFFIX>, dim3(gx, gy), dim3(CLS_T), 0, ctx->stream, ctx->sym.p,
                          ctx->off.p, ctx->fold.p, d_obs_ids, d_lat_ids, begin, pt.n_obs, pt.n_lat, dotf, pt.d.p);
     else
       hipLaunchKernelGGL(class_table_kernel<PCLEAN_CLASS_FORMAT_NAME>, dim3(gx, gy), dim3(CLS_T), 0, ctx->stream, ctx->sym.p,

@@ -168,6 +168,25 @@ struct ScoreTerm {
   int32_t obs_col, pair_table, val_block, val_col, key_block, key_col, nopt_fn, other_val;
 };
 
+// What a PCLEAN_DENS_NAME3 term reads besides its pclean_term (pclean_set_term_name3): where the three values come from,
+// the suffix table, and per value of the four domains where its string lies in the pool (start and folded length)
+struct Name3Term {
+  int32_t term = -1;  // index into Block::terms
+  int32_t src_kind[3] = {0, 0, 0}, src_col[3] = {0, 0, 0};
+  int32_t suffix_table = -1, n_obs = 0, n_first = 0, n_mid = 0, n_last = 0;
+  double log_three = 0.0, log_two = 0.0;
+  DevBuf<int64_t> obs_lo, mid_lo;
+  DevBuf<int32_t> obs_len, first_len, mid_len, last_len;
+  void release() {
+    obs_lo.release();
+    mid_lo.release();
+    obs_len.release();
+    first_len.release();
+    mid_len.release();
+    last_len.release();
+  }
+};
+
 struct Block {
   bool valid = false;
   uint64_t version = 0;              // bumped by every pclean_load_block of this block
@@ -180,6 +199,7 @@ struct Block {
   std::vector<std::vector<int32_t>> node_gauss_more;  // per node: its further terms (pclean_add_node_gauss), in order
   std::vector<pclean_node> nodes;
   std::vector<pclean_term> terms;
+  std::vector<Name3Term> name3;      // the block's PCLEAN_DENS_NAME3 terms (few: looked up by term index)
   std::vector<int32_t> children;
   std::vector<int32_t> colmap;
   int32_t n_ctx = 0;

@@ -5,6 +5,25 @@
 #define PCLEAN_MAX_CHILDREN 16
 #define PCLEAN_MAX_TERMS 16
 
+// What a PCLEAN_DENS_NAME3 term reads besides TermDev (FormatName(first, middle, last), format_name.jl:14-26): a record in
+// device memory behind TermDev's one-pointer slot, so that TermDev — and NodeDev, which travels as a kernel argument — keep
+// their size.  TermDev::pair / n_lat are the prefix table over (observed strings, first names).
+struct Name3Dev {
+  const int32_t* src[3];     // first / middle / last value: [n_cand] candidate column (src_kind 0) or [n_rows] observed column (1)
+  int32_t src_kind[3], n_last;
+  const uint8_t* suffix;     // S[obs][last name]
+  const int32_t* obs_len;    // folded lengths (symbols) per observed / first / middle / last value
+  const int32_t* first_len;
+  const int32_t* mid_len;
+  const int32_t* last_len;
+  const int64_t* obs_lo;     // where the observed / middle strings start in sym
+  const int64_t* mid_lo;
+  const uint16_t* sym;
+  const uint16_t* fold;
+  int32_t n_first, n_mid;
+  double log_three, log_two;
+};
+
 struct TermDev {
   const int32_t* obs_col;   // [n_rows] observed value index, -1 = missing
   const int32_t* cand_col;  // [n_cand] latent value index of each candidate
@@ -16,6 +35,7 @@ struct TermDev {
   union {                   // (one slot: a term is of one kind, and NodeDev travels as a kernel argument)
     const int32_t* aux_col; // MAYBE_SWAP: [n_cand] number of options of the candidate's key group
     const double* cls;      // TABULATED: T[n_lat][4], class densities by (latent value, class; 3 = missing observation)
+    const Name3Dev* n3;     // NAME3: the record above
   };
   int32_t other_val, pad2;  // MAYBE_SWAP: first latent value that is "not one of the options" (the dummy; strings drawn for a chosen dummy follow it)
 };
@@ -241,7 +261,7 @@ int pclean_build_priors(pclean_ctx* ctx, const int64_t* counts, const double* lo
 
 // Product leaf (an option table that is a full grid over two value columns, ctx.h: CandTable::grid_outer_col): which factor
 // every term reads and where its cached values start in LDS.  pclean_product_plan returns false when the launch takes the
-// generic kernels: no grid, PCLEAN_NO_PRODUCT_LEAF, evidence sets, a ctx slot / MaybeSwap / Gaussian term, or cached term
+// generic kernels: no grid, PCLEAN_NO_PRODUCT_LEAF, evidence sets, a ctx slot / MaybeSwap / name3 / Gaussian term, or cached term
 // values (plus, for a grouped launch, the prefix array) beyond the LDS of a workgroup.
 struct ProductDev {
   int32_t n_outer, n_inner, total, lds_prefix;  // total: cached doubles; lds_prefix: 1 = the fixed-point prefix lives in LDS too

@@ -57,6 +57,52 @@ __device__ __forceinline__ double tabulated_density(const TermDev& tm, int o, in
   return tm.cls[(size_t)val * 4 + c];
 }
 
+
+// FormatName(first, middle, last) (PCLEAN_DENS_NAME3, format_name.jl:14-26): for an observed string o and the candidate's
+// three values (f, m, l) the term is log_three when lowercase(o) == lowercase("f m l"), log_two when it is
+// lowercase("f l"), else -1000.0; a missing observation is skipped by the callers.  Two byte tables decide nearly every
+// candidate: P[o][f] (o starts with f and a space) and S[o][l] (o ends with a space and l).  With both set and
+// n = |o| - |f| - |l| in folded symbols, n == 1 is "f l" (the two affixes share their space) and "f m l" needs n == 2 + |m|
+// with m's folded symbols at o[|f| + 1 ..) — the space behind m is the one S vouches for.  The middle name is compared on
+// the symbols themselves: where m occurs in o depends on f (o = "al al al al": offset 3 for f = "al", 6 for f = "al al").
+// value j (0 first, 1 middle, 2 last) of candidate k for observed row `row`: a column of the candidate table, or the row's own
+// directly observed value (-1: missing)
+__device__ __forceinline__ int name3_value(const Name3Dev* n3, int j, int k, int row) {
+  return n3->src[j][n3->src_kind[j] == PCLEAN_NAME3_CAND ? k : row];
+}
+// the rare survivor path (both bytes set, room for a middle name), kept out of line so that the kernels that never meet the
+// term keep their registers: n == 2 + |m| and the |m| folded symbols behind "f " agree
+__device__ __noinline__ bool name3_middle_matches(const Name3Dev* n3, int o, int flen, int m, int n) {
+  const int ml = n3->mid_len[m];
+  if (n != ml + 2) return false;
+  const uint16_t* a = n3->sym + n3->obs_lo[o] + flen + 1;  // (flen + 1 + ml < |o|: |o| = flen + |l| + n)
+  const uint16_t* b = n3->sym + n3->mid_lo[m];
+  for (int i = 0; i < ml; ++i)
+    if (n3->fold[a[i]] != n3->fold[b[i]]) return false;
+  return true;
+}
+// from the loaded bytes and lengths (pb / sb: the prefix / suffix byte; f, m, l < 0: a missing direct observation)
+__device__ __forceinline__ double name3_decide(const Name3Dev* n3, int o, int pb, int sb, int n, int flen, int f, int m, int l) {
+  double r = -1000.0;
+  if (pb != 0 && sb != 0 && f >= 0 && l >= 0) {
+    if (n == 1)
+      r = n3->log_two;
+    else if (n >= 2 && m >= 0 && name3_middle_matches(n3, o, flen, m, n))
+      r = n3->log_three;
+  }
+  return r;
+}
+// o >= 0.  The two byte loads and the lengths are issued together and unconditionally, on index 0 for a missing value.
+__device__ __forceinline__ double name3_density(const TermDev& tm, int o, int f, int m, int l) {
+  const Name3Dev* n3 = tm.n3;
+  const int fs = max(f, 0), ls = max(l, 0);
+  const int pb = (int)tm.pair[(size_t)o * tm.n_lat + fs];
+  const int sb = (int)n3->suffix[(size_t)o * n3->n_last + ls];
+  const int flen = n3->first_len[fs];
+  const int n = n3->obs_len[o] - flen - n3->last_len[ls];
+  return name3_decide(n3, o, pb, sb, n, flen, f, m, l);
+}
+
 // MaybeSwap (maybe_swap.jl:13-28): o = observed value index (-1 missing), same = strings equal
 __device__ __forceinline__ double maybe_swap_density(const TermDev& tm, const DensDev& dn, int o, int d, int val, int k,
                                                      int pidx) {
@@ -121,6 +167,9 @@ __device__ __forceinline__ double gauss_term(const NodeDev& nd, const ItemView& 
 // additions (the oracle restates it, oracle/enumerate.h): terms in plan order; per term the DISTINCT (ctx value,
 // observed value) pairs of the evidence rows in ascending order, each adding multiplicity x density — the ~100
 // referring rows of a hospital hold a handful of distinct values per column; then the Gaussian terms row by row.
+// (N3: the kernel instance is one that a node with a PCLEAN_DENS_NAME3 term launches; every other instance is compiled without
+// that term, so that the kernels of all other plans keep the registers and the scratch they had before it existed)
+template <bool N3 = false>
 __device__ __forceinline__ double candidate_score_ev(const NodeDev& nd, const DensDev& dn, const ItemsDev& it,
                                                      const ItemView& v, int k, double sk) {
   const int oi = it.ev_item ? it.ev_item[v.item] : v.item;
@@ -138,6 +187,20 @@ __device__ __forceinline__ double candidate_score_ev(const NodeDev& nd, const De
         const int c = tm.ctx_mode == 0 ? v.ctxv[tm.ctx_slot] : ec;
         const int d = o < 0 ? 1 : (int)tm.pair[(size_t)o * tm.n_lat + val];
         sk += mult * maybe_swap_density(tm, dn, o, d, val, k, c);
+      }
+      continue;
+    }
+    if (N3 && tm.dens_kind == PCLEAN_DENS_NAME3) {  // distinct observed strings ascending, each multiplicity x density; missing: skipped
+      const int r0 = ag.off[oi];
+      if (r0 < r1) {
+        // a value the term takes from the ROW is a directly observed attribute of the latent row itself: its evidence rows
+        // agree on it (their equality constraints), so the first one is read
+        const int row0 = it.ev_rows[v.ev_lo];
+        const int f = name3_value(tm.n3, 0, k, row0), m = name3_value(tm.n3, 1, k, row0), l = name3_value(tm.n3, 2, k, row0);
+        for (int r = r0; r < r1; ++r) {
+          const int o = (int)(ag.key[r] & 0xffffffull) - 1;
+          if (o >= 0) sk += (double)ag.cnt[r] * name3_density(tm, o, f, m, l);
+        }
       }
       continue;
     }
@@ -247,7 +310,7 @@ __device__ __forceinline__ double candidate_score_ev(const NodeDev& nd, const De
 
 // (EV = false: a launch whose items are single rows — the evidence path is compiled out of the kernel, which keeps the
 // registers of enum_node_kernel's single-row instances where they were before candidate_score_ev held a chunk's loads in flight)
-template <bool EV = true>
+template <bool EV = true, bool N3 = false>
 __device__ __forceinline__ double candidate_score(const NodeDev& nd, const DensDev& dn, const ItemsDev& it,
                                                   const ItemView& v, int k) {
   double sk;
@@ -260,12 +323,17 @@ __device__ __forceinline__ double candidate_score(const NodeDev& nd, const DensD
   } else {
     sk = nd.logc_full[k];
   }
-  if (EV && v.ev_lo >= 0) return candidate_score_ev(nd, dn, it, v, k, sk);
+  if (EV && v.ev_lo >= 0) return candidate_score_ev<N3>(nd, dn, it, v, k, sk);
   for (int ti = 0; ti < nd.n_terms; ++ti) {
     const TermDev& tm = nd.terms[ti];
     const int o = tm.obs_col[v.row];
     if (tm.dens_kind == PCLEAN_DENS_TABULATED) {  // (a missing observation is not skipped)
       sk += tabulated_density(tm, o, tm.cand_col[k]);
+      continue;
+    }
+    if (N3 && tm.dens_kind == PCLEAN_DENS_NAME3) {  // (a missing observation is skipped)
+      if (o >= 0)
+        sk += name3_density(tm, o, name3_value(tm.n3, 0, k, v.row), name3_value(tm.n3, 1, k, v.row), name3_value(tm.n3, 2, k, v.row));
       continue;
     }
     if (o < 0) continue;  // explicitly missing observation (add_typos.jl:51-53)
@@ -285,7 +353,7 @@ __device__ __forceinline__ double candidate_score(const NodeDev& nd, const DensD
 // after the other waits for ~4 dependent round trips per term and candidate; a load under a per-candidate condition becomes
 // a branch with its own wait, so every load here is unconditional on a safe index and what must not count is selected away.
 // kk[c] < n_cand for every c (the caller repeats a valid candidate for the slots beyond the list).
-template <int CPT>
+template <int CPT, bool N3 = false>
 __device__ __forceinline__ void candidate_score_batch(const NodeDev& nd, const DensDev& dn, const ItemView& v, const int* kk,
                                                       double* sk) {
   bool on[CPT];
@@ -314,6 +382,37 @@ __device__ __forceinline__ void candidate_score_batch(const NodeDev& nd, const D
     const TermDev& tm = nd.terms[ti];
     const int o = tm.obs_col[v.row];
     if (o < 0 && tm.dens_kind != PCLEAN_DENS_TABULATED) continue;  // explicitly missing observation (add_typos.jl:51-53)
+    if (N3 && tm.dens_kind == PCLEAN_DENS_NAME3) {  // the three values, then both bytes and the lengths of the CPT candidates together
+      const Name3Dev* n3 = tm.n3;
+      int f[CPT], m[CPT], l[CPT], pb[CPT], sb[CPT], fl[CPT], ll[CPT];
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        f[c] = name3_value(n3, 0, kk[c], v.row);
+        m[c] = name3_value(n3, 1, kk[c], v.row);
+        l[c] = name3_value(n3, 2, kk[c], v.row);
+      }
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {  // (a free slot has no defined values: value 0, and nothing counts)
+        f[c] = on[c] ? f[c] : 0;
+        m[c] = on[c] ? m[c] : 0;
+        l[c] = on[c] ? l[c] : 0;
+      }
+      const size_t pbase = (size_t)o * tm.n_lat, sbase = (size_t)o * n3->n_last;
+      const int ol = n3->obs_len[o];
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        pb[c] = (int)tm.pair[pbase + max(f[c], 0)];
+        sb[c] = (int)n3->suffix[sbase + max(l[c], 0)];
+        fl[c] = n3->first_len[max(f[c], 0)];
+        ll[c] = n3->last_len[max(l[c], 0)];
+      }
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {  // (the symbol compare stays under its condition: the rare survivor path)
+        const double r = name3_decide(n3, o, pb[c], sb[c], ol - fl[c] - ll[c], fl[c], f[c], m[c], l[c]);
+        sk[c] += on[c] ? r : 0.0;
+      }
+      continue;
+    }
     int val[CPT], d[CPT];
 #pragma unroll
     for (int c = 0; c < CPT; ++c) val[c] = tm.cand_col[kk[c]];
@@ -426,7 +525,7 @@ __device__ __forceinline__ double new_score(const NodeDev& nd, const ChildrenDev
 // score is <= ub, and ub < score(e) - 28.5 <= max - 28.5 makes its fixed-point weight exactly 0
 // (pclean_fixw).  Such items skip the evaluation of the children: flag 0.  flag = PCLEAN_CHOICE_NEW (the
 // compaction marker) for items that need them.
-template <bool EV>
+template <bool EV, bool N3 = false>
 __global__ void gate_new_kernel(const NodeDev nd, const DensDev dn, const ItemsDev it, const GateDev gt,
                                 int32_t* __restrict__ flag) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -434,7 +533,7 @@ __global__ void gate_new_kernel(const NodeDev nd, const DensDev dn, const ItemsD
   const ItemView v = item_view(nd, it, t);
   bool need = true;
   if (v.excl >= 0 && !v.deleted) {
-    const double bound = candidate_score<EV>(nd, dn, it, v, v.excl);
+    const double bound = candidate_score<EV, N3>(nd, dn, it, v, v.excl);
     double ub = nd.scal[2] - v.logden;
     for (int c = 0; c < gt.n; ++c) {
       if (gt.cache[c] && v.ev_lo < 0) {
@@ -449,13 +548,28 @@ __global__ void gate_new_kernel(const NodeDev nd, const DensDev dn, const ItemsD
   flag[t] = need ? PCLEAN_CHOICE_NEW : 0;
 }
 
+// does the node hold a PCLEAN_DENS_NAME3 term?  Then its launches take the kernel instances compiled with the term.
+static bool node_has_name3(const NodeDev& nd) {
+  for (int i = 0; i < nd.n_terms && i < PCLEAN_MAX_TERMS; ++i)
+    if (nd.terms[i].dens_kind == PCLEAN_DENS_NAME3) return true;
+  return false;
+}
+
 int pclean_launch_gate(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, const GateDev& gt, int32_t* flag) {
   if (it.n <= 0) return PCLEAN_OK;
+  const bool n3 = node_has_name3(nd);
   DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
-  if (it.ev_lo)
-    hipLaunchKernelGGL((gate_new_kernel<true>), dim3((it.n + 255) / 256), dim3(256), 0, ctx->stream, nd, dn, it, gt, flag);
-  else
-    hipLaunchKernelGGL((gate_new_kernel<false>), dim3((it.n + 255) / 256), dim3(256), 0, ctx->stream, nd, dn, it, gt, flag);
+  if (it.ev_lo) {
+    if (n3)
+      hipLaunchKernelGGL((gate_new_kernel<true, true>), dim3((it.n + 255) / 256), dim3(256), 0, ctx->stream, nd, dn, it, gt, flag);
+    else
+      hipLaunchKernelGGL((gate_new_kernel<true>), dim3((it.n + 255) / 256), dim3(256), 0, ctx->stream, nd, dn, it, gt, flag);
+  } else {
+    if (n3)
+      hipLaunchKernelGGL((gate_new_kernel<false, true>), dim3((it.n + 255) / 256), dim3(256), 0, ctx->stream, nd, dn, it, gt, flag);
+    else
+      hipLaunchKernelGGL((gate_new_kernel<false>), dim3((it.n + 255) / 256), dim3(256), 0, ctx->stream, nd, dn, it, gt, flag);
+  }
   HIPCHK(ctx, hipGetLastError());
   return PCLEAN_OK;
 }
@@ -871,7 +985,7 @@ __device__ __forceinline__ uint64_t block_excl_scan(uint64_t part, uint64_t* wsu
   return base + incl - part;
 }
 
-template <int BT, bool EV>
+template <int BT, bool EV, bool N3 = false>
 __global__ __launch_bounds__(BT) void enum_node_kernel(const NodeDev nd, const DensDev dn, const ItemsDev it,
                                                         const ChildrenDev ch, uint64_t seed, uint32_t sweep,
                                                         uint32_t site, int n_draws, int item_base,
@@ -916,7 +1030,7 @@ __global__ __launch_bounds__(BT) void enum_node_kernel(const NodeDev nd, const D
         double sc[ENUM_CPT];
 #pragma unroll
         for (int c = 0; c < ENUM_CPT; ++c) kk[c] = k0 + c * BT < n ? k0 + c * BT : k0;
-        candidate_score_batch<ENUM_CPT>(nd, dn, v, kk, sc);
+        candidate_score_batch<ENUM_CPT, N3>(nd, dn, v, kk, sc);
 #pragma unroll
         for (int c = 0; c < ENUM_CPT; ++c)
           if (k0 + c * BT < n) {
@@ -927,7 +1041,7 @@ __global__ __launch_bounds__(BT) void enum_node_kernel(const NodeDev nd, const D
       }
     } else {
       for (int k = tid; k < n; k += BT) {
-        const double sk = candidate_score<EV>(nd, dn, it, v, k);
+        const double sk = candidate_score<EV, N3>(nd, dn, it, v, k);
         s[k] = sk;
         if (scores_out) scores_out[(size_t)to * nc + k] = sk;
         lmax = fmax(lmax, sk);
@@ -1007,7 +1121,7 @@ __global__ __launch_bounds__(BT) void enum_node_kernel(const NodeDev nd, const D
 // exact scores come from ONE CANDIDATE PER THREAD over (item, candidate) — the same candidate_score() / new_score(), so the
 // same bits — and enum_node_kernel's workgroup per item starts from them (scores_in).  Workgroup (x, y): candidates
 // 256 x .. 256 x + 255 of the slots y, y + gridDim.y, ...; an indirect launch stops at the list's length.
-template <bool EV>
+template <bool EV, bool N3 = false>
 __global__ __launch_bounds__(256) void enum_scores_kernel(const NodeDev nd, const DensDev dn, const ItemsDev it, const ChildrenDev ch,
                                                           double* __restrict__ scores, int slot_cap) {
   const int n = nd.n_cand;
@@ -1022,7 +1136,7 @@ __global__ __launch_bounds__(256) void enum_scores_kernel(const NodeDev nd, cons
     const ItemView v = item_view(nd, it, t);
     double sk;
     if (k < n) {
-      sk = candidate_score<EV>(nd, dn, it, v, k);
+      sk = candidate_score<EV, N3>(nd, dn, it, v, k);
     } else {
       const int to = it.out_pos ? it.out_pos[t] : t;
       sk = new_score(nd, ch, v, to);
@@ -1033,7 +1147,7 @@ __global__ __launch_bounds__(256) void enum_scores_kernel(const NodeDev nd, cons
 
 // BT threads per item: 256 for launches that fill the chip, 1024 for the few-item launches of the latent sweeps (the
 // re-run of a sub-batch's overflowed rows: a dozen workgroups, each walking the whole option list three times)
-template <int BT, bool EV>
+template <int BT, bool EV, bool N3 = false>
 __global__ __launch_bounds__(BT) void enum_node_big_kernel(const NodeDev nd, const DensDev dn, const ItemsDev it,
                                                             const ChildrenDev ch, uint64_t seed, uint32_t sweep,
                                                             uint32_t site, int n_draws, int item_base,
@@ -1064,7 +1178,7 @@ __global__ __launch_bounds__(BT) void enum_node_big_kernel(const NodeDev nd, con
   // pass A: max (lane-strided, coalesced)
   double lmax = -__builtin_inf();
   for (int k = tid; k < n; k += BT) {
-    const double sk = si ? si[k] : candidate_score<EV>(nd, dn, it, v, k);
+    const double sk = si ? si[k] : candidate_score<EV, N3>(nd, dn, it, v, k);
     if (scores_out) scores_out[(size_t)to * nc + k] = sk;
     lmax = fmax(lmax, sk);
   }
@@ -1084,7 +1198,7 @@ __global__ __launch_bounds__(BT) void enum_node_big_kernel(const NodeDev nd, con
   uint64_t part = 0;
   if (m != -__builtin_inf())
     for (int k = lo; k < hi; ++k) {
-      const double sk = (k == n) ? sn : (si ? si[k] : candidate_score<EV>(nd, dn, it, v, k));
+      const double sk = (k == n) ? sn : (si ? si[k] : candidate_score<EV, N3>(nd, dn, it, v, k));
       part += pclean_fixw(sk - m);
     }
   uint64_t U;
@@ -1107,7 +1221,7 @@ __global__ __launch_bounds__(BT) void enum_node_big_kernel(const NodeDev nd, con
         uint64_t acc = pre;
         int k = lo;
         for (; k < hi; ++k) {
-          const double sk = (k == n) ? sn : (si ? si[k] : candidate_score<EV>(nd, dn, it, v, k));
+          const double sk = (k == n) ? sn : (si ? si[k] : candidate_score<EV, N3>(nd, dn, it, v, k));
           acc += pclean_fixw(sk - m);
           if (acc > x) break;
         }
@@ -1641,6 +1755,7 @@ bool pclean_product_plan(const CandTable& table, const NodeDev& nd, const ItemsD
   for (int ti = 0; ti < nd.n_terms; ++ti) {
     const TermDev& tm = nd.terms[ti];
     if (tm.ctx_slot >= 0 || tm.dens_kind == PCLEAN_DENS_MAYBE_SWAP) return false;
+    if (tm.dens_kind == PCLEAN_DENS_NAME3) return false;  // (reads more than one factor: the generic kernels)
     int col = -1;
     for (int c = 0; c < 2; ++c)
       if (tm.cand_col == t->cols.p + (size_t)c * t->n_rows) col = c;
@@ -1727,6 +1842,7 @@ int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, c
   if (product) return pclean_launch_product(ctx, nd, it, *product, seed, sweep, site, n_draws, lse_out, scores_out, draws_out);
   const int nc = nd.n_cand + (nd.kind == PCLEAN_NODE_FK ? 1 : 0);
   const size_t lds = (size_t)((nc + 1) & ~1) * 8 + (16 + 64) * 8;
+  const bool n3 = node_has_name3(nd);
   DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
   // a launch may not exceed 2^32 threads: chunk the items (grid = chunk, 256 lanes each)
   const int kMaxBlocks = 4 * 1024 * 1024;
@@ -1752,33 +1868,57 @@ int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, c
         slot_cap = pclean_enum_split_slots(it, nc);
         if (it.ev_lo) {
           ++ctx->enum_launches[9];
-          hipLaunchKernelGGL((enum_scores_kernel<true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+          if (n3)
+            hipLaunchKernelGGL((enum_scores_kernel<true, true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+                           ch, scores_tmp, slot_cap);
+          else
+            hipLaunchKernelGGL((enum_scores_kernel<true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
         } else {
           ++ctx->enum_launches[8];
-          hipLaunchKernelGGL((enum_scores_kernel<false>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+          if (n3)
+            hipLaunchKernelGGL((enum_scores_kernel<false, true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+                           ch, scores_tmp, slot_cap);
+          else
+            hipLaunchKernelGGL((enum_scores_kernel<false>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
         }
         scores_in = scores_tmp;
       }
       if (it.ev_lo) {
         ++ctx->enum_launches[7];
-        hipLaunchKernelGGL((enum_node_big_kernel<1024, true>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+        if (n3)
+          hipLaunchKernelGGL((enum_node_big_kernel<1024, true, true>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+                         n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
+        else
+          hipLaunchKernelGGL((enum_node_big_kernel<1024, true>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                          n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
       } else {
         ++ctx->enum_launches[6];
-        hipLaunchKernelGGL((enum_node_big_kernel<1024, false>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+        if (n3)
+          hipLaunchKernelGGL((enum_node_big_kernel<1024, false, true>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+                         n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
+        else
+          hipLaunchKernelGGL((enum_node_big_kernel<1024, false>), dim3(it.n), dim3(1024), 0, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                          n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
       }
     } else {
       for (int base = 0; base < it.n; base += kMaxBlocks)
         if (it.ev_lo) {
           ++ctx->enum_launches[5];
-          hipLaunchKernelGGL((enum_node_big_kernel<256, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
+          if (n3)
+            hipLaunchKernelGGL((enum_node_big_kernel<256, true, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
+                           dn, it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
+          else
+            hipLaunchKernelGGL((enum_node_big_kernel<256, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
                            dn, it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
         } else {
           ++ctx->enum_launches[4];
-          hipLaunchKernelGGL((enum_node_big_kernel<256, false>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
+          if (n3)
+            hipLaunchKernelGGL((enum_node_big_kernel<256, false, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
+                           dn, it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
+          else
+            hipLaunchKernelGGL((enum_node_big_kernel<256, false>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), 0, ctx->stream, nd,
                            dn, it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
         }
     }
@@ -1789,6 +1929,10 @@ int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, c
       HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<256, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<1024, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<256, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)enum_node_kernel<1024, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set = true;
     }
     if (few) {  // (groups or items) too few workgroups to fill the chip: more threads per item
@@ -1799,33 +1943,57 @@ int pclean_launch_enum(pclean_ctx* ctx, const NodeDev& nd, const ItemsDev& it, c
         slot_cap = pclean_enum_split_slots(it, nc);
         if (it.ev_lo) {
           ++ctx->enum_launches[9];
-          hipLaunchKernelGGL((enum_scores_kernel<true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+          if (n3)
+            hipLaunchKernelGGL((enum_scores_kernel<true, true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+                           ch, scores_tmp, slot_cap);
+          else
+            hipLaunchKernelGGL((enum_scores_kernel<true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
         } else {
           ++ctx->enum_launches[8];
-          hipLaunchKernelGGL((enum_scores_kernel<false>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+          if (n3)
+            hipLaunchKernelGGL((enum_scores_kernel<false, true>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
+                           ch, scores_tmp, slot_cap);
+          else
+            hipLaunchKernelGGL((enum_scores_kernel<false>), dim3((nc + 255) / 256, std::min(slot_cap, 1024)), dim3(256), 0, ctx->stream, nd, dn, it,
                            ch, scores_tmp, slot_cap);
         }
         scores_in = scores_tmp;
       }
       if (it.ev_lo) {
         ++ctx->enum_launches[3];
-        hipLaunchKernelGGL((enum_node_kernel<1024, true>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+        if (n3)
+          hipLaunchKernelGGL((enum_node_kernel<1024, true, true>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+                           n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
+        else
+          hipLaunchKernelGGL((enum_node_kernel<1024, true>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                            n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
       } else {
         ++ctx->enum_launches[2];
-        hipLaunchKernelGGL((enum_node_kernel<1024, false>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+        if (n3)
+          hipLaunchKernelGGL((enum_node_kernel<1024, false, true>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
+                           n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
+        else
+          hipLaunchKernelGGL((enum_node_kernel<1024, false>), dim3(it.n), dim3(1024), lds, ctx->stream, nd, dn, it, ch, seed, sweep, site,
                            n_draws, 0, lse_out, scores_out, draws_out, scores_in, slot_cap);
       }
     } else {
       for (int base = 0; base < it.n; base += kMaxBlocks)
         if (it.ev_lo) {
           ++ctx->enum_launches[1];
-          hipLaunchKernelGGL((enum_node_kernel<256, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
+          if (n3)
+            hipLaunchKernelGGL((enum_node_kernel<256, true, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
+                             it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
+          else
+            hipLaunchKernelGGL((enum_node_kernel<256, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
                              it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
         } else {
           ++ctx->enum_launches[0];
-          hipLaunchKernelGGL((enum_node_kernel<256, false>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
+          if (n3)
+            hipLaunchKernelGGL((enum_node_kernel<256, false, true>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
+                             it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
+          else
+            hipLaunchKernelGGL((enum_node_kernel<256, false>), dim3(std::min(kMaxBlocks, it.n - base)), dim3(256), lds, ctx->stream, nd, dn,
                              it, ch, seed, sweep, site, n_draws, base, lse_out, scores_out, draws_out, (const double*)nullptr, 0);
         }
     }

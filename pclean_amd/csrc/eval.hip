@@ -92,6 +92,67 @@ int build_gauss_more(pclean_ctx* ctx, const Block& b, int node_id, const CandTab
   return PCLEAN_OK;
 }
 
+// A name3 record travels as a kernel argument and is written to the call's scratch word by word, as the further Gaussian
+// terms are (build_gauss_more): valid for every kernel launched on ctx->stream afterwards in this call, and for those only.
+static_assert(sizeof(Name3Dev) % 4 == 0 && sizeof(Name3Dev) <= 1024, "Name3Dev: one block of 256 words");
+__global__ __launch_bounds__(256) void name3_store_kernel(Name3Dev a, uint32_t* __restrict__ dst) {
+  const int i = threadIdx.x;
+  if (i < (int)(sizeof(Name3Dev) / 4)) dst[i] = reinterpret_cast<const uint32_t*>(&a)[i];
+}
+
+// term `term_id` of block b (PCLEAN_DENS_NAME3) resolved to device pointers for candidate table t
+static int build_name3_dev(pclean_ctx* ctx, const Block& b, int term_id, const pclean_term& tm, const CandTable& t,
+                           const PairTable& pt, const Name3Dev** out) {
+  const Name3Term* n3 = nullptr;
+  for (const Name3Term& x : b.name3)
+    if (x.term == term_id) n3 = &x;
+  if (!n3)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "name3 term %d: its sources and tables are not set (pclean_set_term_name3)", term_id);
+  if (tm.ctx_slot >= 0 || pt.elem_bytes != 1)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "name3 term %d: needs a 1-byte prefix table and no ctx slot", term_id);
+  const PairTable& ps = ctx->pair[n3->suffix_table];
+  if (!ps.valid || ps.elem_bytes != 1 || ps.n_obs != n3->n_obs || ps.n_lat != n3->n_last || pt.n_obs != n3->n_obs ||
+      pt.n_lat != n3->n_first)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "name3 term %d: the prefix / suffix tables were rebuilt with another shape since "
+                                              "pclean_set_term_name3", term_id);
+  if (ctx->n_fold < ctx->n_symbols)
+    return pclean_fail(ctx, PCLEAN_ERR_STATE, "name3 term %d: the fold table does not cover the pool (pclean_set_fold_table)", term_id);
+  Name3Dev d;
+  memset(&d, 0, sizeof d);
+  for (int j = 0; j < 3; ++j) {
+    d.src_kind[j] = n3->src_kind[j];
+    if (n3->src_kind[j] == PCLEAN_NAME3_CAND) {
+      if (n3->src_col[j] >= t.n_cols) return pclean_fail(ctx, PCLEAN_ERR_ARG, "name3 term %d: candidate column out of range", term_id);
+      d.src[j] = t.cols.p + (size_t)n3->src_col[j] * t.n_rows;
+    } else {
+      if (n3->src_col[j] >= ctx->n_cols) return pclean_fail(ctx, PCLEAN_ERR_ARG, "name3 term %d: observed column out of range", term_id);
+      if (ctx->obs_override)  // (never: a leaf with this term is not cacheable)
+        return pclean_fail(ctx, PCLEAN_ERR_ARG, "name3 term %d: no per-observed-value cache", term_id);
+      d.src[j] = ctx->obs.p + (size_t)n3->src_col[j] * ctx->n_rows + ctx->active_begin;
+    }
+  }
+  d.n_last = n3->n_last;
+  d.n_first = n3->n_first;
+  d.n_mid = n3->n_mid;
+  d.suffix = ps.d.p;
+  d.obs_len = n3->obs_len.p;
+  d.first_len = n3->first_len.p;
+  d.mid_len = n3->mid_len.p;
+  d.last_len = n3->last_len.p;
+  d.obs_lo = n3->obs_lo.p;
+  d.mid_lo = n3->mid_lo.p;
+  d.sym = ctx->sym.p;
+  d.fold = ctx->fold.p;
+  d.log_three = n3->log_three;
+  d.log_two = n3->log_two;
+  Name3Dev* dst = scratch<Name3Dev>(ctx, 1);
+  if (!dst) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(name3_store_kernel, dim3(1), dim3(256), 0, ctx->stream, d, (uint32_t*)dst);
+  HIPCHK(ctx, hipGetLastError());
+  *out = dst;
+  return PCLEAN_OK;
+}
+
 int build_node_dev(pclean_ctx* ctx, const Block& b, int node_id, NodeDev& nd) {
   const pclean_node& n = b.nodes[node_id];
   const CandTable& t = ctx->cand[n.table];
@@ -158,6 +219,11 @@ int build_node_dev(pclean_ctx* ctx, const Block& b, int node_id, NodeDev& nd) {
         return pclean_fail(ctx, PCLEAN_ERR_STATE, "tabulated term %d: pair table %d has no class densities "
                                                   "(pclean_set_class_density)", n.term_begin + i, tm.pair_table);
       td.cls = pt.cls.p;
+      continue;
+    }
+    if (tm.dens_kind == PCLEAN_DENS_NAME3) {
+      const int rc = build_name3_dev(ctx, b, n.term_begin + i, tm, t, pt, &td.n3);
+      if (rc) return rc;
       continue;
     }
     if (tm.ctx_slot >= 0) {
@@ -332,11 +398,13 @@ static int cols_union(pclean_ctx* ctx, CandTable& t, uint64_t base, uint64_t col
   return 1;
 }
 
-// a node with a tabulated term (PCLEAN_DENS_TABULATED) goes through the generic enumeration kernels alone: no compact byte
-// tables, no per-observed-value cache (a missing observation of such a term counts)
+// a node with a tabulated term (PCLEAN_DENS_TABULATED) or a name3 term (PCLEAN_DENS_NAME3) goes through the generic
+// enumeration kernels alone: no compact byte tables, no per-observed-value cache (a missing observation of a tabulated
+// term counts; a name3 term reads three values of the candidate and is no lookup in one table)
 static bool node_has_tabulated(const Block& b, const pclean_node& n) {
   for (int i = 0; i < n.n_terms; ++i)
-    if (b.terms[n.term_begin + i].dens_kind == PCLEAN_DENS_TABULATED) return true;
+    if (b.terms[n.term_begin + i].dens_kind == PCLEAN_DENS_TABULATED || b.terms[n.term_begin + i].dens_kind == PCLEAN_DENS_NAME3)
+      return true;
   return false;
 }
 
@@ -1345,6 +1413,14 @@ static bool subtree_key(pclean_ctx* ctx, const Block& b, int node_id, std::set<i
     const pclean_term& tm = b.terms[n.term_begin + i];
     if (tm.dens_kind == PCLEAN_DENS_MAYBE_SWAP) return false;
     cols.insert(tm.obs_col);
+    if (tm.dens_kind == PCLEAN_DENS_NAME3) {  // (the row's directly observed names are part of what the term reads)
+      const Name3Term* n3 = nullptr;
+      for (const Name3Term& x : b.name3)
+        if (x.term == n.term_begin + i) n3 = &x;
+      if (!n3) return false;
+      for (int j = 0; j < 3; ++j)
+        if (n3->src_kind[j] == PCLEAN_NAME3_OBS) cols.insert(n3->src_col[j]);
+    }
     if (tm.ctx_slot >= 0) use_ctx = true;
   }
   for (int c = 0; c < n.n_children; ++c)
@@ -2052,6 +2128,11 @@ static int eval_node_lse(pclean_ctx* ctx, int block_id, int node_id, const ItemL
     const pclean_term& tm = b.terms[n.term_begin + i];
     ver = ver * 1000003ull + ctx->pair[tm.pair_table].version;
     if (tm.ctx_slot >= 0) ver = ver * 1000003ull + (uint64_t)(tm.fn_table + 1);
+    if (tm.dens_kind == PCLEAN_DENS_NAME3) {  // (its suffix table, and whatever pclean_set_term_name3 last set)
+      for (const Name3Term& x : b.name3)
+        if (x.term == n.term_begin + i) ver = ver * 1000003ull + ctx->pair[x.suffix_table].version;
+      ver = ver * 1000003ull + b.version;
+    }
   }
   SweepState::LeafMemo& mm = s->memo[block_id * 64 + node_id];
   const int cap = 1 << 21;

@@ -1576,6 +1576,10 @@ int prior_mode_supported(pclean_ctx* ctx, const Block& b, const char* who) {
       return pclean_fail(ctx, PCLEAN_ERR_ARG, "%s: a tabulated likelihood term (ExpandOnShortVersion / FormatName) under "
                                               "use_dd_proposals = false (prior proposals) is not supported", who);
   for (const pclean_term& tm : b.terms)
+    if (tm.dens_kind == PCLEAN_DENS_NAME3)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "%s: a name3 likelihood term (FormatName(first, middle, last)) under "
+                                              "use_dd_proposals = false (prior proposals) is not supported", who);
+  for (const pclean_term& tm : b.terms)
     ok = ok && (tm.dens_kind == PCLEAN_DENS_ADD_TYPOS || tm.dens_kind == PCLEAN_DENS_EQUAL || tm.dens_kind == PCLEAN_DENS_MAYBE_SWAP);
   // a Gaussian term: on the slot of an observed-class block (gauss_prior_kernel scores it once per particle at the sampled
   // own choices; its copies on the nodes of a new row's choices are there for the enumeration and are not looked at), or the

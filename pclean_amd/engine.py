@@ -273,14 +273,19 @@ class Engine:
         self._gauss_pending = bool(getattr(lw, "gauss", {}))
 
     def _upload_class_tables(self):
-        """Tabulated terms (ExpandOnShortVersion / FormatName): the class table of every such pair, built on the device,
-        and its densities T[value][class 0..2, missing], evaluated here once in float64 (class_density_rows)."""
+        """Tabulated terms (ExpandOnShortVersion / FormatName): the class table of every such pair, built on the device
+        (for FormatName(first, middle, last) the prefix and suffix tables), and its densities T[value][class 0..2, missing], evaluated here once in float64 (class_density_rows)."""
         lw, hip = self.lw, self.hip
         if not getattr(lw, "class_pairs", None):
             return
         hip.set_fold_table(lw.pool.fold_symbols())
         for pid, (rule, odom, ldom, options) in lw.class_pairs.items():
             li = ldom.id_array()
+            if rule in (_lib.CLASS_NAME_PREFIX, _lib.CLASS_NAME_SUFFIX):
+                # the two byte tables of a three-name FormatName: the separator is the space; no class densities (the
+                # term's two constants travel with set_term_name3, LoweredModel.load_blocks_into)
+                hip.build_class_table(pid, odom.id_array(), li, rule, lw.pool.symbol_of(" "))
+                continue
             hip.build_class_table(pid, odom.id_array(), li, rule, lw.pool.symbol_of("."))
             strings = [ldom.string(v) for v in range(len(ldom))]
             counts = None

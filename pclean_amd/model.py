@@ -14,6 +14,7 @@ The reference JIT-compiles one Julia function per (class, block, observed set)
 (inference/proposal_compiler.jl); here the same enumeration structure is emitted
 once as flat arrays (nodes / terms / children / colmap, include/pclean_hip.h).
 """
+import math
 from contextlib import contextmanager
 
 import numpy as np
@@ -69,15 +70,28 @@ class ExpandOnShortVersion:
 
 
 class FormatName:
-    """format_name.jl:29-55, the one-name method: FormatName(name) is the name itself or its initial + "."."""
+    """format_name.jl:29-55, the one-name method: FormatName(name) is the name itself or its initial + "."; and
+    format_name.jl:14-26, the three-name method, written with keywords: FormatName(first=.., middle=.., last=..) is
+    "first middle last" or "first last" (`refs` holds the three references, `ref` the first).  Several POSITIONAL
+    references stay refused, as they always were: which of them is the first, the middle and the last name is said by name."""
 
-    def __init__(self, ref, *more):
+    def __init__(self, ref=None, *more, first=None, middle=None, last=None):
         if more:
-            raise NotImplementedError("FormatName(first, middle, last): first / middle / last form: not lowered")
-        self.ref = ref
+            raise NotImplementedError("FormatName(first, middle, last): first / middle / last form: not lowered from positional "
+                                      "references; name them: FormatName(first=..., middle=..., last=...)")
+        named = (first, middle, last)
+        if ref is not None and all(x is None for x in named):
+            self.ref, self.refs = ref, None
+        elif ref is None and all(isinstance(x, str) for x in named):
+            self.ref, self.refs = first, named
+        else:
+            raise ValueError("FormatName takes one name, or first=, middle= and last=")
 
 
 TABULATED = (ExpandOnShortVersion, FormatName)
+# the two densities of the three-name FormatName (format_name.jl:18, 22), added left to right as the reference adds them
+NAME3_LOG_THREE = math.log(0.9) + math.log(0.9) + math.log(0.9)
+NAME3_LOG_TWO = math.log(0.1)
 
 
 class TimePrior:
@@ -341,6 +355,7 @@ class LoweredModel:
         self.same_pairs = {}   # pair id -> (observed domain, latent domain): 0 iff same string
         self.class_pairs = {}  # pair id -> (class rule, observed domain, latent domain, options or None): tabulated terms
         self._class_key = {}
+        self.name3_terms = {}  # block id (observed-class block or latent plan) -> {term index: spec}: see _lower_name3
         self.prob_spec = None
         self.gauss = {}        # (block id, node id) -> dict spec (resolved by the engine): the node's first Gaussian term
         self.gauss_more = {}   # (block id, node id) -> [dict spec, ...]: its further terms, in declaration order
@@ -659,12 +674,16 @@ class LoweredModel:
             self._next_pair += 1
         return self.pair_id[key][0]
 
-    def _class_pair_for(self, dirty, lat_dom_key, dist):
-        """class table of a tabulated observation (ExpandOnShortVersion / FormatName) over obs domain x latent domain"""
-        key = (dirty, lat_dom_key)
+    def _class_pair_for(self, dirty, lat_dom_key, dist, rule=None):
+        """class table of a tabulated observation (ExpandOnShortVersion / FormatName) over obs domain x latent domain;
+        `rule` given: one of the two byte tables of a three-name FormatName (CLASS_NAME_PREFIX / CLASS_NAME_SUFFIX)"""
+        key = (dirty, lat_dom_key) if rule is None else (dirty, lat_dom_key, rule)
         if key not in self._class_key:
-            rule, options = ((_lib.CLASS_SHORT_VERSION, list(dist.options)) if isinstance(dist, ExpandOnShortVersion)
-                             else (_lib.CLASS_FORMAT_NAME, None))
+            if rule is not None:
+                options = None
+            else:
+                rule, options = ((_lib.CLASS_SHORT_VERSION, list(dist.options)) if isinstance(dist, ExpandOnShortVersion)
+                                 else (_lib.CLASS_FORMAT_NAME, None))
             if options is not None:
                 self.pool.add_all(options)  # (the device counts over the option strings: they live in the pool)
             self.class_pairs[self._next_pair] = (rule, self.obs_dom[dirty], self.latent_dom[lat_dom_key], options)
@@ -732,6 +751,9 @@ class LoweredModel:
             terms = []
             for a in self._obs_terms_of_block(ocls, names):
                 ref = a.dist.ref
+                if isinstance(a.dist, FormatName) and a.dist.refs is not None:
+                    terms.append(self._lower_name3(a, root_fk))
+                    continue
                 if isinstance(a.dist, TABULATED):
                     # a term DENS_TABULATED exactly where an AddTypos term of the same `ref` would go
                     if "." not in ref:
@@ -814,10 +836,79 @@ class LoweredModel:
                     terms.append(dict(obs=obsname, path=obsname.split(".", 1)[1], pair=self._eq_pair_for(key),
                                       max_typos=None, ctx=None, dens=_lib.DENS_EQUAL))
             self._emit_fk_node(blk, root_fk.target, "", terms, parent=-1, parent_fk_col=-1)
+            if blk.get("name3"):
+                self.name3_terms[bi] = blk["name3"]
             self.blocks.append(blk)
             self._lower_gaussian(bi, blk, ocls, names, root_fk)
 
-    def _emit_term(self, blk, t, cand_col):
+    def _lower_name3(self, a, root_fk):
+        """`a ~ FormatName(first, middle, last)` (format_name.jl:14-26) -> one term DENS_NAME3 that reads three values of the
+        candidate: on the slot's node three columns of the flattened candidate table; in the new-row branch the reference
+        enumerates the unobserved names JOINTLY (proposal_compiler.jl:55-129), which the forest of separable leaves has no
+        place for — so at most one of the three may be an enumerated choice, whose leaf carries the term and reads the
+        other two from the row's own direct observations (never missing, so that the evidence rows of one latent row
+        agree on them); with all three observed the first name's leaf carries it."""
+        m = self.model
+        who = f"{a.name}: FormatName({', '.join(a.dist.refs)})"
+        rests, keys = [], []
+        for ref in a.dist.refs:
+            if "." not in ref:
+                raise NotImplementedError(f"{who}: {ref} is a JuliaNode value or an own attribute, not a value of the block's "
+                                          "reference slot; not lowered")
+            head, rest = ref.split(".", 1)
+            if head != root_fk.name:
+                raise NotImplementedError(f"{who}: {ref} is a reference outside the block's root slot {root_fk.name}")
+            cname, la = m.resolve(root_fk.target, rest)
+            if la.kind != "choice":
+                raise NotImplementedError(f"{who}: {ref} is a JuliaNode value or a reference slot, not a choice; not lowered")
+            if (cname, la.name) not in self.latent_dom:
+                raise NotImplementedError(f"{who}: {ref} is a value without a string domain")
+            rests.append(rest)
+            keys.append((cname, la.name))
+        if len({k[0] for k in keys}) != 1 or len({r.rpartition(".")[0] for r in rests}) != 1:
+            raise NotImplementedError(f"{who}: the three names must be attributes of one class reached through one path")
+        if len(set(keys)) != 3:
+            raise NotImplementedError(f"{who}: the three names must be three different attributes")
+        obsnames = [root_fk.name + "." + r for r in rests]
+        open_ = [i for i, o in enumerate(obsnames) if o not in self.direct_obs]
+        if len(open_) > 1:
+            raise NotImplementedError(f"{who}: {' and '.join(a.dist.refs[i] for i in open_)} are {'both' if len(open_) == 2 else 'all'} enumerated choices of a new "
+                                      f"{keys[0][0]} row; the reference would enumerate the product of their options, which "
+                                      "the separable leaves of a new row cannot hold — at most one of the three names may be "
+                                      "unobserved")
+        for i, o in enumerate(obsnames):
+            if i not in open_ and o not in self._never_missing:
+                raise NotImplementedError(f"{who}: the directly observed name {a.dist.refs[i]} is missing in some rows; then "
+                                          "the reference would enumerate the product of it and the other names")
+        carrier = keys[open_[0] if open_ else 0][1]
+        if (keys[0][0], carrier) in self.product_index or self.indexed.get((keys[0][0], carrier), ("", ""))[0] == "product":
+            raise NotImplementedError(f"{who}: {carrier} is enumerated jointly with another choice (a product leaf); the "
+                                      "reference would enumerate the product with the names")
+        prefix = self._class_pair_for(a.name, keys[0], a.dist, _lib.CLASS_NAME_PREFIX)
+        suffix = self._class_pair_for(a.name, keys[2], a.dist, _lib.CLASS_NAME_SUFFIX)
+        return dict(obs=a.name, path=rests[0], pair=prefix, max_typos=None, ctx=None, dens=_lib.DENS_NAME3,
+                    name3=dict(paths=tuple(rests), suffix=suffix, doms=tuple(keys), carrier=carrier, obsnames=tuple(obsnames)))
+
+    @staticmethod
+    def _below(t, head):
+        """term t as the sub-tree of reference slot `head` sees it (paths relative to it), None when it lives elsewhere"""
+        if "." not in t["path"] or t["path"].split(".", 1)[0] != head:
+            return None
+        t = dict(t, path=t["path"].split(".", 1)[1])
+        if t.get("name3"):  # (the three names share their path: _lower_name3)
+            t["name3"] = dict(t["name3"], paths=tuple(p.split(".", 1)[1] for p in t["name3"]["paths"]))
+        return t
+
+    def name3_call(self, spec):
+        """arguments of set_term_name3 behind (block, term) for the spec `_emit_term` recorded"""
+        odom = self.obs_dom[spec["obs"]]
+        f, mid, last = (self.latent_dom[k] for k in spec["doms"])
+        return ([k for k, _ in spec["src"]], [c for _, c in spec["src"]], spec["suffix"], odom.id_array(), f.id_array(),
+                mid.id_array(), last.id_array(), NAME3_LOG_THREE, NAME3_LOG_TWO)
+
+    def _emit_term(self, blk, t, cand_col, n3src=None):
+        if t.get("name3"):
+            blk.setdefault("name3", {})[len(blk["terms"])] = dict(t["name3"], obs=t["obs"], src=list(n3src))
         blk["terms"].append((self.obs_index[t["obs"]], cand_col, t["pair"], t.get("dens", _lib.DENS_ADD_TYPOS),
                              -1 if t["max_typos"] is None else int(t["max_typos"]),
                              -1 if t["ctx"] is None else t["ctx"][0], -1 if t["ctx"] is None else t["ctx"][1], 0))
@@ -831,15 +922,16 @@ class LoweredModel:
         blk["node_info"].append(dict(kind="fk", cls=cname, attr=None, path=prefix[:-1]))
         tb = len(blk["terms"])
         for t in terms:
-            self._emit_term(blk, t, self.colidx[cname][t["path"]])
+            n3 = t.get("name3")
+            self._emit_term(blk, t, self.colidx[cname][t["path"]],
+                            n3 and [(_lib.NAME3_CAND, self.colidx[cname][p]) for p in n3["paths"]])
         nt = len(blk["terms"]) - tb
         # children: own attributes of the class, in declaration order
         kids = []
         colsrc = {}
         for a in m.classes[cname].attrs:
             if a.kind == "fk":
-                sub = [dict(t, path=t["path"].split(".", 1)[1]) for t in terms if t["path"].split(".", 1)[0] == a.name
-                       and "." in t["path"]]
+                sub = [x for x in (self._below(t, a.name) for t in terms) if x is not None]
                 cid = self._emit_fk_node(blk, a.target, prefix + a.name + ".", sub, nid, self.colidx[cname][a.name])
                 kids.append(cid)
                 colsrc[a.name] = (-1, -1)
@@ -851,10 +943,19 @@ class LoweredModel:
                 prod = self.indexed.get((cname, a.name), ("", ""))
                 prod = prod[1] if prod[0] == "product" else None
                 # (a product leaf: the terms of the index read value column 0, those of the choice column 1, declaration order)
-                sub = [t for t in terms if t["path"] == a.name or (prod is not None and t["path"] == prod)]
+                def here(t):  # (a name3 term sits on the leaf of its carrier, whichever of its names that is)
+                    if t.get("name3"):
+                        return "." not in t["path"] and t["name3"]["carrier"] == a.name
+                    return t["path"] == a.name or (prod is not None and t["path"] == prod)
+                sub = [t for t in terms if here(t)]
                 cid = len(blk["nodes"])
                 ltb = len(blk["terms"])
                 for t in sub:
+                    if t.get("name3"):  # the option's value for this name, the row's own observations for the other two
+                        src = [(_lib.NAME3_CAND, 0) if p == a.name else (_lib.NAME3_OBS, self.obs_index[o])
+                               for p, o in zip(t["name3"]["paths"], t["name3"]["obsnames"])]
+                        self._emit_term(blk, t, 0, src)
+                        continue
                     self._emit_term(blk, t, 1 if prod is not None and t["path"] == a.name else 0)
                 n_leaf_terms = len(sub)
                 keyed_by = self.keyed_index(cname, a.name) if prod is None else None
@@ -868,7 +969,7 @@ class LoweredModel:
                     n_leaf_terms += 1
                 # (the per-observed-value cache has no slot for the missing observation a tabulated term scores)
                 cacheable = int(n_leaf_terms == 1 and len(sub) == 1 and sub[0]["ctx"] is None
-                                and sub[0].get("dens") != _lib.DENS_TABULATED and prod is None)
+                                and sub[0].get("dens") not in (_lib.DENS_TABULATED, _lib.DENS_NAME3) and prod is None)
                 # the ProposalDummyValue of the proposal (string_prior.jl:16-26, time_prior.jl:15-19): which latent
                 # value is the placeholder and what random(dist) samples when the dummy is chosen
                 dval, dspec = 0, 0
@@ -916,6 +1017,11 @@ class LoweredModel:
                 target.load_block(bi, *self.block_arrays(bi))
         for cname, pl in self.latent_plans.items():
             target.load_block(pl["block_id"], *self.latent_block_arrays(cname))
+        for bid, specs in self.name3_terms.items():  # (after the blocks: pclean_load_block forgets them)
+            if not hasattr(target, "set_term_name3"):
+                raise NotImplementedError("FormatName(first, middle, last): this target does not know name3 terms")
+            for ti, spec in specs.items():
+                target.set_term_name3(bid, ti, *self.name3_call(spec))
         if len(set(self.block_group)) < len(self.block_group):  # a model block with several reference slots
             for bi, g in enumerate(self.block_group):
                 target.set_block_group(bi, g)
@@ -1173,10 +1279,12 @@ class LoweredModel:
         plan["nodes"].append(None)
         plan["node_info"].append(dict(info))
         tb = len(plan["terms"])
-        for t in blk["terms"][node[2]:node[2] + node[3]]:
+        for ti, t in enumerate(blk["terms"][node[2]:node[2] + node[3]], start=node[2]):
             t = list(t)
             if t[5] >= 0:
                 t[7] = 1  # ctx now comes from the evidence row (fn[ctx][candidate])
+            if ti in blk.get("name3", {}):  # (its sources go with it: the option's value, the evidence rows' observations)
+                self.name3_terms.setdefault(plan["block_id"], {})[len(plan["terms"])] = blk["name3"][ti]
             plan["terms"].append(tuple(t))
         # cross-block julia observations whose other argument lives in this sub-tree
         for ct in self.cross_terms:
