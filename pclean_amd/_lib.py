@@ -72,6 +72,13 @@ class RootStats(C.Structure):
                 ("resolved_groups", C.c_int32), ("pre_scored", C.c_int32), ("lazy_entries", C.c_int32)]
 
 
+class OwnStats(C.Structure):
+    """pclean_own_stats: what the last pclean_sweep_own / pclean_score_own call did"""
+    _fields_ = [("variants", C.c_int32), ("n_runs", C.c_int32), ("longest_run", C.c_int32), ("n_workgroups", C.c_int32),
+                ("impossible_rows", C.c_int32), ("first_impossible_row", C.c_int32), ("lds_options", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class CommitSlot(C.Structure):
     _fields_ = [("table_id", C.c_int32), ("n_hw", C.c_int32), ("n_free", C.c_int32), ("cols_changed", C.c_int32),
                 ("created", C.c_int32), ("deleted", C.c_int32), ("total", C.c_int64), ("live", C.c_int64),
@@ -1020,6 +1027,59 @@ class HipContext:
                                                    C.c_uint32(sweep), _p(chosen, C.c_int32), _p(tot, C.c_double)),
               "pclean_final_choice")
         return chosen, tot
+
+    # -- own blocks: a flat observed class (csrc/own_block.hip) -----------------------------------------------------
+    def load_own_block(self, block_id, nodes, terms):
+        nodes = np.ascontiguousarray(nodes, dtype=NODE_DTYPE)
+        terms = np.ascontiguousarray(terms, dtype=TERM_DTYPE)
+        check(self.h, self.lib.pclean_load_own_block(
+            self.h, C.c_int32(block_id), C.c_int32(len(nodes)), nodes.ctypes.data_as(C.c_void_p), C.c_int32(len(terms)),
+            terms.ctypes.data_as(C.c_void_p)), "pclean_load_own_block")
+
+    def set_own(self, block_id, vals):
+        """current values int32 [n_nodes][n_rows] of every loaded row (-1 = none yet); None clears them"""
+        if vals is None:
+            check(self.h, self.lib.pclean_set_own(self.h, C.c_int32(block_id), None, C.c_int32(0)), "pclean_set_own")
+            return
+        vals = np.ascontiguousarray(vals, dtype=np.int32)
+        check(self.h, self.lib.pclean_set_own(self.h, C.c_int32(block_id), _p(vals, C.c_int32), C.c_int32(vals.shape[1])),
+              "pclean_set_own")
+
+    def get_own(self, block_id, n_nodes, n_rows):
+        out = np.empty((n_nodes, n_rows), dtype=np.int32)
+        check(self.h, self.lib.pclean_get_own(self.h, C.c_int32(block_id), _p(out, C.c_int32)), "pclean_get_own")
+        return out
+
+    def sweep_own(self, cfg, seed, sweep_idx, n_active, want_outputs=True):
+        """pclean_sweep_own over the active window of n_active rows: (chosen particle, logml), or (None, None)"""
+        chosen = np.empty(n_active, dtype=np.int32) if want_outputs else None
+        logml = np.empty(n_active, dtype=np.float64) if want_outputs else None
+        check(self.h, self.lib.pclean_sweep_own(self.h, C.byref(cfg), C.c_uint64(seed), C.c_uint32(sweep_idx),
+                                                _p(chosen, C.c_int32), _p(logml, C.c_double)), "pclean_sweep_own")
+        return chosen, logml
+
+    def score_own(self, block_id, node_id, rows, seed=0, sweep=0, n_draws=0, n_cand=None, want_scores=False):
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        n = len(rows)
+        lse = np.empty(n, dtype=np.float64)
+        scores = np.empty((n, n_cand), dtype=np.float64) if want_scores else None
+        draws = np.empty((n, n_draws), dtype=np.int32) if n_draws else None
+        check(self.h, self.lib.pclean_score_own(
+            self.h, C.c_int32(block_id), C.c_int32(node_id), C.c_int32(n), _p(rows, C.c_int32), C.c_uint64(seed),
+            C.c_uint32(sweep), C.c_int32(n_draws), _p(lse, C.c_double), _p(scores, C.c_double), _p(draws, C.c_int32)),
+            "pclean_score_own")
+        return lse, scores, draws
+
+    def own_counts(self, block_id, node_id, n_options):
+        out = np.zeros(n_options, dtype=np.int64)
+        check(self.h, self.lib.pclean_own_counts(self.h, C.c_int32(block_id), C.c_int32(node_id), _p(out, C.c_int64)),
+              "pclean_own_counts")
+        return out
+
+    def get_own_stats(self):
+        r = OwnStats()
+        check(self.h, self.lib.pclean_get_own_stats(self.h, C.byref(r)), "pclean_get_own_stats")
+        return r
 
     def debug_detmath(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64)

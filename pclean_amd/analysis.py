@@ -18,6 +18,11 @@ def reconstructed_pool_ids(lowered, trace, row_slice=None, columns=None):
         if columns is not None and col not in columns:
             continue
         own = ocls.attr(ref) if "." not in ref else None
+        if own is not None and ref in getattr(lw, "own_leaf", {}):  # own choice of a flat class: a row of trace.own
+            li = [a for a, _, _ in trace.own_leaves()].index(ref)
+            v = trace.own[li]  # (pulled from the device when the sweeps left it ahead)
+            out[col] = np.where(v >= 0, lw.latent_dom[(q.cls, ref)].id_array()[np.maximum(v, 0)], -1)
+            continue
         if own is not None and own.kind == "choice":  # own discrete choice (e.g. br): option -> string
             bi = next(iter(lw.locals))
             li = lw.locals[bi].index(ref)

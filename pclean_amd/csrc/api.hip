@@ -40,6 +40,7 @@ extern "C" int pclean_ctx_destroy(pclean_ctx* ctx) {
   pclean_commit_state_free(ctx);
   pclean_sweep_state_free(ctx);
   pclean_recon_state_free(ctx);
+  pclean_own_state_free(ctx);
   ctx->stage.release();
   ctx->ustage.release();
   ctx->stats_pack.release();

@@ -311,6 +311,7 @@ struct pclean_ctx {
   void* sweep_state = nullptr;  // owned by sweep.hip
   void* rccl_comm = nullptr;    // ncclComm_t of pclean_comm_init (comm.hip)
   void* recon_state = nullptr;  // owned by recon.hip
+  void* own_state = nullptr;    // owned by own_block.hip
   DevBuf<int64_t> stats_pack;   // pclean_allreduce_stats_fused: the tables' delta counts as one vector
   int32_t comm_ranks = 0, comm_rank = 0;
   // what the collectives of this context moved (pclean_comm_get_stats): HIP events around the last all-gather / all-reduce on
@@ -360,6 +361,8 @@ void pclean_commit_state_free(pclean_ctx* ctx);
 void pclean_commit_table_reuploaded(pclean_ctx* ctx, int table_id);
 // recon.hip
 void pclean_recon_state_free(pclean_ctx* ctx);
+// own_block.hip
+void pclean_own_state_free(pclean_ctx* ctx);
 // comm.hip: collectives queued on the library's stream (no synchronisation)
 int pclean_comm_allreduce_stats_queue(pclean_ctx* ctx, int32_t n_tables, const int32_t* table_ids, int32_t local_is_zero);
 int pclean_comm_allgather_i32(pclean_ctx* ctx, const int32_t* send, int32_t* recv, size_t words_per_rank);

@@ -128,6 +128,11 @@ class Engine:
         if tr is not None and getattr(tr, "_dev", None) is self:
             tr._sync()
         self._ahead = None
+        ref = getattr(self, "_own_ahead", None)  # (the own choices of a flat class: sweep_own)
+        tr = ref() if ref is not None else None
+        if tr is not None and getattr(tr, "_own_dev", None) is self:
+            tr._sync_own()
+        self._own_ahead, self._own_key = None, None
 
     def close(self):
         self._sync_ahead_trace()
@@ -449,6 +454,60 @@ class Engine:
                 trace.pending_locals[bi] = self.hip.get_locals(bi, hi - lo)
         return choice, chosen, logml, new_rows
 
+    # -- a flat observed class: own blocks (csrc/own_block.hip) -----------------------------------------------------
+    def _own_blocks(self, trace):
+        """[(block, first row of trace.own, one past its last)] of the own blocks"""
+        out = []
+        for li, (_, b, _) in enumerate(trace.own_leaves()):
+            if out and out[-1][0] == b:
+                out[-1][2] = li + 1
+            else:
+                out.append([b, li, li + 1])
+        return out
+
+    def _push_own(self, trace):
+        """the trace's own choices -> device, unless the device holds them already (they live there between sweeps)"""
+        key = (id(trace), trace._own_version, id(self.hip))
+        if getattr(trace, "_own_dev", None) is self or getattr(self, "_own_key", None) == key:
+            return
+        for b, l0, l1 in self._own_blocks(trace):
+            self.hip.set_own(b, trace._own[l0:l1])
+        self._own_key = key
+
+    def pull_own(self, trace):
+        """device -> trace._own (Trace.own calls it when the device is ahead)"""
+        for b, l0, l1 in self._own_blocks(trace):
+            trace._own[l0:l1] = self.hip.get_own(b, l1 - l0, trace._own.shape[1])
+        self._own_key = (id(trace), trace._own_version, id(self.hip))
+
+    def sweep_own(self, trace, config, seed, sweep_idx, lo=0, hi=None, want_outputs=True):
+        """One batched sweep of a FLAT observed class over its rows [lo, hi) (default: all): pclean_sweep_own.  The option
+        priors are re-uploaded whenever their parameter moved (upload_trace), the own choices are updated in place on the
+        device (Trace.own pulls them on access) and the Dirichlet counts follow from a device histogram.  Returns (chosen
+        particle, logml) of the window's rows, or (None, None) without want_outputs."""
+        import weakref
+        if not getattr(self.lw, "flat", False):
+            raise _lib.PCleanHipError("Engine.sweep_own: the observed class is not flat (it has reference-slot blocks)")
+        cfg = config.as_c() if isinstance(config, InferenceConfig) else config
+        if not cfg.use_dd_proposals:
+            raise NotImplementedError("use_dd_proposals=False (prior proposals) is not served for a flat observed class")
+        hi = trace._own.shape[1] if hi is None else hi
+        if hi <= lo:
+            return (np.zeros(0, np.int32), np.zeros(0)) if want_outputs else (None, None)
+        self.upload_trace(trace)
+        self._push_own(trace)
+        self.hip.set_active_rows(lo, hi - lo)
+        chosen, logml = self.hip.sweep_own(cfg, seed, sweep_idx, hi - lo, want_outputs)
+        trace._own_dev = self
+        self._own_ahead = weakref.ref(trace)  # (close / reload pull the values first)
+        st = self.hip.get_own_stats()
+        if st.impossible_rows:
+            raise ValueError(f"row {st.first_impossible_row + self.row_offset}: none of the options of an own choice is possible "
+                             f"given the row's observations ({st.impossible_rows} such rows in [{lo}, {hi})); the reference "
+                             "fails on such a row too")
+        trace.refresh_own_counts()
+        return chosen, logml
+
     # -- device-resident commit (csrc/commit.hip) ------------------------------------------------------------------
     def _slack_min(self, cname, t):
         """spare rows a table needs before the next device commit: a few times what the last commits added to its
@@ -506,6 +565,10 @@ class Engine:
         spare capacity from the start, so that no table changes shape later) and every compact table / per-value cache the
         sweeps of all classes will ask for (pclean_prepare).  Optional: results do not depend on it."""
         from . import inference as inf
+        if getattr(self.lw, "flat", False):  # (no latent table, no reference slot: nothing to prepare or to commit)
+            self.upload_trace(trace)
+            self._prepared = True
+            return
         if inf.DEVICE_COMMIT:
             self.enable_device_commit(trace, comm)
         self.upload_trace(trace)

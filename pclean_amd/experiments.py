@@ -228,3 +228,36 @@ def flights_query(m):
         "flight": "flight.flight_id",
         "src": "src.name",
     })
+
+
+# ---- a flat program: one table, known vocabularies, typo-corrupted cells -----------------------------------------------
+FLAT_COLUMNS = ("City", "State", "Condition")
+
+
+def flat_vocabulary(clean, columns=FLAT_COLUMNS):
+    """distinct clean values per column, first-seen order"""
+    return {c: list(dict.fromkeys(v for v in clean[c] if v is not None)) for c in columns}
+
+
+def flat_model(vocab):
+    """`@class Obs`: per column one own block  `col ~ ChooseProportionally(vocab[col], col_p); col_obs ~ AddTypos(col)`
+    with a learned ProportionsParameter — no latent class, no reference slot (a FLAT class: LoweredModel.flat)."""
+    m = Model()
+    o = m.add_class("Obs")
+    for c in vocab:
+        o.param(f"{c}_p", ProportionsParameter(1.0))
+    for c, words in vocab.items():
+        with o.block():
+            o.choice(c, ChooseProportionally(words, f"{c}_p"))
+            o.choice(f"{c}_obs", AddTypos(c))
+    return m
+
+
+def flat_query(m, columns=FLAT_COLUMNS):
+    return Query(m, "Obs", {c: (c, f"{c}_obs") for c in columns})
+
+
+def cell_accuracy(cleaned, clean, columns=FLAT_COLUMNS):
+    """share of the cells of `columns` whose cleaned value is the clean table's"""
+    hit = sum(a == b for c in columns for a, b in zip(cleaned[c], clean[c]))
+    return hit / float(sum(len(clean[c]) for c in columns))

@@ -587,9 +587,35 @@ def _gather_locals(trace, comm, begin, n_local, lo):
     trace.pending_locals = {}
 
 
+def _flat_window(engine, trace, config, seed, sweep_idx, b0, b1, comm):
+    """Rows [b0, b1) of a FLAT observed class (every block an own block, LoweredModel.flat): one pclean_sweep_own against
+    the frozen parameters; the own choices and their counts stay on the device (Engine.sweep_own).  Returns the number of
+    rows that did not keep their values (a chosen particle other than the retained one)."""
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError("a flat observed class (own blocks) is swept by one rank; world_size > 1 is not served")
+    with _timed("observed/own_sweep"):
+        chosen, _ = engine.sweep_own(trace, config, seed, sweep_idx, b0, b1)
+    return int(np.count_nonzero(chosen))
+
+
+def _initialize_flat(engine, trace, config, seed, max_sub_batches=32):
+    """initialize_trace (inference.jl:3-58) of a flat class.  Its rows share nothing but the parameters, so the rows between
+    two parameter moves (inference.jl:40-47: every rejuv_frequency rows) are one window: no row has values yet, every leaf
+    draws from its conditional.  A class without learned parameters is initialised in one window."""
+    trace.own[:] = -1
+    has_par = trace.has_learned_parameters(engine.lw.query.cls)
+    for b0, b1 in sub_batches(trace._own.shape[1], config, max_sub_batches, None, has_par):
+        _flat_window(engine, trace, config, seed, 0x7fffffff, b0, b1, None)
+        if has_par:
+            resample_parameters(trace)
+    return trace
+
+
 def _sweep_window(engine, trace, config, seed, sweep_idx, b0, b1, comm):
     """Rejuvenation of the observed rows [b0, b1) against the current (frozen) tables + commit on every rank:
     the rows are block-partitioned over the ranks.  Returns the global number of rows whose referent changed."""
+    if getattr(engine.lw, "flat", False):
+        return _flat_window(engine, trace, config, seed, sweep_idx, b0, b1, comm)
     lo, hi = shard_bounds(b1 - b0, comm.rank, comm.world)
     lo, hi = lo + b0, hi + b0
     light = hasattr(engine, "sweep_moved")  # the HIP engine reports the moved rows: no per-row outputs needed
@@ -688,6 +714,10 @@ def initialize_trace(engine, trace, config, seed, max_batch=256, comm=None, merg
     (scripts/run_hospital.py --file-order uses it)."""
     comm = comm or Comm()
     lw = engine.lw
+    if getattr(lw, "flat", False):
+        if comm.world > 1:
+            raise NotImplementedError("a flat observed class (own blocks) is swept by one rank; world_size > 1 is not served")
+        return _initialize_flat(engine, trace, config, seed)
     n = trace.cur.shape[1]
     nb = len(lw.blocks)
     trace.cur[:] = -1

@@ -738,7 +738,26 @@ class LoweredModel:
             root_of_block.append(fks[0] if fks else None)
             if fks:
                 fk_block[fks[0]] = bi
+        # A block without a reference slot that holds a choice other than a MaybeSwap observation is an OWN block: its own
+        # discrete choices are enumerated from their observations (_lower_own_block).  Served for FLAT classes alone — every
+        # block an own block: a class that mixes the two kinds would need the own values to follow the ancestor permutation
+        # of the particles inside the sweep.
+        self.own_leaf = {}   # own choice of the observed class -> (block, node) of its leaf
+        own_blocks = [bi for bi, names in enumerate(eblocks) if root_of_block[bi] is None and any(
+            ocls.attr(n).kind == "choice" and not isinstance(ocls.attr(n).dist, MaybeSwap) for n in names)]
+        self.flat = bool(own_blocks) and len(own_blocks) == len(eblocks)
+        if own_blocks and not self.flat:
+            first = next(n for n in eblocks[own_blocks[0]] if ocls.attr(n).kind == "choice")
+            others = [n for k, n in enumerate(root_of_block) if n is not None]
+            raise NotImplementedError(
+                f"{self.query.cls}.{first}: a choice in a block without a reference slot, in a class that also has "
+                + (f"reference-slot blocks ({', '.join(others)})" if others else "a MaybeSwap scoring block")
+                + "; own blocks are served for flat classes alone (every block without a reference slot), mixed classes are "
+                  "not lowered")
         for bi, names in enumerate(eblocks):
+            if bi in own_blocks:
+                self.blocks.append(self._lower_own_block(bi, ocls, names))
+                continue
             if root_of_block[bi] is None:
                 self._lower_score_block(bi, ocls, names, fk_block)
                 self.blocks.append(dict(score=True, nodes=[], terms=[], children=[], colmap=[], node_info=[],
@@ -757,6 +776,9 @@ class LoweredModel:
                 if isinstance(a.dist, TABULATED):
                     # a term DENS_TABULATED exactly where an AddTypos term of the same `ref` would go
                     if "." not in ref:
+                        if ocls.attr(ref).kind == "choice":
+                            raise NotImplementedError(f"{a.name}: {type(a.dist).__name__} of the own choice {ref} in a block with "
+                                                      f"the reference slot {root_fk.name} (joint enumeration) is not lowered")
                         raise NotImplementedError(f"{a.name}: {type(a.dist).__name__} of a JuliaNode value is not lowered")
                     head, rest = ref.split(".", 1)
                     if head != root_fk.name:
@@ -777,7 +799,9 @@ class LoweredModel:
                 else:
                     j = ocls.attr(ref)
                     if j.kind != "julia":
-                        raise NotImplementedError(f"{a.name}: AddTypos of a non-reference")
+                        raise NotImplementedError(f"{a.name}: AddTypos of a non-reference: the own choice {ref} stands in a block "
+                                                  f"with the reference slot {root_fk.name}, where the reference enumerates the two "
+                                                  "jointly; own choices are enumerated in blocks without a reference slot alone")
                     local = [x for x in j.args if x.split(".", 1)[0] == root_fk.name]
                     other = [x for x in j.args if x.split(".", 1)[0] != root_fk.name]
                     if len(local) != 1 or len(other) > 1:
@@ -999,6 +1023,90 @@ class LoweredModel:
                              0, 0)
         return nid
 
+    def _lower_own_block(self, bi, ocls, names):
+        """Block of a flat observed class: every own choice (`ChooseProportionally` with a plain ProportionsParameter,
+        `ChooseUniformly` over strings) becomes one NODE_LEAF on its option table, carrying the block's observations of it in
+        declaration order (AddTypos, ExpandOnShortVersion, one-name FormatName) and, last, the equality term of a direct
+        observation in the query — the order a new row's leaf gives them (_emit_fk_node).  The reference enumerates such a
+        block like any other (proposal_compiler.jl:55-129); the choices of one block are separable (no observation reads two
+        of them), so each is enumerated on its own.  Everything else is refused by name."""
+        cls = self.query.cls
+        blk = dict(own=True, nodes=[], terms=[], children=[], colmap=[], node_info=[], root_class=None, root_fk=None,
+                   ctx_src_block=[], ctx_src_col=[])
+        block_of = {n: k for k, ns in enumerate(self.engine_blocks) for n in ns}
+        choices, observations = [], []
+        for n in names:
+            a = ocls.attr(n)
+            if a.kind != "choice":
+                continue  # (a JuliaNode is refused where an observation reads it)
+            d, who = a.dist, f"{cls}.{n}"
+            if isinstance(d, (AddTypos,) + TABULATED):
+                observations.append(a)
+            elif isinstance(d, (TransformedGaussian, AddNoise)):
+                raise NotImplementedError(f"{who}: a Gaussian observation in a block without a reference slot is not lowered")
+            elif isinstance(d, (StringPrior, TimePrior, NumberCodePrior)):
+                raise NotImplementedError(f"{who}: a {type(d).__name__} own choice is not lowered (its proposal holds a dummy value "
+                                          "or none at all); own choices are ChooseProportionally or ChooseUniformly")
+            elif isinstance(d, ChooseProportionally):
+                if d.index is not None:  # (_resolve_indexed refuses it first)
+                    raise NotImplementedError(f"{who}: an indexed choice among the observed class's own choices is not lowered")
+                choices.append(a)
+            elif isinstance(d, ChooseUniformly):
+                if (cls, n) not in self.latent_dom:
+                    raise NotImplementedError(f"{who}: an own ChooseUniformly choice whose options are not strings is not lowered")
+                choices.append(a)
+            else:
+                raise NotImplementedError(f"{who}: a {type(d).__name__} choice in a block without a reference slot is not lowered")
+        by_choice = {c.name: [] for c in choices}
+        for a in observations:
+            who = f"{cls}.{a.name}"
+            if isinstance(a.dist, FormatName) and a.dist.refs is not None:
+                raise NotImplementedError(f"{who}: FormatName({', '.join(a.dist.refs)}) reads several own choices; the reference "
+                                          "would enumerate their product, which separable leaves cannot hold")
+            ref = a.dist.ref
+            if "." in ref:
+                raise NotImplementedError(f"{who}: {type(a.dist).__name__}({ref}) reads a value behind a reference slot from a "
+                                          "block without one")
+            r = ocls.attr(ref)
+            if r.kind == "julia":
+                raise NotImplementedError(f"{who}: {type(a.dist).__name__} of the JuliaNode {ref} of an own choice is not lowered")
+            if ref not in by_choice:
+                if block_of.get(ref) != bi:
+                    raise NotImplementedError(f"{who}: its choice {ref} is declared in another block; an observation is scored in "
+                                              "the block of its choice")
+                raise NotImplementedError(f"{who}: {ref} is not an enumerated own choice")
+            if a.name in self.obs_index:  # (an observation the query does not bind scores nothing)
+                by_choice[ref].append(a)
+        for c in choices:
+            key = (cls, c.name)
+            dom = self.latent_dom[key]
+            tb = len(blk["terms"])
+            for a in by_choice[c.name]:
+                if isinstance(a.dist, TABULATED):
+                    t = dict(obs=a.name, pair=self._class_pair_for(a.name, key, a.dist), max_typos=None, ctx=None,
+                             dens=_lib.DENS_TABULATED)
+                else:
+                    t = dict(obs=a.name, pair=self._pair_for(a.name, key, dom), max_typos=a.dist.max_typos, ctx=None)
+                self._emit_term(blk, t, 0)
+            if c.name in self.direct_obs:
+                col = self._dirty_columns[self.query_columns[c.name]]
+                stray = sorted({v for v in col if v is not None and dom.get(v) < 0})
+                if stray:
+                    raise ValueError(f"{cls}.{c.name}: observed value {stray[0]!r} is not among the options of the choice")
+                self._emit_term(blk, dict(obs=c.name, pair=self._eq_pair_for(key), max_typos=None, ctx=None,
+                                          dens=_lib.DENS_EQUAL), 0)
+            self.own_leaf[c.name] = (bi, len(blk["nodes"]))
+            blk["nodes"].append((_lib.NODE_LEAF, self.option_id[key], tb, len(blk["terms"]) - tb, 0, 0, -1, -1, 0, 0, 0, 0))
+            blk["node_info"].append(dict(kind="leaf", cls=cls, attr=c.name, path=c.name))
+        if not choices:
+            raise NotImplementedError(f"{cls}: a block without a reference slot and without an own choice "
+                                      f"({', '.join(names)}) is not lowered")
+        return blk
+
+    def own_block_arrays(self, bi):
+        """Arguments of pclean_load_own_block behind the block id: (nodes, terms)."""
+        return self.block_arrays(bi)[:2]
+
     def score_block_args(self, bi):
         """Arguments of pclean_load_score_block for scoring block bi."""
         sb = self.score_blocks[bi]
@@ -1011,7 +1119,11 @@ class LoweredModel:
         """Upload every block plan (observed-class blocks, scoring blocks, latent-class plans) into an
         object exposing load_block / load_score_block (the HIP context or the oracle world)."""
         for bi, blk in enumerate(self.blocks):
-            if blk.get("score"):
+            if blk.get("own"):
+                if not hasattr(target, "load_own_block"):
+                    raise NotImplementedError("a flat observed class (own blocks): this target does not know own blocks")
+                target.load_own_block(bi, *self.own_block_arrays(bi))
+            elif blk.get("score"):
                 target.load_score_block(*self.score_block_args(bi))
             else:
                 target.load_block(bi, *self.block_arrays(bi))

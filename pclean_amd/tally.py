@@ -67,6 +67,9 @@ class ReconPlan:
                 else:
                     self.numeric.append(col)
                 continue
+            if ref in getattr(lw, "own_leaf", {}):  # own choice of a flat class: not served on the device, the host counts it
+                self.host_strings.append(col)
+                continue
             if self.own and own.kind == "choice":
                 bi = next(iter(lw.locals))
                 owns.append((col, dict(kind=_lib.RECON_OWN, block=bi, table=-1, col=lw.locals[bi].index(ref)),

@@ -205,12 +205,62 @@ class Trace:
     def __deepcopy__(self, memo):
         import copy
         self._sync()
+        self._sync_own()
         new = object.__new__(type(self))
         memo[id(self)] = new
         for k, v in self.__dict__.items():
             # (the lowered model is the program, not trace state: shared, as every engine of the trace shares it)
-            new.__dict__[k] = None if k == "_dev" else (v if k == "lw" else copy.deepcopy(v, memo))
+            new.__dict__[k] = None if k in ("_dev", "_own_dev") else (v if k == "lw" else copy.deepcopy(v, memo))
         return new
+
+    # -- own choices of a flat observed class ---------------------------------------------------------------------
+    def own_leaves(self):
+        """[(own choice, block, node)] of a flat observed class in (block, node) order: the rows of `own`"""
+        return sorted(((a, b, n) for a, (b, n) in getattr(self.lw, "own_leaf", {}).items()), key=lambda x: x[1:])
+
+    def _sync_own(self):
+        dev = getattr(self, "_own_dev", None)
+        if dev is not None:
+            self._own_dev = None
+            dev.pull_own(self)
+
+    @property
+    def own(self):
+        self._sync_own()
+        self._own_version += 1  # (conservative: a reader may write through the array it gets)
+        return self._own
+
+    @own.setter
+    def own(self, value):
+        self._own_dev = None
+        self._own_version += 1
+        self._own = np.ascontiguousarray(value, dtype=np.int32)
+
+    def _own_params(self):
+        """[(row of `own`, parameter state)] of the own ChooseProportionally choices"""
+        cls = self.lw.query.cls
+        out = []
+        for li, (a, _, _) in enumerate(self.own_leaves()):
+            d = self.lw.model.classes[cls].attr(a).dist
+            if isinstance(d, ChooseProportionally):
+                out.append((li, self._params[(cls, d.param)]))
+        return out
+
+    def own_counts(self, li):
+        """histogram of row li of `own` over the choice's options: from the device while it is ahead (pclean_own_counts:
+        nothing per row crosses PCIe), else from the host array"""
+        a, b, n = self.own_leaves()[li]
+        k = len(self.lw.latent_dom[(self.lw.query.cls, a)])
+        dev = getattr(self, "_own_dev", None)
+        if dev is not None:
+            return dev.hip.own_counts(b, n, k)
+        v = self._own[li]
+        return np.bincount(v[v >= 0], minlength=k).astype(np.int64)
+
+    def refresh_own_counts(self):
+        """update_sufficient_statistics! of the own choices (row_inference.jl:172-185), for all rows at once"""
+        for li, state in self._own_params():
+            state.counts[:] = self.own_counts(li)
 
     def __init__(self, lowered, n_rows, seed=0):
         self._dev = None       # the Engine whose device state is ahead of the host arrays (None: the host is current)
@@ -240,6 +290,12 @@ class Trace:
         self.row_origin = {}
         self._origin = None
         self.cur = np.full((len(lowered.blocks), n_rows), -1, dtype=np.int32)
+        # a flat observed class (LoweredModel.flat): the own choices of every row, int32 [leaf][n_rows] option indices in the
+        # order of own_leaves() (block, node), -1 = none yet.  The sweeps write them on the device (Engine.sweep_own) and
+        # leave the host array behind: `own` pulls it on access; the Dirichlet counts come from a device histogram.
+        self._own = np.full((len(self.own_leaves()), n_rows), -1, dtype=np.int32)
+        self._own_dev = None      # the Engine whose device values are ahead of _own
+        self._own_version = 0     # bumped by every host access to `own` (the engine re-uploads the values when it moved)
         # own enumerated choices of the observed class (e.g. br, unit) and the Gaussian mean parameter
         self.locals = {bi: np.full((n_rows, 2), -1, dtype=np.int32) for bi in getattr(lowered, "locals", {})}
         self.pending_locals = {}
@@ -577,6 +633,16 @@ class Trace:
         conjugate counts == live rows' choices.  Raises AssertionError with a description."""
         lw = self.lw
         want = {c: np.zeros(t.n, dtype=np.int64) for c, t in self.tables.items()}
+        if getattr(lw, "flat", False):  # own choices: all of a row or none, within the options; counts == their histogram
+            own = self.own
+            assert np.all((own >= 0).all(axis=0) | (own < 0).all(axis=0)), "own choices: a row holds some but not all"
+            for li, (a, _, _) in enumerate(self.own_leaves()):
+                assert own[li].max(initial=-1) < len(lw.latent_dom[(lw.query.cls, a)]), f"{a}: a value beyond the options"
+            for li, state in self._own_params():
+                v = own[li]
+                assert np.array_equal(np.bincount(v[v >= 0], minlength=len(state.counts)), state.counts), \
+                    f"{lw.query.cls}.{self.own_leaves()[li][0]}: Dirichlet counts out of sync"
+            return
         for bi, blk in enumerate(lw.blocks):
             if blk.get("score"):
                 continue
@@ -673,6 +739,8 @@ class Trace:
     def resample_parameters(self, cname=None):
         """resample_value! of every learned parameter (cname=None: initialize_trace, inference.jl:40-47) or
         of the parameters declared in class cname (pgibbs_sweep!, inference.jl:72-77)."""
+        if getattr(self.lw, "flat", False):  # the own choices' counts as the last sweep left them (a device histogram)
+            self.refresh_own_counts()
         for (c, _), p in self.params.items():
             if cname is None or c == cname:
                 p.resample(self.rng)
@@ -777,6 +845,14 @@ class Trace:
         for bi, blk in enumerate(lowered.blocks):
             if blk.get("score"):
                 tr.cur[bi] = 0
+                continue
+            if blk.get("own"):  # a flat class: {own choice: strings per row} -> option indices, counts follow
+                tr.cur[bi] = 0
+                for li, (a, b, _) in enumerate(tr.own_leaves()):
+                    if b == bi:
+                        dom = lowered.latent_dom[(lowered.query.cls, a)]
+                        tr._own[li] = [dom.index_of(s) for s in clean_by_path[bi][a]]
+                tr.refresh_own_counts()
                 continue
             cname = blk["root_class"]
             t = tr.tables[cname]
