@@ -1070,6 +1070,17 @@ class HipContext:
             "pclean_score_own")
         return lse, scores, draws
 
+    def own_marginals(self, block_id, node_id, top, n_active, want_current=True):
+        """pclean_own_marginals over the active window of n_active rows: (options int32 [top][n_active], probabilities
+        float64 [top][n_active], probability of the current value float64 [n_active] or None)"""
+        opt = np.empty((max(top, 0), n_active), dtype=np.int32)
+        prob = np.empty((max(top, 0), n_active), dtype=np.float64)
+        cur = np.empty(n_active, dtype=np.float64) if want_current else None
+        check(self.h, self.lib.pclean_own_marginals(self.h, C.c_int32(block_id), C.c_int32(node_id), C.c_int32(top),
+                                                    _p(opt, C.c_int32), _p(prob, C.c_double), _p(cur, C.c_double)),
+              "pclean_own_marginals")
+        return opt, prob, cur
+
     def own_counts(self, block_id, node_id, n_options):
         out = np.zeros(n_options, dtype=np.int64)
         check(self.h, self.lib.pclean_own_counts(self.h, C.c_int32(block_id), C.c_int32(node_id), _p(out, C.c_int64)),

@@ -223,6 +223,57 @@ def consensus_table(lowered, tally, dirty):
     return out
 
 
+def _map_columns(lowered, marginals):
+    """[(query column, own choice)] of the queried own choices that `marginals` (Engine.own_marginals) covers"""
+    return [(col, ref) for col, ref in lowered.query.cleanmap.items() if ref in marginals]
+
+
+def map_pool_ids(lowered, marginals):
+    """{query column: pool id of the most probable option of its own choice per row} from Engine.own_marginals — the
+    encoding counts_given takes; -1 where no option is possible."""
+    out = {}
+    for col, ref in _map_columns(lowered, marginals):
+        k = np.asarray(marginals[ref][0][0])
+        out[col] = np.where(k >= 0, lowered.latent_dom[(lowered.query.cls, ref)].id_array()[np.maximum(k, 0)], -1)
+    return out
+
+
+def _thresholded_ids(lowered, marginals, dirty, min_confidence):
+    """map_pool_ids with the cells whose MAP probability is below min_confidence put back to their dirty value (-3: a
+    dirty string outside the pool, as counts_given reads it); a missing dirty cell always takes the MAP value.  Also
+    {query column: MAP probability}."""
+    ids, conf = map_pool_ids(lowered, marginals), {}
+    for col, ref in _map_columns(lowered, marginals):
+        conf[col] = np.asarray(marginals[ref][1][0], dtype=np.float64)
+        d = np.asarray(dirty[col][:len(ids[col])], dtype=object)
+        keep_dirty = (conf[col] < min_confidence) & ~np.equal(d, None)
+        ids[col] = np.where(keep_dirty, _pool_ids(lowered.pool.index, d, -3, -4), ids[col])
+    return ids, conf
+
+
+def map_table(lowered, marginals, dirty, min_confidence=0.0):
+    """(table, confidence): the cleaned table whose queried own choices hold their most probable option (the MAP string
+    of the cell's exact conditional) where its probability is >= min_confidence and the dirty cell otherwise — a missing
+    dirty cell always takes the MAP value; every other column is copied.  confidence {query column: MAP probability}."""
+    ids, conf = _thresholded_ids(lowered, marginals, dirty, min_confidence)
+    n = len(next(iter(conf.values()))) if conf else None
+    strings = lowered.pool.strings
+    out = {}
+    for col, vals in dirty.items():
+        if col not in ids:
+            out[col] = list(vals[:n])
+            continue
+        out[col] = [vals[i] if k == -3 else (strings[k] if k >= 0 else None) for i, k in enumerate(ids[col])]
+    return out, conf
+
+
+def evaluate_map_accuracy(lowered, marginals, dirty, clean, min_confidence=0.0):
+    """evaluate_accuracy of map_table(lowered, marginals, dirty, min_confidence)"""
+    ids, conf = _thresholded_ids(lowered, marginals, dirty, min_confidence)
+    n = len(next(iter(conf.values())))
+    return f1_from_counts(counts_given(lowered, ids, n, dirty, clean))
+
+
 def latent_table(lowered, trace, cname):
     """One inferred latent table (save_tables, analysis.jl:8-13): row id + the value of every own attribute and
     reference slot of the class (flattened copies of referents' values are left out, as the reference does
@@ -242,9 +293,21 @@ def latent_table(lowered, trace, cname):
     return out
 
 
-def save_results(directory, name, lowered, trace, dirty, timestamp=True, tally=None):
+def map_confidence_table(lowered, marginals, dirty):
+    """map_table with every queried own column followed by `<column>__confidence`, its MAP probability"""
+    table, conf = map_table(lowered, marginals, dirty)
+    out = {}
+    for col, vals in table.items():
+        out[col] = vals
+        if col in conf:
+            out[col + "__confidence"] = [float(p) for p in conf[col]]
+    return out
+
+
+def save_results(directory, name, lowered, trace, dirty, timestamp=True, tally=None, marginals=None):
     """save_results (analysis.jl:15-33): reconstructed_<class>.csv + inferred_<class>.csv per latent class; with a
-    tally (tally.CellTally) also consensus_<class>.csv (consensus_table)."""
+    tally (tally.CellTally) also consensus_<class>.csv (consensus_table); with marginals (Engine.own_marginals of a flat
+    class) also map_<class>.csv (map_confidence_table)."""
     import datetime
     import os
 
@@ -256,6 +319,9 @@ def save_results(directory, name, lowered, trace, dirty, timestamp=True, tally=N
     if tally is not None:
         pd.DataFrame(consensus_table(lowered, tally, dirty)).to_csv(
             os.path.join(d, f"consensus_{lowered.query.cls}.csv"), index=False)
+    if marginals is not None:
+        pd.DataFrame(map_confidence_table(lowered, marginals, dirty)).to_csv(
+            os.path.join(d, f"map_{lowered.query.cls}.csv"), index=False)
     for cname in trace.tables:
         pd.DataFrame(latent_table(lowered, trace, cname)).to_csv(os.path.join(d, f"inferred_{cname}.csv"), index=False)
     return d

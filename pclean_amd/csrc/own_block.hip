@@ -19,6 +19,10 @@
 //           walk inside the chunk — the sequential scan's  min{k : u_0 + .. + u_k > x}  in two steps
 // Integer sums: maximum, U, lse and every draw are the generic enumeration kernels' (enum_kernels.hip), bit for bit,
 // whatever the variant, the grouping or the window.
+//
+// own_marginal_kernel (pclean_own_marginals) reports what the sweep holds before it draws: passes 1 and 2 as above, then
+// instead of the draws the `top` options of largest u_k (ties: the smaller index) with u_k / U, and u_cur / U of every row's
+// current value.  It writes no value.
 #include "sweep_internal.h"
 
 #define OWN_BT 256
@@ -259,6 +263,197 @@ __global__ __launch_bounds__(OWN_BT) void own_leaf_kernel(const OwnNodeDev nd, c
   }
 }
 
+// ---- exact marginals: the top options of every tuple run and the probability of every row's current value ----------------
+#define OWN_MAX_TOP 8
+
+struct OwnMarginal {
+  const int32_t* piece_off;  // [pieces + 1] into members
+  const int32_t* members;    // rows (index into the loaded rows)
+  int32_t win_lo, win_hi;    // the active window (rows outside are left alone)
+  int32_t top;               // 1 .. OWN_MAX_TOP
+  const int32_t* vals;       // the leaf's current values, indexed by row (read when cur_prob is set)
+  int32_t* top_option;       // [top][win_hi - win_lo]
+  double* top_prob;          // [top][win_hi - win_lo]
+  double* cur_prob;          // [win_hi - win_lo] or null
+  int32_t* bad;              // {rows of the window with U == 0, the smallest of them}
+};
+
+// the order of the selection: the larger weight first, equal weights by the smaller option index (a free slot is (0, -1))
+__device__ __forceinline__ bool own_before(unsigned long long ua, int ka, unsigned long long ub, int kb) {
+  return ua > ub || (ua == ub && ka < kb);
+}
+
+// Passes 1 and 2 are own_leaf_kernel's, operation for operation (without the probe's outputs): m, every u_k and U are the
+// sweep's.  Selection: in pass 2 every lane keeps the CAP first of ITS options (they reach it by ascending index) in
+// registers; then `top` rounds of a workgroup-wide arg-max over the lanes' first entries, the winning lane moving on to its
+// next.  CAP >= top; the result does not depend on it.
+template <bool RESIDENT, int CAP>
+__global__ __launch_bounds__(OWN_BT) void own_marginal_kernel(const OwnNodeDev nd, const DensDev dn, const OwnMarginal L) {
+  __shared__ unsigned long long s_u[OWN_LDS_OPTIONS];
+  __shared__ unsigned long long s_cs[OWN_LDS_OPTIONS / 64];
+  __shared__ double s_red[OWN_BT / 64];
+  __shared__ int s_obs[PCLEAN_MAX_TERMS];
+  __shared__ unsigned long long s_wu[2][OWN_BT / 64];  // the waves' winners of a round (two rounds in flight)
+  __shared__ int s_wk[2][OWN_BT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x;
+  const int m_lo = L.piece_off[g], m_hi = L.piece_off[g + 1];
+  const int n = nd.n_cand;
+  {
+    int any = 0;
+    for (int q = m_lo + tid; q < m_hi; q += OWN_BT) {
+      const int r = L.members[q];
+      any |= (r >= L.win_lo && r < L.win_hi) ? 1 : 0;
+    }
+    if (!__syncthreads_or(any)) return;
+  }
+  {
+    const int row0 = L.members[m_lo];
+    for (int ti = 0; ti < nd.n_terms; ++ti)
+      if (tid == ti) s_obs[ti] = nd.terms[ti].obs_col[row0];
+  }
+  __syncthreads();
+
+  // ---- pass 1: scores and their maximum
+  double* s = reinterpret_cast<double*>(s_u);
+  double lmax = -__builtin_inf();
+  for (int k = tid; k < n; k += OWN_BT) {
+    const double sk = own_score(nd, dn, s_obs, k);
+    if (RESIDENT) s[k] = sk;
+    lmax = fmax(lmax, sk);
+  }
+  lmax = own_wave_max(lmax);
+  if (lane == 0) s_red[wave] = lmax;
+  __syncthreads();
+  double m = s_red[0];
+  for (int w = 1; w < OWN_BT / 64; ++w) m = fmax(m, s_red[w]);
+  const bool dead = m == -__builtin_inf();
+
+  // ---- pass 2: fixed-point weights, one sum per 64 options, inclusive prefix of the sums; the lane's best options
+  unsigned long long lu[CAP];
+  int lk[CAP];
+#pragma unroll
+  for (int j = 0; j < CAP; ++j) {
+    lu[j] = 0ull;
+    lk[j] = -1;
+  }
+  const int nch = (n + 63) >> 6;
+  unsigned long long* pre = RESIDENT ? s_cs : s_u;
+  if (RESIDENT) {
+    for (int k = tid; k < n; k += OWN_BT) {
+      const double sk = s[k];
+      s_u[k] = dead ? 0ull : pclean_fixw(sk - m);
+    }
+    __syncthreads();
+  }
+  for (int c = wave; c < nch; c += OWN_BT / 64) {
+    const int k = (c << 6) + lane;
+    unsigned long long v = 0ull;
+    if (k < n) v = RESIDENT ? s_u[k] : (dead ? 0ull : pclean_fixw(own_score(nd, dn, s_obs, k) - m));
+    if (v > lu[CAP - 1]) {  // (k ascends: an equal weight seen earlier stays in front)
+      lu[CAP - 1] = v;
+      lk[CAP - 1] = k;
+#pragma unroll
+      for (int j = CAP - 1; j > 0; --j)
+        if (lu[j] > lu[j - 1]) {
+          const unsigned long long tu = lu[j];
+          const int tk = lk[j];
+          lu[j] = lu[j - 1];
+          lk[j] = lk[j - 1];
+          lu[j - 1] = tu;
+          lk[j - 1] = tk;
+        }
+    }
+    v = own_wave_sum(v);
+    if (lane == 0) pre[c] = v;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    unsigned long long carry = 0ull;
+    for (int base = 0; base < nch; base += 64) {
+      const int i = base + lane;
+      unsigned long long v = own_wave_scan(i < nch ? pre[i] : 0ull, lane) + carry;
+      if (i < nch) pre[i] = v;
+      carry = __shfl(v, 63, 64);
+    }
+  }
+  __syncthreads();
+  const unsigned long long U = pre[nch - 1];
+  const double Ud = (double)U;
+
+  // ---- selection: round t takes the first of all lanes' entries
+  int top_k[CAP];
+  double top_p[CAP];
+#pragma unroll
+  for (int t = 0; t < CAP; ++t) {
+    top_k[t] = -1;
+    top_p[t] = 0.0;
+    if (t >= L.top) continue;  // (uniform)
+    unsigned long long u = lu[0];
+    int k = lk[0];
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long uo = __shfl_xor(u, o, 64);
+      const int ko = __shfl_xor(k, o, 64);
+      if (own_before(uo, ko, u, k)) {
+        u = uo;
+        k = ko;
+      }
+    }
+    if (lane == 0) {
+      s_wu[t & 1][wave] = u;
+      s_wk[t & 1][wave] = k;
+    }
+    __syncthreads();
+    u = s_wu[t & 1][0];
+    k = s_wk[t & 1][0];
+    for (int w = 1; w < OWN_BT / 64; ++w)
+      if (own_before(s_wu[t & 1][w], s_wk[t & 1][w], u, k)) {
+        u = s_wu[t & 1][w];
+        k = s_wk[t & 1][w];
+      }
+    if (u != 0ull) {
+      top_k[t] = k;
+      top_p[t] = (double)u / Ud;
+      if (lk[0] == k) {
+#pragma unroll
+        for (int j = 0; j + 1 < CAP; ++j) {
+          lu[j] = lu[j + 1];
+          lk[j] = lk[j + 1];
+        }
+        lu[CAP - 1] = 0ull;
+        lk[CAP - 1] = -1;
+      }
+    }
+  }
+
+  // ---- the run's rows: one member per lane
+  const size_t nw = (size_t)(L.win_hi - L.win_lo);
+  for (int q = m_lo + tid; q < m_hi; q += OWN_BT) {
+    const int row = L.members[q];
+    if (row < L.win_lo || row >= L.win_hi) continue;
+    const size_t i = (size_t)(row - L.win_lo);
+#pragma unroll
+    for (int t = 0; t < CAP; ++t)
+      if (t < L.top) {
+        L.top_option[(size_t)t * nw + i] = top_k[t];
+        L.top_prob[(size_t)t * nw + i] = top_p[t];
+      }
+    if (L.cur_prob) {
+      const int cur = L.vals[row];
+      double p = 0.0;
+      if (U != 0ull && cur >= 0 && cur < n) {
+        const unsigned long long uc = RESIDENT ? s_u[cur] : pclean_fixw(own_score(nd, dn, s_obs, cur) - m);
+        p = (double)uc / Ud;
+      }
+      L.cur_prob[i] = p;
+    }
+    if (U == 0ull) {
+      atomicAdd(&L.bad[0], 1);
+      atomicMin(&L.bad[1], row);
+    }
+  }
+}
+
 // row_inference.jl:158-165 on equal weights — final_choice_kernel's operations (sweep.hip) with every weight 0.0
 template <int PMAX>
 __global__ void own_choice_kernel(int N, int P, int use_mh, const double* __restrict__ zero, const int32_t* __restrict__ vals0,
@@ -457,6 +652,17 @@ int launch_leaf(pclean_ctx* ctx, const OwnNodeDev& od, const OwnLaunch& L, int n
   return PCLEAN_OK;
 }
 
+// the constant, the counters of impossible rows and the events around a call's launches
+int ensure_aux(pclean_ctx* ctx, OwnState* s) {
+  if (s->zero.p) return PCLEAN_OK;
+  if (s->zero.alloc(1) || s->bad.alloc(2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  const double z = 0.0;
+  HIPCHK(ctx, hipMemcpy(s->zero.p, &z, 8, hipMemcpyHostToDevice));
+  HIPCHK(ctx, hipEventCreate(&s->ev[0]));
+  HIPCHK(ctx, hipEventCreate(&s->ev[1]));
+  return PCLEAN_OK;
+}
+
 OwnBlock* find_block(pclean_ctx* ctx, int32_t block_id) {
   if (!ctx || block_id < 0 || block_id >= PCLEAN_MAX_BLOCKS || !ctx->own_state) return nullptr;
   OwnBlock& b = own(ctx)->block[block_id];
@@ -580,12 +786,9 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
       if (rc) return rc;
     }
   }
-  if (!s->zero.p) {
-    if (s->zero.alloc(1) || s->bad.alloc(2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-    const double z = 0.0;
-    HIPCHK(ctx, hipMemcpy(s->zero.p, &z, 8, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipEventCreate(&s->ev[0]));
-    HIPCHK(ctx, hipEventCreate(&s->ev[1]));
+  {
+    const int rc = ensure_aux(ctx, s);
+    if (rc) return rc;
   }
   int32_t* d_chosen = scratch<int32_t>(ctx, N);
   int32_t* d_keep = scratch<int32_t>(ctx, N);
@@ -712,6 +915,82 @@ extern "C" int pclean_score_own(pclean_ctx* ctx, int32_t block_id, int32_t node_
   if (scores) HIPCHK(ctx, hipMemcpyAsync(scores, d_scores, (size_t)n_items * K * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (n_draws) HIPCHK(ctx, hipMemcpyAsync(draws, d_draws, (size_t)n_items * n_draws * 4, hipMemcpyDeviceToHost, ctx->stream));
   PCLEAN_SYNC(ctx);  // (h_row / order / poff are read by the copies queued above)
+  return finish_call(ctx);
+}
+
+extern "C" int pclean_own_marginals(pclean_ctx* ctx, int32_t block_id, int32_t node_id, int32_t top, int32_t* top_option,
+                                    double* top_prob, double* cur_prob) {
+  OwnBlock* b = find_block(ctx, block_id);
+  if (!b) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_own_marginals: block %d is not a loaded own block", block_id);
+  if (node_id < 0 || node_id >= (int)b->leaves.size())
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_own_marginals: block %d has no node %d", block_id, node_id);
+  if (top < 1 || top > OWN_MAX_TOP) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_own_marginals: top must be 1 .. %d", OWN_MAX_TOP);
+  if (!top_option || !top_prob) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_own_marginals: null outputs");
+  const int win_lo = ctx->active_begin;
+  const int N = ctx->active_count < 0 ? ctx->n_rows - win_lo : ctx->active_count;
+  if (win_lo < 0 || N < 0 || win_lo + N > ctx->n_rows) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_own_marginals: the active window lies outside the loaded rows");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  {
+    const int rcb = begin_call(ctx);
+    if (rcb) return rcb;
+  }
+  OwnState* s = own(ctx);
+  reset_stats(s);
+  if (N == 0) return PCLEAN_OK;
+  OwnLeaf& lf = b->leaves[node_id];
+  OwnNodeDev od;
+  int rc = leaf_dev(ctx, lf, od);
+  if (!rc) rc = ensure_groups(ctx, lf);
+  if (!rc && cur_prob) rc = ensure_vals(ctx, *b);
+  if (!rc) rc = ensure_aux(ctx, s);
+  if (rc) return rc;
+  int32_t* d_opt = scratch<int32_t>(ctx, (size_t)top * N);
+  double* d_prob = scratch<double>(ctx, (size_t)top * N);
+  double* d_cur = cur_prob ? scratch<double>(ctx, N) : nullptr;
+  if (!d_opt || !d_prob || (cur_prob && !d_cur)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  const int32_t bad0[2] = {0, 0x7fffffff};
+  HIPCHK(ctx, hipMemcpyAsync(s->bad.p, bad0, 8, hipMemcpyHostToDevice, ctx->stream));
+  OwnMarginal L{};
+  L.piece_off = lf.piece_off.p;
+  L.members = lf.piece_rows.p;
+  L.win_lo = win_lo;
+  L.win_hi = win_lo + N;
+  L.top = top;
+  L.vals = cur_prob ? b->vals.p + (size_t)node_id * ctx->n_rows : nullptr;
+  L.top_option = d_opt;
+  L.top_prob = d_prob;
+  L.cur_prob = d_cur;
+  L.bad = s->bad.p;
+  const DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
+  const bool resident = od.n_cand <= OWN_LDS_OPTIONS;
+  HIPCHK(ctx, hipEventRecord(s->ev[0], ctx->stream));
+  if (lf.n_pieces > 0) {  // (a lane keeps 1 entry for top == 1, OWN_MAX_TOP otherwise)
+    const dim3 grid(lf.n_pieces), block(OWN_BT);
+    if (resident && top == 1)
+      hipLaunchKernelGGL((own_marginal_kernel<true, 1>), grid, block, 0, ctx->stream, od, dn, L);
+    else if (resident)
+      hipLaunchKernelGGL((own_marginal_kernel<true, OWN_MAX_TOP>), grid, block, 0, ctx->stream, od, dn, L);
+    else if (top == 1)
+      hipLaunchKernelGGL((own_marginal_kernel<false, 1>), grid, block, 0, ctx->stream, od, dn, L);
+    else
+      hipLaunchKernelGGL((own_marginal_kernel<false, OWN_MAX_TOP>), grid, block, 0, ctx->stream, od, dn, L);
+    HIPCHK(ctx, hipGetLastError());
+    s->stats.variants |= resident ? 1 : 2;
+    s->stats.n_workgroups += lf.n_pieces;
+  }
+  HIPCHK(ctx, hipEventRecord(s->ev[1], ctx->stream));
+  s->stats.n_runs = lf.n_runs;
+  s->stats.longest_run = lf.longest;
+  int32_t bad[2] = {0, 0};
+  HIPCHK(ctx, hipMemcpyAsync(bad, s->bad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(top_option, d_opt, (size_t)top * N * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(top_prob, d_prob, (size_t)top * N * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (cur_prob) HIPCHK(ctx, hipMemcpyAsync(cur_prob, d_cur, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PCLEAN_SYNC(ctx);
+  ctx->timing = pclean_timing{};
+  (void)hipEventElapsedTime(&ctx->timing.total_ms, s->ev[0], s->ev[1]);
+  s->stats.impossible_rows = bad[0];
+  s->stats.first_impossible_row = bad[0] ? bad[1] : -1;
   return finish_call(ctx);
 }
 

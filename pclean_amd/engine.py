@@ -508,6 +508,24 @@ class Engine:
         trace.refresh_own_counts()
         return chosen, logml
 
+    def own_marginals(self, trace, top=1, lo=0, hi=None):
+        """Exact conditionals of the own choices of a FLAT observed class over its rows [lo, hi) (default: all), given the
+        parameters as they stand: pclean_own_marginals once per leaf.  Returns {own choice: (options int32 [top][n], their
+        probabilities float64 [top][n], probability of the row's current value float64 [n])}, the options ordered by
+        probability (ties: the smaller option index), -1 / 0.0 where fewer options are possible.  The option priors are
+        re-uploaded whenever their parameter moved (upload_trace) and the own choices are pushed unless the device holds
+        them; nothing is drawn, written or pulled, and no count changes."""
+        if not getattr(self.lw, "flat", False):
+            raise _lib.PCleanHipError("Engine.own_marginals: the observed class is not flat (it has reference-slot blocks)")
+        hi = trace._own.shape[1] if hi is None else hi
+        n = max(hi - lo, 0)
+        if n == 0:
+            return {a: (np.full((top, 0), -1, np.int32), np.zeros((top, 0)), np.zeros(0)) for a, _, _ in trace.own_leaves()}
+        self.upload_trace(trace)
+        self._push_own(trace)
+        self.hip.set_active_rows(lo, n)
+        return {a: self.hip.own_marginals(b, nd, top, n) for a, b, nd in trace.own_leaves()}
+
     # -- device-resident commit (csrc/commit.hip) ------------------------------------------------------------------
     def _slack_min(self, cname, t):
         """spare rows a table needs before the next device commit: a few times what the last commits added to its

@@ -7,7 +7,13 @@ of its own byte model.  Baseline — the only way the code without own blocks co
 the generic leaf path, pclean_score_node with one draw on the new-row leaf of the twin program (the choice behind a slot;
 host clock around the call).  Warm-up discarded, median of --runs runs (default 7).
 
-usage: own_block_bench.py [--rows N] [--runs R] [--particles P]"""
+--marginals: also times pclean_own_marginals on the same rows (top = 1 without and with the probability of the current value,
+top = 8), every run right after a pclean_sweep_own of the same build so that the two see the same clocks: 2 warm-up rounds
+discarded, then --runs rounds; medians and ranges go into the JSON line under "marginals" and the whole line into --out
+(default profiles/own_marginals_bench.json; the committed file collects three such lines, alternated with the parent
+commit's, under "this_commit").
+
+usage: own_block_bench.py [--rows N] [--runs R] [--particles P] [--marginals [--out FILE]]"""
 import json
 import os
 import sys
@@ -58,6 +64,32 @@ def byte_model(n_rows, K, n_groups, n_terms=1):
     return n_groups * per_group + n_rows * per_row
 
 
+def _summary(xs):
+    return dict(median=round(float(np.median(xs)), 3), min=round(float(min(xs)), 3), max=round(float(max(xs)), 3),
+                all=[round(float(x), 3) for x in xs])
+
+
+def time_marginals(hip, c, n, runs):
+    """device ms (HIP events around the launch) and call ms (host clock, outputs copied back) of pclean_own_marginals, each
+    round: one pclean_sweep_own, then the three marginal calls"""
+    cases = {"top1": (1, False), "top1_with_current": (1, True), "top8": (8, False)}
+    dev = {k: [] for k in ("sweep_own", *cases)}
+    call = {k: [] for k in cases}
+    for r in range(runs + 2):
+        hip.sweep_own(c, 2, r, n)
+        dev["sweep_own"].append(hip.get_timing().total_ms)
+        for name, (top, cur) in cases.items():
+            t0 = time.perf_counter()
+            hip.own_marginals(0, 0, top, n, want_current=cur)
+            call[name].append(1e3 * (time.perf_counter() - t0))
+            dev[name].append(hip.get_timing().total_ms)
+    st = hip.get_own_stats()
+    out = dict(warmup_rounds=2, rounds=runs, workgroups=int(st.n_workgroups), variant="lds" if st.variants == 1 else "chunked",
+               device_ms={k: _summary(v[2:]) for k, v in dev.items()}, call_ms={k: _summary(v[2:]) for k, v in call.items()})
+    out["top1_over_sweep_own"] = round(out["device_ms"]["top1"]["median"] / out["device_ms"]["sweep_own"]["median"], 3)
+    return out
+
+
 def main():
     n, runs, P = _arg("--rows", 1_000_000), _arg("--runs", 7), _arg("--particles", 20)
     t0 = time.time()
@@ -81,6 +113,7 @@ def main():
         host_ms.append(1e3 * (time.perf_counter() - t0))
         dev_ms.append(float(hip.get_timing().total_ms))
     st = hip.get_own_stats()
+    marg = time_marginals(hip, c, n, runs) if "--marginals" in sys.argv else None
     p = tr.params[("Obs", "city_p")].value.copy()
     tr.refresh_own_counts()  # (the timed calls went past Engine.sweep_own, which keeps the counts current)
     tr.check_consistency()
@@ -107,6 +140,14 @@ def main():
                generic_leaf_call_ms=round(float(np.median(base_ms[2:])), 3), generic_leaf_call_ms_all=[round(x, 3) for x in base_ms[2:]],
                model_bytes=int(byte_model(n, K, st.n_workgroups)), generate_s=round(t_gen, 1), initialize_s=round(t_init, 2))
     out["model_gb_per_s"] = round(out["model_bytes"] / (1e6 * out["sweep_own_device_ms"]), 1) if out["sweep_own_device_ms"] else None
+    if marg is not None:
+        out["marginals"] = marg
+        a = sys.argv[1:]
+        path = a[a.index("--out") + 1] if "--out" in a else os.path.join(
+            os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "own_marginals_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
     print(json.dumps(out))
     return out
 
