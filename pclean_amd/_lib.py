@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("PCLEAN_HIP_LIB") or os.path.join(HERE, "libpclean_hip
 
 MAX_CTX = 4
 MAX_GAUSS = 4  # PCLEAN_MAX_GAUSS
+MAX_TERMS = 16  # PCLEAN_MAX_TERMS
 EV_MAX_STEPS = 4  # PCLEAN_EV_MAX_STEPS
 CHOICE_NEW = -1
 DIST_OSA, DIST_DL = 0, 1

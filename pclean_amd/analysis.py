@@ -254,7 +254,10 @@ def _thresholded_ids(lowered, marginals, dirty, min_confidence):
 def map_table(lowered, marginals, dirty, min_confidence=0.0):
     """(table, confidence): the cleaned table whose queried own choices hold their most probable option (the MAP string
     of the cell's exact conditional) where its probability is >= min_confidence and the dirty cell otherwise — a missing
-    dirty cell always takes the MAP value; every other column is copied.  confidence {query column: MAP probability}."""
+    dirty cell always takes the MAP value; every other column is copied.  confidence {query column: MAP probability}.
+    A choice indexed by a sibling choice and that index (one product leaf): the two cells hold the most probable PAIR, and
+    the confidence of both is the pair's JOINT probability, not a per-column marginal (Engine.own_marginals) — so
+    min_confidence keeps or drops the two cells of a row on the same number."""
     ids, conf = _thresholded_ids(lowered, marginals, dirty, min_confidence)
     n = len(next(iter(conf.values()))) if conf else None
     strings = lowered.pool.strings
@@ -268,7 +271,8 @@ def map_table(lowered, marginals, dirty, min_confidence=0.0):
 
 
 def evaluate_map_accuracy(lowered, marginals, dirty, clean, min_confidence=0.0):
-    """evaluate_accuracy of map_table(lowered, marginals, dirty, min_confidence)"""
+    """evaluate_accuracy of map_table(lowered, marginals, dirty, min_confidence); for the two columns of a product leaf
+    min_confidence is compared with the pair's joint probability (see map_table)"""
     ids, conf = _thresholded_ids(lowered, marginals, dirty, min_confidence)
     n = len(next(iter(conf.values())))
     return f1_from_counts(counts_given(lowered, ids, n, dirty, clean))

@@ -20,6 +20,10 @@
 // Integer sums: maximum, U, lse and every draw are the generic enumeration kernels' (enum_kernels.hip), bit for bit,
 // whatever the variant, the grouping or the window.
 //
+// own_product_kernel serves a leaf whose option list is a full grid over two value columns (an own choice indexed by a
+// sibling own choice, enumerated jointly): every term once per value of the factor it reads, then the grid from the cached
+// values — the same doubles in the same order, so the same bits (see the kernel).
+//
 // own_marginal_kernel (pclean_own_marginals) reports what the sweep holds before it draws: passes 1 and 2 as above, then
 // instead of the draws the `top` options of largest u_k (ties: the smaller index) with u_k / U, and u_cur / U of every row's
 // current value.  It writes no value.
@@ -59,6 +63,7 @@ struct OwnState {
   DevBuf<int32_t> bad;       // {rows with logml == -inf, the smallest of them}
   DevBuf<unsigned long long> hist;
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the launches of the last pclean_sweep_own (pclean_timing.total_ms)
+  bool product_attr_set = false;          // own_product_kernel's dynamic-LDS limit is raised on this context's device
 };
 
 OwnState* own(pclean_ctx* ctx) {
@@ -252,6 +257,226 @@ __global__ __launch_bounds__(OWN_BT) void own_leaf_kernel(const OwnNodeDev nd, c
       const int k_end = min(n, k + 64) - 1;  // (the chunk's total exceeds x - acc: the walk stops inside it)
       for (; k < k_end; ++k) {
         acc += RESIDENT ? s_u[k] : pclean_fixw(own_score(nd, dn, s_obs, k) - m);
+        if (acc > x) break;
+      }
+      res = k;
+    }
+    if (L.probe)
+      L.draws_out[(size_t)mem * L.n_draws + j] = res;
+    else
+      L.vals[row] = res;
+  }
+}
+
+// ---- product leaf: an option list that is a full grid a * n_inner + b over two value columns ------------------------------
+// (an own choice indexed by a sibling own choice: model.py, _lower_own_block).  Every term reads ONE of the two factors, so
+// per tuple run its density takes n_outer or n_inner values, not n_outer x n_inner:
+//   phase 1  each term once per value of the factor it reads (own_score's rules: a tabulated term scores a missing
+//            observation, the others skip it), the doubles into LDS; the gathers of a term are independent, in flight together
+//   phase 2  the grid, OWN_SUPER chunks of 64 options per wave at a time (one division per lane and group: (a, b) of option
+//            k + 64 follows from that of k): s_k = logp[k], then += the cached value of every non-skipped term in plan
+//            order — own_score's doubles in own_score's order, so m, u_k = fixw(s_k - m), U, lse and every draw are
+//            own_leaf_kernel's (and enum_product_kernel's on the latent twin), bit for bit.  The pass that finds m
+//            keeps the maximum of every group; the weight pass skips a group whose maximum lies more than
+//            OWN_SKIP_BELOW under m: pclean_fixw is 0 below -28.5, and fp64 subtraction is monotone, so every weight of such
+//            a group is the 0 it would have computed.  One sum per chunk and their inclusive prefix in LDS; draws by
+//            own_leaf_kernel's binary search and a walk that recomputes the weights from the cached values.
+// Dynamic LDS: [total] cached term values, [n_chunks] chunk sums, [n_super] group maxima (left out, with the skip, when
+// they do not fit) — 8 bytes each, at most OWN_PRODUCT_LDS_MAX; a plan beyond that takes own_leaf_kernel<false>.
+#define OWN_PRODUCT_LDS_MAX ((size_t)160 * 1024 - 512)  // (the static arrays of the kernel take the rest of the 160 KiB)
+#define OWN_PRODUCT_WIDE 16384                          // options from which a workgroup has 1024 threads (16 chunks per wave)
+#define OWN_SKIP_BELOW 30.0
+#define OWN_SUPER 8  // chunks of 64 options a wavefront takes together: one division per lane and one maximum per 512 options
+
+struct OwnProductDev {
+  int32_t n_outer, n_inner, total, n_chunks;  // total: cached doubles
+  int32_t use_cmax, n_super;                  // n_super: groups of OWN_SUPER chunks (one maximum each)
+  int32_t q64, r64;                           // 64 / n_inner, 64 % n_inner: the step of (a, b) from option k to k + 64
+  int32_t inner[PCLEAN_MAX_TERMS];  // 1: the term reads the inner factor (k % n_inner), 0: the outer (k / n_inner)
+  int32_t off[PCLEAN_MAX_TERMS];
+};
+
+template <int BT>
+__global__ __launch_bounds__(BT) void own_product_kernel(const OwnNodeDev nd, const DensDev dn, const OwnLaunch L,
+                                                          const OwnProductDev pr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char own_smem[];
+  __shared__ double s_red[BT / 64];
+  __shared__ int s_obs[PCLEAN_MAX_TERMS];
+  double* tv = reinterpret_cast<double*>(own_smem);                                // [pr.total]
+  unsigned long long* pre = reinterpret_cast<unsigned long long*>(tv + pr.total);  // [pr.n_chunks]
+  double* cmax = reinterpret_cast<double*>(pre + pr.n_chunks);                     // [pr.n_super] when pr.use_cmax
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x;
+  const int m_lo = L.piece_off[g], m_hi = L.piece_off[g + 1];
+  const int n = nd.n_cand, n_inner = pr.n_inner, nch = pr.n_chunks;
+  if (!L.probe) {  // a run none of whose rows lies in the window has nothing to do
+    int any = 0;
+    for (int q = m_lo + tid; q < m_hi; q += BT) {
+      const int r = L.members[q];
+      any |= (r >= L.win_lo && r < L.win_hi) ? 1 : 0;
+    }
+    if (!__syncthreads_or(any)) return;
+  }
+  {
+    const int row0 = L.probe ? L.item_row[L.members[m_lo]] : L.members[m_lo];
+    for (int ti = 0; ti < nd.n_terms; ++ti)
+      if (tid == ti) s_obs[ti] = nd.terms[ti].obs_col[row0];
+  }
+  __syncthreads();
+
+  // ---- phase 1: the terms, once per factor value
+  unsigned int skip = 0;
+  for (int ti = 0; ti < nd.n_terms; ++ti) {
+    const TermDev& tm = nd.terms[ti];
+    const int o = s_obs[ti];
+    const bool tab = tm.dens_kind == PCLEAN_DENS_TABULATED;
+    if (!tab && o < 0) {  // a missing observation: the term adds nothing
+      skip |= 1u << ti;
+      continue;
+    }
+    const int nf = pr.inner[ti] ? n_inner : pr.n_outer;
+    const size_t stride = pr.inner[ti] ? 1 : (size_t)n_inner;
+    double* dst = tv + pr.off[ti];
+    for (int j = tid; j < nf; j += BT) {
+      const int val = tm.cand_col[(size_t)j * stride];
+      double x;
+      if (tab) {
+        const int c = o < 0 ? 3 : ((int)tm.pair[(size_t)o * tm.n_lat + val] & 3);
+        x = tm.cls[(size_t)val * 4 + c];
+      } else {
+        const size_t idx = (size_t)o * tm.n_lat + val;
+        const int d = tm.elem_bytes == 1 ? (int)tm.pair[idx] : (int)((const uint16_t*)tm.pair)[idx];
+        x = own_term_density(tm, dn, d, val);
+      }
+      dst[j] = x;
+    }
+  }
+  __syncthreads();
+  // score of option k = a * n_inner + b with (a, b) at hand (a wavefront steps from k to k + 64 without dividing again):
+  // the ONE place where the plan-order sum that the bit parity rests on is written
+  auto score_ab = [&](int k, int a, int b) -> double {
+    double sk = nd.logp[k];
+    for (int ti = 0; ti < nd.n_terms; ++ti)
+      if (!((skip >> ti) & 1u)) sk += tv[pr.off[ti] + (pr.inner[ti] ? b : a)];
+    return sk;
+  };
+  auto score = [&](int k) -> double {  // (the walk of a draw: one option, its (a, b) by division)
+    const int a = k / n_inner;
+    return score_ab(k, a, k - a * n_inner);
+  };
+
+  // ---- phase 2, pass 1: scores (the loads of a group of chunks in flight together), the maximum of every group, the maximum
+  const int nsup = pr.n_super;
+  double lmax = -__builtin_inf();
+  for (int sc = wave; sc < nsup; sc += BT / 64) {
+    const int k0 = sc * (64 * OWN_SUPER) + lane;
+    int a = k0 / n_inner, b = k0 - a * n_inner;
+    double mx = -__builtin_inf();
+#pragma unroll
+    for (int j = 0; j < OWN_SUPER; ++j) {
+      const int k = k0 + (j << 6);
+      if (k < n) {
+        const double sk = score_ab(k, a, b);
+        if (L.probe && L.scores_out)
+          for (int mi = m_lo; mi < m_hi; ++mi) L.scores_out[(size_t)L.members[mi] * n + k] = sk;
+        mx = fmax(mx, sk);
+      }
+      a += pr.q64;
+      b += pr.r64;
+      if (b >= n_inner) {
+        b -= n_inner;
+        ++a;
+      }
+    }
+    const double cm = own_wave_max(mx);  // (one reduction per group: a maximum per 64 options measured slower)
+    if (pr.use_cmax && lane == 0) cmax[sc] = cm;
+    lmax = fmax(lmax, cm);
+  }
+  if (lane == 0) s_red[wave] = lmax;
+  __syncthreads();
+  double m = s_red[0];
+  for (int w = 1; w < BT / 64; ++w) m = fmax(m, s_red[w]);
+  const bool dead = m == -__builtin_inf();
+
+  // ---- pass 2: fixed-point weights, one sum per chunk (the chunks of a group far below the maximum sum to 0), inclusive prefix
+  for (int sc = wave; sc < nsup; sc += BT / 64) {
+    const bool weigh = !dead && (!pr.use_cmax || cmax[sc] - m >= -OWN_SKIP_BELOW);  // (the same for every lane of the wave)
+    const int k0 = sc * (64 * OWN_SUPER) + lane;
+    if (!weigh) {
+      for (int j = lane; j < OWN_SUPER && sc * OWN_SUPER + j < nch; j += 64) pre[sc * OWN_SUPER + j] = 0ull;
+      continue;
+    }
+    int a = k0 / n_inner, b = k0 - a * n_inner;
+    unsigned long long v[OWN_SUPER];
+#pragma unroll
+    for (int j = 0; j < OWN_SUPER; ++j) {
+      const int k = k0 + (j << 6);
+      v[j] = k < n ? pclean_fixw(score_ab(k, a, b) - m) : 0ull;
+      a += pr.q64;
+      b += pr.r64;
+      if (b >= n_inner) {
+        b -= n_inner;
+        ++a;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < OWN_SUPER; ++j) {
+      const int c = sc * OWN_SUPER + j;
+      if (c >= nch) break;  // (the same for every lane of the wave)
+      const unsigned long long t = own_wave_sum(v[j]);
+      if (lane == 0) pre[c] = t;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    unsigned long long carry = 0ull;
+    for (int base = 0; base < nch; base += 64) {
+      const int i = base + lane;
+      unsigned long long v = own_wave_scan(i < nch ? pre[i] : 0ull, lane) + carry;
+      if (i < nch) pre[i] = v;
+      carry = __shfl(v, 63, 64);
+    }
+  }
+  __syncthreads();
+  const unsigned long long U = pre[nch - 1];
+  const double lse = pclean_lse_from_fix(m, U);
+
+  // ---- the run's rows: one member per lane (own_leaf_kernel's draws)
+  const int nd_eff = L.probe ? max(L.n_draws, 1) : 1;
+  const int n_out = (m_hi - m_lo) * nd_eff;
+  for (int q = tid; q < n_out; q += BT) {
+    const int mem = L.members[m_lo + q / nd_eff], j = q % nd_eff;
+    int row, pid;
+    if (L.probe) {
+      row = L.item_row[mem];
+      pid = j;
+      if (j == 0 && L.lse_out) L.lse_out[mem] = lse;
+      if (L.n_draws <= 0) continue;
+    } else {
+      row = mem;
+      if (row < L.win_lo || row >= L.win_hi) continue;
+      const int i = row - L.win_lo;
+      L.logml[i] += lse;
+      if (L.keep[i]) continue;
+      pid = L.chosen[i];
+    }
+    int res = n - 1;
+    if (U != 0ull) {
+      const uint32_t rng_row = (uint32_t)((int64_t)row + L.row_offset);
+      const unsigned long long x = pclean_mulhi64(pclean_rand64(L.seed, rng_row, L.site, (uint32_t)pid, L.sweep), U);
+      int a = 0, b = nch - 1;
+      while (a < b) {  // the first chunk whose inclusive prefix exceeds x
+        const int mid = (a + b) >> 1;
+        if (pre[mid] > x)
+          b = mid;
+        else
+          a = mid + 1;
+      }
+      unsigned long long acc = a ? pre[a - 1] : 0ull;
+      int k = a << 6;
+      const int k_end = min(n, k + 64) - 1;  // (the chunk's total exceeds x - acc: the walk stops inside it)
+      for (; k < k_end; ++k) {
+        acc += pclean_fixw(score(k) - m);
         if (acc > x) break;
       }
       res = k;
@@ -637,10 +862,62 @@ int ensure_groups(pclean_ctx* ctx, OwnLeaf& lf) {
   return PCLEAN_OK;
 }
 
-int launch_leaf(pclean_ctx* ctx, const OwnNodeDev& od, const OwnLaunch& L, int n_pieces, OwnState* s) {
+// The leaf's option table is a full grid over its two value columns (pclean_set_options_cols: grid_outer_col, grid_inner) and
+// every term reads one of them: the plan of own_product_kernel and its dynamic LDS.  False: the generic kernels — no grid,
+// PCLEAN_NO_OWN_PRODUCT (the benchmark's baseline), or cached values and chunk sums beyond OWN_PRODUCT_LDS_MAX.
+// PCLEAN_NO_OWN_SKIP (read once per process, for the benchmark alone) keeps the product kernel and leaves out the group maxima
+// with the skip, as a plan does whose maxima do not fit: the same bits, every group weighed.
+bool own_product_plan(pclean_ctx* ctx, const OwnLeaf& lf, const OwnNodeDev& od, OwnProductDev* pr, size_t* lds) {
+  static const bool off = getenv("PCLEAN_NO_OWN_PRODUCT") != nullptr;
+  static const bool no_skip = getenv("PCLEAN_NO_OWN_SKIP") != nullptr;  // (the benchmark's ablation: every group is weighed)
+  const CandTable& t = ctx->cand[lf.node.table];
+  if (off || od.n_terms < 1 || od.n_terms > PCLEAN_MAX_TERMS) return false;
+  if (!t.valid || !t.is_options || t.logc_full.p != od.logp || t.grid_outer_col < 0 || t.n_cols != 2 || t.n_rows != od.n_cand ||
+      t.grid_inner < 1 || t.n_rows % t.grid_inner)
+    return false;
+  pr->n_inner = t.grid_inner;
+  pr->n_outer = t.n_rows / t.grid_inner;
+  pr->n_chunks = (od.n_cand + 63) >> 6;
+  pr->n_super = (pr->n_chunks + OWN_SUPER - 1) / OWN_SUPER;
+  pr->q64 = 64 / pr->n_inner;
+  pr->r64 = 64 % pr->n_inner;
+  pr->total = 0;
+  for (int ti = 0; ti < od.n_terms; ++ti) {
+    int col = -1;
+    for (int c = 0; c < 2; ++c)
+      if (od.terms[ti].cand_col == t.cols.p + (size_t)c * t.n_rows) col = c;
+    if (col < 0) return false;
+    pr->inner[ti] = col != t.grid_outer_col;
+    pr->off[ti] = pr->total;
+    pr->total += pr->inner[ti] ? pr->n_inner : pr->n_outer;
+  }
+  for (int ti = od.n_terms; ti < PCLEAN_MAX_TERMS; ++ti) pr->inner[ti] = pr->off[ti] = 0;
+  const size_t need = ((size_t)pr->total + (size_t)pr->n_chunks) * 8;
+  if (need > OWN_PRODUCT_LDS_MAX) return false;  // the cached term values do not fit the LDS of a workgroup
+  pr->use_cmax = !no_skip && need + (size_t)pr->n_super * 8 <= OWN_PRODUCT_LDS_MAX ? 1 : 0;
+  *lds = need + (pr->use_cmax ? (size_t)pr->n_super * 8 : 0);
+  return true;
+}
+
+int launch_leaf(pclean_ctx* ctx, const OwnLeaf& lf, const OwnNodeDev& od, const OwnLaunch& L, int n_pieces, OwnState* s) {
   if (n_pieces <= 0) return PCLEAN_OK;
   const DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
-  if (od.n_cand <= OWN_LDS_OPTIONS) {
+  OwnProductDev pr;
+  size_t lds = 0;
+  if (own_product_plan(ctx, lf, od, &pr, &lds)) {
+    if (!s->product_attr_set) {  // (a function attribute belongs to the device: once per context, not per process)
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)own_product_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OWN_PRODUCT_LDS_MAX));
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)own_product_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OWN_PRODUCT_LDS_MAX));
+      s->product_attr_set = true;
+    }
+    // a long grid: 16 wavefronts per workgroup — the LDS of such a plan leaves room for one or two workgroups on a CU, and
+    // every wavefront still has 16 chunks and more to go through
+    if (od.n_cand >= OWN_PRODUCT_WIDE)
+      hipLaunchKernelGGL(own_product_kernel<1024>, dim3(n_pieces), dim3(1024), lds, ctx->stream, od, dn, L, pr);
+    else
+      hipLaunchKernelGGL(own_product_kernel<256>, dim3(n_pieces), dim3(256), lds, ctx->stream, od, dn, L, pr);
+    s->stats.variants |= 4;
+  } else if (od.n_cand <= OWN_LDS_OPTIONS) {
     hipLaunchKernelGGL(own_leaf_kernel<true>, dim3(n_pieces), dim3(OWN_BT), 0, ctx->stream, od, dn, L);
     s->stats.variants |= 1;
   } else {
@@ -825,7 +1102,7 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
       L.seed = seed;
       L.sweep = sweep_idx;
       L.site = PCLEAN_SITE_NODE(bi, ni);
-      const int rc = launch_leaf(ctx, ods[li], L, lf.n_pieces, s);
+      const int rc = launch_leaf(ctx, lf, ods[li], L, lf.n_pieces, s);
       if (rc) return rc;
       s->stats.n_runs += lf.n_runs;
       s->stats.longest_run = std::max(s->stats.longest_run, lf.longest);
@@ -909,7 +1186,7 @@ extern "C" int pclean_score_own(pclean_ctx* ctx, int32_t block_id, int32_t node_
   L.seed = seed;
   L.sweep = sweep;
   L.site = PCLEAN_SITE_NODE(block_id, node_id);
-  rc = launch_leaf(ctx, od, L, n_pieces, s);
+  rc = launch_leaf(ctx, lf, od, L, n_pieces, s);
   if (rc) return rc;
   if (lse) HIPCHK(ctx, hipMemcpyAsync(lse, d_lse, (size_t)n_items * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (scores) HIPCHK(ctx, hipMemcpyAsync(scores, d_scores, (size_t)n_items * K * 8, hipMemcpyDeviceToHost, ctx->stream));

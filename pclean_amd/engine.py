@@ -102,6 +102,23 @@ class InferenceConfig:
                            int(self.use_mh_instead_of_pg), self.rejuv_frequency, self.reporting_frequency)
 
 
+def option_prior(lw, trace, cname, aname):
+    """log prior of every option of the ChooseProportionally choice cname.aname, in option order: logprobs() (utils.jl:33-36);
+    an IndexedProportionsParameter: log theta_key[option], key-major as the options; a product leaf: the joint prior
+    log pA(a) + log theta_a[b], added in that order"""
+    m = lw.model
+    d = m.classes[cname].attr(aname).dist
+    with np.errstate(divide="ignore"):
+        logp = np.log(trace.params[(cname, d.param)].value)
+        ix = getattr(lw, "indexed", {}).get((cname, aname), ("", ""))
+        if ix[0] == "product":
+            da = m.classes[cname].attr(ix[1]).dist
+            la = (np.log(trace.params[(cname, da.param)].value) if isinstance(da, ChooseProportionally)
+                  else np.full(len(da.options), -np.log(len(da.options))))
+            logp = la[:, None] + logp
+        return logp.reshape(-1)
+
+
 class Engine:
     def __init__(self, lowered, obs, device=0, dist_mode=_lib.DIST_DL, row_offset=0):
         self.lw = lowered
@@ -356,16 +373,7 @@ class Engine:
         for (cname, aname), dom in lw.latent_dom.items():
             d = m.classes[cname].attr(aname).dist
             if isinstance(d, ChooseProportionally):
-                with np.errstate(divide="ignore"):
-                    # logprobs(), utils.jl:33-36; an IndexedProportionsParameter: log theta_key[option], key-major as the options
-                    logp = np.log(trace.params[(cname, d.param)].value)
-                    ix = getattr(lw, "indexed", {}).get((cname, aname), ("", ""))
-                    if ix[0] == "product":  # joint prior log pA(a) + log theta_a[b], added in that order
-                        da = m.classes[cname].attr(ix[1]).dist
-                        la = (np.log(trace.params[(cname, da.param)].value) if isinstance(da, ChooseProportionally)
-                              else np.full(len(da.options), -np.log(len(da.options))))
-                        logp = la[:, None] + logp
-                    logp = logp.reshape(-1)
+                logp = option_prior(lw, trace, cname, aname)
                 self.option_logp[(cname, aname)] = logp
                 prev = last.get(("options", cname, aname))
                 if prev is not None and np.array_equal(prev, logp):
@@ -456,7 +464,9 @@ class Engine:
 
     # -- a flat observed class: own blocks (csrc/own_block.hip) -----------------------------------------------------
     def _own_blocks(self, trace):
-        """[(block, first row of trace.own, one past its last)] of the own blocks"""
+        """[(block, first row of trace.own, one past its last)] of the own blocks: the CHOICES of a block as rows of
+        Trace.own.  In a block without a product leaf these are its device leaves too; with one, the device holds one leaf
+        for the pair (_own_device_blocks, which _push_own / pull_own go by)"""
         out = []
         for li, (_, b, _) in enumerate(trace.own_leaves()):
             if out and out[-1][0] == b:
@@ -465,19 +475,36 @@ class Engine:
                 out.append([b, li, li + 1])
         return out
 
+    def _own_device_blocks(self, trace):
+        """[(block, [rows of trace.own per device leaf of the block, in node order])] of the own blocks: one row, or (index's
+        row, choice's row) of a product leaf"""
+        out = []
+        for b, _, rows in trace.own_device_leaves():
+            if out and out[-1][0] == b:
+                out[-1][1].append(rows)
+            else:
+                out.append((b, [rows]))
+        return out
+
     def _push_own(self, trace):
-        """the trace's own choices -> device, unless the device holds them already (they live there between sweeps)"""
+        """the trace's own choices -> device, unless the device holds them already (they live there between sweeps); the two
+        choices of a product leaf go as the joint option index * |B| + choice"""
         key = (id(trace), trace._own_version, id(self.hip))
         if getattr(trace, "_own_dev", None) is self or getattr(self, "_own_key", None) == key:
             return
-        for b, l0, l1 in self._own_blocks(trace):
-            self.hip.set_own(b, trace._own[l0:l1])
+        for b, leaves in self._own_device_blocks(trace):
+            self.hip.set_own(b, np.stack([trace._own[r[0]] if len(r) == 1 else trace.own_joint(trace._own, *r) for r in leaves]))
         self._own_key = key
 
     def pull_own(self, trace):
         """device -> trace._own (Trace.own calls it when the device is ahead)"""
-        for b, l0, l1 in self._own_blocks(trace):
-            trace._own[l0:l1] = self.hip.get_own(b, l1 - l0, trace._own.shape[1])
+        for b, leaves in self._own_device_blocks(trace):
+            vals = self.hip.get_own(b, len(leaves), trace._own.shape[1])
+            for v, r in zip(vals, leaves):
+                if len(r) == 1:
+                    trace._own[r[0]] = v
+                else:
+                    trace._own[r[0]], trace._own[r[1]] = trace.own_split(v, r[1])
         self._own_key = (id(trace), trace._own_version, id(self.hip))
 
     def sweep_own(self, trace, config, seed, sweep_idx, lo=0, hi=None, want_outputs=True):
@@ -514,7 +541,10 @@ class Engine:
         probabilities float64 [top][n], probability of the row's current value float64 [n])}, the options ordered by
         probability (ties: the smaller option index), -1 / 0.0 where fewer options are possible.  The option priors are
         re-uploaded whenever their parameter moved (upload_trace) and the own choices are pushed unless the device holds
-        them; nothing is drawn, written or pulled, and no count changes."""
+        them; nothing is drawn, written or pulled, and no count changes.  A choice indexed by a sibling choice and that
+        index (one product leaf): the top options are those of the PAIR — entry t of both is the t-th most probable pair,
+        decoded per choice — and every probability is the pair's JOINT probability, not a per-column marginal; the probability
+        of the current value is that of the current pair."""
         if not getattr(self.lw, "flat", False):
             raise _lib.PCleanHipError("Engine.own_marginals: the observed class is not flat (it has reference-slot blocks)")
         hi = trace._own.shape[1] if hi is None else hi
@@ -524,7 +554,16 @@ class Engine:
         self.upload_trace(trace)
         self._push_own(trace)
         self.hip.set_active_rows(lo, n)
-        return {a: self.hip.own_marginals(b, nd, top, n) for a, b, nd in trace.own_leaves()}
+        names, out = trace.own_leaves(), {}
+        for b, nd, rows in trace.own_device_leaves():
+            opt, prob, cur = self.hip.own_marginals(b, nd, top, n)
+            if len(rows) == 1:
+                out[names[rows[0]][0]] = (opt, prob, cur)
+                continue
+            # a product leaf: the joint top options, decoded into an entry per choice; both carry the JOINT probability
+            oa, ob = trace.own_split(opt, rows[1])
+            out[names[rows[0]][0]], out[names[rows[1]][0]] = (oa, prob, cur), (ob, prob.copy(), cur.copy())
+        return out
 
     # -- device-resident commit (csrc/commit.hip) ------------------------------------------------------------------
     def _slack_min(self, cname, t):

@@ -6,7 +6,8 @@ import os
 
 import pandas as pd
 
-from .model import (AddTypos, ChooseProportionally, ChooseUniformly, Model, ProportionsParameter, Query, StringPrior)
+from .model import (AddTypos, ChooseProportionally, ChooseUniformly, IndexedProportionsParameter, Model, ProportionsParameter,
+                    Query, StringPrior)
 
 DATA_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "datasets")
 
@@ -239,16 +240,25 @@ def flat_vocabulary(clean, columns=FLAT_COLUMNS):
     return {c: list(dict.fromkeys(v for v in clean[c] if v is not None)) for c in columns}
 
 
-def flat_model(vocab):
+def flat_model(vocab, dependent=None):
     """`@class Obs`: per column one own block  `col ~ ChooseProportionally(vocab[col], col_p); col_obs ~ AddTypos(col)`
-    with a learned ProportionsParameter — no latent class, no reference slot (a FLAT class: LoweredModel.flat)."""
+    with a learned ProportionsParameter — no latent class, no reference slot (a FLAT class: LoweredModel.flat).
+    dependent = (index column, column): the two share one block and the column's choice is indexed by the index column's,
+    `col ~ ChooseProportionally(vocab[col], col_p, index=index column)` with an IndexedProportionsParameter — e.g. the
+    hospital's State given its City (one product leaf: own_block.hip)."""
     m = Model()
     o = m.add_class("Obs")
+    ix, dep = dependent or (None, None)
     for c in vocab:
-        o.param(f"{c}_p", ProportionsParameter(1.0))
+        o.param(f"{c}_p", IndexedProportionsParameter(1.0) if c == dep else ProportionsParameter(1.0))
     for c, words in vocab.items():
+        if c == dep:
+            continue  # (declared in its index's block)
         with o.block():
             o.choice(c, ChooseProportionally(words, f"{c}_p"))
+            if c == ix:
+                o.choice(dep, ChooseProportionally(vocab[dep], f"{dep}_p", index=ix))
+                o.choice(f"{dep}_obs", AddTypos(dep))
             o.choice(f"{c}_obs", AddTypos(c))
     return m
 

@@ -92,6 +92,7 @@ TABULATED = (ExpandOnShortVersion, FormatName)
 # the two densities of the three-name FormatName (format_name.jl:18, 22), added left to right as the reference adds them
 NAME3_LOG_THREE = math.log(0.9) + math.log(0.9) + math.log(0.9)
 NAME3_LOG_TWO = math.log(0.1)
+OWN_MAX_OPTIONS = 64 * 4096  # options of one own option list (csrc/own_block.hip: OWN_MAX_OPTIONS)
 
 
 class TimePrior:
@@ -485,8 +486,8 @@ class LoweredModel:
                 if ia.kind != "choice":
                     raise NotImplementedError(f"{who}: the index {ix} is a reference slot, not a value")
                 if cname == self.query.cls:
-                    raise NotImplementedError(f"{who}: an indexed choice among the observed class's own choices is not lowered "
-                                              "(those are enumerated with the Gaussian observations)")
+                    self._resolve_own_indexed(cname, cls, a, ia, seen)
+                    continue
                 if isinstance(ia.dist, ChooseProportionally) and ia.dist.index is not None:
                     raise NotImplementedError(f"{who}: the index {ix} is itself indexed")
                 if ix in seen:
@@ -525,6 +526,52 @@ class LoweredModel:
                         raise NotImplementedError(f"{who}: the index {ix} is observed through {obsname}, which has missing "
                                                   "values; the keyed form needs the key of every row")
                 self.indexed[(cname, a.name)] = ("keyed", ix)
+
+    def _resolve_own_indexed(self, cname, cls, a, ia, seen):
+        """An indexed own choice of the OBSERVED class: served in a flat class when its index is a sibling own
+        ChooseProportionally choice over strings with a plain ProportionsParameter, declared before it in the same block —
+        the two become one product leaf at the dependent's place (_lower_own_block).  Everything else is refused by name."""
+        ix, who = a.dist.index, f"{cname}.{a.name}"
+        if isinstance(ia.dist, ChooseUniformly):
+            raise NotImplementedError(f"{who}: an indexed choice among the observed class's own choices is not lowered when "
+                                      f"its index ({ix}) is a ChooseUniformly choice; an own index is a ChooseProportionally "
+                                      "choice with a plain ProportionsParameter")
+        fks = [x.name for x in cls.attrs if x.kind == "fk"]
+        if fks:
+            raise NotImplementedError(f"{who}: an indexed own choice in a class with a reference-slot block ({', '.join(fks)}) "
+                                      "is not lowered; own blocks are served for flat classes alone")
+        if not isinstance(ia.dist, ChooseProportionally):
+            if (cname, ix) in self.direct_obs.values():
+                raise NotImplementedError(f"{who}: the index {ix} is observed directly and is not a choice (the keyed form); "
+                                          "among the observed class's own choices the index is a sibling ChooseProportionally "
+                                          "choice")
+            raise NotImplementedError(f"{who}: the index {ix} is a {type(ia.dist).__name__}, not a sibling ChooseProportionally "
+                                      "choice")
+        if ia.dist.index is not None:
+            raise NotImplementedError(f"{who}: the index {ix} is itself indexed")
+        if ix in seen:
+            raise NotImplementedError(f"{who}: {ix} already indexes {seen[ix]}; two dependents on one index are not lowered")
+        seen[ix] = a.name
+        names = [x.name for x in cls.attrs]
+        blk_of = {n: k for k, ns in enumerate(cls.blocks) for n in ns}
+        if blk_of[ix] != blk_of[a.name]:
+            raise NotImplementedError(f"{who}: the index {ix} is declared in another block")
+        if names.index(ix) > names.index(a.name):
+            raise NotImplementedError(f"{who}: the index {ix} must be declared before the choice")
+        for mid in cls.attrs[names.index(ix) + 1:names.index(a.name)]:
+            reads = list(getattr(mid, "args", ())) if mid.kind == "julia" else [
+                getattr(getattr(mid, "dist", None), f, None) for f in ("keyed_by", "index", "ref", "mean", "unit", "val", "key")]
+            if ix in reads:
+                raise NotImplementedError(f"{who}: {mid.name}, declared between the index {ix} and the choice, reads the index; "
+                                          "declare it after the choice")
+        if (cname, ix) not in self.latent_dom:
+            raise NotImplementedError(f"{who}: the options of the index {ix} are not strings")
+        na, nb = len(ia.dist.options), len(a.dist.options)
+        if na * nb > OWN_MAX_OPTIONS:
+            raise NotImplementedError(f"{who}: the product with {ix} has {na} x {nb} = {na * nb} options, more than the "
+                                      f"{OWN_MAX_OPTIONS} an own option list holds (OWN_MAX_OPTIONS)")
+        self.indexed[(cname, a.name)] = ("product", ix)
+        self.product_index[(cname, ix)] = a.name
 
     def keyed_index(self, cname, aname):
         """attribute whose (directly observed) value selects the options of choice aname: StringPrior / TimePrior atoms
@@ -743,6 +790,7 @@ class LoweredModel:
         # block an own block: a class that mixes the two kinds would need the own values to follow the ancestor permutation
         # of the particles inside the sweep.
         self.own_leaf = {}   # own choice of the observed class -> (block, node) of its leaf
+        self.own_product = {}  # own choice indexed by a sibling own choice -> that index: the two share ONE product leaf
         own_blocks = [bi for bi, names in enumerate(eblocks) if root_of_block[bi] is None and any(
             ocls.attr(n).kind == "choice" and not isinstance(ocls.attr(n).dist, MaybeSwap) for n in names)]
         self.flat = bool(own_blocks) and len(own_blocks) == len(eblocks)
@@ -1029,7 +1077,10 @@ class LoweredModel:
         declaration order (AddTypos, ExpandOnShortVersion, one-name FormatName) and, last, the equality term of a direct
         observation in the query — the order a new row's leaf gives them (_emit_fk_node).  The reference enumerates such a
         block like any other (proposal_compiler.jl:55-129); the choices of one block are separable (no observation reads two
-        of them), so each is enumerated on its own.  Everything else is refused by name."""
+        of them), so each is enumerated on its own.  The exception is a choice indexed by a sibling choice
+        (_resolve_own_indexed): the two become ONE leaf at the dependent's place over the grid a * |B| + b of the two-column
+        option table (option_cols), the index's terms on value column 0, then the choice's on column 1; own_leaf maps both
+        choices to that leaf and own_product names the pair.  Everything else is refused by name."""
         cls = self.query.cls
         blk = dict(own=True, nodes=[], terms=[], children=[], colmap=[], node_info=[], root_class=None, root_fk=None,
                    ctx_src_block=[], ctx_src_col=[])
@@ -1048,7 +1099,7 @@ class LoweredModel:
                 raise NotImplementedError(f"{who}: a {type(d).__name__} own choice is not lowered (its proposal holds a dummy value "
                                           "or none at all); own choices are ChooseProportionally or ChooseUniformly")
             elif isinstance(d, ChooseProportionally):
-                if d.index is not None:  # (_resolve_indexed refuses it first)
+                if d.index is not None and self.indexed.get((cls, n), ("", ""))[0] != "product":  # (_resolve_indexed refuses it first)
                     raise NotImplementedError(f"{who}: an indexed choice among the observed class's own choices is not lowered")
                 choices.append(a)
             elif isinstance(d, ChooseUniformly):
@@ -1077,27 +1128,50 @@ class LoweredModel:
                 raise NotImplementedError(f"{who}: {ref} is not an enumerated own choice")
             if a.name in self.obs_index:  # (an observation the query does not bind scores nothing)
                 by_choice[ref].append(a)
-        for c in choices:
+
+        def emit_terms(c, cand_col):
+            """the observations of own choice c in declaration order, then the equality term of its direct observation"""
             key = (cls, c.name)
             dom = self.latent_dom[key]
-            tb = len(blk["terms"])
             for a in by_choice[c.name]:
                 if isinstance(a.dist, TABULATED):
                     t = dict(obs=a.name, pair=self._class_pair_for(a.name, key, a.dist), max_typos=None, ctx=None,
                              dens=_lib.DENS_TABULATED)
                 else:
                     t = dict(obs=a.name, pair=self._pair_for(a.name, key, dom), max_typos=a.dist.max_typos, ctx=None)
-                self._emit_term(blk, t, 0)
+                self._emit_term(blk, t, cand_col)
             if c.name in self.direct_obs:
                 col = self._dirty_columns[self.query_columns[c.name]]
                 stray = sorted({v for v in col if v is not None and dom.get(v) < 0})
                 if stray:
                     raise ValueError(f"{cls}.{c.name}: observed value {stray[0]!r} is not among the options of the choice")
                 self._emit_term(blk, dict(obs=c.name, pair=self._eq_pair_for(key), max_typos=None, ctx=None,
-                                          dens=_lib.DENS_EQUAL), 0)
+                                          dens=_lib.DENS_EQUAL), cand_col)
+
+        for c in choices:
+            key = (cls, c.name)
+            if key in self.product_index:
+                continue  # enumerated jointly with its dependent: value column 0 of that leaf
+            tb = len(blk["terms"])
+            index = self.indexed.get(key, ("", ""))
+            index = index[1] if index[0] == "product" else None
+            if index is not None:
+                # ONE leaf over the grid a * |B| + b (option_cols, key-major): the index's terms read value column 0, the
+                # choice's column 1
+                emit_terms(ocls.attr(index), 0)
+                emit_terms(c, 1)
+                if len(blk["terms"]) - tb > _lib.MAX_TERMS:
+                    raise NotImplementedError(f"{cls}.{c.name}: the product leaf with {index} carries more than "
+                                              f"{_lib.MAX_TERMS} terms (PCLEAN_MAX_TERMS)")
+                self.own_leaf[index] = (bi, len(blk["nodes"]))
+                self.own_product[c.name] = index
+            else:
+                emit_terms(c, 0)
             self.own_leaf[c.name] = (bi, len(blk["nodes"]))
             blk["nodes"].append((_lib.NODE_LEAF, self.option_id[key], tb, len(blk["terms"]) - tb, 0, 0, -1, -1, 0, 0, 0, 0))
             blk["node_info"].append(dict(kind="leaf", cls=cls, attr=c.name, path=c.name))
+            if index is not None:
+                blk["node_info"][-1]["product"] = (index, c.name)
         if not choices:
             raise NotImplementedError(f"{cls}: a block without a reference slot and without an own choice "
                                       f"({', '.join(names)}) is not lowered")

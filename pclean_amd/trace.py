@@ -246,9 +246,63 @@ class Trace:
                 out.append((li, self._params[(cls, d.param)]))
         return out
 
+    def own_pairs(self):
+        """{row of `own` of an own choice indexed by a sibling own choice: row of that index}: the two share ONE device
+        leaf, whose value is index * |options of the choice| + choice (LoweredModel.own_product)"""
+        names = [a for a, _, _ in self.own_leaves()]
+        return {names.index(b): names.index(a) for b, a in getattr(self.lw, "own_product", {}).items()}
+
+    def own_device_leaves(self):
+        """[(block, node, rows of `own`)] of the device's leaves in (block, node) order: one row of `own`, or (index's row,
+        choice's row) of a product leaf"""
+        pairs = self.own_pairs()
+        out = []
+        for li, (_, b, n) in enumerate(self.own_leaves()):
+            if li in pairs.values():
+                continue
+            out.append((b, n, (pairs[li], li) if li in pairs else (li,)))
+        return out
+
+    def _own_sizes(self, rows):
+        return [len(self.lw.latent_dom[(self.lw.query.cls, self.own_leaves()[li][0])]) for li in rows]
+
+    def own_joint(self, own, la, lb):
+        """rows la (index) and lb (choice) of `own` as the product leaf's joint option index * |B| + choice; -1 stays -1, a
+        row with only one of the two set is a ValueError"""
+        va, vb = own[la], own[lb]
+        if np.any((va < 0) != (vb < 0)):
+            i = int(np.flatnonzero((va < 0) != (vb < 0))[0])
+            names = self.own_leaves()
+            raise ValueError(f"row {i}: only one of the own choices {names[la][0]} and {names[lb][0]} is set; the two are "
+                             "enumerated jointly")
+        return np.where(va < 0, -1, va * self._own_sizes((lb,))[0] + vb).astype(np.int32)
+
+    def own_split(self, joint, lb):
+        """(index, choice) option indices of a product leaf's joint values; -1 stays -1 in both"""
+        kb = self._own_sizes((lb,))[0]
+        joint = np.asarray(joint)
+        return np.where(joint < 0, -1, joint // kb).astype(np.int32), np.where(joint < 0, -1, joint % kb).astype(np.int32)
+
+    def own_joint_counts(self, lb):
+        """[index][choice] histogram of the product leaf behind row lb of `own`: IndexedProportionsState.counts"""
+        la = self.own_pairs()[lb]
+        ka, kb = self._own_sizes((la, lb))
+        dev = getattr(self, "_own_dev", None)
+        if dev is not None:
+            _, b, n = self.own_leaves()[lb]
+            return dev.hip.own_counts(b, n, ka * kb).reshape(ka, kb)
+        v = self.own_joint(self._own, la, lb)
+        return np.bincount(v[v >= 0], minlength=ka * kb).astype(np.int64).reshape(ka, kb)
+
     def own_counts(self, li):
         """histogram of row li of `own` over the choice's options: from the device while it is ahead (pclean_own_counts:
-        nothing per row crosses PCIe), else from the host array"""
+        nothing per row crosses PCIe), else from the host array.  An indexed choice: [index][option], the joint histogram
+        of its product leaf; its index: the row sums of that."""
+        pairs = self.own_pairs()
+        if li in pairs:
+            return self.own_joint_counts(li)
+        if li in pairs.values():
+            return self.own_joint_counts(next(b for b, a in pairs.items() if a == li)).sum(axis=1)
         a, b, n = self.own_leaves()[li]
         k = len(self.lw.latent_dom[(self.lw.query.cls, a)])
         dev = getattr(self, "_own_dev", None)
@@ -259,8 +313,16 @@ class Trace:
 
     def refresh_own_counts(self):
         """update_sufficient_statistics! of the own choices (row_inference.jl:172-185), for all rows at once"""
+        pairs, joint = self.own_pairs(), {}
+        index_of = {a: b for b, a in pairs.items()}
         for li, state in self._own_params():
-            state.counts[:] = self.own_counts(li)
+            lb = li if li in pairs else index_of.get(li)
+            if lb is None:
+                state.counts[:] = self.own_counts(li)
+                continue
+            if lb not in joint:  # (one histogram serves both parameters)
+                joint[lb] = self.own_joint_counts(lb)
+            state.counts[:] = joint[lb] if li == lb else joint[lb].sum(axis=1)
 
     def __init__(self, lowered, n_rows, seed=0):
         self._dev = None       # the Engine whose device state is ahead of the host arrays (None: the host is current)
@@ -292,7 +354,9 @@ class Trace:
         self.cur = np.full((len(lowered.blocks), n_rows), -1, dtype=np.int32)
         # a flat observed class (LoweredModel.flat): the own choices of every row, int32 [leaf][n_rows] option indices in the
         # order of own_leaves() (block, node), -1 = none yet.  The sweeps write them on the device (Engine.sweep_own) and
-        # leave the host array behind: `own` pulls it on access; the Dirichlet counts come from a device histogram.
+        # leave the host array behind: `own` pulls it on access; the Dirichlet counts come from a device histogram.  One row per
+        # own CHOICE, each holding that choice's own option index: the two choices of a product leaf (own_pairs) are two rows
+        # here and one joint value index * |B| + choice on the device (Engine._push_own encodes, pull_own decodes).
         self._own = np.full((len(self.own_leaves()), n_rows), -1, dtype=np.int32)
         self._own_dev = None      # the Engine whose device values are ahead of _own
         self._own_version = 0     # bumped by every host access to `own` (the engine re-uploads the values when it moved)
@@ -638,9 +702,11 @@ class Trace:
             assert np.all((own >= 0).all(axis=0) | (own < 0).all(axis=0)), "own choices: a row holds some but not all"
             for li, (a, _, _) in enumerate(self.own_leaves()):
                 assert own[li].max(initial=-1) < len(lw.latent_dom[(lw.query.cls, a)]), f"{a}: a value beyond the options"
+            pairs = self.own_pairs()
             for li, state in self._own_params():
-                v = own[li]
-                assert np.array_equal(np.bincount(v[v >= 0], minlength=len(state.counts)), state.counts), \
+                v = self.own_joint(own, pairs[li], li) if li in pairs else own[li]  # (an indexed choice: [index][option])
+                assert np.array_equal(np.bincount(v[v >= 0], minlength=state.counts.size).reshape(state.counts.shape),
+                                      state.counts), \
                     f"{lw.query.cls}.{self.own_leaves()[li][0]}: Dirichlet counts out of sync"
             return
         for bi, blk in enumerate(lw.blocks):

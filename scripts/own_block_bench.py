@@ -13,7 +13,18 @@ discarded, then --runs rounds; medians and ranges go into the JSON line under "m
 (default profiles/own_marginals_bench.json; the committed file collects three such lines, alternated with the parent
 commit's, under "this_commit").
 
-usage: own_block_bench.py [--rows N] [--runs R] [--particles P] [--marginals [--out FILE]]"""
+--product: City x State of the same generator as ONE product leaf (`state ~ ChooseProportionally(states, theta, index="city")`,
+both observed through AddTypos) — own_product_kernel.  The trace starts from the clean values (the sweep's cost does not
+depend on them) and one parameter move; device ms of pclean_sweep_own by HIP events, 2 warm-ups and --runs runs, with the
+grid size, the distinct tuples, the longest run and the byte model.  If the grid exceeded OWN_MAX_OPTIONS the least
+frequent cities (and their rows) would be dropped until it fits; the generator's 3 657 x 50 needs none dropped.
+--product --alternate N: N rounds of fresh processes of this build, the default path, PCLEAN_NO_OWN_PRODUCT=1 (the generic
+own_leaf_kernel: the only way the code computed these numbers before) and PCLEAN_NO_OWN_SKIP=1 (the product kernel
+without its exact skip: what the skip buys) in turns, on one generated data set; the lines and
+the verdict (the product kernel's median below the baseline's fastest run) go into --out (default
+profiles/own_product_bench.json).
+
+usage: own_block_bench.py [--rows N] [--runs R] [--particles P] [--marginals [--out FILE]] [--product [--alternate N] [--out FILE]]"""
 import json
 import os
 import sys
@@ -24,7 +35,8 @@ import numpy as np
 
 from pclean_amd.engine import Engine, InferenceConfig
 from pclean_amd.inference import initialize_trace
-from pclean_amd.model import AddTypos, ChooseProportionally, LoweredModel, Model, ProportionsParameter, Query
+from pclean_amd.model import (OWN_MAX_OPTIONS, AddTypos, ChooseProportionally, IndexedProportionsParameter, LoweredModel, Model,
+                              ProportionsParameter, Query)
 from pclean_amd.synth import synth_hospital
 from pclean_amd.trace import Trace
 
@@ -90,6 +102,126 @@ def time_marginals(hip, c, n, runs):
     return out
 
 
+def product_byte_model(n_rows, na, nb, n_groups):
+    """bytes own_product_kernel has to move: per workgroup the two factors' values once (value 4, pair byte 1, length 2 each)
+    and the grid's priors twice at most (8 per option and pass; the weight pass skips the chunks far below the maximum);
+    per row what byte_model counts"""
+    per_group = (na + nb) * (4 + 1 + 2) + 2 * na * nb * 8 + 8 + 8
+    per_row = 4 + 8 + 8 + 16 + 8 + 4 + 4
+    return n_groups * per_group + n_rows * per_row
+
+
+def product_data(n):
+    dirty, clean, _ = synth_hospital(n_rows=n, n_hosp=max(n // 100, 10))
+    cities, states = list(dict.fromkeys(clean["City"])), list(dict.fromkeys(clean["State"]))
+    dropped = 0
+    if len(cities) * len(states) > OWN_MAX_OPTIONS:  # the stated rule: the most frequent cities that fit, their rows alone
+        keep = OWN_MAX_OPTIONS // len(states)
+        freq = {}
+        for c in clean["City"]:
+            freq[c] = freq.get(c, 0) + 1
+        kept = set(sorted(cities, key=lambda c: -freq[c])[:keep])
+        rows = [i for i, c in enumerate(clean["City"]) if c in kept]
+        dropped = len(cities) - keep
+        dirty = {k: [dirty[k][i] for i in rows] for k in ("City", "State")}
+        clean = {k: [clean[k][i] for i in rows] for k in ("City", "State")}
+        cities = [c for c in cities if c in kept]
+    return dict(dirty={k: dirty[k] for k in ("City", "State")}, clean={k: clean[k] for k in ("City", "State")}, cities=cities,
+                states=states, dropped_cities=dropped)
+
+
+def product_run(D, runs, P):
+    """one process: the JSON line of --product"""
+    cities, states, dirty = D["cities"], D["states"], D["dirty"]
+    n = len(dirty["City"])
+    m = Model()
+    o = m.add_class("Obs")
+    o.param("city_p", ProportionsParameter(1.0))
+    o.param("theta", IndexedProportionsParameter(1.0))
+    with o.block():
+        o.choice("city", ChooseProportionally(cities, "city_p"))
+        o.choice("state", ChooseProportionally(states, "theta", index="city"))
+        o.choice("city_obs", AddTypos("city"))
+        o.choice("state_obs", AddTypos("state"))
+    lw = LoweredModel(m, Query(m, "Obs", {"City": ("city", "city_obs"), "State": ("state", "state_obs")}), dirty)
+    eng = Engine(lw, lw.encode_observations(dirty))
+    try:
+        tr = Trace.from_clean_values(lw, {0: {"city": D["clean"]["City"], "state": D["clean"]["State"]}}, n)
+        tr.resample_parameters()
+        eng.upload_trace(tr)
+        eng._push_own(tr)
+        hip, c = eng.hip, InferenceConfig(1, P).as_c()
+        hip.set_active_rows(0, n)
+        dev_ms = []
+        for r in range(runs + 2):
+            hip.sweep_own(c, 1, r, n)
+            dev_ms.append(float(hip.get_timing().total_ms))
+        st = hip.get_own_stats()
+        vals = hip.get_own(0, 1, n)[0]
+        assert vals.min() >= 0 and vals.max() < len(cities) * len(states)
+    finally:
+        eng.close()
+    na, nb = len(cities), len(states)
+    out = dict(rows=n, grid=[na, nb], options=na * nb, dropped_cities=D["dropped_cities"], particles=P, warmups=2, runs=runs,
+               path="generic (PCLEAN_NO_OWN_PRODUCT)" if os.environ.get("PCLEAN_NO_OWN_PRODUCT") else (
+                   "product kernel without the skip (PCLEAN_NO_OWN_SKIP)" if os.environ.get("PCLEAN_NO_OWN_SKIP") else "default"),
+               variants=int(st.variants), distinct_tuples=int(st.n_runs), longest_run=int(st.longest_run),
+               workgroups=int(st.n_workgroups), sweep_own_device_ms=_summary(dev_ms[2:]),
+               model_bytes=int(product_byte_model(n, na, nb, st.n_workgroups)),
+               checksum=int(np.bitwise_xor.reduce(vals.astype(np.int64) * (np.arange(n) + 1))))
+    out["model_gb_per_s"] = round(out["model_bytes"] / (1e6 * out["sweep_own_device_ms"]["median"]), 1)
+    return out
+
+
+def product_main():
+    import pickle
+    import subprocess
+    import tempfile
+    a = sys.argv[1:]
+    n, runs, P = _arg("--rows", 1_000_000), _arg("--runs", 7), _arg("--particles", 20)
+    if "--data" in a:  # a child of --alternate
+        with open(a[a.index("--data") + 1], "rb") as f:
+            D = pickle.load(f)
+        print(json.dumps(product_run(D, runs, P)))
+        return
+    D = product_data(n)
+    pairs = _arg("--alternate", 0)
+    if not pairs:
+        print(json.dumps(product_run(D, runs, P)))
+        return
+    lines = {"default": [], "generic": [], "no_skip": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "data.pkl")
+        with open(path, "wb") as f:
+            pickle.dump(D, f)
+        for k in range(pairs):
+            for name in lines:
+                env = dict(os.environ)
+                env.pop("PCLEAN_NO_OWN_PRODUCT", None)
+                env.pop("PCLEAN_NO_OWN_SKIP", None)
+                if name == "generic":
+                    env["PCLEAN_NO_OWN_PRODUCT"] = "1"
+                if name == "no_skip":  # the product kernel without its exact skip of the groups far below the maximum
+                    env["PCLEAN_NO_OWN_SKIP"] = "1"
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--product", "--data", path, "--runs", str(runs),
+                                    "--particles", str(P)], env=env, stdout=subprocess.PIPE, text=True, timeout=900, check=True)
+                lines[name].append(json.loads(r.stdout.strip().splitlines()[-1]))
+                print(f"[{name} {k}] {lines[name][-1]['sweep_own_device_ms']}", flush=True)
+    med = float(np.median([x["sweep_own_device_ms"]["median"] for x in lines["default"]]))
+    fastest = min(x["sweep_own_device_ms"]["min"] for x in lines["generic"])
+    no_skip = float(np.median([x["sweep_own_device_ms"]["median"] for x in lines["no_skip"]]))
+    out = dict(product_median_ms=round(med, 3), baseline_fastest_run_ms=round(fastest, 3), product_below_baseline=bool(med < fastest),
+               product_without_skip_median_ms=round(no_skip, 3),
+               same_values=len({x["checksum"] for v in lines.values() for x in v}) == 1, **lines)
+    dst = a[a.index("--out") + 1] if "--out" in a else os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "own_product_bench.json")
+    with open(dst, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: out[k] for k in ("product_median_ms", "baseline_fastest_run_ms", "product_below_baseline",
+                                          "product_without_skip_median_ms", "same_values")}))
+
+
 def main():
     n, runs, P = _arg("--rows", 1_000_000), _arg("--runs", 7), _arg("--particles", 20)
     t0 = time.time()
@@ -153,4 +285,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    product_main() if "--product" in sys.argv[1:] else main()

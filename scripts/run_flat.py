@@ -6,7 +6,12 @@ cell an AddTypos observation of its row's choice.  initialize_trace + run_infere
 accuracy and F1 of its most probable value next to the last sample's, and with the cells whose MAP probability lies below
 0.5 / 0.9 left at their dirty value.
 
-usage: run_flat.py [particles] [pg|mh] [iterations] [rows] [--map]"""
+--dependent: the same run twice, first as above and then with State indexed by City (experiments.flat_model(dependent=("City",
+"State")): the two choices share one block and one product leaf, State's parameter is an IndexedProportionsParameter), and
+the accuracy of the two models side by side — of the last sample and, with the joint MAP repair (Engine.own_marginals:
+for the pair these are JOINT probabilities), per column.
+
+usage: run_flat.py [particles] [pg|mh] [iterations] [rows] [--map] [--dependent]"""
 import os
 import sys
 import time
@@ -23,13 +28,13 @@ from pclean_amd.model import LoweredModel
 from pclean_amd.trace import Trace
 
 
-def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, with_map=False):
+def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, with_map=False, dependent=None):
     dirty, clean = ex.hospital_data()
     cols = ex.FLAT_COLUMNS
     n = len(dirty[cols[0]]) if n_rows is None else int(n_rows)
     dirty = {c: dirty[c][:n] for c in cols}
     clean = {c: clean[c][:n] for c in cols}
-    m = ex.flat_model(ex.flat_vocabulary(clean))
+    m = ex.flat_model(ex.flat_vocabulary(clean), dependent=dependent)
     lw = LoweredModel(m, ex.flat_query(m), dirty)
     eng = Engine(lw, lw.encode_observations(dirty))
     try:
@@ -56,6 +61,7 @@ def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, wit
                 table, conf = map_table(lw, marg, dirty, min_confidence=thr)
                 a = evaluate_map_accuracy(lw, marg, dirty, clean, min_confidence=thr)
                 a["accuracy"] = ex.cell_accuracy(table, clean)
+                a["by_column"] = {c: ex.cell_accuracy(table, clean, (c,)) for c in cols}
                 present = {c: np.array([v is not None for v in dirty[c]]) for c in cols}
                 a["left_dirty"] = sum(int(((conf[c] < thr) & present[c]).sum()) for c in cols) / float(n * len(cols))
                 acc["map"][thr] = a
@@ -68,7 +74,25 @@ def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, wit
         eng.close()
 
 
+def compare(**kw):
+    """the independent model and the one with State indexed by City, side by side"""
+    out = {}
+    for name, dep in (("independent", None), ("State | City", ("City", "State"))):
+        print(f"---- {name}")
+        out[name] = main(with_map=True, dependent=dep, **kw)
+    print(f"{'model':<14} {'sample acc':>10} {'MAP acc':>8} {'MAP F1':>7}  " + "  ".join(f"{c:>9}" for c in ex.FLAT_COLUMNS))
+    for name, a in out.items():
+        m0 = a["map"][0.0]
+        print(f"{name:<14} {a['accuracy']:>10.4f} {m0['accuracy']:>8.4f} {m0['f1']:>7.4f}  " +
+              "  ".join(f"{m0['by_column'][c]:>9.4f}" for c in ex.FLAT_COLUMNS))
+    return out
+
+
 if __name__ == "__main__":
-    a = [x for x in sys.argv[1:] if x != "--map"]
-    main(with_map="--map" in sys.argv[1:], particles=int(a[0]) if a else 20, mh=(a[1] == "mh") if len(a) > 1 else False, iters=int(a[2]) if len(a) > 2 else 5,
-         n_rows=int(a[3]) if len(a) > 3 else None)
+    a = [x for x in sys.argv[1:] if x not in ("--map", "--dependent")]
+    kw = dict(particles=int(a[0]) if a else 20, mh=(a[1] == "mh") if len(a) > 1 else False, iters=int(a[2]) if len(a) > 2 else 5,
+              n_rows=int(a[3]) if len(a) > 3 else None)
+    if "--dependent" in sys.argv[1:]:
+        compare(**kw)
+    else:
+        main(with_map="--map" in sys.argv[1:], **kw)
