@@ -4,6 +4,7 @@
 // option-list marginals, sampling of the contents of rows proposed as NEW.  Called by the observed-class sweep
 // (sweep.hip) and the latent-class sweep (latent.hip).
 #include "sweep_internal.h"
+#include "static_tiles.h"
 
 int build_gauss_dev(pclean_ctx* ctx, const pclean_gauss& g, const CandTable* t, GaussDev& d) {
   memset(&d, 0, sizeof d);
@@ -1723,16 +1724,26 @@ static int make_item_groups_hash(pclean_ctx* ctx, const ItemList& il, const int3
 }
 
 // ---- grouping from a static tuple order -------------------------------------------------------------------------------
-// When the items are the rows of the active window themselves and the key holds no context value, the key of item i is
-// (tuple_id[i], excl[i]): the tuple id never changes, only the referent does.  The rows are sorted ONCE per loaded table
-// by (hash of the pre-filter values, tuple id) — rows of one tuple form a segment, the segments of one pre-filter family
-// are neighbours (what root_wave.hip's survivor-list reuse wants of the group order) — and the order is cut into tiles
-// of at most 64 positions along the segment boundaries (a segment longer than 64 is cut at multiples of 64).  A sweep
-// then only splits every tile by referent: one wavefront per tile finds the classes of its <= 64 (tuple id, referent)
-// pairs by ballots and writes the members as a permutation of its own positions; a scan over the tiles' piece counts
-// numbers the groups; a streaming pass writes uid / grp_off.  No table, no probing, no atomics.  Two rows of one group
-// that a tile boundary separates become two groups: a split, which the contract above allows (it happens only inside
-// segments longer than 64).  PCLEAN_NO_STATIC_GROUPS=1: the hash table for these items too.
+// When the first items of a list are the rows of the active window themselves, in order, the key of item i is
+// (tuple_id[i], ctx[i], excl[i]): the tuple id never changes, only the context and the referent do.  That is block 0's
+// list (no row array, no context in the key) and the list of a block with a context as ctx_items_kernel leaves it
+// (ItemList::n_primary: item i < N is row i with particle 0's context; the further contexts of a row are EXTRA items
+// behind them — under 200 of 10^6 on the benchmark).  The rows are sorted ONCE per loaded table by (hash of the pre-filter
+// values, tuple id) — rows of one tuple form a segment, the segments of one pre-filter family are neighbours (what
+// root_wave.hip's survivor-list reuse wants of the group order) — and the order is cut into tiles along the segment
+// boundaries (static_tiles.h): segments of at most 64 positions are packed into WAVE tiles and never split; a longer
+// segment becomes LONG tiles of at most STATIC_TILE_LONG = 1024 positions of that segment alone (the benchmark's longest
+// Measure segment has 946: nothing is cut).  A sweep then only splits every tile by the dynamic part of the key
+// (sg_class_kernel): one wavefront per wave tile finds the classes of its <= 64 (tuple id, ctx, referent) keys by ballots,
+// one workgroup per long tile classes its positions by (ctx, referent) through an open-addressing table in LDS; both write
+// the members as a permutation of their own positions.  A scan over the tiles' piece counts numbers the groups; a
+// streaming pass writes uid / grp_off and appends every extra item as a group of one (their number is il.n - n_primary:
+// on the host already).  No global table, no zero fill, no global atomics, no 2 n-slot scan.  Splits, which the contract
+// above allows: two rows of one group that the boundary between two long tiles of ONE segment separates (segments longer
+// than 1024 only), and an extra item whose key another item has.  A list that numbers its items otherwise
+// (PCLEAN_NO_FUSED_CTX_ITEMS=1: n_primary == 0) stays on the hash table.  PCLEAN_NO_STATIC_GROUPS=1: the hash table for all
+// these items; PCLEAN_NO_STATIC_CTX_GROUPS=1: for the lists with a context only.  PCLEAN_TRACE_SYNC=1 prints one line per
+// call: block, node, primary items, extra items, groups, long tiles.
 #define STATIC_ORDER_WINDOWS 8  // cached windows per (block, node); their rows together: at most 2 x the loaded rows
 __global__ void static_key_kernel(int n, const int32_t* __restrict__ tuple_id, const uint32_t* __restrict__ pre_hash,
                                   uint64_t* __restrict__ key, int32_t* __restrict__ idx) {
@@ -1782,11 +1793,11 @@ static int ensure_static_order(pclean_ctx* ctx, int block_id, int node_id, int n
   DevBuf<int32_t> idx;
   DevBuf<unsigned char> tmp;
   int32_t* h_tid = nullptr;
-  int32_t* h_off = nullptr;
+  int32_t* h_stage = nullptr;
   auto cleanup = [&]() {
     key.release(); key_s.release(); idx.release(); tmp.release();
     if (h_tid) (void)hipHostFree(h_tid);
-    if (h_off) (void)hipHostFree(h_off);
+    if (h_stage) (void)hipHostFree(h_stage);
   };
   auto fail = [&](const char* what) {
     cleanup();
@@ -1803,25 +1814,29 @@ static int ensure_static_order(pclean_ctx* ctx, int block_id, int node_id, int n
   hipLaunchKernelGGL(static_tid_kernel, grid1(n), dim3(256), 0, ctx->stream, n, key_s.p, w.tid.p);
   // the tiles: a serial walk over the segments, on the host (once per window; page-locked staging: see HostStage)
   if (hipHostMalloc((void**)&h_tid, (size_t)n * sizeof(int32_t)) != hipSuccess) { h_tid = nullptr; return fail("host alloc failed"); }
-  if (hipHostMalloc((void**)&h_off, ((size_t)n + 1) * sizeof(int32_t)) != hipSuccess) { h_off = nullptr; return fail("host alloc failed"); }
   if (hipMemcpyAsync(h_tid, w.tid.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess)
     return fail("static order: read-back failed");
-  int n_off = 0, start = 0;
-  h_off[n_off++] = 0;
-  for (int sb = 0; sb < n;) {
-    int se = sb + 1;
-    while (se < n && h_tid[se] == h_tid[sb]) ++se;
-    if (se - start > 64) {  // the segment [sb, se) does not fit the open tile
-      if (sb > start) h_off[n_off++] = start = sb;
-      while (se - start > 64) h_off[n_off++] = start = start + 64;
-    }
-    sb = se;
-  }
-  h_off[n_off++] = n;
-  w.n_tiles = n_off - 1;
-  if (w.tile_off.alloc(n_off)) return fail("device alloc failed");
-  if (hipMemcpyAsync(w.tile_off.p, h_off, (size_t)n_off * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+  StaticTiles tiles;
+  static_tiles_walk(h_tid, n, STATIC_TILE_LONG, tiles);
+  w.n_tiles = tiles.n_tiles();
+  w.n_wave = (int)tiles.wave_tiles.size();
+  w.n_long = (int)tiles.long_tiles.size();
+  w.n_chunks = (int)tiles.chunk_tile.size();
+  if (w.n_tiles <= 0) return fail("static order: no tiles");
+  const size_t n_stage = tiles.tile_off.size() + tiles.wave_tiles.size() + tiles.long_tiles.size() + 2 * tiles.chunk_tile.size();
+  if (hipHostMalloc((void**)&h_stage, n_stage * sizeof(int32_t)) != hipSuccess) { h_stage = nullptr; return fail("host alloc failed"); }
+  size_t staged = 0;
+  auto upload = [&](DevBuf<int32_t>& dst, const std::vector<int32_t>& src) -> bool {  // (through page-locked staging)
+    if (dst.alloc(std::max<size_t>(src.size(), 1))) return false;
+    if (src.empty()) return true;
+    int32_t* h = h_stage + staged;
+    staged += src.size();
+    std::copy(src.begin(), src.end(), h);
+    return hipMemcpyAsync(dst.p, h, src.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+  };
+  if (!upload(w.tile_off, tiles.tile_off) || !upload(w.wave_tiles, tiles.wave_tiles) || !upload(w.long_tiles, tiles.long_tiles) ||
+      !upload(w.chunk_tile, tiles.chunk_tile) || !upload(w.chunk_off, tiles.chunk_off) ||
       hipStreamSynchronize(ctx->stream) != hipSuccess)
     return fail("static order: upload failed");
   cleanup();
@@ -1829,30 +1844,165 @@ static int ensure_static_order(pclean_ctx* ctx, int block_id, int node_id, int n
   *out = &t.windows.back();
   return PCLEAN_OK;
 }
-// One wavefront per tile: lane = position of the tile.  Classes of the lanes by (tuple id, referent), in the order of their
-// first lanes; a class of more than 2 split_m - 1 lanes is cut into pieces of split_m (the last piece takes the remainder),
+// Long tiles (blocks [0, n_long), queued first: they run longest): one workgroup per tile, up to SG_LT positions of ONE tuple
+// segment, SG_LT / 256 per thread.  The positions are classed by the dynamic part of the key alone — (ctx words, referent)
+// — through an open-addressing table in LDS: a slot holds a representative POSITION whose key, stored in LDS before the
+// first probe, the others compare with; a position takes its rank within the class from the slot's counter.  LDS atomics
+// only.  A block scan over the slots' (pieces, members) orders the classes by slot; the outputs are those of the wave tiles.
+// Wave tiles (the blocks behind): one wavefront per tile, lane = position of the tile.  Classes of the lanes by (tuple id,
+// ctx words, referent), in the order of their first lanes.  CTX == false: the key holds no context, or the list has none
+// (an absent context compares equal).
+// Either way a class of more than 2 split_m - 1 positions is cut into pieces of split_m (the last piece takes the remainder),
 // exactly as HgPacked / hg_fill_kernel do.  loc[position] = (piece index within the tile) << 1 | first member of its piece.
-__global__ __launch_bounds__(256) void sg_class_kernel(int n_tiles, const int32_t* __restrict__ tile_off,
+#define SG_LT STATIC_TILE_LONG
+#define SG_SLOTS (2 * SG_LT)
+#define SG_PER_THREAD (SG_LT / 256)
+static_assert(SG_LT % 256 == 0 && SG_SLOTS % 256 == 0 && SG_LT < 32768, "long tiles: 256 threads, (pieces, members) in 16 bits each");
+static_assert(PCLEAN_MAX_CTX == 4, "the context words of an item are loaded as one int4");
+__device__ __forceinline__ uint32_t sg_mix(uint32_t h, uint32_t v) {
+  h = (h ^ v) * 0x9e3779b1u;
+  return h ^ (h >> 15);
+}
+template <bool CTX>
+__global__ __launch_bounds__(256) void sg_class_kernel(int n_wave, int n_long, const int32_t* __restrict__ wave_tiles,
+                                                       const int32_t* __restrict__ long_tiles, const int32_t* __restrict__ tile_off,
                                                        const int32_t* __restrict__ order, const int32_t* __restrict__ tid_sorted,
-                                                       const int32_t* __restrict__ excl, int split_m,
-                                                       int32_t* __restrict__ members, int32_t* __restrict__ loc,
+                                                       const int32_t* __restrict__ ctxv, const int32_t* __restrict__ excl,
+                                                       int split_m, int32_t* __restrict__ members, int32_t* __restrict__ loc,
                                                        int32_t* __restrict__ tile_cnt) {
-  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  constexpr int KW = CTX ? PCLEAN_MAX_CTX + 1 : 1;  // key words of a position in LDS: [ctx words,] referent
+  __shared__ int32_t s_rep[SG_SLOTS];   // 0: empty, else representative position + 1; after the scan: (pieces, members) before the slot
+  __shared__ uint32_t s_cnt[SG_SLOTS];  // members of the slot's class
+  __shared__ int32_t s_key[SG_LT * KW];
+  __shared__ uint32_t s_wsum[4];
   const int lane = threadIdx.x & 63;
-  if (tile >= n_tiles) return;
+  if ((int)blockIdx.x < n_long) {
+    const int tile = long_tiles[blockIdx.x];
+    const int t0 = tile_off[tile], len = min(tile_off[tile + 1] - t0, SG_LT);
+    // the table: the power of two from 2 len up, at least a slot per thread (block 0's segments are ~100 positions each:
+    // a table of SG_SLOTS for every one of them cost more in zeroing and scanning than the classing itself)
+    int n_slots = 256;
+    while (n_slots < 2 * len) n_slots <<= 1;
+    const int smask = n_slots - 1;
+    for (int sl = threadIdx.x; sl < n_slots; sl += 256) {
+      s_rep[sl] = 0;
+      s_cnt[sl] = 0u;
+    }
+    int item[SG_PER_THREAD], slot[SG_PER_THREAD], rank[SG_PER_THREAD];
+#pragma unroll
+    for (int k = 0; k < SG_PER_THREAD; ++k) {
+      const int p = (int)threadIdx.x + k * 256;
+      item[k] = 0;
+      slot[k] = 0;
+      rank[k] = 0;
+      if (p < len) {
+        const int i = order[t0 + p];
+        const int e = excl[i];
+        uint32_t h = sg_mix(0x2545f491u, (uint32_t)e);
+        if (CTX) {
+          const int4 c = reinterpret_cast<const int4*>(ctxv)[i];
+          s_key[p * KW + 0] = c.x;
+          s_key[p * KW + 1] = c.y;
+          s_key[p * KW + 2] = c.z;
+          s_key[p * KW + 3] = c.w;
+          h = sg_mix(sg_mix(sg_mix(sg_mix(h, (uint32_t)c.x), (uint32_t)c.y), (uint32_t)c.z), (uint32_t)c.w);
+        }
+        s_key[p * KW + KW - 1] = e;
+        item[k] = i;
+        slot[k] = (int)((h ^ (h >> 11)) & (uint32_t)smask);
+      }
+    }
+    __syncthreads();
+    // claim or join: len keys in at least 2 len slots, so a probe sequence always ends; no lane waits for another
+#pragma unroll
+    for (int k = 0; k < SG_PER_THREAD; ++k) {
+      const int p = (int)threadIdx.x + k * 256;
+      if (p < len) {
+        int sl = slot[k];
+        for (;;) {
+          int v = __hip_atomic_load(&s_rep[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (v == 0) {
+            v = atomicCAS(&s_rep[sl], 0, p + 1);
+            if (v == 0) v = p + 1;  // claimed: this position represents the class
+          }
+          bool same = true;
+          if (v - 1 != p)
+            for (int w = 0; w < KW; ++w) same &= s_key[(v - 1) * KW + w] == s_key[p * KW + w];
+          if (same) break;
+          sl = (sl + 1) & smask;
+        }
+        slot[k] = sl;
+        rank[k] = (int)atomicAdd(&s_cnt[sl], 1u);
+      }
+    }
+    __syncthreads();
+    // exclusive scan over the slots of (pieces << 16 | members): n_slots / 256 consecutive slots per thread
+    constexpr int SPT = SG_SLOTS / 256;
+    const int spt = n_slots >> 8;
+    uint32_t pk[SPT], mine = 0u;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      const uint32_t c = j < spt ? s_cnt[threadIdx.x * spt + j] : 0u;
+      const uint32_t pieces = c == 0u ? 0u : (split_m > 0 ? max(c / (uint32_t)split_m, 1u) : 1u);
+      pk[j] = (pieces << 16) | c;
+      mine += pk[j];
+    }
+    uint32_t incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t x = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += x;
+    }
+    if (lane == 63) s_wsum[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    uint32_t run = incl - mine;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) run += s_wsum[w];
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      if (j < spt) s_rep[threadIdx.x * spt + j] = (int32_t)run;
+      run += pk[j];
+    }
+    if (threadIdx.x == 255) tile_cnt[tile] = (int32_t)(run >> 16);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SG_PER_THREAD; ++k) {
+      const int p = (int)threadIdx.x + k * 256;
+      if (p < len) {
+        const int c = (int)s_cnt[slot[k]], r = rank[k];
+        const uint32_t ex = (uint32_t)s_rep[slot[k]];
+        const int pieces = split_m > 0 ? max(c / split_m, 1) : 1;
+        const int piece = split_m > 0 ? min(r / split_m, pieces - 1) : 0;
+        const bool first = split_m > 0 ? r == piece * split_m : r == 0;
+        const int at = t0 + (int)(ex & 0xffffu) + r;
+        members[at] = item[k];
+        loc[at] = (((int)(ex >> 16) + piece) << 1) | (first ? 1 : 0);
+      }
+    }
+    return;
+  }
+  const int wt = ((int)blockIdx.x - n_long) * 4 + (threadIdx.x >> 6);
+  if (wt >= n_wave) return;
+  const int tile = wave_tiles[wt];
   const int t0 = tile_off[tile], len = tile_off[tile + 1] - t0;
   const bool on = lane < len;
   int i = 0, kt = 0, ke = 0;
+  int4 kc4 = make_int4(0, 0, 0, 0);
   if (on) {
     i = order[t0 + lane];
     kt = tid_sorted[t0 + lane];
     ke = excl[i];
+    if (CTX) kc4 = reinterpret_cast<const int4*>(ctxv)[i];
   }
   int pos_acc = 0, piece_acc = 0, my_at = 0, my_loc = 0;
   for (unsigned long long pend = __ballot(on); pend;) {
     const int ld = __builtin_ctzll(pend);
     const int lt = __builtin_amdgcn_readlane(kt, ld), le = __builtin_amdgcn_readlane(ke, ld);
-    const unsigned long long cls = __ballot(on && kt == lt && ke == le) & pend;
+    bool eq = on && kt == lt && ke == le;
+    if (CTX) {  // (wave-uniform: every lane takes part in the readlanes)
+      const int lx = __builtin_amdgcn_readlane(kc4.x, ld), ly = __builtin_amdgcn_readlane(kc4.y, ld);
+      const int lz = __builtin_amdgcn_readlane(kc4.z, ld), lw = __builtin_amdgcn_readlane(kc4.w, ld);
+      eq &= (kc4.x == lx) & (kc4.y == ly) & (kc4.z == lz) & (kc4.w == lw);
+    }
+    const unsigned long long cls = __ballot(eq) & pend;
     const int c = __popcll(cls);
     const int pieces = split_m > 0 ? max(c / split_m, 1) : 1;
     if ((cls >> lane) & 1ull) {
@@ -1872,49 +2022,89 @@ __global__ __launch_bounds__(256) void sg_class_kernel(int n_tiles, const int32_
   }
   if (lane == 0) tile_cnt[tile] = piece_acc;
 }
-__global__ __launch_bounds__(256) void sg_fill_kernel(int n, int n_tiles, const int32_t* __restrict__ tile_off,
-                                                      const int32_t* __restrict__ loc, const int32_t* __restrict__ tile_cnt,
-                                                      const int32_t* __restrict__ incl, int32_t* __restrict__ uid,
+// One wavefront per chunk of at most 64 positions of a tile (blocks [0, ceil(n_chunks / 4))); behind them one thread per
+// extra item [n_primary, n): a group of one each, numbered after the tiles' groups.
+__global__ __launch_bounds__(256) void sg_fill_kernel(int n, int n_primary, int n_tiles, int n_chunks,
+                                                      const int32_t* __restrict__ chunk_tile, const int32_t* __restrict__ chunk_off,
+                                                      const int32_t* __restrict__ tile_off, const int32_t* __restrict__ loc,
+                                                      const int32_t* __restrict__ tile_cnt, const int32_t* __restrict__ incl,
+                                                      int32_t* __restrict__ members, int32_t* __restrict__ uid,
                                                       int32_t* __restrict__ grp_off) {
-  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (tile >= n_tiles) return;
-  const int t0 = tile_off[tile], len = tile_off[tile + 1] - t0;
-  const int base = incl[tile] - tile_cnt[tile];
-  if (lane < len) {
-    const int v = loc[t0 + lane], grp = base + (v >> 1);
-    uid[t0 + lane] = grp + 1;
-    if (v & 1) grp_off[grp] = t0 + lane;
+  const int chunk_blocks = (n_chunks + 3) / 4;
+  if ((int)blockIdx.x >= chunk_blocks) {
+    const int j = n_primary + ((int)blockIdx.x - chunk_blocks) * 256 + (int)threadIdx.x;
+    if (j < n) {
+      const int grp = incl[n_tiles - 1] + (j - n_primary);
+      members[j] = j;
+      uid[j] = grp + 1;
+      grp_off[grp] = j;
+    }
+    return;
   }
-  if (tile == 0 && lane == 0) grp_off[incl[n_tiles - 1]] = n;
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (chunk >= n_chunks) return;
+  const int tile = chunk_tile[chunk];
+  const int at = chunk_off[chunk] + lane;
+  const int base = incl[tile] - tile_cnt[tile];
+  if (at < tile_off[tile + 1]) {
+    const int v = loc[at], grp = base + (v >> 1);
+    uid[at] = grp + 1;
+    if (v & 1) grp_off[grp] = at;
+  }
+  if (chunk == 0 && lane == 0) grp_off[incl[n_tiles - 1] + (n - n_primary)] = n;
 }
-static int make_item_groups_static(pclean_ctx* ctx, const SweepState::TupleIds::StaticOrder& so, const ItemList& il,
-                                   const int32_t* excl, int split_m, ItemGroups& g) {
-  const int n = il.n, nt = so.n_tiles;
+// `who`: the name the count read-back is reported under (PCLEAN_TRACE_SYNC=1)
+static int static_groups_core(pclean_ctx* ctx, int block_id, int node_id, const SweepState::TupleIds::StaticOrder& so,
+                              const ItemList& il, const int32_t* ctxv, const int32_t* excl, int split_m, ItemGroups& g,
+                              const char* who, int line) {
+  const int n = il.n, np = so.n, n_extra = n - np, nt = so.n_tiles;
   int32_t* members = scratch<int32_t>(ctx, n);
-  int32_t* loc = scratch<int32_t>(ctx, n);
+  int32_t* loc = scratch<int32_t>(ctx, np);
   int32_t* tile_cnt = scratch<int32_t>(ctx, nt);
   int32_t* incl = scratch<int32_t>(ctx, nt);
   size_t tmp_scan = 0;
   HIPCHK(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, tile_cnt, incl, nt, ctx->stream));
   unsigned char* tmp = scratch<unsigned char>(ctx, std::max<size_t>(tmp_scan, 16));
   if (!members || !loc || !tile_cnt || !incl || !tmp) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-  hipLaunchKernelGGL(sg_class_kernel, grid1(nt, 4), dim3(256), 0, ctx->stream, nt, so.tile_off.p, so.order.p, so.tid.p, excl,
-                     split_m, members, loc, tile_cnt);
+  const dim3 class_grid((unsigned)(so.n_long + (so.n_wave + 3) / 4));
+  if (ctxv)
+    hipLaunchKernelGGL(sg_class_kernel<true>, class_grid, dim3(256), 0, ctx->stream, so.n_wave, so.n_long, so.wave_tiles.p,
+                       so.long_tiles.p, so.tile_off.p, so.order.p, so.tid.p, ctxv, excl, split_m, members, loc, tile_cnt);
+  else
+    hipLaunchKernelGGL(sg_class_kernel<false>, class_grid, dim3(256), 0, ctx->stream, so.n_wave, so.n_long, so.wave_tiles.p,
+                       so.long_tiles.p, so.tile_off.p, so.order.p, so.tid.p, ctxv, excl, split_m, members, loc, tile_cnt);
   HIPCHK(ctx, hipcub::DeviceScan::InclusiveSum(tmp, tmp_scan, tile_cnt, incl, nt, ctx->stream));
-  int32_t n_unique = 0;
-  PCLEAN_READ_COUNT(ctx, incl + (nt - 1), &n_unique);
+  int32_t n_tiled = 0;
+  { const int rcr = read_count(ctx, incl + (nt - 1), &n_tiled, who, line); if (rcr) return rcr; }
+  const int32_t n_unique = n_tiled > 0 ? n_tiled + n_extra : 0;  // every extra item: a group of one
+  static const bool trace = getenv("PCLEAN_TRACE_SYNC") != nullptr;
+  if (trace)
+    fprintf(stderr, "[pclean static groups] block %d node %d: primary items %d, extra items %d, groups %d, long tiles %d%s\n", block_id,
+            node_id, np, n_extra, (int)n_unique, so.n_long, il.row ? " (context list)" : "");
   if (n_unique <= 0 || (double)n_unique > 0.75 * n) return PCLEAN_OK;  // not worth the indirection
   int32_t* uid = scratch<int32_t>(ctx, n);
   int32_t* grp_off = scratch<int32_t>(ctx, (size_t)n_unique + 1);
   if (!uid || !grp_off) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-  hipLaunchKernelGGL(sg_fill_kernel, grid1(nt, 4), dim3(256), 0, ctx->stream, n, nt, so.tile_off.p, loc, tile_cnt, incl, uid, grp_off);
+  const dim3 fill_grid((unsigned)((so.n_chunks + 3) / 4 + (n_extra + 255) / 256));
+  hipLaunchKernelGGL(sg_fill_kernel, fill_grid, dim3(256), 0, ctx->stream, n, np, nt, so.n_chunks, so.chunk_tile.p, so.chunk_off.p,
+                     so.tile_off.p, loc, tile_cnt, incl, members, uid, grp_off);
   g.n_groups = n_unique;
   g.grp_off = grp_off;
   g.members = members;
   g.head = nullptr;
   g.uid = uid;
   return PCLEAN_OK;
+}
+// the window's own rows, keyed by (tuple id, referent)
+static int make_item_groups_static(pclean_ctx* ctx, int block_id, int node_id, const SweepState::TupleIds::StaticOrder& so,
+                                   const ItemList& il, const int32_t* excl, int split_m, ItemGroups& g) {
+  return static_groups_core(ctx, block_id, node_id, so, il, nullptr, excl, split_m, g, __func__, __LINE__);
+}
+// a list with a context: the primary items through the tiles, keyed by (tuple id, ctx, referent); the extras behind them
+static int make_item_groups_static_ctx(pclean_ctx* ctx, int block_id, int node_id, const SweepState::TupleIds::StaticOrder& so,
+                                       const ItemList& il, const int32_t* ctxv, const int32_t* excl, int split_m, ItemGroups& g) {
+  return static_groups_core(ctx, block_id, node_id, so, il, ctxv, excl, split_m, g, __func__, __LINE__);
 }
 
 // Groups the items of `il` by (observed values of the sub-tree of node_id, ctx, excl).  g.n_groups == 0
@@ -1960,13 +2150,19 @@ static int make_item_groups(pclean_ctx* ctx, int block_id, int node_id, const It
     if (np2 == 0) kc.pre_hash = nullptr;
   }
   static const bool sort_groups = getenv("PCLEAN_SORT_GROUPS") != nullptr;
-  // the window's own rows, keyed by (tuple id, referent) alone: split the static tuple order by referent
+  // the window's own rows (a list that says so: n_primary), keyed by (tuple id[, ctx], referent): split the static tuple
+  // order by the dynamic part of the key; a list that numbers its items otherwise stays on the hash table
   static const bool no_static = getenv("PCLEAN_NO_STATIC_GROUPS") != nullptr;
-  if (want_members && excl && !il.row && (!kc.use_ctx || !il.ctx) && kc.tuple_id && !sort_groups && !no_static) {
+  static const bool no_static_ctx = getenv("PCLEAN_NO_STATIC_CTX_GROUPS") != nullptr;
+  const bool ctx_list = il.row || (kc.use_ctx && il.ctx);
+  const int n_primary = ctx_list ? ((il.row && il.n_primary <= n) ? il.n_primary : 0) : n;
+  if (want_members && excl && n_primary > 0 && !(ctx_list && no_static_ctx) && kc.tuple_id && !sort_groups && !no_static) {
     const SweepState::TupleIds::StaticOrder* so = nullptr;
-    int rc = ensure_static_order(ctx, block_id, node_id, n, &so);
+    int rc = ensure_static_order(ctx, block_id, node_id, n_primary, &so);
     if (rc) return rc;
-    if (so) return make_item_groups_static(ctx, *so, il, excl, split_m, g);
+    if (so && ctx_list)
+      return make_item_groups_static_ctx(ctx, block_id, node_id, *so, il, (kc.use_ctx && il.ctx) ? il.ctx : nullptr, excl, split_m, g);
+    if (so) return make_item_groups_static(ctx, block_id, node_id, *so, il, excl, split_m, g);
   }
   if (!sort_groups) return make_item_groups_hash(ctx, il, excl, kc, split_m, want_members, g);
   uint64_t* key = scratch<uint64_t>(ctx, n);

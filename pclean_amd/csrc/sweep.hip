@@ -2113,6 +2113,7 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
       int32_t* draws_item = scratch<int32_t>(ctx, (size_t)n_items * P);
       if (!lse_item || !draws_item) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
       il = ItemList{(int)n_items, d_row, d_ctx, nullptr, nullptr};
+      if (!no_fused_items) il.n_primary = N;  // (ctx_items_kernel: item i < N is row i; ctx_fill_kernel numbers row by row)
       if (fuse_final || split_final) s->lazy_req = SweepState::LazyReq{true, split_final ? emit_rows : nullptr};
       rc = eval_node(ctx, bi, 0, il, d_excl, seed, sweep_idx, P, lse_item, draws_item, nullptr, nullptr, bi == ctx->timed_block);
       s->lazy_req = SweepState::LazyReq();

@@ -53,6 +53,9 @@ struct ItemList {  // device arrays describing enumeration work items
   const int32_t* ev_ctx = nullptr;
   const int32_t* rng_row = nullptr;
   int draw_is = 0, draw_ds = 0;  // ItemsDev::draw_is / draw_ds of the draws this list produces
+  // items [0, n_primary) are the active window's rows in order (row[i] == i), items [n_primary, n) further contexts of
+  // some of them (sweep.hip: ctx_items_kernel); 0: the list says nothing about its order
+  int n_primary = 0;
 };
 struct ItemGroups {
   int n_groups = 0;              // 0: grouping not applicable / not worth it

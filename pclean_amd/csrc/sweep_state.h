@@ -108,12 +108,18 @@ struct SweepState {
     DevBuf<uint32_t> pre;
     uint64_t sig = 0;
     // static order of the rows of one active window (eval.hip: ensure_static_order): the window's items sorted by
-    // (pre-filter hash, tuple id), their tuple ids in that order, and the order cut into tiles of at most 64 positions
-    // along the tuple segments.  Immutable between rebuilds of `id`; a few windows per entry (STATIC_ORDER_WINDOWS)
+    // (pre-filter hash, tuple id), their tuple ids in that order, and the order cut into tiles along the tuple segments
+    // (static_tiles.h): wave tiles of at most 64 positions and the long tiles of the segments longer than that, each
+    // listed by its tile index; chunks of at most 64 positions for the streaming pass.  Immutable between rebuilds of
+    // `id`; a few windows per entry (STATIC_ORDER_WINDOWS)
     struct StaticOrder {
-      int begin = 0, n = 0, n_tiles = 0;
+      int begin = 0, n = 0, n_tiles = 0, n_wave = 0, n_long = 0, n_chunks = 0;
       DevBuf<int32_t> order, tid, tile_off;  // [n], [n], [n_tiles + 1]
-      void release() { order.release(); tid.release(); tile_off.release(); }
+      DevBuf<int32_t> wave_tiles, long_tiles, chunk_tile, chunk_off;  // [n_wave], [n_long], [n_chunks], [n_chunks]
+      void release() {
+        order.release(); tid.release(); tile_off.release();
+        wave_tiles.release(); long_tiles.release(); chunk_tile.release(); chunk_off.release();
+      }
     };
     std::vector<StaticOrder> windows;
     void release() {
