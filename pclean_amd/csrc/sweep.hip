@@ -11,6 +11,7 @@
 //   process_plan!      proposal_compiler.jl:363-388 (children of a new row enumerated
 //       independently; log-marginals added)
 #include "sweep_internal.h"
+#include "tail_tiles.h"
 
 // every blocking point of the orchestration goes through here: PCLEAN_TRACE_SYNC=1 lists them per call
 int g_pclean_sync_count = 0;
@@ -724,10 +725,137 @@ __global__ __launch_bounds__(256) void finalize_block_kernel(int n_rows, const i
   }
 }
 
+// Every block's finalize pass in ONE launch over (workgroup, block), which also lists the rows whose chosen particle
+// proposed a NEW referent where their contents are sampled afterwards (lazy: chosen_new_kernel's work — the same words
+// are read here anyway).  A workgroup walks a contiguous range of 256-row tiles (tail_tiles.h): it zeroes its LDS histogram
+// once, accumulates its tiles' deltas and flushes once — per tile, zeroing and flushing 4 416 counters for ~10 moves was
+// most of the per-block kernel's time.  The per-tile counts of tail_scan_kernel / tail_scatter_kernel are written per tile
+// exactly as finalize_block_kernel writes them.  Integer sums only: the order of the additions does not show.
+struct TailBlock {
+  const int32_t* pchoice;
+  int32_t* pnewpos;
+  const int32_t* cur_b;
+  int32_t* choice;
+  int32_t* chosen_newpos;
+  unsigned long long* stats;
+  int32_t* moved_flag;
+  int32_t* new_flag;
+  unsigned int* wg_moved;
+  unsigned int* wg_new;
+  unsigned int* new_ctr;  // lazy: length of new_slots so far
+  int32_t* new_slots;
+  int32_t hist_rows, on, lazy, pad;
+};
+struct TailBlocks {
+  TailBlock b[PCLEAN_MAX_BLOCKS];
+};
+#define TAIL_WG_THREADS 1024                              // threads per workgroup of finalize_tail_kernel ...
+#define TAIL_STEP (TAIL_WG_THREADS / TAIL_TILE_ROWS)     // ... which takes that many tiles at a time (four wavefronts a tile)
+__global__ __launch_bounds__(TAIL_WG_THREADS) void finalize_tail_kernel(int n_rows, int n_tiles, const int32_t* __restrict__ chosen,
+                                                                        TailBlocks tb) {
+  extern __shared__ int32_t hist[];
+  __shared__ unsigned int wcnt[2][2][TAIL_WG_THREADS / 64];  // [step parity][moved / new][wavefront]
+  const TailBlock& b = tb.b[blockIdx.y];
+  if (!b.on) return;
+  const TailTileRange tr = tail_tile_range(n_tiles, (int)gridDim.x, (int)blockIdx.x);
+  if (tr.begin >= tr.end) return;
+  const int hist_rows = b.hist_rows;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = threadIdx.x / TAIL_TILE_ROWS, in_tile = threadIdx.x % TAIL_TILE_ROWS;  // this thread's tile of the step, its row there
+  for (int k = threadIdx.x; k < hist_rows; k += TAIL_WG_THREADS) hist[k] = 0;
+  if (hist_rows) __syncthreads();
+  // (the next step's chosen particle and current referent are in flight while this step's choice — a dependent load — is
+  // fetched: one round trip per step instead of two)
+  int ch_next = 0, o_next = 0;
+  {
+    const int i0 = (tr.begin + sub) * TAIL_TILE_ROWS + in_tile;
+    if (tr.begin + sub < tr.end && i0 < n_rows) {
+      ch_next = chosen[i0];
+      o_next = b.cur_b[i0];
+    }
+  }
+  for (int t0 = tr.begin; t0 < tr.end; t0 += TAIL_STEP) {
+    const int tile = t0 + sub;
+    const bool mine = tile < tr.end;  // (the last step of a range may hold fewer tiles)
+    const int i = mine ? tile * TAIL_TILE_ROWS + in_tile : n_rows;
+    const int par = ((t0 - tr.begin) / TAIL_STEP) & 1;
+    bool is_moved = false, is_new = false, wants_pos = false;
+    size_t s = 0;
+    int c = 0;
+    const int ch = ch_next, o = o_next;
+    {
+      const int i1 = (tile + TAIL_STEP) * TAIL_TILE_ROWS + in_tile;
+      if (tile + TAIL_STEP < tr.end && i1 < n_rows) {
+        ch_next = chosen[i1];
+        o_next = b.cur_b[i1];
+      }
+    }
+    if (i < n_rows) {
+      s = (size_t)ch * n_rows + i;
+      c = b.pchoice[s];
+      wants_pos = b.lazy && c == PCLEAN_CHOICE_NEW;
+    }
+    // lazy: the rows of this wavefront whose chosen particle proposed a NEW referent take consecutive list positions (one
+    // atomic per wavefront; order irrelevant: every use is keyed by (row, particle))
+    int np = -1;
+    if (b.lazy) {
+      const unsigned long long mk = __ballot(wants_pos);
+      if (mk) {
+        unsigned int base = 0;
+        if (lane == __builtin_ctzll(mk)) base = atomicAdd(b.new_ctr, (unsigned int)__popcll(mk));
+        base = __shfl(base, __builtin_ctzll(mk), 64);
+        if (wants_pos) {
+          np = (int)(base + (unsigned int)__popcll(mk & ((1ull << lane) - 1ull)));
+          b.new_slots[np] = (int32_t)s;
+          b.pnewpos[s] = np;
+        }
+      }
+    } else if (i < n_rows && c == PCLEAN_CHOICE_NEW) {
+      np = b.pnewpos[s];
+    }
+    if (i < n_rows) {
+      b.choice[i] = c;
+      b.chosen_newpos[i] = np;
+      is_new = np >= 0;
+      is_moved = c != o;
+      b.new_flag[i] = is_new ? 1 : 0;
+      b.moved_flag[i] = is_moved ? 1 : 0;
+      if (o != c) {
+        if (hist_rows) {
+          if (o >= 0) atomicAdd(&hist[o], -1);
+          if (c >= 0) atomicAdd(&hist[c], 1);
+        } else {
+          if (o >= 0) atomicAdd(&b.stats[o], (unsigned long long)(-1ll));
+          if (c >= 0) atomicAdd(&b.stats[c], 1ull);
+        }
+      }
+    }
+    // every tile's share of the two ordered lists (the counters alternate between two sets: one barrier per step)
+    const unsigned long long mm = __ballot(is_moved), mn = __ballot(is_new);
+    if (lane == 0) {
+      wcnt[par][0][wave] = (unsigned int)__popcll(mm);
+      wcnt[par][1][wave] = (unsigned int)__popcll(mn);
+    }
+    __syncthreads();
+    if (in_tile == 0 && mine) {  // (wave: the first of the tile's four)
+      b.wg_moved[tile] = wcnt[par][0][wave] + wcnt[par][0][wave + 1] + wcnt[par][0][wave + 2] + wcnt[par][0][wave + 3];
+      b.wg_new[tile] = wcnt[par][1][wave] + wcnt[par][1][wave + 1] + wcnt[par][1][wave + 2] + wcnt[par][1][wave + 3];
+    }
+  }
+  if (hist_rows) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < hist_rows; k += TAIL_WG_THREADS) {
+      const int v = hist[k];
+      if (v) atomicAdd(&b.stats[k], (unsigned long long)(long long)v);
+    }
+  }
+}
+
 // ---- ordered lists of the rows that moved / got a new referent, every block's at once: the per-workgroup counts
 // finalize_block_kernel left -> offsets (one workgroup per list) -> the rows, ascending (one workgroup per 256-row tile and
 // list).  Two dispatches per sweep where four hipcub::DeviceSelect calls were sixteen.
 #define TAIL_MAX_LISTS (2 * PCLEAN_MAX_BLOCKS)
+#define TAIL_CUS_PER_WG 2  // compute units per workgroup and block of finalize_tail_kernel (measured)
 __global__ __launch_bounds__(1024) void tail_scan_kernel(int nb, unsigned int* __restrict__ wg_cnt, int32_t* __restrict__ totals) {
   __shared__ unsigned int wsum[16];
   unsigned int* c = wg_cnt + (size_t)blockIdx.x * nb;
@@ -2257,20 +2385,25 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
                                         (size_t)1, (size_t)N, use_mh, 1, cur_base, seed, sweep_idx,
                                         s->row_offset + ctx->active_begin, s->chosen.p, (double*)nullptr,
                                         s->logml_acc.p, s->logml.p, final_only_rows));
-    for (int bi = 0; bi < n_blocks; ++bi) {  // deferred new-row contents of the last block (chosen particles only)
+    // PCLEAN_NO_FUSED_FINALIZE=1: chosen_new_kernel + one finalize_block_kernel per block (the launches finalize_tail_kernel
+    // replaces); PCLEAN_TAIL_WGS=<n>: workgroups per block of finalize_tail_kernel
+    static const bool no_fused_finalize = getenv("PCLEAN_NO_FUSED_FINALIZE") != nullptr;
+    static const int forced_tail_wgs = getenv("PCLEAN_TAIL_WGS") ? std::max(1, atoi(getenv("PCLEAN_TAIL_WGS"))) : 0;
+    static const bool trace_tail = getenv("PCLEAN_TRACE_SYNC") != nullptr;
+    unsigned int* chosen_ctr[PCLEAN_MAX_BLOCKS] = {};  // blocks whose chosen NEW rows are listed: the list's length
+    // deferred new-row contents of the last block (chosen particles only): the listed slots' rows are sampled
+    auto sample_chosen = [&](int bi) -> int {
       BlockRun& r = s->run[bi];
       Block& bb = ctx->block[bi];
-      if (bb.is_score || !r.lazy_new || r.n_new == 0) continue;
       ProfScope ps2(ctx, "new_row_sampling_chosen");
       const int nn = (int)bb.nodes.size();
       const int32_t* cur_b = cur_base + (size_t)bi * cur_ld;
-      unsigned int* cnt_ctr = fresh_counter(ctx);
-      hipLaunchKernelGGL(chosen_new_kernel, grid1(N), dim3(256), 0, ctx->stream, N, s->chosen.p, r.pchoice.p, cnt_ctr,
-                         r.new_slots.p, r.pnewpos.p);
       unsigned int cnt = 0;
-      PCLEAN_READ_COUNT(ctx, cnt_ctr, &cnt);
+      PCLEAN_READ_COUNT(ctx, chosen_ctr[bi], &cnt);
+      if (trace_tail) fprintf(stderr, "[pclean tail] block %d: %u chosen NEW rows listed by %s\n", bi, cnt,
+                              no_fused_finalize ? "chosen_new_kernel" : "finalize_tail_kernel");
       if (r.vals.alloc(std::max<size_t>((size_t)cnt * nn, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-      if (!cnt) continue;
+      if (!cnt) return PCLEAN_OK;
       hipLaunchKernelGGL(fill_i32_kernel, grid1((size_t)cnt * nn), dim3(256), 0, ctx->stream, r.vals.p, (size_t)cnt * nn, -2);
       int32_t* row = scratch<int32_t>(ctx, cnt);
       int32_t* cx = scratch<int32_t>(ctx, (size_t)cnt * PCLEAN_MAX_CTX);
@@ -2283,10 +2416,20 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
       hipLaunchKernelGGL(set_col_kernel, grid1(cnt), dim3(256), 0, ctx->stream, (int)cnt, nn, 0, (int32_t)PCLEAN_CHOICE_NEW,
                          r.vals.p);
       ItemList sub{(int)cnt, row, cx, part, org};
-      int rc = sample_children(ctx, bi, 0, sub, ex, seed, sweep_idx, r.vals.p, nn);
+      return sample_children(ctx, bi, 0, sub, ex, seed, sweep_idx, r.vals.p, nn);
+    };
+    for (int bi = 0; bi < n_blocks; ++bi) {
+      BlockRun& r = s->run[bi];
+      if (ctx->block[bi].is_score || !r.lazy_new || r.n_new == 0) continue;
+      chosen_ctr[bi] = fresh_counter(ctx);
+      if (!chosen_ctr[bi]) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
+      if (!no_fused_finalize) continue;  // (finalize_tail_kernel lists them; sampled behind the tail kernels)
+      hipLaunchKernelGGL(chosen_new_kernel, grid1(N), dim3(256), 0, ctx->stream, N, s->chosen.p, r.pchoice.p, chosen_ctr[bi],
+                         r.new_slots.p, r.pnewpos.p);
+      const int rc = sample_chosen(bi);
       if (rc) return rc;
     }
-    const int nb_wg = (N + 255) / 256;
+    const int nb_wg = (N + TAIL_TILE_ROWS - 1) / TAIL_TILE_ROWS;
     unsigned int* wg_cnt = scratch<unsigned int>(ctx, (size_t)2 * n_blocks * nb_wg);
     if (!wg_cnt) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
     TailLists tl{};
@@ -2303,6 +2446,8 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
       const int rcz = zero_list_flush(ctx, zl);
       if (rcz) return rcz;
     }
+    TailBlocks tb{};
+    int max_hist = 0;
     for (int bi = 0; bi < n_blocks; ++bi) {
       BlockRun& r = s->run[bi];
       Block& bb = ctx->block[bi];
@@ -2317,14 +2462,71 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
       const int rows_in_use = (rt.n_used > 0 && rt.n_used <= rt.n_rows) ? std::min(rt.n_rows, (rt.n_used + 63) & ~63) : rt.n_rows;
       static const bool no_hist = getenv("PCLEAN_NO_HIST") != nullptr;  // (measurement switch: plain atomics for every table)
       const int hist_rows = (rt.n_rows <= 12288 && !no_hist) ? rows_in_use : 0;  // (48 KB of LDS per workgroup at most; larger tables: plain atomics)
-      hipLaunchKernelGGL(finalize_block_kernel, grid1(N), dim3(256), (size_t)hist_rows * sizeof(int32_t), ctx->stream, N,
-                         s->chosen.p, r.pchoice.p, r.pnewpos.p, cur_b, r.choice.p, r.chosen_newpos.p,
-                         (unsigned long long*)rt.stats.p, hist_rows, r.moved_flag.p, r.new_flag.p,
-                         wg_cnt + (size_t)(2 * bi) * nb_wg, wg_cnt + (size_t)(2 * bi + 1) * nb_wg);
+      if (no_fused_finalize) {
+        hipLaunchKernelGGL(finalize_block_kernel, grid1(N), dim3(256), (size_t)hist_rows * sizeof(int32_t), ctx->stream, N,
+                           s->chosen.p, r.pchoice.p, r.pnewpos.p, cur_b, r.choice.p, r.chosen_newpos.p,
+                           (unsigned long long*)rt.stats.p, hist_rows, r.moved_flag.p, r.new_flag.p,
+                           wg_cnt + (size_t)(2 * bi) * nb_wg, wg_cnt + (size_t)(2 * bi + 1) * nb_wg);
+      } else {
+        TailBlock& t = tb.b[bi];
+        t.pchoice = r.pchoice.p;
+        t.pnewpos = r.pnewpos.p;
+        t.cur_b = cur_b;
+        t.choice = r.choice.p;
+        t.chosen_newpos = r.chosen_newpos.p;
+        t.stats = (unsigned long long*)rt.stats.p;
+        t.moved_flag = r.moved_flag.p;
+        t.new_flag = r.new_flag.p;
+        t.wg_moved = wg_cnt + (size_t)(2 * bi) * nb_wg;
+        t.wg_new = wg_cnt + (size_t)(2 * bi + 1) * nb_wg;
+        t.new_ctr = chosen_ctr[bi];
+        t.new_slots = r.new_slots.p;
+        t.hist_rows = hist_rows;
+        t.on = 1;
+        t.lazy = chosen_ctr[bi] ? 1 : 0;
+        max_hist = std::max(max_hist, hist_rows);
+      }
       tl.flag[2 * bi] = r.moved_flag.p;
       tl.list[2 * bi] = r.moved_list.p;
       tl.flag[2 * bi + 1] = r.new_flag.p;
       tl.list[2 * bi + 1] = r.new_list.p;
+    }
+    if (!no_fused_finalize) {
+      // a capped grid, each workgroup walking a contiguous range of tiles (tail_tiles.h; DESIGN.md §6: the count)
+      static int tail_cap = 0;
+      if (!tail_cap) {
+        int n_cu = 256;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+        tail_cap = std::max(1, n_cu / TAIL_CUS_PER_WG);
+      }
+      const int n_wgs = tail_wg_count(nb_wg, tail_cap, forced_tail_wgs);
+      if (trace_tail)
+        fprintf(stderr, "[pclean tail] finalize_tail_kernel: %d tiles, %d workgroups per block, at most %d tiles per workgroup\n",
+                nb_wg, n_wgs, (nb_wg + n_wgs - 1) / n_wgs);
+      hipLaunchKernelGGL(finalize_tail_kernel, dim3(n_wgs, n_blocks), dim3(TAIL_WG_THREADS), (size_t)max_hist * sizeof(int32_t), ctx->stream, N,
+                         nb_wg, s->chosen.p, tb);
+    } else if (trace_tail) {
+      fprintf(stderr, "[pclean tail] finalize_block_kernel: one launch per block\n");
+    }
+    {  // (a scoring block's two slots: their workgroup counts were never written — zero them so that the totals read 0)
+      for (int bi = 0; bi < n_blocks; ++bi)
+        if (ctx->block[bi].is_score)
+          HIPCHK(ctx, hipMemsetAsync(wg_cnt + (size_t)(2 * bi) * nb_wg, 0, (size_t)2 * nb_wg * sizeof(unsigned int), ctx->stream));
+      hipLaunchKernelGGL(tail_scan_kernel, dim3(2 * n_blocks), dim3(1024), 0, ctx->stream, nb_wg, wg_cnt, s->tail_counts.p);
+      hipLaunchKernelGGL(tail_scatter_kernel, dim3(nb_wg, 2 * n_blocks), dim3(256), 0, ctx->stream, N, nb_wg, tl, wg_cnt);
+    }
+    if (!no_fused_finalize)  // the listed rows' contents: nothing above needed them
+      for (int bi = 0; bi < n_blocks; ++bi)
+        if (chosen_ctr[bi]) {
+          const int rc = sample_chosen(bi);
+          if (rc) return rc;
+        }
+    for (int bi = 0; bi < n_blocks; ++bi) {  // per-row outputs that read the new rows' contents
+      BlockRun& r = s->run[bi];
+      Block& bb = ctx->block[bi];
+      if (bb.is_score) continue;
+      CandTable& rt = ctx->cand[bb.nodes[0].table];
       if (choice)
         HIPCHK(ctx, hipMemcpyAsync(choice + (size_t)bi * N, r.choice.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
       if (!bb.node_gauss.empty() && bb.node_gauss[0] >= 0 && bb.gauss[bb.node_gauss[0]].n_locals > 0) {
@@ -2348,13 +2550,6 @@ extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uin
           HIPCHK(ctx, hipMemcpyAsync(bb.locals_host.data(), r.locals.p, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
         }
       }
-    }
-    {  // (a scoring block's two slots: their workgroup counts were never written — zero them so that the totals read 0)
-      for (int bi = 0; bi < n_blocks; ++bi)
-        if (ctx->block[bi].is_score)
-          HIPCHK(ctx, hipMemsetAsync(wg_cnt + (size_t)(2 * bi) * nb_wg, 0, (size_t)2 * nb_wg * sizeof(unsigned int), ctx->stream));
-      hipLaunchKernelGGL(tail_scan_kernel, dim3(2 * n_blocks), dim3(1024), 0, ctx->stream, nb_wg, wg_cnt, s->tail_counts.p);
-      hipLaunchKernelGGL(tail_scatter_kernel, dim3(nb_wg, 2 * n_blocks), dim3(256), 0, ctx->stream, N, nb_wg, tl, wg_cnt);
     }
     (void)hipEventRecord(s->eve, ctx->stream);
     if (chosen_particle) HIPCHK(ctx, hipMemcpyAsync(chosen_particle, s->chosen.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
