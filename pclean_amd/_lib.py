@@ -1088,6 +1088,28 @@ class HipContext:
               "pclean_own_counts")
         return out
 
+    def add_own_gauss(self, block_id, node_id, g):
+        """append a Gaussian term to an own leaf (after load_own_block, the option table and the numeric columns)"""
+        check(self.h, self.lib.pclean_add_own_gauss(self.h, C.c_int32(block_id), C.c_int32(node_id), C.byref(g)),
+              "pclean_add_own_gauss")
+
+    def own_gauss_exponent(self, block_id, node_id, term):
+        """e of the term's fixed-point statistics (fixed when the term was attached)"""
+        e = C.c_int32(0)
+        check(self.h, self.lib.pclean_own_gauss_stats(self.h, C.c_int32(block_id), C.c_int32(node_id), C.c_int32(term), None,
+                                                      None, C.byref(e)), "pclean_own_gauss_stats")
+        return int(e.value)
+
+    def own_gauss_stats(self, block_id, node_id, term, n_mean):
+        """pclean_own_gauss_stats: (count int64 [n_mean], qsum int64 [n_mean], e) over the loaded rows' current values"""
+        count = np.zeros(n_mean, dtype=np.int64)
+        qsum = np.zeros(n_mean, dtype=np.int64)
+        e = C.c_int32(0)
+        check(self.h, self.lib.pclean_own_gauss_stats(self.h, C.c_int32(block_id), C.c_int32(node_id), C.c_int32(term),
+                                                      _p(count, C.c_int64), _p(qsum, C.c_int64), C.byref(e)),
+              "pclean_own_gauss_stats")
+        return count, qsum, int(e.value)
+
     def get_own_stats(self):
         r = OwnStats()
         check(self.h, self.lib.pclean_get_own_stats(self.h, C.byref(r)), "pclean_get_own_stats")

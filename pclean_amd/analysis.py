@@ -37,6 +37,14 @@ def reconstructed_pool_ids(lowered, trace, row_slice=None, columns=None):
         if gi is not None:
             # corrected = round(unit.backward(x)) (experiments/rents/run.jl:25): numeric, compared as a number
             spec = lw.gauss_specs[gi]
+            if "leaf" in spec:  # a flat class: the unit is an own choice, a row of trace.own (a row without values: option 0)
+                n = trace._own.shape[1]
+                u = np.zeros(n, dtype=np.int32)
+                if spec["t_local"] is not None:
+                    unit = spec["locals"][spec["t_local"]]
+                    u = np.maximum(trace.own[[a for a, _, _ in trace.own_leaves()].index(unit)], 0)
+                out[col] = ("numeric", np.round(lw.gauss_backward(np.arange(n), u, gi)))
+                continue
             bi = lw.gauss_block
             u = (np.zeros(trace.cur.shape[1], dtype=np.int32) if spec["t_local"] is None  # AddNoise: round(x)
                  else np.maximum(trace.locals[bi][:, spec["t_local"]], 0))
@@ -251,18 +259,54 @@ def _thresholded_ids(lowered, marginals, dirty, min_confidence):
     return ids, conf
 
 
+def _map_numeric(lowered, marginals, dirty, min_confidence=0.0):
+    """{query column: (values float64, MAP probability)} of the queried numeric columns of a flat class whose Gaussian term
+    chooses a unit: round(unit.backward(x)) under the MAP unit — the unit of the most probable option of the Gaussian leaf,
+    so the confidence is that option's JOINT probability (Engine.own_marginals) — where it is >= min_confidence, the dirty
+    number otherwise; NaN where the number is missing."""
+    lw = lowered
+    ocls = lw.model.classes[lw.query.cls]
+    out = {}
+    for col, ref in lw.query.cleanmap.items():
+        if "." in ref or ocls.attr(ref).kind != "julia":
+            continue
+        gi = next((g for g, sp in enumerate(lw.gauss_specs) if sp["gauss_attr"] == lw.query.obsmap[col] and "leaf" in sp), None)
+        if gi is None or lw.gauss_specs[gi]["t_local"] is None:
+            continue
+        spec = lw.gauss_specs[gi]
+        unit = spec["locals"][spec["t_local"]]
+        if unit not in marginals:
+            continue
+        k = np.asarray(marginals[unit][0][0])
+        conf = np.asarray(marginals[unit][1][0], dtype=np.float64)
+        n = len(k)
+        vals = np.round(lw.gauss_backward(np.arange(n), np.maximum(k, 0), gi))
+        x = lw.xnum[spec["x_col"], :n]
+        out[col] = (np.where((k < 0) | (conf < min_confidence), x, vals), conf)
+    return out
+
+
 def map_table(lowered, marginals, dirty, min_confidence=0.0):
     """(table, confidence): the cleaned table whose queried own choices hold their most probable option (the MAP string
     of the cell's exact conditional) where its probability is >= min_confidence and the dirty cell otherwise — a missing
     dirty cell always takes the MAP value; every other column is copied.  confidence {query column: MAP probability}.
     A choice indexed by a sibling choice and that index (one product leaf): the two cells hold the most probable PAIR, and
     the confidence of both is the pair's JOINT probability, not a per-column marginal (Engine.own_marginals) — so
-    min_confidence keeps or drops the two cells of a row on the same number."""
+    min_confidence keeps or drops the two cells of a row on the same number.  A Gaussian leaf of a flat class (a string
+    choice and a unit, or one of them): the string cell holds the string of the most probable option, and the queried
+    numeric cell is reported under that option's unit, round(unit.backward(x)), with the same joint confidence
+    (_map_numeric)."""
     ids, conf = _thresholded_ids(lowered, marginals, dirty, min_confidence)
+    nums = _map_numeric(lowered, marginals, dirty, min_confidence)
+    for col, (_, p) in nums.items():
+        conf[col] = p
     n = len(next(iter(conf.values()))) if conf else None
     strings = lowered.pool.strings
     out = {}
     for col, vals in dirty.items():
+        if col in nums:
+            out[col] = _render_numbers(nums[col][0])
+            continue
         if col not in ids:
             out[col] = list(vals[:n])
             continue
@@ -274,6 +318,8 @@ def evaluate_map_accuracy(lowered, marginals, dirty, clean, min_confidence=0.0):
     """evaluate_accuracy of map_table(lowered, marginals, dirty, min_confidence); for the two columns of a product leaf
     min_confidence is compared with the pair's joint probability (see map_table)"""
     ids, conf = _thresholded_ids(lowered, marginals, dirty, min_confidence)
+    for col, (vals, p) in _map_numeric(lowered, marginals, dirty, min_confidence).items():
+        ids[col], conf[col] = ("numeric", vals), p
     n = len(next(iter(conf.values())))
     return f1_from_counts(counts_given(lowered, ids, n, dirty, clean))
 

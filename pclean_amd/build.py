@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpclean_hip.so")
 SOURCES = ["api.hip", "comm.hip", "commit.hip", "dist_kernels.hip", "class_kernels.hip", "enum_kernels.hip", "root_wave.hip", "random_kernels.hip", "sweep.hip", "eval.hip", "latent.hip", "recon.hip", "own_block.hip"]
-HEADERS = ["ctx.h", "../../include/pclean_hip.h", "../../include/pclean_detmath.h", "../../include/pclean_philox.h"]
+HEADERS = ["ctx.h", "../../include/pclean_hip.h", "../../include/pclean_detmath.h", "../../include/pclean_philox.h",
+           "../../include/pclean_ownq.h"]
 # -ffp-contract=off: the parity contract (include/pclean_detmath.h) needs plain
 # IEEE mul/add on device, identical to the gcc-built oracle.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -28,6 +28,7 @@
 // instead of the draws the `top` options of largest u_k (ties: the smaller index) with u_k / U, and u_cur / U of every row's
 // current value.  It writes no value.
 #include "sweep_internal.h"
+#include "../../include/pclean_ownq.h"
 
 #define OWN_BT 256
 #define OWN_LDS_OPTIONS 4096                   // options whose fixed-point weights stay in LDS (32 KiB of a workgroup)
@@ -47,6 +48,9 @@ struct OwnLeaf {
   int n_runs = 0, longest = 0, n_pieces = 0;
   DevBuf<int32_t> piece_off, piece_rows;
   std::vector<int32_t> h_piece_of_row, h_run_of_piece, h_run_len;
+  // Gaussian terms (pclean_add_own_gauss) in attach order, and the exponent of each one's fixed-point statistics
+  std::vector<pclean_gauss> gauss;
+  std::vector<int32_t> gauss_e;
 };
 
 struct OwnBlock {
@@ -62,6 +66,7 @@ struct OwnState {
   DevBuf<double> zero;       // one 0.0: the equal weights of the final choice
   DevBuf<int32_t> bad;       // {rows with logml == -inf, the smallest of them}
   DevBuf<unsigned long long> hist;
+  DevBuf<unsigned long long> gstat;  // pclean_own_gauss_stats: [count | qsum]
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the launches of the last pclean_sweep_own (pclean_timing.total_ms)
   bool product_attr_set = false;          // own_product_kernel's dynamic-LDS limit is raised on this context's device
 };
@@ -679,6 +684,319 @@ __global__ __launch_bounds__(OWN_BT) void own_marginal_kernel(const OwnNodeDev n
   }
 }
 
+// ---- Gaussian leaf: numeric observations make every row its own tuple -------------------------------------------------------
+// (pclean_add_own_gauss; model.py, _lower_own_block.)  The static grouping stays that of the STRING terms' observations (a leaf
+// without string terms is one run cut into pieces); a workgroup takes a piece:
+//   phase 1  every string term once per latent value of the column it reads (own_score's rules), the doubles into LDS —
+//            indexed by the VALUE cand_col[k], so nothing rests on the table being recognised as a grid (1 x n, n x 1).  A
+//            plan whose values exceed OWN_GAUSS_LDS_MAX evaluates the terms per option instead (the same doubles).
+//   phase 2  the rows of the piece are dealt to groups of W = min(64, next power of two >= K) lanes, 64 / W rows per
+//            wavefront at a time; the lanes of a group run over the options, step c covers options c W .. c W + W - 1 (only
+//            W = 64 has more than one step, at most 64 of them).  Per row three passes, nothing in LDS:
+//              1  s_k = logp[k] + string terms in plan order + per present number gauss_add_term, in attach order; maximum
+//              2  u_k = fixw(s_k - m), one group sum per step, lane c keeps step c's total; one inclusive scan: U, lse
+//              3  x = mulhi64(R, U): the step by ballot on the prefix, its W weights again, scanned, the option by ballot —
+//                 min{k : u_0 + .. + u_k > x}, as own_leaf_kernel finds it
+//            (the scores of step 0 stay in a register; further steps are recomputed from the cached values.)
+// MARG: instead of pass 3, `top` rounds of a group arg-max over u_k (equal weights: the smaller index), each round taking
+// only what comes after the last winner in that order; u_k / U; cur_prob by own_marginal_kernel's rule.
+// Every shuffle and ballot is executed by all 64 lanes: rows past the piece's end or outside the window compute on the
+// piece's first row and write nothing.
+#define OWN_GAUSS_MAX_OPTIONS 4096
+#define OWN_GAUSS_LDS_MAX ((size_t)60 * 1024)  // cached term values (within the default dynamic-LDS limit of a launch)
+
+struct OwnGaussDev {
+  int32_t n_gauss, n_cols, lw, cached;  // lw: log2 of the lanes per row
+  int32_t local_n[2];
+  const int32_t* col[2];  // the option table's value columns (col[1] null: one column)
+  int32_t off[PCLEAN_MAX_TERMS];  // cached values of string term ti: tv[off[ti] + latent value]
+  GaussDev g[PCLEAN_MAX_GAUSS];
+};
+
+// one string term for observed value o and latent value val (own_score's body; the caller skips a non-tabulated term of a
+// missing observation)
+__device__ __forceinline__ double own_term_value(const TermDev& tm, const DensDev& dn, int o, int val) {
+  if (tm.dens_kind == PCLEAN_DENS_TABULATED) {
+    const int c = o < 0 ? 3 : ((int)tm.pair[(size_t)o * tm.n_lat + val] & 3);
+    return tm.cls[(size_t)val * 4 + c];
+  }
+  const size_t idx = (size_t)o * tm.n_lat + val;
+  const int d = tm.elem_bytes == 1 ? (int)tm.pair[idx] : (int)((const uint16_t*)tm.pair)[idx];
+  return own_term_density(tm, dn, d, val);
+}
+
+__device__ __forceinline__ int own_gauss_no_val(const GaussDev&, int) { return 0; }  // (every index dimension is an option column)
+
+// the ONE place where the score of option k for `row` is written: own_score's sum, then gauss_add_term per present number
+__device__ __forceinline__ double own_gauss_score(const OwnNodeDev& nd, const DensDev& dn, const OwnGaussDev& gd, const double* tv,
+                                                  const int* obs, unsigned int skip, int row, const double* xv, int k) {
+  double sk = nd.logp[k];
+  for (int ti = 0; ti < nd.n_terms; ++ti) {
+    if ((skip >> ti) & 1u) continue;
+    const TermDev& tm = nd.terms[ti];
+    const int val = tm.cand_col[k];
+    sk += gd.cached ? tv[gd.off[ti] + val] : own_term_value(tm, dn, obs[ti], val);
+  }
+  const int l0 = gd.col[0][k], l1 = gd.n_cols > 1 ? gd.col[1][k] : 0;
+  if ((unsigned)l0 >= (unsigned)gd.local_n[0] || (unsigned)l1 >= (unsigned)gd.local_n[1]) return -__builtin_inf();
+#pragma unroll
+  for (int gi = 0; gi < PCLEAN_MAX_GAUSS; ++gi) {
+    if (gi >= gd.n_gauss) break;
+    const double x = xv[gi];
+    if (x != x) continue;  // (a missing number: the term is skipped)
+    int ls[2];
+    const int base = gauss_index_base(gd.g[gi], own_gauss_no_val, ls);
+    sk = gauss_add_term(gd.g[gi], sk, x, row, nullptr, base, ls, l0, l1);
+  }
+  return sk;
+}
+
+// the lanes of this lane's group (W = 1 << lw of them) for which pred holds, bit 0 = the group's first lane
+__device__ __forceinline__ unsigned long long own_group_ballot(int pred, int lane, int lw) {
+  const unsigned long long b = __ballot(pred);
+  if (lw == 6) return b;
+  const int W = 1 << lw;
+  return (b >> (lane & ~(W - 1))) & ((1ull << W) - 1ull);
+}
+
+template <bool MARG>
+__global__ __launch_bounds__(OWN_BT) void own_gauss_kernel(const OwnNodeDev nd, const DensDev dn, const OwnGaussDev gd,
+                                                           const OwnLaunch L, const OwnMarginal M) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char own_smem[];
+  __shared__ int s_obs[PCLEAN_MAX_TERMS];
+  double* tv = reinterpret_cast<double*>(own_smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t* piece_off = MARG ? M.piece_off : L.piece_off;
+  const int32_t* members = MARG ? M.members : L.members;
+  const int win_lo = MARG ? M.win_lo : L.win_lo, win_hi = MARG ? M.win_hi : L.win_hi;
+  const bool probe = !MARG && L.probe;
+  const int m_lo = piece_off[blockIdx.x], m_hi = piece_off[blockIdx.x + 1];
+  const int n = nd.n_cand;
+  if (!probe) {  // a run none of whose rows lies in the window has nothing to do
+    int any = 0;
+    for (int q = m_lo + tid; q < m_hi; q += OWN_BT) {
+      const int r = members[q];
+      any |= (r >= win_lo && r < win_hi) ? 1 : 0;
+    }
+    if (!__syncthreads_or(any)) return;
+  }
+  {
+    const int row0 = probe ? L.item_row[members[m_lo]] : members[m_lo];
+    for (int ti = 0; ti < nd.n_terms; ++ti)
+      if (tid == ti) s_obs[ti] = nd.terms[ti].obs_col[row0];
+  }
+  __syncthreads();
+
+  // ---- phase 1: the string terms, once per latent value
+  unsigned int skip = 0;
+  for (int ti = 0; ti < nd.n_terms; ++ti) {
+    const TermDev& tm = nd.terms[ti];
+    const int o = s_obs[ti];
+    if (tm.dens_kind != PCLEAN_DENS_TABULATED && o < 0) {  // a missing observation: the term adds nothing
+      skip |= 1u << ti;
+      continue;
+    }
+    if (!gd.cached) continue;
+    double* dst = tv + gd.off[ti];
+    for (int val = tid; val < tm.n_lat; val += OWN_BT) dst[val] = own_term_value(tm, dn, o, val);
+  }
+  __syncthreads();
+
+  // ---- phase 2: a group of W lanes per row
+  const int lw = gd.lw, W = 1 << lw, rpw = 64 >> lw;
+  const int gl = lane & (W - 1), sub = lane >> lw;
+  const int steps = (n + W - 1) >> lw;  // (W < 64: one)
+  const int n_mem = m_hi - m_lo;
+  const size_t nw = (size_t)(win_hi - win_lo);
+  for (int base = 0; base < n_mem; base += (OWN_BT / 64) * rpw) {
+    const int qi = base + wave * rpw + sub;
+    const bool valid = qi < n_mem;
+    const int mem = members[m_lo + (valid ? qi : 0)];
+    const int row = probe ? L.item_row[mem] : mem;
+    const bool live = valid && (probe || (row >= win_lo && row < win_hi));
+    double xv[PCLEAN_MAX_GAUSS];
+#pragma unroll
+    for (int gi = 0; gi < PCLEAN_MAX_GAUSS; ++gi) xv[gi] = gi < gd.n_gauss ? gd.g[gi].x[row] : 0.0;
+    auto score = [&](int k) -> double { return own_gauss_score(nd, dn, gd, tv, s_obs, skip, row, xv, k); };
+
+    // pass 1: scores and their maximum
+    const double s0 = gl < n ? score(gl) : -__builtin_inf();
+    double m = s0;
+    if (!MARG && probe && L.scores_out && live && gl < n) L.scores_out[(size_t)mem * n + gl] = s0;
+    for (int c = 1; c < steps; ++c) {
+      const int k = (c << lw) + gl;
+      if (k < n) {
+        const double sk = score(k);
+        if (!MARG && probe && L.scores_out && live) L.scores_out[(size_t)mem * n + k] = sk;
+        m = fmax(m, sk);
+      }
+    }
+    for (int o = W >> 1; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));  // (o < W: the partner lies in the group)
+    const bool dead = m == -__builtin_inf();
+
+    // pass 2: fixed-point weights, one sum per step (lane c keeps step c's), their inclusive prefix
+    unsigned long long pre = 0ull;
+    for (int c = 0; c < steps; ++c) {
+      const int k = (c << lw) + gl;
+      unsigned long long v = (k < n && !dead) ? pclean_fixw((c == 0 ? s0 : score(k)) - m) : 0ull;
+      for (int o = W >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (gl == c) pre = v;
+    }
+    for (int o = 1; o < W; o <<= 1) {
+      const unsigned long long t = __shfl_up(pre, o, 64);
+      if (gl >= o) pre += t;
+    }
+    const unsigned long long U = __shfl(pre, (lane & ~(W - 1)) + W - 1, 64);
+    const double lse = pclean_lse_from_fix(m, U);
+
+    if (!MARG) {
+      // pass 3: the draws
+      int n_dr = 1, pid0 = 0;
+      bool draw = live;
+      if (probe) {
+        if (live && gl == 0 && L.lse_out) L.lse_out[mem] = lse;
+        n_dr = L.n_draws;
+      } else if (live) {
+        const int i = row - win_lo;
+        if (gl == 0) L.logml[i] += lse;  // (a row lies in exactly one run of the leaf; the leaves are launched one after the other)
+        draw = !L.keep[i];
+        pid0 = L.chosen[i];
+      }
+      for (int j = 0; j < n_dr; ++j) {  // (uniform: the probe's n_draws, the sweep's one)
+        const int pid = probe ? j : pid0;
+        const uint32_t rng_row = (uint32_t)((int64_t)row + L.row_offset);
+        const unsigned long long x = pclean_mulhi64(pclean_rand64(L.seed, rng_row, L.site, (uint32_t)pid, L.sweep), U);
+        int chunk = 0;
+        unsigned long long acc0 = 0ull;
+        if (steps > 1) {  // (W == 64: one row per wavefront, so this is uniform) the first step whose inclusive prefix exceeds x
+          const unsigned long long cm = __ballot(lane < steps && pre > x);
+          chunk = cm ? __builtin_ctzll(cm) : steps - 1;
+          acc0 = __shfl(pre, chunk ? chunk - 1 : 0, 64);
+          if (!chunk) acc0 = 0ull;
+        }
+        const int k = (chunk << lw) + gl;
+        unsigned long long v = (k < n && !dead) ? pclean_fixw((chunk == 0 ? s0 : score(k)) - m) : 0ull;
+        for (int o = 1; o < W; o <<= 1) {
+          const unsigned long long t = __shfl_up(v, o, 64);
+          if (gl >= o) v += t;
+        }
+        const unsigned long long hit = own_group_ballot(k < n && acc0 + v > x, lane, lw);
+        int res = n - 1;
+        if (U != 0ull) res = hit ? (chunk << lw) + __builtin_ctzll(hit) : min(n, (chunk + 1) << lw) - 1;
+        if (draw && gl == 0) {
+          if (probe)
+            L.draws_out[(size_t)mem * L.n_draws + j] = res;
+          else
+            L.vals[row] = res;
+        }
+      }
+    } else {
+      // the `top` options of largest weight, then the probability of the current value
+      const double Ud = (double)U;
+      unsigned long long last_u = 0ull;
+      int last_k = -1;
+      bool open = true;  // (a round that finds nothing: every later one finds nothing either)
+      for (int t = 0; t < M.top; ++t) {
+        unsigned long long bu = 0ull;
+        int bk = -1;
+        for (int c = 0; c < steps && open; ++c) {
+          const int k = (c << lw) + gl;
+          if (k >= n || dead) continue;
+          const unsigned long long u = pclean_fixw((c == 0 ? s0 : score(k)) - m);
+          if (u != 0ull && (last_k < 0 || own_before(last_u, last_k, u, k)) && own_before(u, k, bu, bk)) {
+            bu = u;
+            bk = k;
+          }
+        }
+        for (int o = W >> 1; o > 0; o >>= 1) {
+          const unsigned long long uo = __shfl_xor(bu, o, 64);
+          const int ko = __shfl_xor(bk, o, 64);
+          if (own_before(uo, ko, bu, bk)) {
+            bu = uo;
+            bk = ko;
+          }
+        }
+        if (bu != 0ull) {
+          last_u = bu;
+          last_k = bk;
+        } else {
+          open = false;
+        }
+        if (live && gl == 0) {
+          const size_t i = (size_t)(row - win_lo);
+          M.top_option[(size_t)t * nw + i] = bu != 0ull ? bk : -1;
+          M.top_prob[(size_t)t * nw + i] = bu != 0ull ? (double)bu / Ud : 0.0;
+        }
+      }
+      if (live && gl == 0) {
+        const size_t i = (size_t)(row - win_lo);
+        if (M.cur_prob) {
+          const int cur = M.vals[row];
+          double p = 0.0;
+          if (U != 0ull && cur >= 0 && cur < n) p = (double)pclean_fixw(score(cur) - m) / Ud;
+          M.cur_prob[i] = p;
+        }
+        if (U == 0ull) {
+          atomicAdd(&M.bad[0], 1);
+          atomicMin(&M.bad[1], row);
+        }
+      }
+    }
+  }
+}
+
+// pclean_own_gauss_stats: count and fixed-point sum of the backward values per mean index, over the rows' current options.
+// The unit and bx are gauss_add_term's (u from the option column the term names; the derived column if the unit has one,
+// else x * t_scale[u]).  n_mean <= OWN_GAUSS_STAT_LDS: a workgroup adds up in LDS and flushes its non-zero entries once.
+#define OWN_GAUSS_STAT_LDS 1024
+__global__ __launch_bounds__(256) void own_gauss_stats_kernel(int n_rows, int K, const int32_t* __restrict__ vals, const OwnGaussDev gd,
+                                                              int gi, int n_mean, double scale, unsigned long long* __restrict__ count,
+                                                              unsigned long long* __restrict__ qsum) {
+  __shared__ unsigned long long s_q[OWN_GAUSS_STAT_LDS];
+  __shared__ unsigned int s_c[OWN_GAUSS_STAT_LDS];
+  const bool lds = n_mean <= OWN_GAUSS_STAT_LDS;
+  if (lds) {
+    for (int j = threadIdx.x; j < n_mean; j += blockDim.x) {
+      s_q[j] = 0ull;
+      s_c[j] = 0u;
+    }
+    __syncthreads();
+  }
+  const GaussDev& g = gd.g[gi];
+  int ls[2];
+  const int base = gauss_index_base(g, own_gauss_no_val, ls);
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n_rows; i += stride) {
+    const int v = vals[i];
+    if (v < 0 || v >= K) continue;
+    const double x = g.x[i];
+    if (x != x) continue;
+    const int l0 = gd.col[0][v], l1 = gd.n_cols > 1 ? gd.col[1][v] : 0;
+    if ((unsigned)l0 >= (unsigned)gd.local_n[0] || (unsigned)l1 >= (unsigned)gd.local_n[1]) continue;
+    const int idx = base + ls[0] * l0 + ls[1] * l1;
+    if (idx < 0 || idx >= n_mean) continue;
+    const int u = g.t_kind == PCLEAN_GSRC_LOCAL ? (g.t_src == 0 ? l0 : l1) : 0;
+    const double bx = g.tx[u] ? g.tx[u][i] : x * g.t_scale[u];
+    if (!(fabs(bx) <= 1.7976931348623157e308)) continue;  // (NaN or infinite)
+    const unsigned long long q = (unsigned long long)pclean_ownq(bx, scale);  // (two's complement: the sum is the signed one)
+    if (lds) {
+      atomicAdd(&s_c[idx], 1u);
+      atomicAdd(&s_q[idx], q);
+    } else {
+      atomicAdd(&count[idx], 1ull);
+      atomicAdd(&qsum[idx], q);
+    }
+  }
+  if (lds) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < n_mean; j += blockDim.x)
+      if (s_c[j]) {
+        atomicAdd(&count[j], (unsigned long long)s_c[j]);
+        atomicAdd(&qsum[j], s_q[j]);
+      }
+  }
+}
+
 // row_inference.jl:158-165 on equal weights — final_choice_kernel's operations (sweep.hip) with every weight 0.0
 template <int PMAX>
 __global__ void own_choice_kernel(int N, int P, int use_mh, const double* __restrict__ zero, const int32_t* __restrict__ vals0,
@@ -899,9 +1217,107 @@ bool own_product_plan(pclean_ctx* ctx, const OwnLeaf& lf, const OwnNodeDev& od, 
   return true;
 }
 
+// What pclean_add_own_gauss checks of a term against the node's option table and the numeric columns as they are now (the
+// launches check again: either may have been set anew since)
+int check_own_gauss(pclean_ctx* ctx, const OwnLeaf& lf, const pclean_gauss& g, int status, const char* who) {
+  if (g.n_locals < 1 || g.n_locals > 2 || g.n_dims < 0 || g.n_dims > 4 || g.fixed_locals != 0)
+    return pclean_fail(ctx, status, "%s: n_locals (the option table's value columns) must be 1 or 2, n_dims 0 .. 4, fixed_locals 0", who);
+  int64_t K = 1, top = 0;
+  for (int c = 0; c < g.n_locals; ++c) {
+    if (g.local_n[c] < 1 || g.local_n[c] > OWN_GAUSS_MAX_OPTIONS) return pclean_fail(ctx, status, "%s: local_n[%d] = %d", who, c, g.local_n[c]);
+    K *= g.local_n[c];
+  }
+  if (K > OWN_GAUSS_MAX_OPTIONS)
+    return pclean_fail(ctx, status, "%s: a grid of %lld options (at most %d are served)", who, (long long)K, OWN_GAUSS_MAX_OPTIONS);
+  for (int d = 0; d < g.n_dims; ++d) {
+    if (g.src_kind[d] != PCLEAN_GSRC_LOCAL)
+      return pclean_fail(ctx, status, "%s: index source %d is of kind %d; an own leaf's term reads option columns alone "
+                                      "(PCLEAN_GSRC_LOCAL), no candidate, observed, ctx or evidence value", who, d, g.src_kind[d]);
+    if (g.src[d] < 0 || g.src[d] >= g.n_locals || g.stride[d] < 0) return pclean_fail(ctx, status, "%s: index source %d: bad column or stride", who, d);
+    top += (int64_t)g.stride[d] * (g.local_n[g.src[d]] - 1);
+  }
+  if (top > 0x7fffffff) return pclean_fail(ctx, status, "%s: mean index out of range", who);
+  if (g.transform_src_kind != -1) {
+    if (g.transform_src_kind != PCLEAN_GSRC_LOCAL)
+      return pclean_fail(ctx, status, "%s: transformation source of kind %d; an option column (PCLEAN_GSRC_LOCAL) or none (-1)", who,
+                         g.transform_src_kind);
+    if (g.transform_src < 0 || g.transform_src >= g.n_locals || g.local_n[g.transform_src] > 4)
+      return pclean_fail(ctx, status, "%s: the transformation column must be an option column with at most 4 values", who);
+  }
+  if (!(g.sigma > 0.0) || g.mean_table < 0 || g.mean_table >= PCLEAN_MAX_TABLES) return pclean_fail(ctx, status, "%s: bad sigma or mean table", who);
+  const CandTable& t = ctx->cand[lf.node.table];
+  if (!t.valid || !t.is_options) return pclean_fail(ctx, status, "%s: the node's option table is not set", who);
+  if (t.n_cols != g.n_locals || (int64_t)t.n_rows != K)
+    return pclean_fail(ctx, status, "%s: the option table holds %d options in %d columns, the term names %lld in %d", who, t.n_rows, t.n_cols,
+                       (long long)K, g.n_locals);
+  if (!ctx->xnum.p || ctx->n_xcols <= 0 || g.x_col < 0 || g.x_col >= ctx->n_xcols)
+    return pclean_fail(ctx, status, "%s: numeric column %d is not loaded (pclean_load_numeric_columns)", who, g.x_col);
+  for (int u = 0; u < 4; ++u)
+    if (g.t_x_col[u] >= 0 || g.t_lad_col[u] >= 0)
+      if (g.t_x_col[u] < 0 || g.t_x_col[u] >= ctx->n_xcols || g.t_lad_col[u] < 0 || g.t_lad_col[u] >= ctx->n_xcols)
+        return pclean_fail(ctx, status, "%s: transformation column out of range", who);
+  return PCLEAN_OK;
+}
+
+// The device view of a Gaussian leaf: its terms resolved (build_gauss_dev, rows addressed by loaded row), the option columns,
+// the lanes per row and the layout of the cached string-term values
+int own_gauss_plan(pclean_ctx* ctx, const OwnLeaf& lf, const OwnNodeDev& od, OwnGaussDev& gd, size_t* lds) {
+  memset(&gd, 0, sizeof gd);
+  const CandTable& t = ctx->cand[lf.node.table];
+  if (od.n_cand > OWN_GAUSS_MAX_OPTIONS)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "own block: a Gaussian leaf of %d options (at most %d)", od.n_cand, OWN_GAUSS_MAX_OPTIONS);
+  gd.n_gauss = (int)lf.gauss.size();
+  for (int gi = 0; gi < gd.n_gauss; ++gi) {
+    pclean_gauss g = lf.gauss[gi];
+    int rc = check_own_gauss(ctx, lf, g, PCLEAN_ERR_STATE, "own block (Gaussian term)");
+    if (rc) return rc;
+    g.local_obs_col[0] = g.local_obs_col[1] = -1;  // (not read: the choices' observations are the leaf's string terms)
+    rc = build_gauss_dev(ctx, g, nullptr, gd.g[gi]);
+    if (rc) return rc;
+    GaussDev& d = gd.g[gi];
+    d.x -= ctx->active_begin;  // (the own kernels address rows by loaded row)
+    for (int u = 0; u < 4; ++u)
+      if (d.tx[u]) {
+        d.tx[u] -= ctx->active_begin;
+        d.tl[u] -= ctx->active_begin;
+      }
+    int64_t top = 0;
+    for (int dd = 0; dd < g.n_dims; ++dd) top += (int64_t)g.stride[dd] * (g.local_n[g.src[dd]] - 1);
+    if (top >= ctx->mean[g.mean_table].n)
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "own block: mean table %d holds %d values, the term's largest index is %lld", g.mean_table,
+                         ctx->mean[g.mean_table].n, (long long)top);
+    gd.n_cols = g.n_locals;
+    gd.local_n[0] = g.local_n[0];
+    gd.local_n[1] = g.n_locals > 1 ? g.local_n[1] : 1;
+  }
+  gd.col[0] = t.cols.p;
+  gd.col[1] = gd.n_cols > 1 ? t.cols.p + (size_t)t.n_rows : nullptr;
+  gd.lw = 0;
+  while (gd.lw < 6 && (1 << gd.lw) < od.n_cand) ++gd.lw;
+  size_t total = 0;
+  for (int ti = 0; ti < od.n_terms; ++ti) {
+    gd.off[ti] = (int32_t)total;
+    total += (size_t)std::max(od.terms[ti].n_lat, 0);
+  }
+  gd.cached = total * 8 <= OWN_GAUSS_LDS_MAX ? 1 : 0;
+  *lds = gd.cached ? total * 8 : 0;
+  return PCLEAN_OK;
+}
+
 int launch_leaf(pclean_ctx* ctx, const OwnLeaf& lf, const OwnNodeDev& od, const OwnLaunch& L, int n_pieces, OwnState* s) {
   if (n_pieces <= 0) return PCLEAN_OK;
   const DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
+  if (!lf.gauss.empty()) {
+    OwnGaussDev gd;
+    size_t glds = 0;
+    const int rc = own_gauss_plan(ctx, lf, od, gd, &glds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(own_gauss_kernel<false>, dim3(n_pieces), dim3(OWN_BT), glds, ctx->stream, od, dn, gd, L, OwnMarginal{});
+    HIPCHK(ctx, hipGetLastError());
+    s->stats.variants |= 8;
+    s->stats.n_workgroups += n_pieces;
+    return PCLEAN_OK;
+  }
   OwnProductDev pr;
   size_t lds = 0;
   if (own_product_plan(ctx, lf, od, &pr, &lds)) {
@@ -965,6 +1381,7 @@ void pclean_own_state_free(pclean_ctx* ctx) {
   s->zero.release();
   s->bad.release();
   s->hist.release();
+  s->gstat.release();
   for (hipEvent_t e : s->ev)
     if (e) (void)hipEventDestroy(e);
   delete s;
@@ -1060,6 +1477,11 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
       ods.emplace_back();
       rc = leaf_dev(ctx, lf, ods.back());
       if (!rc) rc = ensure_groups(ctx, lf);
+      if (!rc && !lf.gauss.empty()) {  // (a missing mean table, an option table set anew in another shape)
+        OwnGaussDev gd;
+        size_t glds = 0;
+        rc = own_gauss_plan(ctx, lf, ods.back(), gd, &glds);
+      }
       if (rc) return rc;
     }
   }
@@ -1240,8 +1662,19 @@ extern "C" int pclean_own_marginals(pclean_ctx* ctx, int32_t block_id, int32_t n
   L.bad = s->bad.p;
   const DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
   const bool resident = od.n_cand <= OWN_LDS_OPTIONS;
+  OwnGaussDev gd;
+  size_t glds = 0;
+  if (!lf.gauss.empty()) {
+    rc = own_gauss_plan(ctx, lf, od, gd, &glds);
+    if (rc) return rc;
+  }
   HIPCHK(ctx, hipEventRecord(s->ev[0], ctx->stream));
-  if (lf.n_pieces > 0) {  // (a lane keeps 1 entry for top == 1, OWN_MAX_TOP otherwise)
+  if (lf.n_pieces > 0 && !lf.gauss.empty()) {
+    hipLaunchKernelGGL(own_gauss_kernel<true>, dim3(lf.n_pieces), dim3(OWN_BT), glds, ctx->stream, od, dn, gd, OwnLaunch{}, L);
+    HIPCHK(ctx, hipGetLastError());
+    s->stats.variants |= 8;
+    s->stats.n_workgroups += lf.n_pieces;
+  } else if (lf.n_pieces > 0) {  // (a lane keeps 1 entry for top == 1, OWN_MAX_TOP otherwise)
     const dim3 grid(lf.n_pieces), block(OWN_BT);
     if (resident && top == 1)
       hipLaunchKernelGGL((own_marginal_kernel<true, 1>), grid, block, 0, ctx->stream, od, dn, L);
@@ -1292,6 +1725,82 @@ extern "C" int pclean_own_counts(pclean_ctx* ctx, int32_t block_id, int32_t node
   }
   HIPCHK(ctx, hipMemcpyAsync(counts, s->hist.p, (size_t)K * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCLEAN_SYNC(ctx);
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_add_own_gauss(pclean_ctx* ctx, int32_t block_id, int32_t node_id, const pclean_gauss* g) {
+  OwnBlock* b = find_block(ctx, block_id);
+  if (!b) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_add_own_gauss: block %d is not a loaded own block", block_id);
+  if (node_id < 0 || node_id >= (int)b->leaves.size() || !g)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_add_own_gauss: block %d has no node %d", block_id, node_id);
+  OwnLeaf& lf = b->leaves[node_id];
+  int rc = check_own_gauss(ctx, lf, *g, PCLEAN_ERR_ARG, "pclean_add_own_gauss");
+  if (rc) return rc;
+  if (!lf.gauss.empty() && (lf.gauss[0].n_locals != g->n_locals || lf.gauss[0].local_n[0] != g->local_n[0] ||
+                            (g->n_locals > 1 && lf.gauss[0].local_n[1] != g->local_n[1])))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_add_own_gauss: the terms of a node share its option columns (n_locals, local_n)");
+  if ((int)lf.gauss.size() >= PCLEAN_MAX_GAUSS)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "pclean_add_own_gauss: more than %d Gaussian terms on node %d", PCLEAN_MAX_GAUSS, node_id);
+  // the exponent of the term's fixed-point statistics: the largest finite |bx| over its units and the present rows
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int N = ctx->n_rows;
+  const int n_units = g->transform_src_kind == PCLEAN_GSRC_LOCAL ? g->local_n[g->transform_src] : 1;
+  double M = 0.0;
+  if (N > 0) {
+    std::vector<double> x(N), tx(N);
+    HIPCHK(ctx, hipMemcpy(x.data(), ctx->xnum.p + (size_t)g->x_col * N, (size_t)N * 8, hipMemcpyDeviceToHost));
+    for (int u = 0; u < n_units; ++u) {
+      if (g->t_x_col[u] >= 0) HIPCHK(ctx, hipMemcpy(tx.data(), ctx->xnum.p + (size_t)g->t_x_col[u] * N, (size_t)N * 8, hipMemcpyDeviceToHost));
+      for (int i = 0; i < N; ++i) {
+        if (x[i] != x[i]) continue;
+        const double bx = std::fabs(g->t_x_col[u] >= 0 ? tx[i] : x[i] * g->t_scale[u]);
+        if (bx <= 1.7976931348623157e308 && bx > M) M = bx;
+      }
+    }
+  }
+  lf.gauss.push_back(*g);
+  lf.gauss_e.push_back(pclean_ownq_exponent(M, N));
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_own_gauss_stats(pclean_ctx* ctx, int32_t block_id, int32_t node_id, int32_t term, int64_t* count, int64_t* qsum,
+                                      int32_t* exponent) {
+  OwnBlock* b = find_block(ctx, block_id);
+  if (!b || node_id < 0 || node_id >= (int)b->leaves.size())
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_own_gauss_stats: block %d node %d is not a node of a loaded own block", block_id, node_id);
+  OwnLeaf& lf = b->leaves[node_id];
+  if (term < 0 || term >= (int)lf.gauss.size() || (!count) != (!qsum))
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_own_gauss_stats: node %d has no Gaussian term %d (or only one of count / qsum is given)",
+                       node_id, term);
+  if (exponent) *exponent = lf.gauss_e[term];
+  if (!count) return PCLEAN_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  OwnNodeDev od;
+  OwnGaussDev gd;
+  size_t glds = 0;
+  int rc = leaf_dev(ctx, lf, od);
+  if (!rc) rc = own_gauss_plan(ctx, lf, od, gd, &glds);
+  if (!rc) rc = ensure_vals(ctx, *b);
+  OwnState* s = own(ctx);
+  if (!rc) rc = ensure_aux(ctx, s);
+  if (rc) return rc;
+  const int n_mean = ctx->mean[lf.gauss[term].mean_table].n;
+  if (s->gstat.alloc((size_t)2 * n_mean)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  HIPCHK(ctx, hipEventRecord(s->ev[0], ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(s->gstat.p, 0, (size_t)2 * n_mean * 8, ctx->stream));
+  if (ctx->n_rows) {
+    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)ctx->n_rows + 255) / 256, 1024);
+    hipLaunchKernelGGL(own_gauss_stats_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->n_rows, od.n_cand,
+                       (const int32_t*)(b->vals.p + (size_t)node_id * ctx->n_rows), gd, term, n_mean, pclean_ownq_scale(lf.gauss_e[term]),
+                       s->gstat.p, s->gstat.p + n_mean);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  HIPCHK(ctx, hipEventRecord(s->ev[1], ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(count, s->gstat.p, (size_t)n_mean * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(qsum, s->gstat.p + n_mean, (size_t)n_mean * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PCLEAN_SYNC(ctx);
+  ctx->timing = pclean_timing{};
+  (void)hipEventElapsedTime(&ctx->timing.total_ms, s->ev[0], s->ev[1]);  // (the clearing and the kernel: pclean_get_timing)
   return PCLEAN_OK;
 }
 

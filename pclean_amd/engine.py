@@ -119,6 +119,19 @@ def option_prior(lw, trace, cname, aname):
         return logp.reshape(-1)
 
 
+def own_gauss_prior(lw, trace, leaf):
+    """log prior of every option of a Gaussian leaf (LoweredModel.own_gauss): log p(a) + log p(b) over the factors' grid,
+    added in that order, key-major; one factor: that choice's own log prior (ChooseProportionally: logprobs() of its
+    parameter; ChooseUniformly: -log(#options))"""
+    cls = lw.query.cls
+    parts = []
+    for f in leaf["factors"]:
+        d = lw.model.classes[cls].attr(f).dist
+        parts.append(option_prior(lw, trace, cls, f) if isinstance(d, ChooseProportionally)
+                     else np.full(len(d.options), -np.log(len(d.options))))
+    return parts[0] if len(parts) == 1 else (parts[0][:, None] + parts[1][None, :]).reshape(-1)
+
+
 class Engine:
     def __init__(self, lowered, obs, device=0, dist_mode=_lib.DIST_DL, row_offset=0):
         self.lw = lowered
@@ -293,6 +306,7 @@ class Engine:
             hip.set_options(tid, lw.option_values[(cname, aname)], logp)
         lw.load_blocks_into(hip)
         self._gauss_pending = bool(getattr(lw, "gauss", {}))
+        self._own_gauss_pending = bool(getattr(lw, "own_gauss", {}))  # (pclean_load_own_block forgot the terms)
 
     def _upload_class_tables(self):
         """Tabulated terms (ExpandOnShortVersion / FormatName): the class table of every such pair, built on the device
@@ -391,7 +405,7 @@ class Engine:
             if last.get("prob") is None or not np.array_equal(last["prob"], pt):
                 hip.set_prob_table(pt)
                 last["prob"] = pt.copy()
-        if getattr(lw, "gauss", None):
+        if getattr(lw, "gauss", None) or getattr(lw, "own_gauss", None):
             for g, mp in enumerate(trace.mean_params):  # term g reads mean table g
                 mv, key = mp.value, "mean" if g == 0 else ("mean", g)
                 if last.get(key) is None or not np.array_equal(last[key], mv):
@@ -400,6 +414,18 @@ class Engine:
             if self._gauss_pending:  # needs the mean table to exist
                 self._upload_gauss()
                 self._gauss_pending = False
+        for (bi, nid), leaf in getattr(lw, "own_gauss", {}).items():
+            # a Gaussian leaf of a flat class: the joint prior over the factors' grid, on the leaf's own option table
+            logp = own_gauss_prior(lw, trace, leaf)
+            prev = last.get(("own_gauss", bi, nid))
+            if prev is None or not np.array_equal(prev, logp):
+                hip.set_options_cols(leaf["table"], leaf["cols"], logp)
+                last[("own_gauss", bi, nid)] = logp.copy()
+        if getattr(self, "_own_gauss_pending", False):  # after pclean_load_own_block, the option tables and the numeric columns
+            for (bi, nid), leaf in lw.own_gauss.items():
+                for spec in leaf["specs"]:
+                    hip.add_own_gauss(bi, nid, make_gauss(spec))
+            self._own_gauss_pending = False
 
     @staticmethod
     def _debug_upload(prev, cname):

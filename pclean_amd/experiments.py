@@ -267,6 +267,36 @@ def flat_query(m, columns=FLAT_COLUMNS):
     return Query(m, "Obs", {c: (c, f"{c}_obs") for c in columns})
 
 
+FLAT_NUMERIC_COLUMNS = ("Room Type", "Monthly Rent")
+
+
+def flat_numeric_model(rooms, units=None, std=150.0, prior=(1500.0, 1000.0)):
+    """A flat program with a numeric column: ONE own block
+        room ~ ChooseProportionally(rooms, room_p);  unit ~ ChooseUniformly(units)
+        rent ~ TransformedGaussian(avg_rent[room], std, unit);  corrected = round(unit.backward(rent))
+    — the rents table's Monthly Rent given its Room Type, some rents stated in the wrong unit, without a latent class.  room
+    and unit are the factors of one Gaussian leaf (model.py: _lower_own_gauss).  units: default the rents program's two."""
+    from .model import IndexedLookup, IndexedMeanParameter, TransformedGaussian, Transformation
+    if units is None:
+        units = [Transformation(lambda x: x, lambda x: x, lambda x: 1.0),
+                 Transformation(lambda x: x / 1000.0, lambda x: x * 1000.0, lambda x: 1 / 1000.0)]
+    m = Model()
+    o = m.add_class("Obs")
+    o.param("room_p", ProportionsParameter(1.0))
+    o.param("avg_rent", IndexedMeanParameter(*prior))
+    with o.block():
+        o.choice("room", ChooseProportionally(list(rooms), "room_p"))
+        o.choice("unit", ChooseUniformly(list(units)))
+        o.julia("rent_base", IndexedLookup("avg_rent"), ["room"])
+        o.choice("rent", TransformedGaussian("rent_base", float(std), "unit"))
+        o.julia("corrected", lambda unit, rent: round(unit.backward(rent)), ["unit", "rent"])
+    return m
+
+
+def flat_numeric_query(m):
+    return Query(m, "Obs", {"Room Type": "room", "Monthly Rent": ("corrected", "rent")})
+
+
 def cell_accuracy(cleaned, clean, columns=FLAT_COLUMNS):
     """share of the cells of `columns` whose cleaned value is the clean table's"""
     hit = sum(a == b for c in columns for a, b in zip(cleaned[c], clean[c]))

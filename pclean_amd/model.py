@@ -93,6 +93,7 @@ TABULATED = (ExpandOnShortVersion, FormatName)
 NAME3_LOG_THREE = math.log(0.9) + math.log(0.9) + math.log(0.9)
 NAME3_LOG_TWO = math.log(0.1)
 OWN_MAX_OPTIONS = 64 * 4096  # options of one own option list (csrc/own_block.hip: OWN_MAX_OPTIONS)
+OWN_GAUSS_MAX_OPTIONS = 4096  # options of an own leaf that carries Gaussian terms (csrc/own_block.hip: OWN_GAUSS_MAX_OPTIONS)
 
 
 class TimePrior:
@@ -791,6 +792,7 @@ class LoweredModel:
         # of the particles inside the sweep.
         self.own_leaf = {}   # own choice of the observed class -> (block, node) of its leaf
         self.own_product = {}  # own choice indexed by a sibling own choice -> that index: the two share ONE product leaf
+        self.own_gauss = {}  # (block, node) of a Gaussian leaf -> dict(table, factors, sizes, cols, specs): _lower_own_gauss
         own_blocks = [bi for bi, names in enumerate(eblocks) if root_of_block[bi] is None and any(
             ocls.attr(n).kind == "choice" and not isinstance(ocls.attr(n).dist, MaybeSwap) for n in names)]
         self.flat = bool(own_blocks) and len(own_blocks) == len(eblocks)
@@ -1086,6 +1088,10 @@ class LoweredModel:
                    ctx_src_block=[], ctx_src_col=[])
         block_of = {n: k for k, ns in enumerate(self.engine_blocks) for n in ns}
         choices, observations = [], []
+        # Gaussian observations of the block that the query binds (an unbound one scores nothing) and the unit choices they name
+        gauss_obs = [ocls.attr(n) for n in names if ocls.attr(n).kind == "choice"
+                     and isinstance(ocls.attr(n).dist, (TransformedGaussian, AddNoise)) and n in self.numeric_obs]
+        gauss_units = list(dict.fromkeys(g.dist.unit for g in gauss_obs if isinstance(g.dist, TransformedGaussian)))
         for n in names:
             a = ocls.attr(n)
             if a.kind != "choice":
@@ -1094,7 +1100,9 @@ class LoweredModel:
             if isinstance(d, (AddTypos,) + TABULATED):
                 observations.append(a)
             elif isinstance(d, (TransformedGaussian, AddNoise)):
-                raise NotImplementedError(f"{who}: a Gaussian observation in a block without a reference slot is not lowered")
+                continue  # (a term of the block's Gaussian leaf: _lower_own_gauss)
+            elif n in gauss_units and isinstance(d, ChooseUniformly) and (cls, n) not in self.latent_dom:
+                choices.append(a)  # (a unit: a factor of the Gaussian leaf)
             elif isinstance(d, (StringPrior, TimePrior, NumberCodePrior)):
                 raise NotImplementedError(f"{who}: a {type(d).__name__} own choice is not lowered (its proposal holds a dummy value "
                                           "or none at all); own choices are ChooseProportionally or ChooseUniformly")
@@ -1121,6 +1129,9 @@ class LoweredModel:
             r = ocls.attr(ref)
             if r.kind == "julia":
                 raise NotImplementedError(f"{who}: {type(a.dist).__name__} of the JuliaNode {ref} of an own choice is not lowered")
+            if ref in gauss_units:
+                raise NotImplementedError(f"{who}: {type(a.dist).__name__} of the unit choice {ref} (its options are "
+                                          "Transformations, not strings) is not lowered")
             if ref not in by_choice:
                 if block_of.get(ref) != bi:
                     raise NotImplementedError(f"{who}: its choice {ref} is declared in another block; an observation is scored in "
@@ -1148,8 +1159,13 @@ class LoweredModel:
                 self._emit_term(blk, dict(obs=c.name, pair=self._eq_pair_for(key), max_typos=None, ctx=None,
                                           dens=_lib.DENS_EQUAL), cand_col)
 
+        factors, looks = self._own_gauss_factors(bi, ocls, names, choices, gauss_obs, gauss_units) if gauss_obs else ([], [])
         for c in choices:
             key = (cls, c.name)
+            if c.name in factors:
+                if c.name == factors[-1]:  # the Gaussian leaf stands at the place of the factor declared last
+                    self._lower_own_gauss(bi, blk, ocls, factors, gauss_obs, looks, emit_terms)
+                continue
             if key in self.product_index:
                 continue  # enumerated jointly with its dependent: value column 0 of that leaf
             tb = len(blk["terms"])
@@ -1176,6 +1192,133 @@ class LoweredModel:
             raise NotImplementedError(f"{cls}: a block without a reference slot and without an own choice "
                                       f"({', '.join(names)}) is not lowered")
         return blk
+
+    def _own_gauss_factors(self, bi, ocls, names, choices, gauss_obs, gauss_units):
+        """(factors, lookups) of the Gaussian observations of own block bi.  The factors are the choices of the block that
+        some Gaussian term reads — a mean index argument or the unit — in declaration order: at most one string choice
+        (ChooseProportionally with a plain ProportionsParameter, ChooseUniformly over strings) and at most one unit.
+        Everything else is refused by name."""
+        cls = self.query.cls
+
+        def get(n):
+            try:
+                return ocls.attr(n)
+            except (KeyError, TypeError):
+                return None
+        if len(gauss_obs) > _lib.MAX_GAUSS:
+            raise NotImplementedError(f"{cls}.{gauss_obs[_lib.MAX_GAUSS].name}: more than {_lib.MAX_GAUSS} Gaussian observations "
+                                      "in one block (PCLEAN_MAX_GAUSS)")
+        by_name = {c.name: c for c in choices}
+        looks, seen, strings = [], {}, []
+        for g in gauss_obs:
+            who = f"{cls}.{g.name}"
+            look = get(g.dist.mean)
+            if (look is None or look.kind != "julia" or not isinstance(look.fn, IndexedLookup)
+                    or not isinstance(getattr(get(look.fn.param), "prior", None), IndexedMeanParameter)):
+                raise NotImplementedError(f"{who}: the mean {g.dist.mean} of a Gaussian observation in an own block must be an "
+                                          "IndexedLookup of an IndexedMeanParameter")
+            if look.fn.param in seen:
+                raise NotImplementedError(f"{who}: only one Gaussian observation per block may read the mean parameter "
+                                          f"{look.fn.param} ({seen[look.fn.param]} already does)")
+            seen[look.fn.param] = g.name
+            looks.append(look)
+            for arg in look.args:
+                if "." in arg:
+                    raise NotImplementedError(f"{who}: the mean index {arg} lies behind a reference; in an own block a mean is "
+                                              "indexed by an own string choice of the same block")
+                r = get(arg)
+                if r is not None and r.kind == "julia":
+                    raise NotImplementedError(f"{who}: the mean index {arg} is a JuliaNode; in an own block a mean is indexed by "
+                                              "an own string choice of the same block")
+                if arg in gauss_units or arg not in by_name:
+                    what = ("a unit choice" if arg in gauss_units else
+                            "observed directly and not a choice" if (cls, arg) in self.direct_obs.values() else
+                            "declared in another block" if {n: k for k, ns in enumerate(self.engine_blocks) for n in ns}.get(arg, bi) != bi
+                            else "no enumerated own choice")
+                    raise NotImplementedError(f"{who}: the mean index {arg} is {what}; in an own block a mean is indexed by an own "
+                                              "string choice of the same block")
+                if arg not in strings:
+                    strings.append(arg)
+        if len(strings) > 1:
+            raise NotImplementedError(f"{cls}: the Gaussian observations of a block read two string factors "
+                                      f"({', '.join(strings)}); at most one string factor and one unit are enumerated jointly")
+        if len(gauss_units) > 1:
+            raise NotImplementedError(f"{cls}: the Gaussian observations of a block read more than two factors (the units "
+                                      f"{', '.join(gauss_units)}); at most one string factor and one unit are enumerated jointly")
+        for u in gauss_units:
+            ua = get(u)
+            if ua is None or u not in by_name or not isinstance(ua.dist, ChooseUniformly) or not all(
+                    isinstance(o, Transformation) for o in ua.dist.options):
+                raise NotImplementedError(f"{cls}.{u}: the unit of a Gaussian observation in an own block must be a ChooseUniformly "
+                                          "choice over Transformations declared in the same block")
+            if len(ua.dist.options) > 4:
+                raise NotImplementedError(f"{cls}.{u}: more than 4 units to choose from (pclean_gauss::t_scale[4])")
+            if u in self.direct_obs:
+                raise NotImplementedError(f"{cls}.{u}: a directly observed unit choice is not lowered")
+        for f in strings:
+            d = by_name[f].dist
+            if (isinstance(d, ChooseProportionally) and d.index is not None) or (cls, f) in self.product_index:
+                raise NotImplementedError(f"{cls}.{f}: a factor of a Gaussian observation that is itself indexed, or that indexes "
+                                          "a sibling choice, is not lowered (no product leaf inside a Gaussian leaf)")
+        factors = [c.name for c in choices if c.name in strings or c.name in gauss_units]
+        if not factors:
+            raise NotImplementedError(f"{cls}.{gauss_obs[0].name}: a Gaussian observation that reads no own choice of its block "
+                                      "(a constant mean and no unit) is not lowered")
+        k = int(np.prod([len(by_name[f].dist.options) for f in factors], dtype=np.int64))
+        if k > OWN_GAUSS_MAX_OPTIONS:
+            raise NotImplementedError(f"{cls}: the Gaussian leaf over {' x '.join(factors)} has {k} options, more than the "
+                                      f"{OWN_GAUSS_MAX_OPTIONS} it may hold (OWN_GAUSS_MAX_OPTIONS)")
+        # The cleaned column of a numeric observation is the query's JuliaNode on the observation (and its unit), e.g.
+        # round(unit.backward(rent)), as on the rents path.  A column whose clean side is the observation itself or the mean
+        # lookup would be reported as something else than the program says (the raw number; the mean parameter's value).
+        for g in gauss_obs:
+            col = next(c for c, d in self.query.obsmap.items() if d == g.name)
+            clean = get(self.query.cleanmap[col]) if "." not in self.query.cleanmap[col] else None
+            if clean is None or clean.kind != "julia" or isinstance(clean.fn, IndexedLookup) or g.name not in clean.args:
+                raise NotImplementedError(
+                    f"{cls}.{g.name}: a Gaussian observation in a block without a reference slot is lowered only when the query "
+                    f"reports its column ({col}) through a JuliaNode of the observation (and its unit), e.g. "
+                    f"round(unit.backward({g.name})); {self.query.cleanmap[col]} is none")
+        return factors, looks
+
+    def _lower_own_gauss(self, bi, blk, ocls, factors, gauss_obs, looks, emit_terms):
+        """The Gaussian leaf of own block bi: ONE NODE_LEAF over the factors' full grid a * |B| + b (key-major, as the product
+        leaf's; one factor: its options), on an option table of its own with one value column per factor.  Its terms: the
+        string terms of the factors in factor order (emit_terms: declaration order, the equality term of a direct observation
+        last), then — attached by the engine after pclean_load_own_block — the Gaussian terms in declaration order
+        (self.own_gauss[(block, node)]["specs"], also appended to self.gauss_specs: term g reads mean table g).  own_leaf maps
+        every factor to the leaf; two factors are a pair of own_product, so Trace.own keeps one row per choice and the joint
+        value is encoded as the product leaf's is."""
+        cls = self.query.cls
+        tb, nid = len(blk["terms"]), len(blk["nodes"])
+        sizes = [len(ocls.attr(f).dist.options) for f in factors]
+        for col, f in enumerate(factors):
+            if (cls, f) in self.latent_dom:
+                emit_terms(ocls.attr(f), col)
+        if len(blk["terms"]) - tb > _lib.MAX_TERMS:
+            raise NotImplementedError(f"{cls}.{factors[-1]}: the Gaussian leaf carries more than {_lib.MAX_TERMS} string terms "
+                                      "(PCLEAN_MAX_TERMS)")
+        tid = self._next_table
+        self._next_table += 1
+        if len(factors) == 2:
+            cols = np.stack([np.repeat(np.arange(sizes[0], dtype=np.int32), sizes[1]),
+                             np.tile(np.arange(sizes[1], dtype=np.int32), sizes[0])])
+            self.own_product[factors[1]] = factors[0]
+        else:
+            cols = np.arange(sizes[0], dtype=np.int32)[None, :]
+        specs = []
+        for g, look in zip(gauss_obs, looks):
+            spec, dims, transform = self._gaussian_term(len(self.gauss_specs), g, look, ocls, None, factors)
+            spec = dict(spec, kinds=[("local", d[1]) for d in dims], n_locals=len(factors), transform=transform, leaf=(bi, nid),
+                        term=len(specs))
+            self.gauss_specs.append(spec)
+            specs.append(spec)
+        self.gauss_spec = self.gauss_specs[0]
+        for f in factors:
+            self.own_leaf[f] = (bi, nid)
+        self.own_gauss[(bi, nid)] = dict(table=tid, factors=list(factors), sizes=sizes, cols=cols, specs=specs)
+        blk["nodes"].append((_lib.NODE_LEAF, tid, tb, len(blk["terms"]) - tb, 0, 0, -1, -1, 0, 0, 0, 0))
+        blk["node_info"].append(dict(kind="leaf", cls=cls, attr=factors[-1], path=factors[-1], gauss=tuple(factors)))
 
     def own_block_arrays(self, bi):
         """Arguments of pclean_load_own_block behind the block id: (nodes, terms)."""

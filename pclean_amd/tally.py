@@ -61,6 +61,9 @@ class ReconPlan:
             own = ocls.attr(ref)
             if own.kind == "julia" and any(sp["gauss_attr"] == q.obsmap[col] for sp in lw.gauss_specs):
                 if self.own:  # term g of the block sits on its root node (0), in declaration order
+                    if getattr(lw, "own_gauss", None):
+                        raise NotImplementedError(f"{col}: the numeric column of a flat class (a Gaussian observation in an own "
+                                                  "block) is not tallied on the device; CellTally(own=False) leaves it to the host")
                     g = next(g for g, sp in enumerate(lw.gauss_specs) if sp["gauss_attr"] == q.obsmap[col])
                     nums.append((col, dict(kind=_lib.RECON_NUM, block=lw.gauss_block, table=0, col=g), np.zeros(0, np.int32)))
                     self.device_numeric.append(col)

@@ -9,6 +9,8 @@ per observed row the current referent of each block's root reference slot.
 counts move, new latent rows are created recursively, rows whose count reaches
 zero are garbage-collected recursively, conjugate counts follow.
 """
+import math
+
 import numpy as np
 
 from .model import ChooseProportionally, ChooseUniformly, StringPrior
@@ -66,6 +68,16 @@ class MeanTableState:
         """Gibbs update given observations xs (already transformed back) of entries idx (74-82)."""
         n = np.bincount(idx, minlength=len(self.value)).astype(np.float64)
         sm = np.bincount(idx, weights=xs, minlength=len(self.value))
+        var0 = self.prior_std ** 2
+        var = 1.0 / (1.0 / var0 + n / self.sigma ** 2)
+        mean = var * (self.prior_mean / var0 + sm / self.sigma ** 2)
+        self.value = rng.normal(mean, np.sqrt(var))
+
+    def resample_from_stats(self, rng, n, sm):
+        """resample's arithmetic from the sufficient statistics themselves: n[i] observations of entry i whose backward
+        values sum to sm[i] (a flat class: fixed-point sums, pclean_own_gauss_stats or their NumPy restatement)."""
+        n = np.asarray(n, dtype=np.float64)
+        sm = np.asarray(sm, dtype=np.float64)
         var0 = self.prior_std ** 2
         var = 1.0 / (1.0 / var0 + n / self.sigma ** 2)
         mean = var * (self.prior_mean / var0 + sm / self.sigma ** 2)
@@ -264,7 +276,16 @@ class Trace:
         return out
 
     def _own_sizes(self, rows):
-        return [len(self.lw.latent_dom[(self.lw.query.cls, self.own_leaves()[li][0])]) for li in rows]
+        """number of options of the own choices behind rows of `own` (a unit choice has no string domain: its options)"""
+        cls, names = self.lw.query.cls, self.own_leaves()
+        return [len(self.lw.latent_dom[(cls, names[li][0])]) if (cls, names[li][0]) in self.lw.latent_dom
+                else len(self.lw.model.classes[cls].attr(names[li][0]).dist.options) for li in rows]
+
+    def _own_gauss_rows(self):
+        """rows of `own` whose choice is a factor of a Gaussian leaf (its parameter, if any, is a plain ProportionsParameter:
+        its counts are the row or column sums of the leaf's joint histogram)"""
+        names = [a for a, _, _ in self.own_leaves()]
+        return {names.index(f) for leaf in getattr(self.lw, "own_gauss", {}).values() for f in leaf["factors"]}
 
     def own_joint(self, own, la, lb):
         """rows la (index) and lb (choice) of `own` as the product leaf's joint option index * |B| + choice; -1 stays -1, a
@@ -294,17 +315,63 @@ class Trace:
         v = self.own_joint(self._own, la, lb)
         return np.bincount(v[v >= 0], minlength=ka * kb).astype(np.int64).reshape(ka, kb)
 
+    def own_gauss_exponent(self, g):
+        """e of Gaussian term g's fixed-point statistics (include/pclean_ownq.h): M = the largest finite |backward value| over
+        the term's units and the rows whose number is present, n = the number of rows; e = min(40, 62 - frexp exponent of M -
+        bit length of n), 40 for M == 0.  Fixed per term: the numeric columns do not move."""
+        cache = self.__dict__.setdefault("_own_gauss_e", {})
+        if g not in cache:
+            lw = self.lw
+            spec = lw.gauss_specs[g]
+            rows = np.flatnonzero(~np.isnan(lw.xnum[spec["x_col"]]))
+            big = 0.0
+            for u in range(len(spec["units"])):
+                bx = np.abs(lw.gauss_backward(rows, np.full(len(rows), u, np.int32), g))
+                bx = bx[np.isfinite(bx)]
+                big = max(big, float(bx.max(initial=0.0)))
+            n = lw.xnum.shape[1]
+            cache[g] = 40 if big == 0.0 else min(40, 62 - math.frexp(big)[1] - int(n).bit_length())
+        return cache[g]
+
+    def own_gauss_stats(self, g):
+        """(count int64 [n_mean], qsum int64 [n_mean], e) of Gaussian term g of a flat class over the rows that have a value and
+        whose number is present: qsum[idx] = sum of rint(bx * 2^e), bx the backward value under the row's current unit (a
+        non-finite one is skipped).  While the device is ahead: pclean_own_gauss_stats; else the same integers in NumPy."""
+        lw = self.lw
+        spec = lw.gauss_specs[g]
+        bi, nid = spec["leaf"]
+        dev = getattr(self, "_own_dev", None)
+        if dev is not None:
+            return dev.hip.own_gauss_stats(bi, nid, spec["term"], spec["n_mean"])
+        e = self.own_gauss_exponent(g)
+        names = [a for a, _, _ in self.own_leaves()]
+        fr = [self._own[names.index(f)] for f in lw.own_gauss[(bi, nid)]["factors"]]
+        rows = np.flatnonzero((fr[0] >= 0) & ~np.isnan(lw.xnum[spec["x_col"]]))
+        idx = np.zeros(len(rows), dtype=np.int64)
+        for d, st in zip(spec["dims"], spec["strides"]):
+            idx += st * fr[d[1]][rows]
+        unit = np.zeros(len(rows), dtype=np.int32) if spec["t_local"] is None else fr[spec["t_local"]][rows]
+        bx = lw.gauss_backward(rows, unit, g)
+        ok = np.isfinite(bx)
+        q = np.rint(bx[ok] * 2.0 ** e).astype(np.int64)
+        count = np.bincount(idx[ok], minlength=spec["n_mean"]).astype(np.int64)
+        qsum = np.zeros(spec["n_mean"], dtype=np.int64)
+        np.add.at(qsum, idx[ok], q)
+        return count, qsum, e
+
     def own_counts(self, li):
         """histogram of row li of `own` over the choice's options: from the device while it is ahead (pclean_own_counts:
         nothing per row crosses PCIe), else from the host array.  An indexed choice: [index][option], the joint histogram
         of its product leaf; its index: the row sums of that."""
         pairs = self.own_pairs()
+        if li in pairs and li in self._own_gauss_rows():  # (the second factor of a Gaussian leaf: the column sums)
+            return self.own_joint_counts(li).sum(axis=0)
         if li in pairs:
             return self.own_joint_counts(li)
         if li in pairs.values():
             return self.own_joint_counts(next(b for b, a in pairs.items() if a == li)).sum(axis=1)
         a, b, n = self.own_leaves()[li]
-        k = len(self.lw.latent_dom[(self.lw.query.cls, a)])
+        k = self._own_sizes((li,))[0]
         dev = getattr(self, "_own_dev", None)
         if dev is not None:
             return dev.hip.own_counts(b, n, k)
@@ -322,7 +389,10 @@ class Trace:
                 continue
             if lb not in joint:  # (one histogram serves both parameters)
                 joint[lb] = self.own_joint_counts(lb)
-            state.counts[:] = joint[lb] if li == lb else joint[lb].sum(axis=1)
+            if li == lb:  # (an indexed choice: [index][option]; the second factor of a Gaussian leaf: the column sums)
+                state.counts[:] = joint[lb] if state.counts.ndim == 2 else joint[lb].sum(axis=0)
+            else:
+                state.counts[:] = joint[lb].sum(axis=1)
 
     def __init__(self, lowered, n_rows, seed=0):
         self._dev = None       # the Engine whose device state is ahead of the host arrays (None: the host is current)
@@ -701,10 +771,11 @@ class Trace:
             own = self.own
             assert np.all((own >= 0).all(axis=0) | (own < 0).all(axis=0)), "own choices: a row holds some but not all"
             for li, (a, _, _) in enumerate(self.own_leaves()):
-                assert own[li].max(initial=-1) < len(lw.latent_dom[(lw.query.cls, a)]), f"{a}: a value beyond the options"
+                assert own[li].max(initial=-1) < self._own_sizes((li,))[0], f"{a}: a value beyond the options"
             pairs = self.own_pairs()
             for li, state in self._own_params():
-                v = self.own_joint(own, pairs[li], li) if li in pairs else own[li]  # (an indexed choice: [index][option])
+                # (an indexed choice: [index][option]; a factor of a Gaussian leaf has a plain parameter: its own histogram)
+                v = self.own_joint(own, pairs[li], li) if li in pairs and state.counts.ndim == 2 else own[li]
                 assert np.array_equal(np.bincount(v[v >= 0], minlength=state.counts.size).reshape(state.counts.shape),
                                       state.counts), \
                     f"{lw.query.cls}.{self.own_leaves()[li][0]}: Dirichlet counts out of sync"
@@ -813,6 +884,13 @@ class Trace:
         if self.prob_param is not None and (cname is None or self.lw.prob_spec["param"][0] == cname):
             self.resample_prob_param()
         if self.mean_param is not None and (cname is None or self.lw.gauss_spec["param"][0] == cname):
+            if getattr(self.lw, "own_gauss", None):
+                # a flat class: count and fixed-point sum per mean index — from the device while it is ahead (nothing per row
+                # crosses PCIe), else the NumPy restatement of the same integers: the same bits either way
+                for g, mp in enumerate(self.mean_params):
+                    n, q, e = self.own_gauss_stats(g)
+                    mp.resample_from_stats(self.rng, n, q.astype(np.float64) / 2.0 ** e)
+                return
             for g, mp in enumerate(self.mean_params):  # each parameter's conjugate draw from its own term's rows
                 _, idx, x = self.gaussian_index(g)
                 mp.resample(self.rng, idx, x)

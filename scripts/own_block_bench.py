@@ -24,7 +24,16 @@ without its exact skip: what the skip buys) in turns, on one generated data set;
 the verdict (the product kernel's median below the baseline's fastest run) go into --out (default
 profiles/own_product_bench.json).
 
-usage: own_block_bench.py [--rows N] [--runs R] [--particles P] [--marginals [--out FILE]] [--product [--alternate N] [--out FILE]]"""
+--gauss: a Gaussian leaf (own_gauss_kernel): synthetic rows `room ~ ChooseProportionally; room_obs ~ AddTypos(room);
+unit ~ ChooseUniformly; rent ~ TransformedGaussian(avg[room], 150, unit)` in two shapes, 5 rooms x 2 units and 1000 x 4.  Per
+shape and process: device ms of pclean_sweep_own (HIP events, 2 warm-ups and --runs runs) and of pclean_own_gauss_stats, a
+byte and fp64-operation model, and the yardstick — the parent cannot run this program at all, so it is the SAME build's
+string-only sweep of the same rows and string factor with the Gaussian terms left off (`room`, `room_obs` alone: the
+nearest thing the parent computes); the ratio is stated, not asserted.  --processes N (default 3) fresh processes; the
+lines go into --out (default profiles/own_gauss_bench.json).
+
+usage: own_block_bench.py [--rows N] [--runs R] [--particles P] [--marginals [--out FILE]] [--product [--alternate N] [--out FILE]]
+                          [--gauss [--processes N] [--out FILE]]"""
 import json
 import os
 import sys
@@ -222,6 +231,132 @@ def product_main():
                                           "product_without_skip_median_ms", "same_values")}))
 
 
+GAUSS_SHAPES = ((5, 2), (1000, 4))
+
+
+def gauss_data(n, na, nb, seed=0):
+    """n synthetic rows: a room (Zipf-like frequencies), its name with a typo in a fifth of the rows and missing in 2 %, a rent
+    around the room's mean stated in a unit other than the first in a tenth of the rows and missing in 5 %"""
+    rng = np.random.default_rng(seed)
+    letters = np.array(list("abcdefghijklmnopqrstuvwxyz"))
+    rooms = list(dict.fromkeys("".join(rng.choice(letters, 8)) for _ in range(2 * na)))[:na]
+    p = 1.0 / np.arange(1, na + 1)
+    a = rng.choice(na, size=n, p=p / p.sum())
+    b = np.where(rng.random(n) < 0.1, rng.integers(1, max(nb, 2), n), 0) if nb > 1 else np.zeros(n, np.int64)
+    scale = np.array([1.0, 1000.0, 12.0, 7.0])[:nb]
+    rent = rng.normal(1500.0 + 1500.0 * (a % 50), 150.0) / scale[b]
+    typo, miss = rng.random(n) < 0.2, rng.random(n) < 0.02
+    pos, ch = rng.integers(0, 2, n), rng.choice(letters[:4], n)  # (few distinct typos: a pair table takes 65 535 observed strings)
+    obs = [None if miss[i] else (rooms[a[i]][:pos[i]] + ch[i] + rooms[a[i]][pos[i] + 1:] if typo[i] else rooms[a[i]]) for i in range(n)]
+    xmiss = rng.random(n) < 0.05
+    return rooms, {"Room": obs, "Rent": [None if xmiss[i] else float(rent[i]) for i in range(n)]}
+
+
+def gauss_models(rooms, nb):
+    from pclean_amd.model import ChooseUniformly, IndexedLookup, IndexedMeanParameter, Transformation, TransformedGaussian
+    sc = [1.0, 1000.0, 12.0, 7.0][:nb]
+    units = [Transformation(lambda x, c=c: x / c, lambda x, c=c: x * c, lambda x, c=c: 1.0 / c) for c in sc]
+    out = []
+    for with_gauss in (True, False):
+        m = Model()
+        o = m.add_class("Obs")
+        o.param("room_p", ProportionsParameter(1.0))
+        o.param("avg", IndexedMeanParameter(1500.0, 100000.0))
+        with o.block():
+            o.choice("room", ChooseProportionally(rooms, "room_p"))
+            o.choice("room_obs", AddTypos("room"))
+            if with_gauss:
+                o.choice("unit", ChooseUniformly(units))
+                o.julia("base", IndexedLookup("avg"), ["room"])
+                o.choice("rent", TransformedGaussian("base", 150.0, "unit"))
+                o.julia("corrected", lambda unit, rent: round(unit.backward(rent)), ["unit", "rent"])
+        bind = {"Room": ("room", "room_obs")}
+        if with_gauss:
+            bind["Rent"] = ("corrected", "rent")
+        out.append((m, Query(m, "Obs", bind)))
+    return out
+
+
+def gauss_models_bytes(n, na, nb, n_groups, n_present):
+    """bytes and fp64 operations of one sweep of the Gaussian leaf.  Bytes: per workgroup the grid's priors and value columns
+    (8 + 8 per option) and the string term's pair bytes and lengths per room (3); per row what byte_model counts plus the
+    number (8).  Operations per row and option: the prior and the string term (1 add), the Gaussian term where the number is
+    present (mul, sub, div, 2 mul, 3 sub: 8), one subtraction and one exp (about 30) for the weight, the maximum; a draw
+    evaluates one step of at most 64 options again."""
+    K = na * nb
+    bytes_ = n_groups * (K * 16 + na * 3 + 16) + n * (4 + 8 + 8 + 16 + 8 + 4 + 4 + 8)
+    ops = n * K * (1 + 1 + 31) + n_present * K * 8 + n * min(K, 64) * 31
+    return int(bytes_), int(ops)
+
+
+def gauss_run(n, runs, P):
+    """one process: both shapes, the Gaussian leaf and the string-only yardstick"""
+    out = []
+    for na, nb in GAUSS_SHAPES:
+        rooms, dirty = gauss_data(n, na, nb)
+        line = dict(rows=n, grid=[na, nb], options=na * nb, particles=P, warmups=2, runs=runs)
+        for name, (m, q) in zip(("gauss", "string_only"), gauss_models(rooms, nb)):
+            d = {c: dirty[c] for c in q.obsmap}
+            lw = LoweredModel(m, q, d)
+            eng = Engine(lw, lw.encode_observations(d))
+            try:
+                tr = Trace(lw, n, 0)
+                cfg = InferenceConfig(1, P)
+                initialize_trace(eng, tr, cfg, 0)
+                hip, c = eng.hip, cfg.as_c()
+                eng.upload_trace(tr)
+                hip.set_active_rows(0, n)
+                dev = []
+                for r in range(runs + 2):
+                    hip.sweep_own(c, 1, r, n, want_outputs=False)
+                    dev.append(float(hip.get_timing().total_ms))
+                st = hip.get_own_stats()
+                line[name] = dict(variants=int(st.variants), distinct_tuples=int(st.n_runs), longest_run=int(st.longest_run),
+                                  workgroups=int(st.n_workgroups), sweep_own_device_ms=_summary(dev[2:]))
+                if name == "gauss":
+                    sd = []
+                    for r in range(runs + 2):
+                        hip.own_gauss_stats(0, 0, 0, na)
+                        sd.append(float(hip.get_timing().total_ms))
+                    n_present = sum(v is not None for v in dirty["Rent"])
+                    mb, ops = gauss_models_bytes(n, na, nb, st.n_workgroups, n_present)
+                    med = line[name]["sweep_own_device_ms"]["median"]
+                    line[name].update(own_gauss_stats_device_ms=_summary(sd[2:]), model_bytes=mb, model_fp64_ops=ops,
+                                      model_gb_per_s=round(mb / (1e6 * med), 1), model_gflop_per_s=round(ops / (1e6 * med), 1))
+            finally:
+                eng.close()
+        line["gauss_over_string_only"] = round(line["gauss"]["sweep_own_device_ms"]["median"] /
+                                               line["string_only"]["sweep_own_device_ms"]["median"], 3)
+        out.append(line)
+    return out
+
+
+def gauss_main():
+    import subprocess
+    a = sys.argv[1:]
+    n, runs, P = _arg("--rows", 1_000_000), _arg("--runs", 7), _arg("--particles", 20)
+    if "--child" in a:
+        print(json.dumps(gauss_run(n, runs, P)))
+        return
+    procs = []
+    for k in range(_arg("--processes", 3)):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gauss", "--child", "--rows", str(n), "--runs", str(runs),
+                            "--particles", str(P)], stdout=subprocess.PIPE, text=True, timeout=1100, check=True)
+        procs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        for line in procs[-1]:
+            print(f"[process {k}] {line['grid']}: gauss {line['gauss']['sweep_own_device_ms']['median']} ms, string only "
+                  f"{line['string_only']['sweep_own_device_ms']['median']} ms, stats "
+                  f"{line['gauss']['own_gauss_stats_device_ms']['median']} ms", flush=True)
+    out = dict(profiled=False, note="device ms by HIP events; the yardstick is the same build's string-only sweep of the same "
+               "rows and string factor (the parent cannot run the Gaussian program); the ratio is stated, not asserted",
+               processes=procs)
+    dst = a[a.index("--out") + 1] if "--out" in a else os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "own_gauss_bench.json")
+    with open(dst, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     n, runs, P = _arg("--rows", 1_000_000), _arg("--runs", 7), _arg("--particles", 20)
     t0 = time.time()
@@ -285,4 +420,7 @@ def main():
 
 
 if __name__ == "__main__":
-    product_main() if "--product" in sys.argv[1:] else main()
+    if "--gauss" in sys.argv[1:]:
+        gauss_main()
+    else:
+        product_main() if "--product" in sys.argv[1:] else main()

@@ -11,7 +11,12 @@ accuracy and F1 of its most probable value next to the last sample's, and with t
 the accuracy of the two models side by side — of the last sample and, with the joint MAP repair (Engine.own_marginals:
 for the pair these are JOINT probabilities), per column.
 
-usage: run_flat.py [particles] [pg|mh] [iterations] [rows] [--map] [--dependent]"""
+--numeric: another table — Room Type and Monthly Rent of datasets/rents_*.csv as ONE own block with a Gaussian observation
+(experiments.flat_numeric_model: the rent's mean depends on the room type, some rents are stated in thousands): no latent
+class.  Prints the accuracy and F1 of the last sample and of the MAP repair (the numeric cell under the MAP unit); the
+figures are reported, not asserted.
+
+usage: run_flat.py [particles] [pg|mh] [iterations] [rows] [--map] [--dependent] [--numeric]"""
 import os
 import sys
 import time
@@ -74,6 +79,50 @@ def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, wit
         eng.close()
 
 
+def numeric(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True):
+    dirty, clean = ex.rents_data()
+    cols = ex.FLAT_NUMERIC_COLUMNS
+    n = len(dirty[cols[0]]) if n_rows is None else int(n_rows)
+    dirty = {c: dirty[c][:n] for c in cols}
+    clean = {c: clean[c][:n] for c in cols}
+    rooms = list(dict.fromkeys(v for v in clean["Room Type"] if v is not None))
+    m = ex.flat_numeric_model(rooms)
+    lw = LoweredModel(m, ex.flat_numeric_query(m), dirty)
+    eng = Engine(lw, lw.encode_observations(dirty))
+    try:
+        tr = Trace(lw, n, seed)
+        cfg = InferenceConfig(iters, particles, use_mh_instead_of_pg=mh)
+        t0 = time.time()
+        initialize_trace(eng, tr, cfg, seed)
+        t1 = time.time()
+        run_inference(eng, tr, cfg, seed)
+        t2 = time.time()
+        tr.check_consistency()
+
+        def numbers(table):  # (the clean file holds the rents as integers in text, the cleaned table as numbers)
+            same = lambda a, b: (a is None and b is None) or (a is not None and b is not None and float(a) == float(b))  # noqa: E731
+            return {"Room Type": sum(a == b for a, b in zip(table["Room Type"], clean["Room Type"])) / float(n),
+                    "Monthly Rent": sum(same(a, b) for a, b in zip(table["Monthly Rent"], clean["Monthly Rent"])) / float(n)}
+        acc = evaluate_accuracy(lw, tr, dirty, clean)
+        acc["by_column"] = numbers(reconstructed_table(lw, tr, dirty))
+        marg = eng.own_marginals(tr, top=1)
+        table, conf = map_table(lw, marg, dirty)
+        acc["map"] = evaluate_map_accuracy(lw, marg, dirty, clean)
+        acc["map"]["by_column"] = numbers(table)
+        acc["mean_rent"] = dict(zip(rooms, (float(v) for v in tr.mean_params[0].value)))
+        if verbose:
+            st = eng.hip.get_own_stats()
+            print(f"{n} rows, {iters} iterations, {particles} particles ({'MH' if mh else 'PG'}): init {t1 - t0:.2f}s, "
+                  f"inference {t2 - t1:.2f}s; kernel variants of the last call {st.variants}")
+            print(f"dirty: {numbers(dirty)}")
+            print(f"last sample: F1 {acc['f1']:.4f}  {acc['by_column']}")
+            print(f"MAP:         F1 {acc['map']['f1']:.4f}  {acc['map']['by_column']}")
+            print(f"mean rent per room type: {acc['mean_rent']}")
+        return acc
+    finally:
+        eng.close()
+
+
 def compare(**kw):
     """the independent model and the one with State indexed by City, side by side"""
     out = {}
@@ -89,10 +138,12 @@ def compare(**kw):
 
 
 if __name__ == "__main__":
-    a = [x for x in sys.argv[1:] if x not in ("--map", "--dependent")]
+    a = [x for x in sys.argv[1:] if x not in ("--map", "--dependent", "--numeric")]
     kw = dict(particles=int(a[0]) if a else 20, mh=(a[1] == "mh") if len(a) > 1 else False, iters=int(a[2]) if len(a) > 2 else 5,
               n_rows=int(a[3]) if len(a) > 3 else None)
-    if "--dependent" in sys.argv[1:]:
+    if "--numeric" in sys.argv[1:]:
+        numeric(**kw)
+    elif "--dependent" in sys.argv[1:]:
         compare(**kw)
     else:
         main(with_map="--map" in sys.argv[1:], **kw)
