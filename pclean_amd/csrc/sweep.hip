@@ -10,6 +10,8 @@
 //       (row, block, context) serves all particles and only the draws are per particle.
 //   process_plan!      proposal_compiler.jl:363-388 (children of a new row enumerated
 //       independently; log-marginals added)
+#include <optional>
+
 #include "sweep_internal.h"
 #include "tail_tiles.h"
 
@@ -1817,765 +1819,761 @@ static void zero_list_add(pclean_ctx* ctx, ZeroList& zl, void* p, size_t bytes) 
   ++zl.n;
 }
 
-extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uint64_t seed, uint32_t sweep_idx,
-                            int32_t n_blocks, const int32_t* cur, int32_t* choice, int32_t* chosen_particle,
-                            double* logml) {
-  if (!ctx || !cfg || n_blocks <= 0 || n_blocks > PCLEAN_MAX_BLOCKS)
-    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_sweep: bad arguments");
+// ---- pclean_sweep: a driver over phases (which phase enqueues what) ---------------------------------------
+// the switches of pclean_sweep, read once per process (a function-local static const there)
+static bool env_on(const char* name) { return getenv(name) != nullptr; }
+struct SweepSwitches {
+  const bool no_prefetch = env_on("PCLEAN_NO_COMPACT_PREFETCH");      // no refresh of the later blocks' root tables on a side stream
+  const bool late_prefetch = env_on("PCLEAN_LATE_COMPACT_PREFETCH");  // ... queued once block 0's kernels are, not at the first wait
+  const bool no_pu_stage = env_on("PCLEAN_NO_PU_STAGE");  // particle_update_kernel reads row-major draws directly, not through LDS
+  const bool no_w_uni = env_on("PCLEAN_NO_UNIFORM_W");    // the first block stores its particles' equal weights (SweepCall::w_uni)
+  const bool eager_all = env_on("PCLEAN_EAGER_NEW");      // every NEW slot of the last block is sampled before the final choice
+  const bool no_partial = env_on("PCLEAN_NO_PARTIAL_EAGER");       // ... wherever a dummy can be drawn, not only on the rows that can
+  const bool no_fuse_final = env_on("PCLEAN_NO_FUSED_FINAL");      // the last block's update and the final choice stay separate kernels
+  const bool no_fused_items = env_on("PCLEAN_NO_FUSED_CTX_ITEMS");  // context items numbered row by row in four launches
+  const bool always_resample = env_on("PCLEAN_ALWAYS_RESAMPLE");    // the resampling kernels run behind equal weights too
+  const bool no_fused_finalize = env_on("PCLEAN_NO_FUSED_FINALIZE");  // =1: chosen_new_kernel + one finalize_block_kernel per block
+  // PCLEAN_TAIL_WGS=<n>: workgroups per block of finalize_tail_kernel (the launch that replaces those)
+  const int forced_tail_wgs = getenv("PCLEAN_TAIL_WGS") ? std::max(1, atoi(getenv("PCLEAN_TAIL_WGS"))) : 0;
+  const bool trace_tail = env_on("PCLEAN_TRACE_SYNC");  // the "[pclean tail] ..." lines
+  const bool no_hist = env_on("PCLEAN_NO_HIST");        // (measurement switch: plain atomics for every table)
+};
+// one call of pclean_sweep: what its phases share; built once the call has begun, destroyed on every exit from then on
+struct SweepCall {
+  pclean_ctx* ctx;
+  SweepState* s;
+  const pclean_infer_config* cfg;
+  const SweepSwitches& sw;
+  int N, P, n_blocks;
+  size_t NP;
+  uint64_t seed;
+  uint32_t sweep_idx;
+  int use_mh;
+  bool prior_mode;
+  // cur_base + bi * cur_ld = current referents of block bi over the active window
+  const int32_t* cur_base = nullptr;
+  size_t cur_ld = 0;
+  int pu_stage_stride = 0;  // particle_update_kernel's LDS staging of row-major draws (sweep_begin); 0: none
+  size_t pu_stage_bytes = 0;
+  // particle weights start at +0.0: the first block's particle_update_kernel stores instead of accumulating (a sweep that
+  // begins with a scoring block accumulates onto zeros)
+  bool w_by_first_block = false;
+  // The first block's log marginal is shared by the particles of a row (no context yet to tell them apart): its launch of
+  // particle_update_kernel stores no weights (w_uni = that block's lse; 160 MB written and read back per 1M rows x 20
+  // particles otherwise) and the next block's update starts from it.  Whoever touches individual weights in between (dummy
+  // corrections, a resampling step, a scoring block, the separate final choice) gets them materialised first.
+  const double* w_uni = nullptr;
+  bool final_fused = false;                  // the last block's particle update made the final choice as well
+  const int32_t* final_only_rows = nullptr;  // ... for the rows outside this flag array (the final choice kernel takes the flagged ones)
+  bool hot_timed = false, prefetching = false, prefetch_started = false;
+  const int32_t* cur_of(int bi) const { return cur_base + (size_t)bi * cur_ld; }
+  // No exit of the call leaves the context in prior mode, or the first-wait hook behind (it refers to this record); and an
+  // error exit between the fork and the join still joins the side stream: its work must not overlap the next call
+  ~SweepCall() {
+    s->on_first_wait = nullptr;
+    if (prefetching) (void)hipStreamWaitEvent(ctx->stream, s->pre_join, 0);
+    ctx->prior_mode = false;
+  }
+};
+static void materialise_w(SweepCall& c) {
+  if (!c.w_uni) return;
+  hipLaunchKernelGGL(materialise_w_kernel, grid1(c.N), dim3(256), 0, c.ctx->stream, c.N, c.P, c.w_uni, c.s->w.p);
+  c.w_uni = nullptr;
+}
+// the later blocks' root tables refresh on a side stream while block 0 runs (eval.hip: prefetch_fast_root): enqueued at the
+// call's first wait, or once block 0's kernels are (propose_block), so that the host time of those launches is not block 0's
+static int start_prefetch(SweepCall& c) {
+  c.prefetch_started = true;
+  if (c.sw.no_prefetch || c.prior_mode || c.ctx->force_generic || c.n_blocks <= 1) return PCLEAN_OK;
+  HIPCHK(c.ctx, hipStreamWaitEvent(c.s->pre_stream, c.s->pre_fork, 0));  // (recorded at the START of the sweep: nothing of block 0)
+  for (int bi = 1; bi < c.n_blocks; ++bi) {
+    const Block& pb = c.ctx->block[bi];
+    if (pb.is_score || pb.nodes.empty() || (!pb.node_gauss.empty() && pb.node_gauss[0] >= 0)) continue;
+    if (const int rcp = prefetch_fast_root(c.ctx, bi, 0, c.s->pre_stream)) return rcp;
+  }
+  HIPCHK(c.ctx, hipEventRecord(c.s->pre_join, c.s->pre_stream));
+  c.prefetching = true;
+  return PCLEAN_OK;
+}
+
+// lazy events / side stream / host buffer, allocations, upload of the current referents, zeroing, prefetch fork, LDS attribute
+static int sweep_begin(SweepCall& c, const int32_t* cur, bool dev_cur) {
+  const int N = c.N, n_blocks = c.n_blocks;
+  if (!c.s->ev0)
+    for (hipEvent_t* e : {&c.s->ev0, &c.s->ev1, &c.s->evs, &c.s->eve, &c.s->evg0, &c.s->evg1}) HIPCHK(c.ctx, hipEventCreate(e));
+  c.s->gate_timed = false;
+  if (!c.s->h_counts) HIPCHK(c.ctx, hipHostMalloc((void**)&c.s->h_counts, 4 * PCLEAN_MAX_BLOCKS * sizeof(int32_t), hipHostMallocDefault));
+  if (c.s->cur.alloc((size_t)N * n_blocks) || c.s->chosen.alloc(N) || c.s->ancestors.alloc(c.NP) || c.s->w.alloc(c.NP) || c.s->log_total.alloc(N) ||
+      c.s->logml_inc.alloc(N) || c.s->logml_acc.alloc(N) || c.s->logml.alloc(N) || c.s->counter.alloc(4) || c.s->arr_ptrs.alloc(2 * PCLEAN_MAX_BLOCKS) ||
+      c.s->did.alloc(N) || c.s->tail_counts.alloc(2 * PCLEAN_MAX_BLOCKS))
+    return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  c.cur_base = dev_cur ? c.ctx->dev_cur.p + c.ctx->active_begin : c.s->cur.p;
+  c.cur_ld = dev_cur ? (size_t)c.ctx->n_rows : (size_t)N;
+  if (!dev_cur && c.ctx->cur_stride > 0 && c.ctx->cur_stride != N) {
+    if (c.ctx->cur_stride < N) return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "pclean_sweep: cur stride smaller than the active window");
+    for (int b = 0; b < n_blocks; ++b)
+      HIPCHK(c.ctx, hipMemcpyAsync(c.s->cur.p + (size_t)b * N, cur + (size_t)b * c.ctx->cur_stride, (size_t)N * 4, hipMemcpyHostToDevice,
+                                   c.ctx->stream));
+  } else if (!dev_cur) {
+    HIPCHK(c.ctx, hipMemcpyAsync(c.s->cur.p, cur, (size_t)N * n_blocks * 4, hipMemcpyHostToDevice, c.ctx->stream));
+  }
+  c.s->last_cur_base = c.cur_base;
+  c.s->last_cur_ld = c.cur_ld;
+  c.s->last_N = N;
+  c.s->last_blocks = n_blocks;
+  c.s->last_dev_cur = dev_cur;
+  (void)hipEventRecord(c.s->evs, c.ctx->stream);
+  c.w_by_first_block = !c.ctx->block[0].is_score;
+  if (!c.w_by_first_block) { const int rcz = dev_zero(c.ctx, c.s->w.p, c.NP * sizeof(double)); if (rcz) return rcz; }
+  { const int rcz = dev_zero(c.ctx, c.s->logml_acc.p, (size_t)N * sizeof(double)); if (rcz) return rcz; }
+  c.ctx->timing = pclean_timing{};
+  if (!c.s->pre_stream) {
+    HIPCHK(c.ctx, hipStreamCreateWithFlags(&c.s->pre_stream, hipStreamNonBlocking));
+    HIPCHK(c.ctx, hipEventCreateWithFlags(&c.s->pre_fork, hipEventDisableTiming));
+    HIPCHK(c.ctx, hipEventCreateWithFlags(&c.s->pre_join, hipEventDisableTiming));
+  }
+  HIPCHK(c.ctx, hipEventRecord(c.s->pre_fork, c.ctx->stream));
+  if (!c.sw.late_prefetch) c.s->on_first_wait = [&c]() -> int { return c.prefetch_started ? PCLEAN_OK : start_prefetch(c); };
+  // particle_update_kernel stages the root kernels' row-major draws through LDS (rows of P words, an odd stride apart):
+  // (P | 1) x PU_T words: 84 KB at 20 particles; beyond PU_STAGE_MAX_BYTES of LDS (P >= 37: 64 particles would ask for 266 KB
+  // of the CU's 160) the kernel reads the draws directly, as it did before the staging existed
+  constexpr size_t PU_STAGE_MAX_BYTES = 150 * 1024;
+  c.pu_stage_stride = c.sw.no_pu_stage ? 0 : (c.P | 1);
+  if ((size_t)c.pu_stage_stride * PU_T * sizeof(int32_t) > PU_STAGE_MAX_BYTES) c.pu_stage_stride = 0;
+  c.pu_stage_bytes = (size_t)c.pu_stage_stride * PU_T * sizeof(int32_t);
+  static bool attr_set = false;
+  if (c.pu_stage_bytes > 48 * 1024 && !attr_set) {
+    HIPCHK(c.ctx, hipFuncSetAttribute((const void*)particle_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PU_STAGE_MAX_BYTES));
+    attr_set = true;
+  }
+  return PCLEAN_OK;
+}
+// pure scoring block: every particle's weight += sum of its observed choices' log-densities
+static int run_score_block(SweepCall& c, int bi) {
+  Block& b = c.ctx->block[bi];
+  if (bi != c.n_blocks - 1) return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "a scoring block must be the last block");
+  ProfScope ps(c.ctx, "score_block");
+  ScoreBlockDev sb{};
+  auto make_src = [&](int blk, int col, SrcDev& out) -> int {
+    if (blk < 0 || blk >= bi || c.ctx->block[blk].is_score) return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "score block: bad source block");
+    const CandTable& rt = c.ctx->cand[c.ctx->block[blk].nodes[0].table];
+    if (col < 0 || col >= rt.n_cols) return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "score block: bad source column");
+    out = SrcDev{c.s->run[blk].pchoice.p, c.s->run[blk].pnewpos.p, c.s->run[blk].vals.p, rt.cols.p + (size_t)col * rt.n_rows,
+                 (int)c.ctx->block[blk].nodes.size(), col, c.s->run[blk].plan};
+    return 0;
+  };
+  const FnTable& pf = c.ctx->fn[b.prob_fn];
+  if (!pf.valid || c.ctx->n_prob == 0) return pclean_fail(c.ctx, PCLEAN_ERR_STATE, "score block: prob fn / prob table not set");
+  sb.n_terms = (int)b.score_terms.size();
+  sb.prob_nb = pf.n_b;
+  sb.prob_fn = pf.fn.p;
+  sb.prob_same = c.ctx->prob_same.p;
+  sb.prob_diff = c.ctx->prob_diff.p;
+  sb.logn = c.ctx->logn.p;
+  int rc2 = make_src(b.prob_a_block, b.prob_a_col, sb.pa);
+  if (!rc2) rc2 = make_src(b.prob_b_block, b.prob_b_col, sb.pb);
+  for (int k = 0; k < sb.n_terms && !rc2; ++k) {
+    const ScoreTerm& st_ = b.score_terms[k];
+    const PairTable& pt = c.ctx->pair[st_.pair_table];
+    const FnTable& nf = c.ctx->fn[st_.nopt_fn];
+    if (!pt.valid || !nf.valid || st_.obs_col < 0 || st_.obs_col >= c.ctx->n_cols)
+      return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "score block: term %d malformed", k);
+    sb.t[k].obs_col = c.ctx->obs.p + (size_t)st_.obs_col * c.ctx->n_rows + c.ctx->active_begin;
+    sb.t[k].pair = pt.d.p;
+    sb.t[k].n_lat = pt.n_lat;
+    sb.t[k].nopt_fn = nf.fn.p;
+    sb.t[k].other_val = st_.other_val;
+    rc2 = make_src(st_.val_block, st_.val_col, sb.t[k].val);
+    if (!rc2) rc2 = make_src(st_.key_block, st_.key_col, sb.t[k].key);
+  }
+  if (rc2) return rc2;
+  materialise_w(c);
+  hipLaunchKernelGGL(score_block_kernel, grid1(c.NP), dim3(256), 0, c.ctx->stream, c.N, c.P, sb, c.s->w.p);
+  return PCLEAN_OK;
+}
+
+// what the phases of one proposing block hand on
+struct BlockStep {
+  bool drawable = false;               // a new row of the block can draw a ProposalDummyValue ...
+  const int32_t* emit_rows = nullptr;  // ... on the rows flagged here only (dummy_rows_flags; null: anywhere)
+  // last block, nothing between its particle update and the final choice: one fused kernel (particle_update_final_kernel); when
+  // only a few rows can draw a dummy (emit_rows), those rows take the separate kernels and all the others the fused one (split)
+  bool fuse_final = false, split_final = false;
+  unsigned int* n_new_ctr = nullptr;  // particles of the block that proposed a NEW referent (fresh_counter)
+};
+// a block's draws and log marginals: row-major ([N][P], [N]: no context, an item per row) or per context item (slot_item[P][N])
+struct DrawSrc {
+  const int32_t* draws_rm;
+  const double* lse_rm;
+  const int32_t* slot_item;
+  const int32_t* draws_item;
+  const double* lse_item;
+};
+// the particles' sources of block bi's context values: one per context slot, each an earlier block
+static int build_ctx_src(SweepCall& c, int bi, CtxSrc& cs) {
+  const Block& b = c.ctx->block[bi];
+  cs = CtxSrc{};
+  cs.n_ctx = b.n_ctx;
+  for (int k = 0; k < b.n_ctx; ++k) {
+    const int sb = b.ctx_src_block[k];
+    if (sb < 0 || sb >= bi) return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "block %d: ctx source must be an earlier block", bi);
+    const Block& src = c.ctx->block[sb];
+    const CandTable& rt = c.ctx->cand[src.nodes[0].table];
+    if (b.ctx_src_col[k] < 0 || b.ctx_src_col[k] >= rt.n_cols) return pclean_fail(c.ctx, PCLEAN_ERR_ARG, "ctx column out of range");
+    cs.pchoice[k] = c.s->run[sb].pchoice.p;
+    cs.pnewpos[k] = c.s->run[sb].pnewpos.p;
+    cs.vals[k] = c.s->run[sb].vals.p;
+    cs.n_nodes[k] = (int)src.nodes.size();
+    cs.root_col[k] = rt.cols.p + (size_t)b.ctx_src_col[k] * rt.n_rows;
+    cs.col[k] = b.ctx_src_col[k];
+    cs.plan[k] = c.s->run[sb].plan;
+  }
+  return PCLEAN_OK;
+}
+// the one launch of particle_update_kernel: LDS staging for row-major draws only
+static int launch_particle_update(SweepCall& c, int bi, const DrawSrc& d, const int32_t* emit_rows, bool split, bool skip_w,
+                                  unsigned int* n_new_ctr) {
+  BlockRun& r = c.s->run[bi];
+  const bool rm = d.draws_rm != nullptr;
+  hipLaunchKernelGGL(particle_update_kernel, dim3((c.N + PU_T - 1) / PU_T), dim3(PU_T), rm ? c.pu_stage_bytes : 0, c.ctx->stream,
+                     c.N, c.P, d.draws_rm, d.lse_rm, d.slot_item, d.draws_item, d.lse_item, c.cur_of(bi), r.pchoice.p, c.s->w.p,
+                     n_new_ctr, r.new_slots.p, r.pnewpos.p, (c.w_by_first_block && bi == 0) ? 1 : 0, emit_rows, split ? 1 : 0,
+                     rm ? c.pu_stage_stride : 0, c.w_uni, skip_w ? 1 : 0);
+  HIPCHK(c.ctx, hipGetLastError());
+  return PCLEAN_OK;
+}
+// the one launch of particle_update_final_kernel (only_rows: the flagged rows are left to the separate kernels)
+static void launch_update_final(SweepCall& c, int bi, const DrawSrc& d, const int32_t* only_rows, bool lazy_valid) {
+  BlockRun& r = c.s->run[bi];
+  DISPATCH_PMAX(c.P, hipLaunchKernelGGL(particle_update_final_kernel<PMAX>, grid1(c.N), dim3(256), 0, c.ctx->stream, c.N, c.P, d.draws_rm, d.lse_rm,
+                                        d.slot_item, d.draws_item, d.lse_item, c.cur_of(bi), r.pchoice.p, c.s->w.p, (c.w_by_first_block &&
+                                        bi == 0) ? 1 : 0, c.use_mh, c.cur_base, c.seed, c.sweep_idx, c.s->row_offset + c.ctx->active_begin,
+                                        c.s->chosen.p, c.s->logml_acc.p, c.s->logml.p, only_rows, lazy_valid ? 1 : 0, c.w_uni));
+}
+// the root kernels left lists instead of draws (last block: enum.h RootExtra): the chosen particles' draws follow the final choice
+static int lazy_draws(SweepCall& c, int bi, SweepState::LazyOut& lazy) {
+  if (!lazy.valid) return PCLEAN_OK;
+  ProfScope psl(c.ctx, "lazy_draws");
+  lazy.args.n_rows = c.N;
+  lazy.args.n_particles = c.P;
+  lazy.args.chosen = c.s->chosen.p;
+  lazy.args.cur_b = c.cur_of(bi);
+  lazy.args.pchoice = c.s->run[bi].pchoice.p;
+  return pclean_launch_lazy_draws(c.ctx, lazy.args, c.seed, c.sweep_idx, lazy.site);
+}
+// the root of block bi over the items of `il`, asked for lazy lists where the final choice is fused with the update
+static int eval_block_root(SweepCall& c, int bi, const BlockStep& bs, const ItemList& il, const int32_t* excl, double* lse, int32_t* draws) {
+  if (bs.fuse_final || bs.split_final) c.s->lazy_req = SweepState::LazyReq{true, bs.split_final ? bs.emit_rows : nullptr};
+  const int rc = eval_node(c.ctx, bi, 0, il, excl, c.seed, c.sweep_idx, c.P, lse, draws, nullptr, nullptr, bi == c.ctx->timed_block);
+  c.s->lazy_req = SweepState::LazyReq();
+  return rc;
+}
+// ... and what follows it: the particle update, fused with the final choice (fuse_final), beside it (split_final) or plain
+static int update_after_eval(SweepCall& c, int bi, BlockStep& bs, const DrawSrc& d) {
+  SweepState::LazyOut lazy = c.s->lazy_out;
+  c.s->lazy_out.valid = false;
+  lazy.args.slot_item = d.slot_item;
+  if (bi == c.ctx->timed_block) {  // (the elapsed time of the launch is read at the end of the call: no synchronisation here)
+    c.hot_timed = true;
+    c.ctx->timing.hot_kernel_launches += 1;
+  }
+  ProfScope ps(c.ctx, "particle_update");
+  if (bs.fuse_final) {
+    launch_update_final(c, bi, d, nullptr, lazy.valid);
+    c.final_fused = true;
+    return lazy_draws(c, bi, lazy);
+  }
+  if (!(bs.n_new_ctr = fresh_counter(c.ctx))) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
+  // (the first block of several: its weights are the block's log marginal for every particle of a row — not stored)
+  const bool skip_w = bi == 0 && c.w_by_first_block && bi < c.n_blocks - 1 && !bs.split_final && !bs.emit_rows && !c.sw.no_w_uni;
+  if (const int rc = launch_particle_update(c, bi, d, bs.emit_rows, bs.split_final, skip_w, bs.n_new_ctr)) return rc;
+  if (skip_w || !bs.split_final) c.w_uni = skip_w ? c.s->run[bi].lse.p : nullptr;  // (null: every row's weights are in w now)
+  if (!bs.split_final) return PCLEAN_OK;
+  launch_update_final(c, bi, d, bs.emit_rows, lazy.valid);
+  c.final_only_rows = bs.emit_rows;
+  return lazy_draws(c, bi, lazy);
+}
+// use_dd_proposals = false: every (row, particle) draws its referent from the CRP prior; the block's log marginal plays no part
+static int propose_prior(SweepCall& c, int bi, BlockStep& bs) {
+  Block& b = c.ctx->block[bi];
+  BlockRun& r = c.s->run[bi];
+  const ItemList il{c.N, nullptr, nullptr, nullptr, nullptr};
+  c.ctx->prior_mode = true;
+  const int rc = eval_node(c.ctx, bi, 0, il, c.cur_of(bi), c.seed, c.sweep_idx, c.P, nullptr, r.draws.p, nullptr, nullptr, false);
+  if (rc) return rc;  // (~SweepCall takes the context out of prior mode)
+  { const int rcz = dev_zero(c.ctx, r.lse.p, (size_t)c.N * sizeof(double)); if (rcz) return rcz; }
+  if (!(bs.n_new_ctr = fresh_counter(c.ctx))) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
+  const int rcu = launch_particle_update(c, bi, DrawSrc{r.draws.p, r.lse.p, nullptr, nullptr, nullptr}, nullptr, false, false, bs.n_new_ctr);
+  if (rcu) return rcu;
+  if (b.n_ctx > 0) {  // the particles' contexts: read by the likelihood terms and handed to the new rows' items
+    { const int rci = ensure_it_ctx(c.ctx, r, c.NP, b.n_ctx); if (rci) return rci; }
+    CtxSrc cs;
+    if (const int rcs = build_ctx_src(c, bi, cs)) return rcs;
+    hipLaunchKernelGGL(gather_ctx_kernel, grid1(c.NP), dim3(256), 0, c.ctx->stream, c.NP, cs, r.it_ctx.p);
+  }
+  return PCLEAN_OK;
+}
+// a block without context: one item per row, draws row-major [N][P] (one 80-byte store per row)
+static int propose_plain(SweepCall& c, int bi, BlockStep& bs) {
+  BlockRun& r = c.s->run[bi];
+  const ItemList il{c.N, nullptr, nullptr, nullptr, nullptr};
+  if (const int rc = eval_block_root(c, bi, bs, il, c.cur_of(bi), r.lse.p, r.draws.p)) return rc;
+  return update_after_eval(c, bi, bs, DrawSrc{r.draws.p, r.lse.p, nullptr, nullptr, nullptr});
+}
+// One enumeration per distinct (row, context): particles whose earlier choices give the same context share the candidate
+// scores and differ only in their Philox draws.  slot_item[P][N]; per item its row, context, excluded referent
+struct CtxItems {
+  unsigned int n = 0;
+  int32_t *slot_item = nullptr, *row = nullptr, *ctx = nullptr, *excl = nullptr;
+};
+static int context_items(SweepCall& c, int bi, const CtxSrc& cs, CtxItems& it) {
+  Block& b = c.ctx->block[bi];
+  BlockRun& r = c.s->run[bi];
+  const int N = c.N, P = c.P;
+  const int32_t* cur_b = c.cur_of(bi);
+  it.slot_item = scratch<int32_t>(c.ctx, c.NP);
+  if (!it.slot_item) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  if (!c.sw.no_fused_items) {
+    // one pass (ctx_items_kernel): item i = row i with particle 0's context, extra items behind them; room for the extra
+    // items from the last sweep's number (a sweep that needs more runs the kernel again)
+    ProfScope ps(c.ctx, "ctx_items");
+    for (int attempt = 0;; ++attempt) {
+      const int cap = std::max(r.ctx_extra_cap, 4096);
+      it.row = scratch<int32_t>(c.ctx, (size_t)N + cap);
+      it.ctx = scratch<int32_t>(c.ctx, ((size_t)N + cap) * PCLEAN_MAX_CTX);
+      it.excl = scratch<int32_t>(c.ctx, (size_t)N + cap);
+      unsigned int* extra_ctr = fresh_counter(c.ctx);
+      if (!it.row || !it.ctx || !it.excl || !extra_ctr) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+      hipLaunchKernelGGL(ctx_items_kernel, grid1(N), dim3(256), 0, c.ctx->stream, N, P, cs, cur_b, r.it_ctx.p, it.slot_item, it.row,
+                         it.ctx, it.excl, extra_ctr, cap);
+      unsigned int n_extra = 0;
+      PCLEAN_READ_COUNT(c.ctx, extra_ctr, &n_extra);
+      r.ctx_extra_cap = (int)std::min<size_t>((size_t)n_extra * 2 + 4096, c.NP);
+      if (n_extra <= (unsigned int)cap) {
+        it.n = (unsigned int)N + n_extra;
+        return PCLEAN_OK;
+      }
+      if (attempt >= 2) return pclean_fail(c.ctx, PCLEAN_ERR_STATE, "pclean_sweep: the context items did not fit twice in a row");
+    }
+  }
+  int32_t* rep = scratch<int32_t>(c.ctx, c.NP);
+  int32_t* n_distinct = scratch<int32_t>(c.ctx, (size_t)N + 1);
+  int32_t* off = scratch<int32_t>(c.ctx, (size_t)N + 1);
+  size_t tmp_scan = 0;
+  HIPCHK(c.ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, n_distinct, off, N + 1, c.ctx->stream));
+  unsigned char* tmp = scratch<unsigned char>(c.ctx, tmp_scan);
+  if (!rep || !n_distinct || !off || !tmp) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  {
+    ProfScope ps(c.ctx, "ctx_items");
+    hipLaunchKernelGGL(gather_ctx_kernel, grid1(c.NP), dim3(256), 0, c.ctx->stream, c.NP, cs, r.it_ctx.p);
+    HIPCHK(c.ctx, hipMemsetAsync(n_distinct + N, 0, sizeof(int32_t), c.ctx->stream));
+    hipLaunchKernelGGL(ctx_count_kernel, grid1(N), dim3(256), 0, c.ctx->stream, N, P, (int)b.n_ctx, r.it_ctx.p, rep, n_distinct);
+    HIPCHK(c.ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_scan, n_distinct, off, N + 1, c.ctx->stream));
+    PCLEAN_READ_COUNT(c.ctx, off + N, &it.n);
+  }
+  it.row = scratch<int32_t>(c.ctx, it.n);
+  it.ctx = scratch<int32_t>(c.ctx, (size_t)it.n * PCLEAN_MAX_CTX);
+  it.excl = scratch<int32_t>(c.ctx, it.n);
+  if (!it.row || !it.ctx || !it.excl) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(ctx_fill_kernel, grid1(N), dim3(256), 0, c.ctx->stream, N, P, (int)b.n_ctx, r.it_ctx.p, rep, off, cur_b,
+                     it.slot_item, it.row, it.ctx, it.excl);
+  return PCLEAN_OK;
+}
+// a block with context: the root is evaluated per context item
+static int propose_ctx(SweepCall& c, int bi, BlockStep& bs) {
+  Block& b = c.ctx->block[bi];
+  { const int rci = ensure_it_ctx(c.ctx, c.s->run[bi], c.NP, b.n_ctx); if (rci) return rci; }
+  CtxSrc cs;
+  if (const int rc = build_ctx_src(c, bi, cs)) return rc;
+  CtxItems it;
+  if (const int rc = context_items(c, bi, cs, it)) return rc;
+  double* lse_item = scratch<double>(c.ctx, it.n);
+  int32_t* draws_item = scratch<int32_t>(c.ctx, (size_t)it.n * c.P);
+  if (!lse_item || !draws_item) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  ItemList il{(int)it.n, it.row, it.ctx, nullptr, nullptr};
+  if (!c.sw.no_fused_items) il.n_primary = c.N;  // (ctx_items_kernel: item i < N is row i; ctx_fill_kernel numbers row by row)
+  if (const int rc = eval_block_root(c, bi, bs, il, it.excl, lse_item, draws_item)) return rc;
+  return update_after_eval(c, bi, bs, DrawSrc{nullptr, nullptr, it.slot_item, draws_item, lse_item});
+}
+// the referents of block bi: every particle's proposal and its weight
+static int propose_block(SweepCall& c, int bi, BlockStep& bs) {
+  Block& b = c.ctx->block[bi];
+  BlockRun& r = c.s->run[bi];
+  const int N = c.N;
+  if (c.prefetching && bi >= 1) {  // (the refreshed tables of this and the later blocks: one join)
+    HIPCHK(c.ctx, hipStreamWaitEvent(c.ctx->stream, c.s->pre_join, 0));
+    c.prefetching = false;
+  }
+  if (r.pchoice.alloc(c.NP) || r.pnewpos.alloc(c.NP) || r.new_slots.alloc(c.NP) || r.choice.alloc(N) || r.chosen_newpos.alloc(N) ||
+      r.moved_flag.alloc(N) || r.new_flag.alloc(N) || r.moved_list.alloc(N) || r.new_list.alloc(N) ||
+      ((c.prior_mode || b.n_ctx == 0) && (r.draws.alloc(c.NP) || r.lse.alloc(N))))  // (row-major draws: no context items)
+    return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  if (const int rc = ensure_plan_dev(c.ctx, bi)) return rc;
+  // The contents of a proposed new row matter (a) as context / scored values of LATER blocks — every particle's —
+  // and (b) for the particle that is finally chosen.  For the last block only (b) is left: its sampling is
+  // deferred until after the final choice and done for the chosen particles alone (same Philox counters, so
+  // the values are the ones eager sampling would have produced; typically 20x fewer items).
+  // A chosen ProposalDummyValue changes its particle's weight (apply_dummy_corrections): where one can be drawn
+  // the NEW slots are sampled before the final choice — all of them, or, when every list that can draw its dummy knows
+  // for which observed values (cacheable lists: leaf_udummy), those of the few rows that hold such a value (emit_rows).
+  const bool last = bi == c.n_blocks - 1;
+  bool dummy_by_row = false;
+  bs.drawable = c.prior_mode;  // (prior draws of a StringPrior choice are the dummy almost surely)
+  if (!c.prior_mode)
+    if (const int rc = block_dummy_drawable(c.ctx, bi, &bs.drawable, &dummy_by_row)) return rc;
+  if (last && !c.sw.eager_all && !c.sw.no_partial && !c.prior_mode && bs.drawable && dummy_by_row) {
+    bool none = false;
+    if (const int rc = dummy_rows_flags(c.ctx, bi, N, &bs.emit_rows, &none)) return rc;
+    if (none) bs.drawable = false;  // the dummy's fixed-point weight is 0 for every row of the window: it cannot be drawn
+  }
+  const bool last_plain = last && !c.prior_mode && !c.sw.eager_all && !c.sw.no_fuse_final;
+  bs.fuse_final = last_plain && !bs.drawable;
+  bs.split_final = last_plain && bs.drawable && bs.emit_rows != nullptr;
+  r.plocals_on = false;
+  if (const int rc = c.prior_mode ? propose_prior(c, bi, bs) : b.n_ctx > 0 ? propose_ctx(c, bi, bs) : propose_plain(c, bi, bs)) return rc;
+  // (this block's kernels are queued: the host has time for the later blocks' table refresh)
+  return c.prefetch_started ? PCLEAN_OK : start_prefetch(c);
+}
+// the contents of the new rows of the first `count` slots listed in new_slots (the same Philox counters whoever asks)
+static int sample_new_rows(SweepCall& c, int bi, unsigned int count) {
+  Block& b = c.ctx->block[bi];
+  BlockRun& r = c.s->run[bi];
+  const int nn = (int)b.nodes.size();
+  hipLaunchKernelGGL(fill_i32_kernel, grid1((size_t)count * nn), dim3(256), 0, c.ctx->stream, r.vals.p, (size_t)count * nn, -2);
+  int32_t* row = scratch<int32_t>(c.ctx, count);
+  int32_t* cx = scratch<int32_t>(c.ctx, (size_t)count * PCLEAN_MAX_CTX);
+  int32_t* part = scratch<int32_t>(c.ctx, count);
+  int32_t* org = scratch<int32_t>(c.ctx, count);
+  int32_t* ex = scratch<int32_t>(c.ctx, count);
+  if (!row || !cx || !part || !org || !ex) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(rootlist_items_kernel, grid1(count), dim3(256), 0, c.ctx->stream, (int)count, c.N, c.NP, r.new_slots.p,
+                     b.n_ctx > 0 ? r.it_ctx.p : nullptr, c.cur_of(bi), row, cx, part, org, ex);
+  hipLaunchKernelGGL(set_col_kernel, grid1(count), dim3(256), 0, c.ctx->stream, (int)count, nn, 0, (int32_t)PCLEAN_CHOICE_NEW, r.vals.p);
+  ItemList sub{(int)count, row, cx, part, org};
+  return sample_children(c.ctx, bi, 0, sub, ex, c.seed, c.sweep_idx, r.vals.p, nn);
+}
+// the Gaussian term(s) on the slot of block bi
+static int slot_gauss_dev(SweepCall& c, int bi, GaussDev& gd, const GaussDev** more, int* n_more) {
+  const Block& b = c.ctx->block[bi];
+  const CandTable& rt = c.ctx->cand[b.nodes[0].table];
+  const int rc = build_gauss_dev(c.ctx, b.gauss[b.node_gauss[0]], &rt, gd);
+  return rc ? rc : build_gauss_more(c.ctx, b, 0, &rt, more, n_more);
+}
+// prior proposals: the likelihood of the sampled sub-tree (pclean_launch_prior_terms), then a Gaussian term on the slot, scored per
+// particle at own choices sampled from their priors; the dummy corrections follow (the order of the fp64 additions)
+static int prior_terms_and_gauss(SweepCall& c, int bi) {
+  Block& b = c.ctx->block[bi];
+  BlockRun& r = c.s->run[bi];
+  const int nn = (int)b.nodes.size();
+  c.ctx->prior_mode = false;
+  const NodeDev* nds;
+  const int32_t *dnc, *dcb, *dch;
+  int rc = upload_plan_nodes(c.ctx, bi, &nds, &dnc, &dcb, &dch);
+  if (!rc)
+    rc = pclean_launch_prior_terms(c.ctx, c.NP, c.N, nn, nds, dnc, dcb, dch, r.pchoice.p, r.pnewpos.p, r.vals.p,
+                                   b.n_ctx > 0 ? r.it_ctx.p : nullptr, c.s->w.p);
+  if (rc || b.node_gauss.empty() || b.node_gauss[0] < 0) return rc;
+  GaussDev gd;
+  const GaussDev* gmore;
+  int n_gmore;
+  if (const int rc = slot_gauss_dev(c, bi, gd, &gmore, &n_gmore)) return rc;
+  if (r.plocals.alloc((size_t)c.NP * 2)) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  const int32_t* cl = (b.cur_locals.p && b.cur_locals_rows == c.ctx->n_rows) ? b.cur_locals.p + (size_t)c.ctx->active_begin * 2 : nullptr;
+  hipLaunchKernelGGL(gauss_prior_kernel, grid1(c.NP), dim3(256), 0, c.ctx->stream, c.N, c.P, gd, gmore, n_gmore, r.plan, r.pchoice.p, r.pnewpos.p,
+                     r.vals.p, nn, c.cur_of(bi), cl, c.seed, c.sweep_idx, (uint32_t)bi, c.s->row_offset + c.ctx->active_begin, c.s->w.p, r.plocals.p);
+  r.plocals_on = true;
+  return PCLEAN_OK;
+}
+
+// particles that proposed a NEW referent: their number, their rows' contents where the final choice needs them (weights_touched:
+// the particles of a row may differ in weight now)
+static int new_rows_of_block(SweepCall& c, int bi, const BlockStep& bs, bool* weights_touched) {
+  BlockRun& r = c.s->run[bi];
+  const int nn = (int)c.ctx->block[bi].nodes.size();
+  unsigned int n_new = 0;
+  if (!c.final_fused) PCLEAN_READ_COUNT(c.ctx, bs.n_new_ctr, &n_new);  // (fused with the final choice: nothing is sampled now, nobody asks)
+  const bool degenerate_rows = (n_new & 0x80000000u) != 0u;  // some row's block marginal is -inf (particle_update_kernel)
+  n_new &= 0x7fffffffu;
+  r.n_new = c.final_fused ? -1 : (int)n_new;
+  r.lazy_new = c.final_fused || (bi == c.n_blocks - 1 && !c.sw.eager_all && (!bs.drawable || bs.emit_rows != nullptr));
+  if (r.lazy_new && !bs.emit_rows) n_new = 0;  // nothing sampled now
+  if (bs.emit_rows) r.n_new = -1;  // (the list held the flagged rows' slots only: whether anybody proposed a NEW referent is not known)
+  if (r.vals.alloc(std::max<size_t>((size_t)n_new * nn, 1))) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  *weights_touched = (bs.drawable && n_new > 0) || degenerate_rows;
+  std::optional<ProfScope> ps;  // (it covers the prior terms and the corrections of a block that sampled)
+  int rc = PCLEAN_OK;
+  if (n_new) {
+    ps.emplace(c.ctx, "new_row_sampling");
+    if (const int rc = sample_new_rows(c, bi, n_new)) return rc;
+  }
+  if (c.prior_mode)  // (nobody proposed a new referent: the likelihood of the chosen referents alone)
+    if (const int rc = prior_terms_and_gauss(c, bi)) return rc;
+  if (n_new && bs.drawable) {
+    if (!bs.split_final) materialise_w(c);  // (split: the flagged rows' weights were stored, nobody looks at the others')
+    rc = apply_dummy_corrections(c.ctx, bi, r.new_slots.p, r.vals.p, (int)n_new, c.N, c.seed, c.sweep_idx, c.s->w.p);
+  }
+  c.ctx->prior_mode = false;
+  // (pnewpos is only read where pchoice == NEW, so it needs no initialisation when nobody proposed one)
+  return rc;
+}
+// resampling between blocks (row_inference.jl:152-155)
+static int resample_between_blocks(SweepCall& c, int bi, bool weights_touched) {
+  const Block& b = c.ctx->block[bi];
+  const int N = c.N, P = c.P;
+  const int grp_here = b.group >= 0 ? b.group : bi;
+  const int grp_next = bi + 1 < c.n_blocks ? (c.ctx->block[bi + 1].group >= 0 ? c.ctx->block[bi + 1].group : bi + 1) : -2;
+  // After the FIRST block of a sweep every particle of a row carries the same weight — the block's log marginal, shared by
+  // the particles (no context yet to tell them apart) — unless a dummy-value correction or a prior-mode likelihood touched
+  // individual particles: the effective sample size is exactly P, maybe_resample (row_inference.jl:87-105) keeps every
+  // particle and adds 0 to the log-ML estimate (a row whose marginal is -inf has total weight 0 and IS resampled: those
+  // rows are reported through bit 31 of the NEW-slot counter).  Two kernels over all rows that can only ever do nothing are
+  // not launched.
+  const bool equal_weights = bi == 0 && c.w_by_first_block && b.n_ctx == 0 && !c.prior_mode && !weights_touched;
+  // (the slots of one model block: no resampling in between)
+  if (c.use_mh || bi >= c.n_blocks - 1 || grp_here == grp_next || (equal_weights && !c.sw.always_resample)) return PCLEAN_OK;
+  ProfScope ps(c.ctx, "resample");
+  materialise_w(c);
+  DISPATCH_PMAX(P, hipLaunchKernelGGL(maybe_resample_kernel<PMAX>, grid1(N), dim3(256), 0, c.ctx->stream, N, P, c.s->w.p, (size_t)1, (size_t)N, 1,
+                                      c.cur_of(bi), c.seed, c.sweep_idx, (uint32_t)bi, c.s->row_offset + c.ctx->active_begin, c.s->ancestors.p,
+                                      c.s->logml_inc.p, (double*)nullptr, c.s->did.p));
+  AncestorArrays arrs{};
+  int n_arr = 0;
+  for (int k = 0; k <= bi; ++k) {
+    if (c.ctx->block[k].is_score) continue;
+    arrs.p[n_arr++] = c.s->run[k].pchoice.p;
+    arrs.p[n_arr++] = c.s->run[k].pnewpos.p;
+    if (c.s->run[k].plocals_on) arrs.pairs[arrs.n_pairs++] = reinterpret_cast<int64_t*>(c.s->run[k].plocals.p);
+  }
+  hipLaunchKernelGGL(apply_ancestors_kernel, grid1(N), dim3(256), 0, c.ctx->stream, N, P, c.s->ancestors.p, n_arr, arrs, c.s->w.p,
+                     c.s->did.p, c.s->logml_inc.p, c.s->logml_acc.p);
+  return PCLEAN_OK;
+}
+// the final choice, unless the last block's particle update made it (for every row, or for the rows outside final_only_rows)
+static void final_choice(SweepCall& c) {
+  if (c.final_fused) return;
+  if (!c.final_only_rows) materialise_w(c);  // (never pending here: a plain update of every row stored them)
+  DISPATCH_PMAX(c.P, hipLaunchKernelGGL(final_choice_kernel<PMAX>, grid1(c.N), dim3(256), 0, c.ctx->stream, c.N, c.P, c.s->w.p, (size_t)1,
+                                        (size_t)c.N, c.use_mh, 1, c.cur_base, c.seed, c.sweep_idx, c.s->row_offset + c.ctx->active_begin, c.s->chosen.p,
+                                        (double*)nullptr, c.s->logml_acc.p, c.s->logml.p, c.final_only_rows));
+}
+
+// ---- the tail: per block the chosen particles' referents, the tables' delta reference counts, ordered lists of the rows that
+// moved / got a new referent (ONE read-back of their counts, when the call ends), the chosen particles' deferred new rows
+struct SweepTail {
+  int nb_wg = 0;                                     // tiles of TAIL_TILE_ROWS rows
+  unsigned int* wg_cnt = nullptr;                    // [2 * n_blocks][nb_wg] moved / new rows per tile
+  unsigned int* chosen_ctr[PCLEAN_MAX_BLOCKS] = {};  // blocks whose chosen NEW rows are listed: the list's length
+  int hist_rows[PCLEAN_MAX_BLOCKS] = {};             // rows of the block's table counted in an LDS histogram (0: plain atomics)
+  TailLists tl{};
+  ZeroList zl{};  // the tables' delta reference counts start at zero: one kernel over every root table, not a memset apiece
+};
+// deferred new-row contents of the last block (chosen particles only): the listed slots' rows are sampled
+static int sample_chosen(SweepCall& c, const SweepTail& t, int bi) {
+  BlockRun& r = c.s->run[bi];
+  ProfScope ps2(c.ctx, "new_row_sampling_chosen");
+  const int nn = (int)c.ctx->block[bi].nodes.size();
+  unsigned int cnt = 0;
+  PCLEAN_READ_COUNT(c.ctx, t.chosen_ctr[bi], &cnt);
+  if (c.sw.trace_tail)
+    fprintf(stderr, "[pclean tail] block %d: %u chosen NEW rows listed by %s\n", bi, cnt,
+            c.sw.no_fused_finalize ? "chosen_new_kernel" : "finalize_tail_kernel");
+  if (r.vals.alloc(std::max<size_t>((size_t)cnt * nn, 1))) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  return cnt ? sample_new_rows(c, bi, cnt) : PCLEAN_OK;
+}
+static int tail_begin(SweepCall& c, SweepTail& t) {
+  t.wg_cnt = scratch<unsigned int>(c.ctx, (size_t)2 * c.n_blocks * t.nb_wg);
+  return t.wg_cnt ? zero_list_flush(c.ctx, t.zl) : pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+}
+// tile counts -> totals and ordered lists
+static int tail_lists(SweepCall& c, const SweepTail& t) {
+  // (a scoring block's two slots: their workgroup counts were never written — zero them so that the totals read 0)
+  for (int bi = 0; bi < c.n_blocks; ++bi)
+    if (c.ctx->block[bi].is_score)
+      HIPCHK(c.ctx, hipMemsetAsync(t.wg_cnt + (size_t)(2 * bi) * t.nb_wg, 0, (size_t)2 * t.nb_wg * sizeof(unsigned int), c.ctx->stream));
+  hipLaunchKernelGGL(tail_scan_kernel, dim3(2 * c.n_blocks), dim3(1024), 0, c.ctx->stream, t.nb_wg, t.wg_cnt, c.s->tail_counts.p);
+  hipLaunchKernelGGL(tail_scatter_kernel, dim3(t.nb_wg, 2 * c.n_blocks), dim3(256), 0, c.ctx->stream, c.N, t.nb_wg, t.tl, t.wg_cnt);
+  return PCLEAN_OK;
+}
+// finalize_tail_kernel: every block in one launch, which lists the chosen NEW rows too; their contents last (nobody needed them)
+static int tail_fused(SweepCall& c, SweepTail& t) {
+  if (const int rc = tail_begin(c, t)) return rc;
+  TailBlocks tb{};
+  int max_hist = 0;
+  for (int bi = 0; bi < c.n_blocks; ++bi) {
+    if (c.ctx->block[bi].is_score) continue;
+    BlockRun& r = c.s->run[bi];
+    tb.b[bi] = TailBlock{r.pchoice.p, r.pnewpos.p, c.cur_of(bi), r.choice.p, r.chosen_newpos.p,
+                         (unsigned long long*)c.ctx->cand[c.ctx->block[bi].nodes[0].table].stats.p, r.moved_flag.p, r.new_flag.p,
+                         t.wg_cnt + (size_t)(2 * bi) * t.nb_wg, t.wg_cnt + (size_t)(2 * bi + 1) * t.nb_wg, t.chosen_ctr[bi], r.new_slots.p,
+                         t.hist_rows[bi], /*on*/ 1, /*lazy*/ t.chosen_ctr[bi] ? 1 : 0, 0};
+    max_hist = std::max(max_hist, t.hist_rows[bi]);
+  }
+  // a capped grid, each workgroup walking a contiguous range of tiles (tail_tiles.h; DESIGN.md §6: the count)
+  static int tail_cap = 0;
+  if (!tail_cap) {
+    int n_cu = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c.ctx->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+    tail_cap = std::max(1, n_cu / TAIL_CUS_PER_WG);
+  }
+  const int n_wgs = tail_wg_count(t.nb_wg, tail_cap, c.sw.forced_tail_wgs);
+  if (c.sw.trace_tail)
+    fprintf(stderr, "[pclean tail] finalize_tail_kernel: %d tiles, %d workgroups per block, at most %d tiles per workgroup\n",
+            t.nb_wg, n_wgs, (t.nb_wg + n_wgs - 1) / n_wgs);
+  hipLaunchKernelGGL(finalize_tail_kernel, dim3(n_wgs, c.n_blocks), dim3(TAIL_WG_THREADS), (size_t)max_hist * sizeof(int32_t), c.ctx->stream,
+                     c.N, t.nb_wg, c.s->chosen.p, tb);
+  int rc = tail_lists(c, t);
+  for (int bi = 0; bi < c.n_blocks && !rc; ++bi)
+    if (t.chosen_ctr[bi]) rc = sample_chosen(c, t, bi);
+  return rc;
+}
+// PCLEAN_NO_FUSED_FINALIZE=1: chosen_new_kernel lists the chosen NEW rows (sampled right away), one finalize_block_kernel per block
+static int tail_per_block(SweepCall& c, SweepTail& t) {
+  for (int bi = 0; bi < c.n_blocks; ++bi) {
+    if (!t.chosen_ctr[bi]) continue;
+    BlockRun& r = c.s->run[bi];
+    hipLaunchKernelGGL(chosen_new_kernel, grid1(c.N), dim3(256), 0, c.ctx->stream, c.N, c.s->chosen.p, r.pchoice.p, t.chosen_ctr[bi],
+                       r.new_slots.p, r.pnewpos.p);
+    if (const int rc = sample_chosen(c, t, bi)) return rc;
+  }
+  if (const int rc = tail_begin(c, t)) return rc;
+  for (int bi = 0; bi < c.n_blocks; ++bi) {
+    if (c.ctx->block[bi].is_score) continue;
+    BlockRun& r = c.s->run[bi];
+    hipLaunchKernelGGL(finalize_block_kernel, grid1(c.N), dim3(256), (size_t)t.hist_rows[bi] * sizeof(int32_t), c.ctx->stream, c.N,
+                       c.s->chosen.p, r.pchoice.p, r.pnewpos.p, c.cur_of(bi), r.choice.p, r.chosen_newpos.p,
+                       (unsigned long long*)c.ctx->cand[c.ctx->block[bi].nodes[0].table].stats.p, t.hist_rows[bi], r.moved_flag.p,
+                       r.new_flag.p, t.wg_cnt + (size_t)(2 * bi) * t.nb_wg, t.wg_cnt + (size_t)(2 * bi + 1) * t.nb_wg);
+  }
+  if (c.sw.trace_tail) fprintf(stderr, "[pclean tail] finalize_block_kernel: one launch per block\n");
+  return tail_lists(c, t);
+}
+static int sweep_tail(SweepCall& c) {
+  SweepTail t;
+  t.nb_wg = (c.N + TAIL_TILE_ROWS - 1) / TAIL_TILE_ROWS;
+  for (int bi = 0; bi < c.n_blocks; ++bi) {
+    BlockRun& r = c.s->run[bi];
+    Block& bb = c.ctx->block[bi];
+    bb.locals_host.clear();
+    r.locals_rows = 0;
+    if (bb.is_score) continue;
+    if (r.lazy_new && r.n_new != 0) {
+      if (!(t.chosen_ctr[bi] = fresh_counter(c.ctx))) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
+    }
+    const CandTable& rt = c.ctx->cand[bb.nodes[0].table];
+    // (an LDS histogram per workgroup: a few rows take most of the moves — 28 true measures for 1M records.  It covers the
+    // rows below the table's high-water mark only: nobody refers to, or chooses, the spare capacity behind it, and zeroing
+    // + flushing the counters of 8 240 rows in each of 4 000 workgroups was 0.05 ms per sweep)
+    const int rows_in_use = (rt.n_used > 0 && rt.n_used <= rt.n_rows) ? std::min(rt.n_rows, (rt.n_used + 63) & ~63) : rt.n_rows;
+    // (48 KB of LDS per workgroup at most; larger tables: plain atomics)
+    t.hist_rows[bi] = (rt.n_rows <= 12288 && !c.sw.no_hist) ? rows_in_use : 0;
+    bool seen = false;
+    for (int k = 0; k < t.zl.n; ++k) seen |= t.zl.p[k] == (void*)rt.stats.p;
+    if (!seen) zero_list_add(c.ctx, t.zl, rt.stats.p, (size_t)std::max(rt.n_rows, 1) * 8);
+    t.tl.flag[2 * bi] = r.moved_flag.p;
+    t.tl.list[2 * bi] = r.moved_list.p;
+    t.tl.flag[2 * bi + 1] = r.new_flag.p;
+    t.tl.list[2 * bi + 1] = r.new_list.p;
+  }
+  return c.sw.no_fused_finalize ? tail_per_block(c, t) : tail_fused(c, t);
+}
+// per-row outputs (they may read the new rows' contents): choices, own choices of a Gaussian slot, chosen particles, logml
+static int block_outputs(SweepCall& c, int32_t* choice, int32_t* chosen_particle, double* logml) {
+  const int N = c.N;
+  for (int bi = 0; bi < c.n_blocks; ++bi) {
+    BlockRun& r = c.s->run[bi];
+    Block& bb = c.ctx->block[bi];
+    if (bb.is_score) continue;
+    if (choice) HIPCHK(c.ctx, hipMemcpyAsync(choice + (size_t)bi * N, r.choice.p, (size_t)N * 4, hipMemcpyDeviceToHost, c.ctx->stream));
+    if (bb.node_gauss.empty() || bb.node_gauss[0] < 0 || bb.gauss[bb.node_gauss[0]].n_locals <= 0) continue;
+    if (r.locals.alloc((size_t)N * 2)) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "device alloc failed");
+    if (r.plocals_on) {  // prior proposals: what the chosen particle sampled (or kept)
+      hipLaunchKernelGGL(locals_pick_kernel, grid1(N), dim3(256), 0, c.ctx->stream, N, c.s->chosen.p, r.plocals.p, r.locals.p);
+    } else {
+      GaussDev gd;
+      const GaussDev* gmore;
+      int n_gmore;
+      if (const int rc = slot_gauss_dev(c, bi, gd, &gmore, &n_gmore)) return rc;
+      hipLaunchKernelGGL(locals_tail_kernel, grid1(N), dim3(256), 0, c.ctx->stream, N, c.P, gd, gmore, n_gmore, r.plan, c.s->chosen.p,
+                         r.pchoice.p, r.pnewpos.p, r.vals.p, (int)bb.nodes.size(), c.seed, c.sweep_idx, (uint32_t)bi,
+                         c.s->row_offset + c.ctx->active_begin, r.locals.p);
+    }
+    r.locals_rows = N;
+    if (!c.ctx->defer_outputs) {  // (deferred outputs: pclean_get_locals copies them when asked)
+      bb.locals_host.resize((size_t)N * 2);
+      HIPCHK(c.ctx, hipMemcpyAsync(bb.locals_host.data(), r.locals.p, (size_t)N * 8, hipMemcpyDeviceToHost, c.ctx->stream));
+    }
+  }
+  (void)hipEventRecord(c.s->eve, c.ctx->stream);
+  if (chosen_particle) HIPCHK(c.ctx, hipMemcpyAsync(chosen_particle, c.s->chosen.p, (size_t)N * 4, hipMemcpyDeviceToHost, c.ctx->stream));
+  if (logml) HIPCHK(c.ctx, hipMemcpyAsync(logml, c.s->logml.p, (size_t)N * 8, hipMemcpyDeviceToHost, c.ctx->stream));
+  return PCLEAN_OK;
+}
+// the timing model, and the end of the call: deferred (nothing read back) or synchronous
+static int sweep_end(SweepCall& c, int32_t* choice) {
+  c.s->last_hot_timed = c.hot_timed;
+  c.s->outputs_pending = true;
+  c.s->lists_on_host = false;
+  // bytes(row) = sum_b [4 F_b + (K_b+1)(8 F_b + 4)] + 8 P (full enumeration); reported beside the
+  // byte model of the implemented algorithm (bench.py)
+  const int tb = c.ctx->timed_block;
+  const Block& b0 = c.ctx->block[(tb >= 0 && tb < c.n_blocks && !c.ctx->block[tb].is_score) ? tb : 0];
+  const double F = b0.nodes[0].n_terms, K = c.ctx->cand[b0.nodes[0].table].n_rows;
+  c.ctx->timing.hot_kernel_alg_bytes = (double)c.N * (4.0 * F + (K + 1.0) * (8.0 * F + 4.0) + 8.0 * c.P);
+  if (c.ctx->defer_outputs) return PCLEAN_OK;  // nothing read back, no synchronisation: pclean_commit_device / pclean_sweep_fetch finish the call
+  if (const int rcf = pclean_sweep_finish_queue(c.ctx)) return rcf;
+  PCLEAN_SYNC(c.ctx);
+  if (const int rcf = pclean_sweep_finish_synced(c.ctx)) return rcf;
+  if (choice)
+    for (int bi = 0; bi < c.n_blocks; ++bi)
+      if (c.ctx->block[bi].is_score)
+        for (int i = 0; i < c.N; ++i) choice[(size_t)bi * c.N + i] = 0;
+  return pclean_sweep_fetch_lists(c.ctx);
+}
+
+extern "C" int pclean_sweep(pclean_ctx* ctx, const pclean_infer_config* cfg, uint64_t seed, uint32_t sweep_idx, int32_t n_blocks,
+                            const int32_t* cur, int32_t* choice, int32_t* chosen_particle, double* logml) {
+  if (!ctx || !cfg || n_blocks <= 0 || n_blocks > PCLEAN_MAX_BLOCKS) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_sweep: bad arguments");
   // cur == NULL: the current referents are the device-resident array of pclean_set_cur / the last pclean_commit_device
   const bool dev_cur = cur == nullptr;
   if (dev_cur && (!ctx->dev_cur_valid || ctx->dev_cur_blocks != n_blocks || !ctx->dev_cur.p))
     return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_sweep: cur == NULL needs pclean_set_cur (device-resident referents)");
-  const bool defer = ctx->defer_outputs;
-  if (defer && (choice || chosen_particle || logml))
+  if (ctx->defer_outputs && (choice || chosen_particle || logml))
     return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_sweep: deferred outputs (pclean_set_sweep_mode) take no per-row output buffers");
   const bool prior_mode = !cfg->use_dd_proposals;
-  if (prior_mode)
-    for (int b = 0; b < n_blocks; ++b) {
-      const int rcp = prior_mode_supported(ctx, ctx->block[b], "pclean_sweep");
-      if (rcp) return rcp;
-    }
+  for (int b = 0; b < n_blocks && prior_mode; ++b)
+    if (const int rcp = prior_mode_supported(ctx, ctx->block[b], "pclean_sweep")) return rcp;
   const int N = ctx->active_count >= 0 ? ctx->active_count : ctx->n_rows;
-  int P = cfg->num_particles;
   const int use_mh = cfg->use_mh_instead_of_pg != 0;
-  if (use_mh) P = 2;  // infer_config.jl:11-13
+  const int P = use_mh ? 2 : cfg->num_particles;  // infer_config.jl:11-13
   if (N <= 0) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_sweep: no observed rows loaded");
   if (P < 1 || P > MAXP) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_sweep: num_particles must be in 1..%d", MAXP);
   for (int b = 0; b < n_blocks; ++b)
     if (!ctx->block[b].valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_sweep: block %d not loaded", b);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  SweepState* s = st(ctx);
-  {
-    const int rcb = begin_call(ctx);
-    if (rcb) return rcb;
-  }
-  struct PriorModeGuard {  // no exit of this call (error returns included) leaves the context in prior mode
-    pclean_ctx* c;
-    ~PriorModeGuard() { c->prior_mode = false; }
-  } prior_guard{ctx};
-  if (!s->ev0) {
-    HIPCHK(ctx, hipEventCreate(&s->ev0));
-    HIPCHK(ctx, hipEventCreate(&s->ev1));
-    HIPCHK(ctx, hipEventCreate(&s->evs));
-    HIPCHK(ctx, hipEventCreate(&s->eve));
-    HIPCHK(ctx, hipEventCreate(&s->evg0));
-    HIPCHK(ctx, hipEventCreate(&s->evg1));
-  }
-  s->gate_timed = false;
-  if (!s->h_counts) HIPCHK(ctx, hipHostMalloc((void**)&s->h_counts, 4 * PCLEAN_MAX_BLOCKS * sizeof(int32_t), hipHostMallocDefault));
-  const size_t NP = (size_t)N * P;
-  if (s->cur.alloc((size_t)N * n_blocks) || s->chosen.alloc(N) || s->ancestors.alloc(NP) || s->w.alloc(NP) ||
-      s->log_total.alloc(N) || s->logml_inc.alloc(N) || s->logml_acc.alloc(N) || s->logml.alloc(N) ||
-      s->counter.alloc(4) || s->arr_ptrs.alloc(2 * PCLEAN_MAX_BLOCKS) || s->did.alloc(N) ||
-      s->tail_counts.alloc(2 * PCLEAN_MAX_BLOCKS))
-    return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-  // cur_base + bi * cur_ld = current referents of block bi over the active window
-  const int32_t* cur_base = s->cur.p;
-  size_t cur_ld = (size_t)N;
-  if (dev_cur) {
-    cur_base = ctx->dev_cur.p + ctx->active_begin;
-    cur_ld = (size_t)ctx->n_rows;
-  } else if (ctx->cur_stride > 0 && ctx->cur_stride != N) {
-    if (ctx->cur_stride < N) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_sweep: cur stride smaller than the active window");
-    for (int b = 0; b < n_blocks; ++b)
-      HIPCHK(ctx, hipMemcpyAsync(s->cur.p + (size_t)b * N, cur + (size_t)b * ctx->cur_stride, (size_t)N * 4,
-                                 hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    HIPCHK(ctx, hipMemcpyAsync(s->cur.p, cur, (size_t)N * n_blocks * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  s->last_cur_base = cur_base;
-  s->last_cur_ld = cur_ld;
-  s->last_N = N;
-  s->last_blocks = n_blocks;
-  s->last_dev_cur = dev_cur;
-  (void)hipEventRecord(s->evs, ctx->stream);
-  // particle weights start at +0.0: the first block's particle_update_kernel stores instead of accumulating (a sweep that
-  // begins with a scoring block accumulates onto zeros)
-  const bool w_by_first_block = !ctx->block[0].is_score;
-  if (!w_by_first_block) { const int rcz = dev_zero(ctx, s->w.p, NP * sizeof(double)); if (rcz) return rcz; }
-  { const int rcz = dev_zero(ctx, s->logml_acc.p, (size_t)N * sizeof(double)); if (rcz) return rcz; }
-  ctx->timing = pclean_timing{};
-  // the later blocks' root tables refresh on a side stream while block 0 runs (eval.hip: prefetch_fast_root): enqueued
-  // once block 0's kernels are (see the block loop), so that the host time of those launches is not block 0's
-  static const bool no_prefetch = getenv("PCLEAN_NO_COMPACT_PREFETCH") != nullptr;
-  bool prefetching = false, prefetch_started = false;
-  if (!s->pre_stream) {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&s->pre_stream, hipStreamNonBlocking));
-    HIPCHK(ctx, hipEventCreateWithFlags(&s->pre_fork, hipEventDisableTiming));
-    HIPCHK(ctx, hipEventCreateWithFlags(&s->pre_join, hipEventDisableTiming));
-  }
-  HIPCHK(ctx, hipEventRecord(s->pre_fork, ctx->stream));
-  auto start_prefetch = [&]() -> int {
-    prefetch_started = true;
-    if (no_prefetch || prior_mode || ctx->force_generic || n_blocks <= 1) return PCLEAN_OK;
-    HIPCHK(ctx, hipStreamWaitEvent(s->pre_stream, s->pre_fork, 0));  // (recorded at the START of the sweep: nothing of block 0)
-    for (int bi = 1; bi < n_blocks; ++bi) {
-      const Block& pb = ctx->block[bi];
-      if (pb.is_score || pb.nodes.empty() || (!pb.node_gauss.empty() && pb.node_gauss[0] >= 0)) continue;
-      const int rcp = prefetch_fast_root(ctx, bi, 0, s->pre_stream);
-      if (rcp) return rcp;
-    }
-    HIPCHK(ctx, hipEventRecord(s->pre_join, s->pre_stream));
-    prefetching = true;
-    return PCLEAN_OK;
-  };
-  struct FirstWaitGuard {  // (the hook refers to this frame: no exit of the call leaves it behind; and an error exit between
-    SweepState* st_;       // the fork and the join still joins the side stream: its work must not overlap the next call)
-    pclean_ctx* c_;
-    bool* prefetching_;
-    ~FirstWaitGuard() {
-      st_->on_first_wait = nullptr;
-      if (*prefetching_) (void)hipStreamWaitEvent(c_->stream, st_->pre_join, 0);
-    }
-  } first_wait_guard{s, ctx, &prefetching};
-  static const bool late_prefetch = getenv("PCLEAN_LATE_COMPACT_PREFETCH") != nullptr;
-  if (!late_prefetch)
-    s->on_first_wait = [&]() -> int { return prefetch_started ? PCLEAN_OK : start_prefetch(); };
-  bool hot_timed = false;
-  // particle_update_kernel stages the root kernels' row-major draws through LDS (rows of P words, an odd stride apart)
-  static const bool no_pu_stage = getenv("PCLEAN_NO_PU_STAGE") != nullptr;
-  // (P | 1) x PU_T words: 84 KB at 20 particles; beyond PU_STAGE_MAX_BYTES of LDS (P >= 37: 64 particles would ask for 266 KB
-  // of the CU's 160) the kernel reads the draws directly, as it did before the staging existed
-  constexpr size_t PU_STAGE_MAX_BYTES = 150 * 1024;
-  int pu_stage_stride = no_pu_stage ? 0 : (P | 1);
-  if ((size_t)pu_stage_stride * PU_T * sizeof(int32_t) > PU_STAGE_MAX_BYTES) pu_stage_stride = 0;
-  const size_t pu_stage_bytes = (size_t)pu_stage_stride * PU_T * sizeof(int32_t);
-  if (pu_stage_bytes > 48 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      HIPCHK(ctx, hipFuncSetAttribute((const void*)particle_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)PU_STAGE_MAX_BYTES));
-      attr_set = true;
-    }
-  }
-  // The first block's log marginal is shared by the particles of a row (no context yet to tell them apart): its launch of
-  // particle_update_kernel stores no weights (w_uni = that block's lse; 160 MB written and read back per 1M rows x 20
-  // particles otherwise) and the next block's update starts from it.  Whoever touches individual weights in between (dummy
-  // corrections, a resampling step, a scoring block, the separate final choice) gets them materialised first.
-  static const bool no_w_uni = getenv("PCLEAN_NO_UNIFORM_W") != nullptr;
-  const double* w_uni = nullptr;
-  auto materialise_w = [&]() {
-    if (!w_uni) return;
-    hipLaunchKernelGGL(materialise_w_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, w_uni, s->w.p);
-    w_uni = nullptr;
-  };
-  bool final_fused = false;            // the last block's particle update made the final choice as well
-  const int32_t* final_only_rows = nullptr;  // ... for the rows outside this flag array (the final choice kernel takes the flagged ones)
-  const bool defer_final_off = false;  // (placeholder of a condition that would forbid it)
-
+  if (const int rc = begin_call(ctx)) return rc;
+  static const SweepSwitches sw;
+  SweepCall call{ctx, st(ctx), cfg, sw, N, P, n_blocks, (size_t)N * P, seed, sweep_idx, use_mh, prior_mode};
+  if (const int rc = sweep_begin(call, cur, dev_cur)) return rc;
   for (int bi = 0; bi < n_blocks; ++bi) {
-    Block& b = ctx->block[bi];
-    BlockRun& r = s->run[bi];
-    if (b.is_score) {
-      // pure scoring block: every particle's weight += sum of its observed choices' log-densities
-      if (bi != n_blocks - 1) return pclean_fail(ctx, PCLEAN_ERR_ARG, "a scoring block must be the last block");
-      ProfScope ps(ctx, "score_block");
-      ScoreBlockDev sb{};
-      auto make_src = [&](int blk, int col, SrcDev& out) -> int {
-        if (blk < 0 || blk >= bi || ctx->block[blk].is_score) return pclean_fail(ctx, PCLEAN_ERR_ARG, "score block: bad source block");
-        const CandTable& rt = ctx->cand[ctx->block[blk].nodes[0].table];
-        if (col < 0 || col >= rt.n_cols) return pclean_fail(ctx, PCLEAN_ERR_ARG, "score block: bad source column");
-        out = SrcDev{s->run[blk].pchoice.p, s->run[blk].pnewpos.p, s->run[blk].vals.p, rt.cols.p + (size_t)col * rt.n_rows,
-                     (int)ctx->block[blk].nodes.size(), col, s->run[blk].plan};
-        return 0;
-      };
-      const FnTable& pf = ctx->fn[b.prob_fn];
-      if (!pf.valid || ctx->n_prob == 0) return pclean_fail(ctx, PCLEAN_ERR_STATE, "score block: prob fn / prob table not set");
-      sb.n_terms = (int)b.score_terms.size();
-      sb.prob_nb = pf.n_b;
-      sb.prob_fn = pf.fn.p;
-      sb.prob_same = ctx->prob_same.p;
-      sb.prob_diff = ctx->prob_diff.p;
-      sb.logn = ctx->logn.p;
-      int rc2 = make_src(b.prob_a_block, b.prob_a_col, sb.pa);
-      if (!rc2) rc2 = make_src(b.prob_b_block, b.prob_b_col, sb.pb);
-      for (int k = 0; k < sb.n_terms && !rc2; ++k) {
-        const ScoreTerm& st_ = b.score_terms[k];
-        const PairTable& pt = ctx->pair[st_.pair_table];
-        const FnTable& nf = ctx->fn[st_.nopt_fn];
-        if (!pt.valid || !nf.valid || st_.obs_col < 0 || st_.obs_col >= ctx->n_cols)
-          return pclean_fail(ctx, PCLEAN_ERR_ARG, "score block: term %d malformed", k);
-        sb.t[k].obs_col = ctx->obs.p + (size_t)st_.obs_col * ctx->n_rows + ctx->active_begin;
-        sb.t[k].pair = pt.d.p;
-        sb.t[k].n_lat = pt.n_lat;
-        sb.t[k].nopt_fn = nf.fn.p;
-        sb.t[k].other_val = st_.other_val;
-        rc2 = make_src(st_.val_block, st_.val_col, sb.t[k].val);
-        if (!rc2) rc2 = make_src(st_.key_block, st_.key_col, sb.t[k].key);
-      }
-      if (rc2) return rc2;
-      materialise_w();
-      hipLaunchKernelGGL(score_block_kernel, grid1(NP), dim3(256), 0, ctx->stream, N, P, sb, s->w.p);
+    if (ctx->block[bi].is_score) {
+      if (const int rc = run_score_block(call, bi)) return rc;
       continue;
     }
-    if (prefetching && bi >= 1) {  // (the refreshed tables of this and the later blocks: one join)
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s->pre_join, 0));
-      prefetching = false;
-    }
-    const int nn = (int)b.nodes.size();
-    const int32_t* cur_b = cur_base + (size_t)bi * cur_ld;
-    if (r.pchoice.alloc(NP) || r.pnewpos.alloc(NP) || r.new_slots.alloc(NP) || r.choice.alloc(N) || r.chosen_newpos.alloc(N) ||
-        r.moved_flag.alloc(N) || r.new_flag.alloc(N) || r.moved_list.alloc(N) || r.new_list.alloc(N))
-      return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-    int rc = ensure_plan_dev(ctx, bi);
-    if (rc) return rc;
-    const bool has_ctx = b.n_ctx > 0;
-    // The contents of a proposed new row matter (a) as context / scored values of LATER blocks — every particle's —
-    // and (b) for the particle that is finally chosen.  For the last block only (b) is left: its sampling is
-    // deferred until after the final choice and done for the chosen particles alone (same Philox counters, so
-    // the values are the ones eager sampling would have produced; typically 20x fewer items).
-    // A chosen ProposalDummyValue changes its particle's weight (apply_dummy_corrections): where one can be drawn
-    // the NEW slots are sampled before the final choice — all of them, or, when every list that can draw its dummy knows
-    // for which observed values (cacheable lists: leaf_udummy), those of the few rows that hold such a value (emit_rows).
-    static const bool eager_all = getenv("PCLEAN_EAGER_NEW") != nullptr;
-    static const bool no_partial = getenv("PCLEAN_NO_PARTIAL_EAGER") != nullptr;
-    bool drawable = prior_mode, dummy_by_row = false;  // (prior draws of a StringPrior choice are the dummy almost surely)
-    if (!prior_mode) {
-      rc = block_dummy_drawable(ctx, bi, &drawable, &dummy_by_row);
-      if (rc) return rc;
-    }
-    const int32_t* emit_rows = nullptr;
-    if (bi == n_blocks - 1 && !eager_all && !no_partial && !prior_mode && drawable && dummy_by_row) {
-      bool none = false;
-      rc = dummy_rows_flags(ctx, bi, N, &emit_rows, &none);
-      if (rc) return rc;
-      if (none) drawable = false;  // the dummy's fixed-point weight is 0 for every row of the window: it cannot be drawn
-    }
-    // last block and nothing between its particle update and the final choice: one fused kernel (particle_update_final_kernel)
-    static const bool no_fuse_final = getenv("PCLEAN_NO_FUSED_FINAL") != nullptr;
-    const bool last_plain = bi == n_blocks - 1 && !prior_mode && !eager_all && !no_fuse_final && !defer_final_off;
-    const bool fuse_final = last_plain && !drawable;
-    // ... and when only a few rows can draw one (emit_rows): those rows take the separate kernels, all the others the fused one
-    const bool split_final = last_plain && drawable && emit_rows != nullptr;
-    // prior proposals, Gaussian term on the slot: scored per particle at own choices sampled from their priors, after the
-    // likelihood terms of the sampled sub-tree (pclean_launch_prior_terms) and before the dummy corrections
-    r.plocals_on = false;
-    auto gauss_prior = [&]() -> int {
-      if (b.node_gauss.empty() || b.node_gauss[0] < 0) return PCLEAN_OK;
-      GaussDev gd;
-      const CandTable& rt = ctx->cand[b.nodes[0].table];
-      const GaussDev* gmore;
-      int n_gmore;
-      int rcg = build_gauss_dev(ctx, b.gauss[b.node_gauss[0]], &rt, gd);
-      if (!rcg) rcg = build_gauss_more(ctx, b, 0, &rt, &gmore, &n_gmore);
-      if (rcg) return rcg;
-      if (r.plocals.alloc((size_t)NP * 2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-      const int32_t* cl = (b.cur_locals.p && b.cur_locals_rows == ctx->n_rows) ? b.cur_locals.p + (size_t)ctx->active_begin * 2 : nullptr;
-      hipLaunchKernelGGL(gauss_prior_kernel, grid1(NP), dim3(256), 0, ctx->stream, N, P, gd, gmore, n_gmore, r.plan, r.pchoice.p,
-                         r.pnewpos.p, r.vals.p, (int)b.nodes.size(), cur_b, cl, seed, sweep_idx, (uint32_t)bi,
-                         s->row_offset + ctx->active_begin, s->w.p, r.plocals.p);
-      r.plocals_on = true;
-      return PCLEAN_OK;
-    };
-    ItemList il;
-    const int32_t* excl;
-    unsigned int* n_new_ctr = nullptr;  // particles of the block that proposed a NEW referent (fresh_counter)
-    SweepState::LazyOut lazy;           // the root kernels left lists instead of draws (last block: enum.h RootExtra)
-    auto lazy_draws = [&]() -> int {    // ... and the chosen particles' draws follow the fused final choice
-      if (!lazy.valid) return PCLEAN_OK;
-      ProfScope psl(ctx, "lazy_draws");
-      lazy.args.n_rows = N;
-      lazy.args.n_particles = P;
-      lazy.args.chosen = s->chosen.p;
-      lazy.args.cur_b = cur_b;
-      lazy.args.pchoice = r.pchoice.p;
-      return pclean_launch_lazy_draws(ctx, lazy.args, seed, sweep_idx, lazy.site);
-    };
-    if (prior_mode) {
-      // every (row, particle) draws its referent from the CRP prior; the block's log marginal plays no part
-      il = ItemList{N, nullptr, nullptr, nullptr, nullptr};
-      excl = cur_b;
-      if (r.draws.alloc(NP) || r.lse.alloc(N)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-      ctx->prior_mode = true;
-      rc = eval_node(ctx, bi, 0, il, excl, seed, sweep_idx, P, nullptr, r.draws.p, nullptr, nullptr, false);
-      if (rc) {
-        ctx->prior_mode = false;
-        return rc;
-      }
-      { const int rcz = dev_zero(ctx, r.lse.p, (size_t)N * sizeof(double)); if (rcz) return rcz; }
-      n_new_ctr = fresh_counter(ctx);
-      if (!n_new_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
-      hipLaunchKernelGGL(particle_update_kernel, dim3((N + PU_T - 1) / PU_T), dim3(PU_T), pu_stage_bytes, ctx->stream, N, P, r.draws.p, r.lse.p,
-                         (const int32_t*)nullptr, (const int32_t*)nullptr, (const double*)nullptr, cur_b, r.pchoice.p,
-                         s->w.p, n_new_ctr, r.new_slots.p, r.pnewpos.p, (w_by_first_block && bi == 0) ? 1 : 0,
-                         (const int32_t*)nullptr, 0, pu_stage_stride, (const double*)nullptr, 0);
-      HIPCHK(ctx, hipGetLastError());
-      if (has_ctx) {  // the particles' contexts: read by the likelihood terms and handed to the new rows' items
-        { const int rci = ensure_it_ctx(ctx, r, NP, b.n_ctx); if (rci) return rci; }
-        CtxSrc cs{};
-        cs.n_ctx = b.n_ctx;
-        for (int c = 0; c < b.n_ctx; ++c) {
-          const int sb = b.ctx_src_block[c];
-          if (sb < 0 || sb >= bi) return pclean_fail(ctx, PCLEAN_ERR_ARG, "block %d: ctx source must be an earlier block", bi);
-          const Block& src = ctx->block[sb];
-          const CandTable& rt = ctx->cand[src.nodes[0].table];
-          if (b.ctx_src_col[c] < 0 || b.ctx_src_col[c] >= rt.n_cols) return pclean_fail(ctx, PCLEAN_ERR_ARG, "ctx column out of range");
-          cs.pchoice[c] = s->run[sb].pchoice.p;
-          cs.pnewpos[c] = s->run[sb].pnewpos.p;
-          cs.vals[c] = s->run[sb].vals.p;
-          cs.n_nodes[c] = (int)src.nodes.size();
-          cs.root_col[c] = rt.cols.p + (size_t)b.ctx_src_col[c] * rt.n_rows;
-          cs.col[c] = b.ctx_src_col[c];
-          cs.plan[c] = s->run[sb].plan;
-        }
-        hipLaunchKernelGGL(gather_ctx_kernel, grid1(NP), dim3(256), 0, ctx->stream, NP, cs, r.it_ctx.p);
-      }
-    } else if (!has_ctx) {
-      il = ItemList{N, nullptr, nullptr, nullptr, nullptr};  // draws row-major [N][P]: one 80-byte store per row
-      excl = cur_b;
-      if (r.draws.alloc(NP) || r.lse.alloc(N)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-      if (fuse_final || split_final) s->lazy_req = SweepState::LazyReq{true, split_final ? emit_rows : nullptr};
-      rc = eval_node(ctx, bi, 0, il, excl, seed, sweep_idx, P, r.lse.p, r.draws.p, nullptr, nullptr, bi == ctx->timed_block);
-      s->lazy_req = SweepState::LazyReq();
-      if (rc) return rc;
-      lazy = s->lazy_out;
-      s->lazy_out.valid = false;
-      if (bi == ctx->timed_block) {  // (the elapsed time of the launch is read at the end of the call: no synchronisation here)
-        hot_timed = true;
-        ctx->timing.hot_kernel_launches += 1;
-      }
-      ProfScope ps(ctx, "particle_update");
-      if (fuse_final) {
-        DISPATCH_PMAX(P, hipLaunchKernelGGL(particle_update_final_kernel<PMAX>, grid1(N), dim3(256), 0, ctx->stream, N, P, r.draws.p,
-                                            r.lse.p, (const int32_t*)nullptr, (const int32_t*)nullptr, (const double*)nullptr, cur_b,
-                                            r.pchoice.p, s->w.p, (w_by_first_block && bi == 0) ? 1 : 0, use_mh, cur_base, seed,
-                                            sweep_idx, s->row_offset + ctx->active_begin, s->chosen.p, s->logml_acc.p, s->logml.p,
-                                            (const int32_t*)nullptr, lazy.valid ? 1 : 0, w_uni));
-        final_fused = true;
-        { const int rcl = lazy_draws(); if (rcl) return rcl; }
-      } else {
-      n_new_ctr = fresh_counter(ctx);
-      if (!n_new_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
-      // (the first block of several: its weights are the block's log marginal for every particle of a row — not stored)
-      const bool skip_w = bi == 0 && w_by_first_block && bi < n_blocks - 1 && !split_final && !emit_rows && !no_w_uni;
-      hipLaunchKernelGGL(particle_update_kernel, dim3((N + PU_T - 1) / PU_T), dim3(PU_T), pu_stage_bytes, ctx->stream, N, P, r.draws.p, r.lse.p,
-                         (const int32_t*)nullptr, (const int32_t*)nullptr, (const double*)nullptr, cur_b, r.pchoice.p,
-                         s->w.p, n_new_ctr, r.new_slots.p, r.pnewpos.p, (w_by_first_block && bi == 0) ? 1 : 0, emit_rows, split_final ? 1 : 0,
-                         pu_stage_stride, w_uni, skip_w ? 1 : 0);
-      HIPCHK(ctx, hipGetLastError());
-      if (skip_w)
-        w_uni = r.lse.p;
-      else if (!split_final)
-        w_uni = nullptr;  // (every row's weights are in w now)
-      if (split_final) {
-        DISPATCH_PMAX(P, hipLaunchKernelGGL(particle_update_final_kernel<PMAX>, grid1(N), dim3(256), 0, ctx->stream, N, P, r.draws.p,
-                                            r.lse.p, (const int32_t*)nullptr, (const int32_t*)nullptr, (const double*)nullptr, cur_b,
-                                            r.pchoice.p, s->w.p, (w_by_first_block && bi == 0) ? 1 : 0, use_mh, cur_base, seed,
-                                            sweep_idx, s->row_offset + ctx->active_begin, s->chosen.p, s->logml_acc.p, s->logml.p,
-                                            emit_rows, lazy.valid ? 1 : 0, w_uni));
-        final_only_rows = emit_rows;
-        { const int rcl = lazy_draws(); if (rcl) return rcl; }
-      }
-      }
-    } else {
-      { const int rci = ensure_it_ctx(ctx, r, NP, b.n_ctx); if (rci) return rci; }
-      CtxSrc cs{};
-      cs.n_ctx = b.n_ctx;
-      for (int c = 0; c < b.n_ctx; ++c) {
-        const int sb = b.ctx_src_block[c];
-        if (sb < 0 || sb >= bi) return pclean_fail(ctx, PCLEAN_ERR_ARG, "block %d: ctx source must be an earlier block", bi);
-        const Block& src = ctx->block[sb];
-        const CandTable& rt = ctx->cand[src.nodes[0].table];
-        if (b.ctx_src_col[c] < 0 || b.ctx_src_col[c] >= rt.n_cols) return pclean_fail(ctx, PCLEAN_ERR_ARG, "ctx column out of range");
-        cs.pchoice[c] = s->run[sb].pchoice.p;
-        cs.pnewpos[c] = s->run[sb].pnewpos.p;
-        cs.vals[c] = s->run[sb].vals.p;
-        cs.n_nodes[c] = (int)src.nodes.size();
-        cs.root_col[c] = rt.cols.p + (size_t)b.ctx_src_col[c] * rt.n_rows;
-        cs.col[c] = b.ctx_src_col[c];
-        cs.plan[c] = s->run[sb].plan;
-      }
-      // One enumeration per distinct (row, context): particles whose earlier choices give the same
-      // context share the candidate scores and differ only in their Philox draws.
-      int32_t* slot_item = scratch<int32_t>(ctx, NP);
-      if (!slot_item) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      unsigned int n_items = 0;
-      int32_t *d_row = nullptr, *d_ctx = nullptr, *d_excl = nullptr;
-      static const bool no_fused_items = getenv("PCLEAN_NO_FUSED_CTX_ITEMS") != nullptr;
-      if (!no_fused_items) {
-        // one pass (ctx_items_kernel): item i = row i with particle 0's context, extra items behind them; room for the extra
-        // items from the last sweep's number (a sweep that needs more runs the kernel again)
-        ProfScope ps(ctx, "ctx_items");
-        for (int attempt = 0;; ++attempt) {
-          const int cap = std::max(r.ctx_extra_cap, 4096);
-          d_row = scratch<int32_t>(ctx, (size_t)N + cap);
-          d_ctx = scratch<int32_t>(ctx, ((size_t)N + cap) * PCLEAN_MAX_CTX);
-          d_excl = scratch<int32_t>(ctx, (size_t)N + cap);
-          unsigned int* extra_ctr = fresh_counter(ctx);
-          if (!d_row || !d_ctx || !d_excl || !extra_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-          hipLaunchKernelGGL(ctx_items_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, cs, cur_b, r.it_ctx.p, slot_item, d_row, d_ctx,
-                             d_excl, extra_ctr, cap);
-          unsigned int n_extra = 0;
-          PCLEAN_READ_COUNT(ctx, extra_ctr, &n_extra);
-          r.ctx_extra_cap = (int)std::min<size_t>((size_t)n_extra * 2 + 4096, NP);
-          if (n_extra <= (unsigned int)cap) {
-            n_items = (unsigned int)N + n_extra;
-            break;
-          }
-          if (attempt >= 2) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_sweep: the context items did not fit twice in a row");
-        }
-      } else {
-      int32_t* rep = scratch<int32_t>(ctx, NP);
-      int32_t* n_distinct = scratch<int32_t>(ctx, (size_t)N + 1);
-      int32_t* off = scratch<int32_t>(ctx, (size_t)N + 1);
-      size_t tmp_scan = 0;
-      HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, n_distinct, off, N + 1, ctx->stream));
-      unsigned char* tmp = scratch<unsigned char>(ctx, tmp_scan);
-      if (!rep || !n_distinct || !off || !tmp) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      {
-        ProfScope ps(ctx, "ctx_items");
-        hipLaunchKernelGGL(gather_ctx_kernel, grid1(NP), dim3(256), 0, ctx->stream, NP, cs, r.it_ctx.p);
-        HIPCHK(ctx, hipMemsetAsync(n_distinct + N, 0, sizeof(int32_t), ctx->stream));
-        hipLaunchKernelGGL(ctx_count_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, (int)b.n_ctx, r.it_ctx.p, rep, n_distinct);
-        HIPCHK(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_scan, n_distinct, off, N + 1, ctx->stream));
-        PCLEAN_READ_COUNT(ctx, off + N, &n_items);
-      }
-      d_row = scratch<int32_t>(ctx, n_items);
-      d_ctx = scratch<int32_t>(ctx, (size_t)n_items * PCLEAN_MAX_CTX);
-      d_excl = scratch<int32_t>(ctx, n_items);
-      if (!d_row || !d_ctx || !d_excl) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      hipLaunchKernelGGL(ctx_fill_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, (int)b.n_ctx, r.it_ctx.p, rep, off, cur_b, slot_item,
-                         d_row, d_ctx, d_excl);
-      }
-      double* lse_item = scratch<double>(ctx, n_items);
-      int32_t* draws_item = scratch<int32_t>(ctx, (size_t)n_items * P);
-      if (!lse_item || !draws_item) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      il = ItemList{(int)n_items, d_row, d_ctx, nullptr, nullptr};
-      if (!no_fused_items) il.n_primary = N;  // (ctx_items_kernel: item i < N is row i; ctx_fill_kernel numbers row by row)
-      if (fuse_final || split_final) s->lazy_req = SweepState::LazyReq{true, split_final ? emit_rows : nullptr};
-      rc = eval_node(ctx, bi, 0, il, d_excl, seed, sweep_idx, P, lse_item, draws_item, nullptr, nullptr, bi == ctx->timed_block);
-      s->lazy_req = SweepState::LazyReq();
-      if (rc) return rc;
-      if (bi == ctx->timed_block) {
-        hot_timed = true;
-        ctx->timing.hot_kernel_launches += 1;
-      }
-      lazy = s->lazy_out;
-      s->lazy_out.valid = false;
-      lazy.args.slot_item = slot_item;
-      ProfScope ps(ctx, "particle_update");
-      if (fuse_final) {
-        DISPATCH_PMAX(P, hipLaunchKernelGGL(particle_update_final_kernel<PMAX>, grid1(N), dim3(256), 0, ctx->stream, N, P,
-                                            (const int32_t*)nullptr, (const double*)nullptr, slot_item, draws_item, lse_item, cur_b,
-                                            r.pchoice.p, s->w.p, (w_by_first_block && bi == 0) ? 1 : 0, use_mh, cur_base, seed,
-                                            sweep_idx, s->row_offset + ctx->active_begin, s->chosen.p, s->logml_acc.p, s->logml.p,
-                                            (const int32_t*)nullptr, lazy.valid ? 1 : 0, w_uni));
-        final_fused = true;
-        { const int rcl = lazy_draws(); if (rcl) return rcl; }
-      } else {
-      n_new_ctr = fresh_counter(ctx);
-      if (!n_new_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
-      hipLaunchKernelGGL(particle_update_kernel, dim3((N + PU_T - 1) / PU_T), dim3(PU_T), 0, ctx->stream, N, P, (const int32_t*)nullptr,
-                         (const double*)nullptr, slot_item, draws_item, lse_item, cur_b, r.pchoice.p, s->w.p,
-                         n_new_ctr, r.new_slots.p, r.pnewpos.p, (w_by_first_block && bi == 0) ? 1 : 0, emit_rows, split_final ? 1 : 0, 0,
-                         w_uni, 0);
-      if (!split_final) w_uni = nullptr;  // (every row's weights are in w now)
-      if (split_final) {
-        DISPATCH_PMAX(P, hipLaunchKernelGGL(particle_update_final_kernel<PMAX>, grid1(N), dim3(256), 0, ctx->stream, N, P,
-                                            (const int32_t*)nullptr, (const double*)nullptr, slot_item, draws_item, lse_item, cur_b,
-                                            r.pchoice.p, s->w.p, (w_by_first_block && bi == 0) ? 1 : 0, use_mh, cur_base, seed,
-                                            sweep_idx, s->row_offset + ctx->active_begin, s->chosen.p, s->logml_acc.p, s->logml.p,
-                                            emit_rows, lazy.valid ? 1 : 0, w_uni));
-        final_only_rows = emit_rows;
-        { const int rcl = lazy_draws(); if (rcl) return rcl; }
-      }
-      }
-    }
-    // ---- particles that proposed a NEW referent: sample the new row's contents
-    if (!prefetch_started) {  // (this block's kernels are queued: the host has time for the later blocks' table refresh)
-      const int rcp = start_prefetch();
-      if (rcp) return rcp;
-    }
-    unsigned int n_new = 0;
-    if (!final_fused) PCLEAN_READ_COUNT(ctx, n_new_ctr, &n_new);  // (fused with the final choice: nothing is sampled now, nobody asks)
-    const bool degenerate_rows = (n_new & 0x80000000u) != 0u;  // some row's block marginal is -inf (particle_update_kernel)
-    n_new &= 0x7fffffffu;
-    r.n_new = final_fused ? -1 : (int)n_new;
-    r.lazy_new = final_fused || (bi == n_blocks - 1 && !eager_all && (!drawable || emit_rows != nullptr));
-    if (r.lazy_new && !emit_rows) n_new = 0;  // nothing sampled now
-    if (emit_rows) r.n_new = -1;  // (the list held the flagged rows' slots only: whether anybody proposed a NEW referent is not known)
-    if (r.vals.alloc(std::max<size_t>((size_t)n_new * nn, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-    if (n_new) {
-      ProfScope ps(ctx, "new_row_sampling");
-      const int32_t* list = r.new_slots.p;
-      hipLaunchKernelGGL(fill_i32_kernel, grid1((size_t)n_new * nn), dim3(256), 0, ctx->stream, r.vals.p,
-                         (size_t)n_new * nn, -2);
-      int32_t* row = scratch<int32_t>(ctx, n_new);
-      int32_t* cx = scratch<int32_t>(ctx, (size_t)n_new * PCLEAN_MAX_CTX);
-      int32_t* part = scratch<int32_t>(ctx, n_new);
-      int32_t* org = scratch<int32_t>(ctx, n_new);
-      int32_t* ex = scratch<int32_t>(ctx, n_new);
-      if (!row || !cx || !part || !org || !ex) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      hipLaunchKernelGGL(rootlist_items_kernel, grid1(n_new), dim3(256), 0, ctx->stream, (int)n_new, N, NP, list,
-                         has_ctx ? r.it_ctx.p : nullptr, cur_b, row, cx, part, org, ex);
-      hipLaunchKernelGGL(set_col_kernel, grid1(n_new), dim3(256), 0, ctx->stream, (int)n_new, nn, 0,
-                         (int32_t)PCLEAN_CHOICE_NEW, r.vals.p);
-      ItemList sub{(int)n_new, row, cx, part, org};
-      rc = sample_children(ctx, bi, 0, sub, ex, seed, sweep_idx, r.vals.p, nn);
-      if (rc) return rc;
-      if (prior_mode) {
-        ctx->prior_mode = false;
-        const NodeDev* nds;
-        const int32_t *dnc, *dcb, *dch;
-        rc = upload_plan_nodes(ctx, bi, &nds, &dnc, &dcb, &dch);
-        if (!rc)
-          rc = pclean_launch_prior_terms(ctx, NP, N, nn, nds, dnc, dcb, dch, r.pchoice.p, r.pnewpos.p, r.vals.p,
-                                         has_ctx ? r.it_ctx.p : nullptr, s->w.p);
-        if (!rc) rc = gauss_prior();
-        if (rc) return rc;
-      }
-      if (drawable) {
-        if (!split_final) materialise_w();  // (split: the flagged rows' weights were stored, nobody looks at the others')
-        rc = apply_dummy_corrections(ctx, bi, r.new_slots.p, r.vals.p, (int)n_new, N, seed, sweep_idx, s->w.p);
-        if (rc) return rc;
-      }
-    } else if (prior_mode) {  // nobody proposed a new referent: the likelihood of the chosen referents alone
-      ctx->prior_mode = false;
-      const NodeDev* nds;
-      const int32_t *dnc, *dcb, *dch;
-      rc = upload_plan_nodes(ctx, bi, &nds, &dnc, &dcb, &dch);
-      if (!rc)
-        rc = pclean_launch_prior_terms(ctx, NP, N, nn, nds, dnc, dcb, dch, r.pchoice.p, r.pnewpos.p, r.vals.p,
-                                       has_ctx ? r.it_ctx.p : nullptr, s->w.p);
-      if (!rc) rc = gauss_prior();
-      if (rc) return rc;
-    }
-    ctx->prior_mode = false;
-    // (pnewpos is only read where pchoice == NEW, so it needs no initialisation when nobody proposed one)
-
-    // ---- resampling between blocks (row_inference.jl:152-155)
-    const int grp_here = b.group >= 0 ? b.group : bi;
-    const int grp_next = bi + 1 < n_blocks ? (ctx->block[bi + 1].group >= 0 ? ctx->block[bi + 1].group : bi + 1) : -2;
-    // After the FIRST block of a sweep every particle of a row carries the same weight — the block's log marginal, shared by
-    // the particles (no context yet to tell them apart) — unless a dummy-value correction or a prior-mode likelihood touched
-    // individual particles: the effective sample size is exactly P, maybe_resample (row_inference.jl:87-105) keeps every
-    // particle and adds 0 to the log-ML estimate (a row whose marginal is -inf has total weight 0 and IS resampled: those
-    // rows are reported through bit 31 of the NEW-slot counter).  Two kernels over all rows that can only ever do nothing are
-    // not launched.
-    const bool equal_weights = bi == 0 && w_by_first_block && !has_ctx && !prior_mode && !(drawable && n_new > 0) && !degenerate_rows;
-    static const bool always_resample = getenv("PCLEAN_ALWAYS_RESAMPLE") != nullptr;
-    if (!use_mh && bi < n_blocks - 1 && grp_here != grp_next && (!equal_weights || always_resample)) {  // (the slots of one model block: no resampling in between)
-      ProfScope ps(ctx, "resample");
-      materialise_w();
-      DISPATCH_PMAX(P, hipLaunchKernelGGL(maybe_resample_kernel<PMAX>, grid1(N), dim3(256), 0, ctx->stream, N, P, s->w.p,
-                                          (size_t)1, (size_t)N, 1, cur_b, seed, sweep_idx, (uint32_t)bi,
-                                          s->row_offset + ctx->active_begin, s->ancestors.p, s->logml_inc.p,
-                                          (double*)nullptr, s->did.p));
-      AncestorArrays arrs{};
-      int n_arr = 0;
-      for (int k = 0; k <= bi; ++k) {
-        if (ctx->block[k].is_score) continue;
-        arrs.p[n_arr++] = s->run[k].pchoice.p;
-        arrs.p[n_arr++] = s->run[k].pnewpos.p;
-        if (s->run[k].plocals_on) arrs.pairs[arrs.n_pairs++] = reinterpret_cast<int64_t*>(s->run[k].plocals.p);
-      }
-      hipLaunchKernelGGL(apply_ancestors_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, s->ancestors.p, n_arr, arrs, s->w.p,
-                         s->did.p, s->logml_inc.p, s->logml_acc.p);
-    }
+    BlockStep bs;
+    bool weights_touched = false;
+    if (const int rc = propose_block(call, bi, bs)) return rc;
+    if (const int rc = new_rows_of_block(call, bi, bs, &weights_touched)) return rc;
+    if (const int rc = resample_between_blocks(call, bi, weights_touched)) return rc;
   }
-
-  if (prefetching) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, s->pre_join, 0));  // (no later block took it)
-  // ---- final choice + per-block outputs: one pass per block, ordered compaction of the rows that moved /
-  // got a new referent (hipcub select keeps ascending row order), ONE read-back of the counts
+  if (call.prefetching) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, call.s->pre_join, 0));  // (no later block took it)
   {
     ProfScope ps(ctx, "final_choice_and_outputs");
-    if (!final_fused && !final_only_rows) materialise_w();  // (never pending here: a plain update of every row stored them)
-    if (!final_fused)
-    DISPATCH_PMAX(P, hipLaunchKernelGGL(final_choice_kernel<PMAX>, grid1(N), dim3(256), 0, ctx->stream, N, P, s->w.p,
-                                        (size_t)1, (size_t)N, use_mh, 1, cur_base, seed, sweep_idx,
-                                        s->row_offset + ctx->active_begin, s->chosen.p, (double*)nullptr,
-                                        s->logml_acc.p, s->logml.p, final_only_rows));
-    // PCLEAN_NO_FUSED_FINALIZE=1: chosen_new_kernel + one finalize_block_kernel per block (the launches finalize_tail_kernel
-    // replaces); PCLEAN_TAIL_WGS=<n>: workgroups per block of finalize_tail_kernel
-    static const bool no_fused_finalize = getenv("PCLEAN_NO_FUSED_FINALIZE") != nullptr;
-    static const int forced_tail_wgs = getenv("PCLEAN_TAIL_WGS") ? std::max(1, atoi(getenv("PCLEAN_TAIL_WGS"))) : 0;
-    static const bool trace_tail = getenv("PCLEAN_TRACE_SYNC") != nullptr;
-    unsigned int* chosen_ctr[PCLEAN_MAX_BLOCKS] = {};  // blocks whose chosen NEW rows are listed: the list's length
-    // deferred new-row contents of the last block (chosen particles only): the listed slots' rows are sampled
-    auto sample_chosen = [&](int bi) -> int {
-      BlockRun& r = s->run[bi];
-      Block& bb = ctx->block[bi];
-      ProfScope ps2(ctx, "new_row_sampling_chosen");
-      const int nn = (int)bb.nodes.size();
-      const int32_t* cur_b = cur_base + (size_t)bi * cur_ld;
-      unsigned int cnt = 0;
-      PCLEAN_READ_COUNT(ctx, chosen_ctr[bi], &cnt);
-      if (trace_tail) fprintf(stderr, "[pclean tail] block %d: %u chosen NEW rows listed by %s\n", bi, cnt,
-                              no_fused_finalize ? "chosen_new_kernel" : "finalize_tail_kernel");
-      if (r.vals.alloc(std::max<size_t>((size_t)cnt * nn, 1))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-      if (!cnt) return PCLEAN_OK;
-      hipLaunchKernelGGL(fill_i32_kernel, grid1((size_t)cnt * nn), dim3(256), 0, ctx->stream, r.vals.p, (size_t)cnt * nn, -2);
-      int32_t* row = scratch<int32_t>(ctx, cnt);
-      int32_t* cx = scratch<int32_t>(ctx, (size_t)cnt * PCLEAN_MAX_CTX);
-      int32_t* part = scratch<int32_t>(ctx, cnt);
-      int32_t* org = scratch<int32_t>(ctx, cnt);
-      int32_t* ex = scratch<int32_t>(ctx, cnt);
-      if (!row || !cx || !part || !org || !ex) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      hipLaunchKernelGGL(rootlist_items_kernel, grid1(cnt), dim3(256), 0, ctx->stream, (int)cnt, N, NP, r.new_slots.p,
-                         bb.n_ctx > 0 ? r.it_ctx.p : nullptr, cur_b, row, cx, part, org, ex);
-      hipLaunchKernelGGL(set_col_kernel, grid1(cnt), dim3(256), 0, ctx->stream, (int)cnt, nn, 0, (int32_t)PCLEAN_CHOICE_NEW,
-                         r.vals.p);
-      ItemList sub{(int)cnt, row, cx, part, org};
-      return sample_children(ctx, bi, 0, sub, ex, seed, sweep_idx, r.vals.p, nn);
-    };
-    for (int bi = 0; bi < n_blocks; ++bi) {
-      BlockRun& r = s->run[bi];
-      if (ctx->block[bi].is_score || !r.lazy_new || r.n_new == 0) continue;
-      chosen_ctr[bi] = fresh_counter(ctx);
-      if (!chosen_ctr[bi]) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
-      if (!no_fused_finalize) continue;  // (finalize_tail_kernel lists them; sampled behind the tail kernels)
-      hipLaunchKernelGGL(chosen_new_kernel, grid1(N), dim3(256), 0, ctx->stream, N, s->chosen.p, r.pchoice.p, chosen_ctr[bi],
-                         r.new_slots.p, r.pnewpos.p);
-      const int rc = sample_chosen(bi);
-      if (rc) return rc;
-    }
-    const int nb_wg = (N + TAIL_TILE_ROWS - 1) / TAIL_TILE_ROWS;
-    unsigned int* wg_cnt = scratch<unsigned int>(ctx, (size_t)2 * n_blocks * nb_wg);
-    if (!wg_cnt) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-    TailLists tl{};
-    // the tables' delta reference counts start at zero: one kernel over every root table instead of a memset apiece
-    {
-      ZeroList zl{};
-      for (int bi = 0; bi < n_blocks; ++bi) {
-        if (ctx->block[bi].is_score) continue;
-        CandTable& rt = ctx->cand[ctx->block[bi].nodes[0].table];
-        bool seen = false;
-        for (int k = 0; k < zl.n; ++k) seen |= zl.p[k] == (void*)rt.stats.p;
-        if (!seen) zero_list_add(ctx, zl, rt.stats.p, (size_t)std::max(rt.n_rows, 1) * 8);
-      }
-      const int rcz = zero_list_flush(ctx, zl);
-      if (rcz) return rcz;
-    }
-    TailBlocks tb{};
-    int max_hist = 0;
-    for (int bi = 0; bi < n_blocks; ++bi) {
-      BlockRun& r = s->run[bi];
-      Block& bb = ctx->block[bi];
-      bb.locals_host.clear();
-      r.locals_rows = 0;
-      if (bb.is_score) continue;
-      const int32_t* cur_b = cur_base + (size_t)bi * cur_ld;
-      CandTable& rt = ctx->cand[bb.nodes[0].table];
-      // (an LDS histogram per workgroup: a few rows take most of the moves — 28 true measures for 1M records.  It covers the
-      // rows below the table's high-water mark only: nobody refers to, or chooses, the spare capacity behind it, and zeroing
-      // + flushing the counters of 8 240 rows in each of 4 000 workgroups was 0.05 ms per sweep)
-      const int rows_in_use = (rt.n_used > 0 && rt.n_used <= rt.n_rows) ? std::min(rt.n_rows, (rt.n_used + 63) & ~63) : rt.n_rows;
-      static const bool no_hist = getenv("PCLEAN_NO_HIST") != nullptr;  // (measurement switch: plain atomics for every table)
-      const int hist_rows = (rt.n_rows <= 12288 && !no_hist) ? rows_in_use : 0;  // (48 KB of LDS per workgroup at most; larger tables: plain atomics)
-      if (no_fused_finalize) {
-        hipLaunchKernelGGL(finalize_block_kernel, grid1(N), dim3(256), (size_t)hist_rows * sizeof(int32_t), ctx->stream, N,
-                           s->chosen.p, r.pchoice.p, r.pnewpos.p, cur_b, r.choice.p, r.chosen_newpos.p,
-                           (unsigned long long*)rt.stats.p, hist_rows, r.moved_flag.p, r.new_flag.p,
-                           wg_cnt + (size_t)(2 * bi) * nb_wg, wg_cnt + (size_t)(2 * bi + 1) * nb_wg);
-      } else {
-        TailBlock& t = tb.b[bi];
-        t.pchoice = r.pchoice.p;
-        t.pnewpos = r.pnewpos.p;
-        t.cur_b = cur_b;
-        t.choice = r.choice.p;
-        t.chosen_newpos = r.chosen_newpos.p;
-        t.stats = (unsigned long long*)rt.stats.p;
-        t.moved_flag = r.moved_flag.p;
-        t.new_flag = r.new_flag.p;
-        t.wg_moved = wg_cnt + (size_t)(2 * bi) * nb_wg;
-        t.wg_new = wg_cnt + (size_t)(2 * bi + 1) * nb_wg;
-        t.new_ctr = chosen_ctr[bi];
-        t.new_slots = r.new_slots.p;
-        t.hist_rows = hist_rows;
-        t.on = 1;
-        t.lazy = chosen_ctr[bi] ? 1 : 0;
-        max_hist = std::max(max_hist, hist_rows);
-      }
-      tl.flag[2 * bi] = r.moved_flag.p;
-      tl.list[2 * bi] = r.moved_list.p;
-      tl.flag[2 * bi + 1] = r.new_flag.p;
-      tl.list[2 * bi + 1] = r.new_list.p;
-    }
-    if (!no_fused_finalize) {
-      // a capped grid, each workgroup walking a contiguous range of tiles (tail_tiles.h; DESIGN.md §6: the count)
-      static int tail_cap = 0;
-      if (!tail_cap) {
-        int n_cu = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        tail_cap = std::max(1, n_cu / TAIL_CUS_PER_WG);
-      }
-      const int n_wgs = tail_wg_count(nb_wg, tail_cap, forced_tail_wgs);
-      if (trace_tail)
-        fprintf(stderr, "[pclean tail] finalize_tail_kernel: %d tiles, %d workgroups per block, at most %d tiles per workgroup\n",
-                nb_wg, n_wgs, (nb_wg + n_wgs - 1) / n_wgs);
-      hipLaunchKernelGGL(finalize_tail_kernel, dim3(n_wgs, n_blocks), dim3(TAIL_WG_THREADS), (size_t)max_hist * sizeof(int32_t), ctx->stream, N,
-                         nb_wg, s->chosen.p, tb);
-    } else if (trace_tail) {
-      fprintf(stderr, "[pclean tail] finalize_block_kernel: one launch per block\n");
-    }
-    {  // (a scoring block's two slots: their workgroup counts were never written — zero them so that the totals read 0)
-      for (int bi = 0; bi < n_blocks; ++bi)
-        if (ctx->block[bi].is_score)
-          HIPCHK(ctx, hipMemsetAsync(wg_cnt + (size_t)(2 * bi) * nb_wg, 0, (size_t)2 * nb_wg * sizeof(unsigned int), ctx->stream));
-      hipLaunchKernelGGL(tail_scan_kernel, dim3(2 * n_blocks), dim3(1024), 0, ctx->stream, nb_wg, wg_cnt, s->tail_counts.p);
-      hipLaunchKernelGGL(tail_scatter_kernel, dim3(nb_wg, 2 * n_blocks), dim3(256), 0, ctx->stream, N, nb_wg, tl, wg_cnt);
-    }
-    if (!no_fused_finalize)  // the listed rows' contents: nothing above needed them
-      for (int bi = 0; bi < n_blocks; ++bi)
-        if (chosen_ctr[bi]) {
-          const int rc = sample_chosen(bi);
-          if (rc) return rc;
-        }
-    for (int bi = 0; bi < n_blocks; ++bi) {  // per-row outputs that read the new rows' contents
-      BlockRun& r = s->run[bi];
-      Block& bb = ctx->block[bi];
-      if (bb.is_score) continue;
-      CandTable& rt = ctx->cand[bb.nodes[0].table];
-      if (choice)
-        HIPCHK(ctx, hipMemcpyAsync(choice + (size_t)bi * N, r.choice.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-      if (!bb.node_gauss.empty() && bb.node_gauss[0] >= 0 && bb.gauss[bb.node_gauss[0]].n_locals > 0) {
-        if (r.locals.alloc((size_t)N * 2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-        if (r.plocals_on) {  // prior proposals: what the chosen particle sampled (or kept)
-          hipLaunchKernelGGL(locals_pick_kernel, grid1(N), dim3(256), 0, ctx->stream, N, s->chosen.p, r.plocals.p, r.locals.p);
-        } else {
-          GaussDev gd;
-          const GaussDev* gmore;
-          int n_gmore;
-          int rc = build_gauss_dev(ctx, bb.gauss[bb.node_gauss[0]], &rt, gd);
-          if (!rc) rc = build_gauss_more(ctx, bb, 0, &rt, &gmore, &n_gmore);
-          if (rc) return rc;
-          hipLaunchKernelGGL(locals_tail_kernel, grid1(N), dim3(256), 0, ctx->stream, N, P, gd, gmore, n_gmore, r.plan, s->chosen.p,
-                             r.pchoice.p, r.pnewpos.p, r.vals.p, (int)bb.nodes.size(), seed, sweep_idx, (uint32_t)bi,
-                             s->row_offset + ctx->active_begin, r.locals.p);
-        }
-        r.locals_rows = N;
-        if (!defer) {  // (deferred outputs: pclean_get_locals copies them when asked)
-          bb.locals_host.resize((size_t)N * 2);
-          HIPCHK(ctx, hipMemcpyAsync(bb.locals_host.data(), r.locals.p, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-      }
-    }
-    (void)hipEventRecord(s->eve, ctx->stream);
-    if (chosen_particle) HIPCHK(ctx, hipMemcpyAsync(chosen_particle, s->chosen.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (logml) HIPCHK(ctx, hipMemcpyAsync(logml, s->logml.p, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
+    final_choice(call);
+    if (const int rc = sweep_tail(call)) return rc;
+    if (const int rc = block_outputs(call, choice, chosen_particle, logml)) return rc;
   }
-  s->last_hot_timed = hot_timed;
-  s->outputs_pending = true;
-  s->lists_on_host = false;
-  {
-    // bytes(row) = sum_b [4 F_b + (K_b+1)(8 F_b + 4)] + 8 P (full enumeration); reported beside the
-    // byte model of the implemented algorithm (bench.py)
-    const Block& b0 = ctx->block[(ctx->timed_block >= 0 && ctx->timed_block < n_blocks && !ctx->block[ctx->timed_block].is_score) ? ctx->timed_block : 0];
-    const double F = b0.nodes[0].n_terms, K = ctx->cand[b0.nodes[0].table].n_rows;
-    ctx->timing.hot_kernel_alg_bytes = (double)N * (4.0 * F + (K + 1.0) * (8.0 * F + 4.0) + 8.0 * P);
-  }
-  if (defer) return PCLEAN_OK;  // nothing read back, no synchronisation: pclean_commit_device / pclean_sweep_fetch finish the call
-  int rcf = pclean_sweep_finish_queue(ctx);
-  if (rcf) return rcf;
-  PCLEAN_SYNC(ctx);
-  rcf = pclean_sweep_finish_synced(ctx);
-  if (rcf) return rcf;
-  if (choice)
-    for (int bi = 0; bi < n_blocks; ++bi)
-      if (ctx->block[bi].is_score)
-        for (int i = 0; i < N; ++i) choice[(size_t)bi * N + i] = 0;
-  return pclean_sweep_fetch_lists(ctx);
+  return sweep_end(call, choice);
 }
 
 // ---- end of a sweep, in three steps so that a caller with more work for the stream (pclean_commit_device) pays ONE

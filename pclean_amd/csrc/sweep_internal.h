@@ -196,8 +196,6 @@ __device__ __forceinline__ int fix_pick(const FixW<PMAX>& f, int P, uint64_t R) 
   } while (0)
 
 // ---- small kernels -------------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
-// small kernels
 static __global__ void iota_missing_kernel(int32_t* p, int n_obs) {  // [0..n_obs-1, -1]
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n_obs) p[i] = i < n_obs ? i : -1;
