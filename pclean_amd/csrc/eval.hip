@@ -347,8 +347,6 @@ static int prefilter_terms(pclean_ctx* ctx, const Block& b, const pclean_node& n
   return n_pre;
 }
 
-// Fast path of a reference slot (root_wave.hip): returns 1 and fills `fr` when the node is an FK
-// with many candidates whose terms are all plain AddTypos lookups in byte tables; 0 otherwise.
 // The rows the host's re-uploads of table t rewrote between cols_version `base` and the current one (CandTable::delta_log),
 // on the device (t.union_rows, memoised per base).  Returns 1 with *n_out rows, 0 when no chain of known deltas leads from
 // `base` to the current version (or the union is not worth it), < 0 on errors.
@@ -409,251 +407,368 @@ static bool node_has_tabulated(const Block& b, const pclean_node& n) {
   return false;
 }
 
-static int try_fast_root(pclean_ctx* ctx, int block_id, int node_id, FastRootDev& fr, bool ev_mode = false) {
-  Block& b = ctx->block[block_id];
-  if (node_id >= 64) return 0;
-  const pclean_node& n = b.nodes[node_id];
-  const CandTable& t = ctx->cand[n.table];
-  const bool leaf = n.kind == PCLEAN_NODE_LEAF;
-  static const bool no_leaf = getenv("PCLEAN_NO_FAST_LEAF") != nullptr;
-  if (!t.valid || t.n_rows < 1024 || n.n_terms < 1 || n.n_terms > PCLEAN_MAX_TERMS || (leaf && no_leaf)) return 0;
-  if (leaf != t.is_options || node_has_tabulated(b, n)) return 0;
+// ---- the switches of eval_node and try_fast_root (DESIGN.md §6 lists both groups) -----------------------------------------
+static bool env_on(const char* name) { return getenv(name) != nullptr; }
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+struct EvalSwitches {
+  struct Cached {  // read once per process (once(): a function-local static const)
+    const bool no_fast_leaf = env_on("PCLEAN_NO_FAST_LEAF");      // option lists never take the compact-table kernels
+    const bool no_delta = env_on("PCLEAN_NO_COMPACT_DELTA");      // compact tables are rebuilt whole, never refreshed row by row
+    const bool no_chain = env_on("PCLEAN_NO_DELTA_CHAIN");        // ... not along a chain of upload deltas
+    const bool dbg_chain = env_on("PCLEAN_DEBUG_CHAIN");          // one "[chain] ..." line per decision about such a chain
+    const bool no_obs_rm = env_on("PCLEAN_NO_OBS_ROWMAJOR");      // no row-major copy of the observed values
+    const bool no_kscan = env_on("PCLEAN_NO_KSCAN");              // the scans walk a table's spare capacity too
+    const bool no_lazy = env_on("PCLEAN_NO_LAZY_DRAWS");          // the sweep's last block leaves draws, never lists
+    const bool lazy_split = env_on("PCLEAN_LAZY_SPLIT");          // large groups are cut into pieces under lazy draws too
+    const bool no_group_gate = env_on("PCLEAN_NO_GROUP_GATE");    // the new-row branch per item, never per group
+    const bool no_coarse = env_on("PCLEAN_NO_COARSE_LEAF");       // cacheable option lists by enumeration, not by the coarse prefix
+    const bool no_small_generic = env_on("PCLEAN_NO_SMALL_GENERIC");        // short marginal-only lists try the compact tables too
+    const int ev_slot_min_items = env_int("PCLEAN_EV_SLOT_MIN_ITEMS", 64);  // evidence scans of reference slots from here on
+    const bool no_fast_over = env_on("PCLEAN_NO_FAST_OVERFLOW");  // overflowed items: a count, then the generic kernel
+    const bool no_ev_list = env_on("PCLEAN_NO_EV_LIST");          // ... of an evidence scan: a count, not a device list
+    const bool no_ev_split = env_on("PCLEAN_NO_EV_SPLIT");        // huge evidence sets are summed by the row's own workgroup
+  };
+  struct Live {  // read at every eval_node call that gets to them, as ever: tests flip these inside one process
+    int gate_min() const { return env_int("PCLEAN_GATE_MIN", 2048); }  // the shortest list whose new-row branch is gated
+    bool no_gate() const { return env_on("PCLEAN_NO_GATE"); }
+    bool gate_always() const { return env_on("PCLEAN_GATE_ALWAYS"); }  // no gate pauses (GateStat)
+    bool no_fast_ev_slots() const { return env_on("PCLEAN_NO_FAST_EV_SLOTS"); }  // no evidence scans of reference slots
+    bool no_fast_ev() const { return env_on("PCLEAN_NO_FAST_EV"); }              // no evidence scans at all
+    bool debug_overflow() const { return env_on("PCLEAN_DEBUG_OVERFLOW"); }
+  };
+  static const Cached& once() {
+    static const Cached c;
+    return c;
+  }
+  const Cached& cached = once();
+  const Live live;
+};
+
+// ---- try_fast_root: the compact-table fast path of a node (root_wave.hip), in parts ----------------------------------------
+struct FastRootCall {  // one call: what the parts share
+  pclean_ctx* ctx;
+  const int block_id, node_id;
+  const bool ev_mode;
+  const EvalSwitches::Cached& sw;
+  const Block& b;
+  const pclean_node& n;
+  CandTable& t;
+  const bool leaf;
+  FastRootDev& fr;
+  int lmax = 0, dmax = 0, kpad = 0, cstride = 0;
+  FastRoot* f = nullptr;  // the node's cache entry (fast_root_eligible)
+  const pclean_term& term(int i) const { return b.terms[n.term_begin + i]; }
+};
+
+// whether the node takes the compact-table kernels: many candidates, every term a plain AddTypos lookup in a byte table
+static bool fast_root_eligible(FastRootCall& c) {
+  const pclean_node& n = c.n;
+  const CandTable& t = c.t;
+  pclean_ctx* ctx = c.ctx;
+  if (!t.valid || t.n_rows < 1024 || n.n_terms < 1 || n.n_terms > PCLEAN_MAX_TERMS || (c.leaf && c.sw.no_fast_leaf)) return false;
+  if (c.leaf != t.is_options || node_has_tabulated(c.b, n)) return false;
   int lmax = 0, dmax = 0;
   for (int i = 0; i < n.n_terms; ++i) {
-    const pclean_term& tm = b.terms[n.term_begin + i];
+    const pclean_term& tm = c.term(i);
     const PairTable& pt = ctx->pair[tm.pair_table];
-    if (!pt.valid || tm.dens_kind != PCLEAN_DENS_ADD_TYPOS || pt.elem_bytes != 1) return 0;
+    if (!pt.valid || tm.dens_kind != PCLEAN_DENS_ADD_TYPOS || pt.elem_bytes != 1) return false;
     // evidence sets (ev_leaf_block_kernel): ctx terms are only ever scored exactly (by candidate_score), any mode goes
-    if (tm.ctx_slot >= 0 && ((!ev_mode && tm.ctx_mode != 0) || !ctx->fn[tm.fn_table].valid)) return 0;
-    if (tm.ctx_slot >= 2) return 0;  // the wave kernel's group descriptor carries two context values
+    if (tm.ctx_slot >= 0 && ((!c.ev_mode && tm.ctx_mode != 0) || !ctx->fn[tm.fn_table].valid)) return false;
+    if (tm.ctx_slot >= 2) return false;  // the wave kernel's group descriptor carries two context values
     lmax = std::max(lmax, pt.max_lat_len);
     dmax = std::max(dmax, std::max(pt.max_lat_len, pt.max_obs_len));
   }
-  if (lmax > 255 || dmax > 255) return 0;
-  if (leaf && !ev_mode) {
+  if (lmax > 255 || dmax > 255) return false;
+  if (c.leaf && !c.ev_mode) {
     // An option list scored against ONE observed string: the integer pre-filter keeps every option within
     // ~10 edits of it (28.5 nats / cost of an edit), i.e. everything when the strings are short (codes, zip
     // codes, phone numbers) — only long strings (names, addresses) are worth the compact tables.
     double best = 0.0;
-    for (int i = 0; i < n.n_terms; ++i) {
-      const pclean_term& tm = b.terms[n.term_begin + i];
-      if (tm.ctx_slot < 0) best = std::max(best, ctx->pair[tm.pair_table].mean_lat_len);
-    }
-    if (best < 16.0) return 0;
+    for (int i = 0; i < n.n_terms; ++i)
+      if (c.term(i).ctx_slot < 0) best = std::max(best, ctx->pair[c.term(i).pair_table].mean_lat_len);
+    if (best < 16.0) return false;
   }
-  const int kpad = (t.n_rows + 15) & ~15;
-  FastRoot& f = st(ctx)->fast[block_id * 64 + node_id];
-  if (f.disabled > 0) {
-    --f.disabled;
-    return 0;
-  }
-  if ((int)f.comp.size() != n.n_terms) {
-    for (auto& c : f.comp) c.release();
-    for (auto& c : f.clen) c.release();
-    for (auto& c : f.cblk) c.release();
-    f.cblk.assign(n.n_terms, DevBuf<uint8_t>());
-    f.comp.assign(n.n_terms, DevBuf<uint8_t>());
-    f.clen.assign(n.n_terms, DevBuf<uint8_t>());
-    f.ver.assign(n.n_terms, 0);
-    f.kpad = kpad;
-    f.prior_ver = 0;
-  } else if (f.kpad != kpad) {
-    // the table grew (or shrank) by a few rows: the byte tables are rebuilt with the new stride INTO the buffers they
-    // have (allocated with headroom below) — freeing and allocating a dozen buffers of up to a GB each costs tens of
-    // milliseconds on some boxes (the first full iteration was measured at 0.4 s or 0.8 s depending on it)
-    f.ver.assign(n.n_terms, 0);
-    f.kpad = kpad;
-    f.prior_ver = 0;
-  }
-  auto grow = [](DevBuf<uint8_t>& b, size_t need) -> int {  // 1/8 of headroom whenever it has to grow
-    need = std::max<size_t>(need, 16);
-    return need <= b.n && b.p ? 0 : b.alloc(need + need / 8);
-  };
+  c.lmax = lmax;
+  c.dmax = dmax;
+  c.kpad = (t.n_rows + 15) & ~15;
   // block minima of the compact rows (one byte per 64 candidates): the coarse level of the pre-filter scan
-  const int cstride = ((((kpad + 63) >> 6) + 15) & ~15);
-  for (int i = 0; i < n.n_terms; ++i) {
-    const pclean_term& tm = b.terms[n.term_begin + i];
+  c.cstride = ((((c.kpad + 63) >> 6) + 15) & ~15);
+  c.f = &st(ctx)->fast[c.block_id * 64 + c.node_id];
+  if (c.f->disabled > 0) {
+    --c.f->disabled;
+    return false;
+  }
+  return true;
+}
+
+static int grow_bytes(DevBuf<uint8_t>& b, size_t need) {  // 1/8 of headroom whenever it has to grow
+  need = std::max<size_t>(need, 16);
+  return need <= b.n && b.p ? 0 : b.alloc(need + need / 8);
+}
+
+// the compact byte rows and the block minima of term i for the candidates rows[0 .. n) (a device list) whose values changed
+static int refresh_compact_rows(const FastRootCall& c, int i, const int32_t* rows, int n) {
+  if (n <= 0) return PCLEAN_OK;
+  const pclean_term& tm = c.term(i);
+  const PairTable& pt = c.ctx->pair[tm.pair_table];
+  FastRoot& f = *c.f;
+  int rc = pclean_update_compact(c.ctx, pt.d.p, pt.n_obs, pt.n_lat, c.t.cols.p + (size_t)tm.cand_col * c.t.n_rows, pt.lat_len.p, rows,
+                                 n, c.kpad, f.comp[i].p, f.clen[i].p);
+  if (!rc) rc = pclean_update_compact_min(c.ctx, f.comp[i].p, pt.n_obs, c.kpad, c.cstride, rows, n, f.cblk[i].p);
+  return rc;
+}
+
+// Term i's tables stem from an older version of the columns that a chain of known deltas connects with the current one: the
+// device commit's rows (still on the device), then the union of the rows the host's re-uploads rewrote since
+// (CandTable::delta_log) — the observed class's tables after the sub-batches of the latent classes' sweeps (14 rebuilds = 9 ms
+// per iteration at 1M rows).  Moves f.ver[i] to `ver` when it refreshed them.
+static int refresh_along_chain(FastRootCall& c, int i, uint64_t ver) {
+  FastRoot& f = *c.f;
+  CandTable& tw = c.t;
+  const PairTable& pt = c.ctx->pair[c.term(i).pair_table];
+  uint64_t at = 0;
+  bool have = false, via_commit = false;
+  if (tw.commit_delta_n >= 0 && f.ver[i] == tw.commit_delta_base * 1000003ull + pt.version) {
+    at = tw.commit_delta_next;
+    have = via_commit = true;
+  } else {
+    for (const auto& e : tw.delta_log)
+      if (f.ver[i] == e.base * 1000003ull + pt.version) {
+        at = e.base;
+        have = true;
+        break;
+      }
+  }
+  int un = 0;
+  bool ok = have;
+  if (ok && at != tw.cols_version) {
+    uint64_t node_mask = 0;  // the value columns the node's byte tables are built from
+    for (int q = 0; q < c.n.n_terms; ++q)
+      if (c.term(q).ctx_slot < 0) node_mask |= 1ull << std::min(c.term(q).cand_col, 63);
+    const int rcu = cols_union(c.ctx, tw, at, node_mask, &un);
+    if (rcu < 0) return rcu;
+    ok = rcu == 1;
+  }
+  const int64_t total = (int64_t)(via_commit ? tw.commit_delta_n : 0) + un;
+  if (c.sw.dbg_chain && i == 0)
+    fprintf(stderr, "[chain] block %d node %d table %d (%d rows): have %d via_commit %d (commit rows %d) log %zu entries, union %s %d rows\n",
+            c.block_id, c.node_id, (int)c.n.table, tw.n_rows, (int)have, (int)via_commit, tw.commit_delta_n, tw.delta_log.size(),
+            ok ? "ok" : "none", un);
+  if (!ok || total * 8 > tw.n_rows) return PCLEAN_OK;
+  ProfScope psd(c.ctx, "compact_table_update");
+  int rc = via_commit ? refresh_compact_rows(c, i, tw.commit_delta_rows, tw.commit_delta_n) : PCLEAN_OK;
+  if (!rc) rc = refresh_compact_rows(c, i, tw.union_rows.p, un);
+  if (rc) return rc;
+  f.ver[i] = ver;
+  return PCLEAN_OK;
+}
+
+// the compact tables of plain term i at the current version of the columns and the pair table: refreshed for the rows that
+// changed where the changes are known and few, else rebuilt
+static int ensure_compact_term(FastRootCall& c, int i) {
+  pclean_ctx* ctx = c.ctx;
+  FastRoot& f = *c.f;
+  const CandTable& t = c.t;
+  const pclean_term& tm = c.term(i);
+  const PairTable& pt = ctx->pair[tm.pair_table];
+  const uint64_t ver = t.cols_version * 1000003ull + pt.version;
+  const bool refreshable = f.comp[i].p && f.cblk[i].p && !c.sw.no_delta;
+  if (f.ver[i] != ver && refreshable && t.cols_delta_n >= 0 && t.cols_delta_n * 8 <= t.n_rows &&
+      f.ver[i] == t.cols_delta_base * 1000003ull + pt.version) {
+    // built from the columns as they were before the last device commit, which wrote a few rows: refresh those rows
+    // (and the block minima), not the whole table
+    ProfScope psd(ctx, "compact_table_update");
+    const int rc = refresh_compact_rows(c, i, t.cols_delta_rows, t.cols_delta_n);
+    if (rc) return rc;
+    f.ver[i] = ver;
+  }
+  if (f.ver[i] != ver && refreshable && !c.sw.no_chain) {
+    const int rc = refresh_along_chain(c, i, ver);
+    if (rc) return rc;
+  }
+  if (f.ver[i] != ver || !f.comp[i].p) {
+    ProfScope psd(ctx, "compact_table_rebuild");
+    if (grow_bytes(f.comp[i], (size_t)pt.n_obs * c.kpad) || grow_bytes(f.clen[i], (size_t)c.kpad))
+      return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed (compact tables)");
+    int rc = pclean_build_compact(ctx, pt.d.p, pt.n_obs, pt.n_lat, t.cols.p + (size_t)tm.cand_col * t.n_rows, pt.lat_len.p,
+                                  t.n_rows, c.kpad, f.comp[i].p, f.clen[i].p);
+    if (rc) return rc;
+    if (grow_bytes(f.cblk[i], (size_t)pt.n_obs * c.cstride))
+      return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed (compact tables)");
+    rc = pclean_build_compact_min(ctx, f.comp[i].p, pt.n_obs, c.kpad, c.cstride, f.cblk[i].p);
+    if (rc) return rc;
+    f.ver[i] = ver;
+  }
+  return PCLEAN_OK;
+}
+
+// fr.terms: every term's lookups, and the compact tables of the plain ones brought up to date
+static int ensure_compact_tables(FastRootCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  FastRoot& f = *c.f;
+  const CandTable& t = c.t;
+  const int nt = c.n.n_terms;
+  const bool other_terms = (int)f.comp.size() != nt;
+  if (other_terms) {
+    for (auto& b : f.comp) b.release();
+    for (auto& b : f.clen) b.release();
+    for (auto& b : f.cblk) b.release();
+    f.cblk.assign(nt, DevBuf<uint8_t>());
+    f.comp.assign(nt, DevBuf<uint8_t>());
+    f.clen.assign(nt, DevBuf<uint8_t>());
+  }
+  if (other_terms || f.kpad != c.kpad) {
+    // ... or the table grew (or shrank) by a few rows: the byte tables are rebuilt with the new stride INTO the buffers they
+    // have (allocated with headroom) — freeing and allocating a dozen buffers of up to a GB each costs tens of
+    // milliseconds on some boxes (the first full iteration was measured at 0.4 s or 0.8 s depending on it)
+    f.ver.assign(nt, 0);
+    f.kpad = c.kpad;
+    f.prior_ver = 0;
+  }
+  for (int i = 0; i < nt; ++i) {
+    const pclean_term& tm = c.term(i);
     const PairTable& pt = ctx->pair[tm.pair_table];
-    fr.terms[i] = FastTermDev{};
-    fr.terms[i].obs_col = ctx->obs_override ? ctx->obs_override : ctx->obs.p + (size_t)tm.obs_col * ctx->n_rows + ctx->active_begin;
-    fr.terms[i].max_typos = tm.max_typos;
-    fr.terms[i].ctx_slot = tm.ctx_slot;
-    fr.terms[i].pair = (const uint8_t*)pt.d.p;  // ctx terms gather from it; plain terms look up the true distance
-    fr.terms[i].lat_len = pt.lat_len.p;         // behind a saturated compact byte
-    fr.terms[i].cand_col = t.cols.p + (size_t)tm.cand_col * t.n_rows;
-    fr.terms[i].n_lat = pt.n_lat;
+    FastTermDev& ft = c.fr.terms[i];
+    ft = FastTermDev{};
+    ft.obs_col = ctx->obs_override ? ctx->obs_override : ctx->obs.p + (size_t)tm.obs_col * ctx->n_rows + ctx->active_begin;
+    ft.max_typos = tm.max_typos;
+    ft.ctx_slot = tm.ctx_slot;
+    ft.pair = (const uint8_t*)pt.d.p;  // ctx terms gather from it; plain terms look up the true distance
+    ft.lat_len = pt.lat_len.p;         // behind a saturated compact byte
+    ft.cand_col = t.cols.p + (size_t)tm.cand_col * t.n_rows;
+    ft.n_lat = pt.n_lat;
     if (tm.ctx_slot >= 0) {  // scored by gathering (few survivors reach it)
       const FnTable& fnt = ctx->fn[tm.fn_table];
-      fr.terms[i].fn = fnt.fn.p;
-      fr.terms[i].fn_nb = fnt.n_b;
+      ft.fn = fnt.fn.p;
+      ft.fn_nb = fnt.n_b;
       continue;
     }
-    const uint64_t ver = t.cols_version * 1000003ull + pt.version;
-    static const bool no_delta = getenv("PCLEAN_NO_COMPACT_DELTA") != nullptr;
-    if (f.ver[i] != ver && f.comp[i].p && f.cblk[i].p && !no_delta && t.cols_delta_n >= 0 && t.cols_delta_n * 8 <= t.n_rows &&
-        f.ver[i] == t.cols_delta_base * 1000003ull + pt.version) {
-      // built from the columns as they were before the last device commit, which wrote a few rows: refresh those rows
-      // (and the block minima), not the whole table
-      ProfScope psd(ctx, "compact_table_update");
-      int rc = PCLEAN_OK;
-      if (t.cols_delta_n > 0)
-        rc = pclean_update_compact(ctx, pt.d.p, pt.n_obs, pt.n_lat, t.cols.p + (size_t)tm.cand_col * t.n_rows, pt.lat_len.p,
-                                     t.cols_delta_rows, t.cols_delta_n, kpad, f.comp[i].p, f.clen[i].p);
-      if (rc) return rc;
-      if (t.cols_delta_n > 0)
-        rc = pclean_update_compact_min(ctx, f.comp[i].p, pt.n_obs, kpad, cstride, t.cols_delta_rows, t.cols_delta_n, f.cblk[i].p);
-      if (rc) return rc;
-      f.ver[i] = ver;
-    }
-    // ... or from an older version that a chain of known deltas connects with the current one: the device commit's rows
-    // (still on the device), then the union of the rows the host's re-uploads rewrote since (CandTable::delta_log) — the
-    // observed class's tables after the sub-batches of the latent classes' sweeps (14 rebuilds = 9 ms per iteration at 1M rows)
-    static const bool no_chain = getenv("PCLEAN_NO_DELTA_CHAIN") != nullptr;
-    if (f.ver[i] != ver && f.comp[i].p && f.cblk[i].p && !no_delta && !no_chain) {
-      CandTable& tw = ctx->cand[n.table];
-      uint64_t at = 0;
-      bool have = false, via_commit = false;
-      if (tw.commit_delta_n >= 0 && f.ver[i] == tw.commit_delta_base * 1000003ull + pt.version) {
-        at = tw.commit_delta_next;
-        have = via_commit = true;
-      } else {
-        for (const auto& e : tw.delta_log)
-          if (f.ver[i] == e.base * 1000003ull + pt.version) {
-            at = e.base;
-            have = true;
-            break;
-          }
-      }
-      int un = 0;
-      bool ok = have;
-      if (ok && at != tw.cols_version) {
-        uint64_t node_mask = 0;  // the value columns the node's byte tables are built from
-        for (int q = 0; q < n.n_terms; ++q)
-          if (b.terms[n.term_begin + q].ctx_slot < 0) node_mask |= 1ull << std::min(b.terms[n.term_begin + q].cand_col, 63);
-        const int rcu = cols_union(ctx, tw, at, node_mask, &un);
-        if (rcu < 0) return rcu;
-        ok = rcu == 1;
-      }
-      const int64_t total = (int64_t)(via_commit ? tw.commit_delta_n : 0) + un;
-      static const bool dbg_chain = getenv("PCLEAN_DEBUG_CHAIN") != nullptr;
-      if (dbg_chain && i == 0)
-        fprintf(stderr, "[chain] block %d node %d table %d (%d rows): have %d via_commit %d (commit rows %d) log %zu entries, union %s %d rows\n",
-                block_id, node_id, (int)n.table, tw.n_rows, (int)have, (int)via_commit, tw.commit_delta_n, tw.delta_log.size(),
-                ok ? "ok" : "none", un);
-      if (ok && total * 8 <= tw.n_rows) {
-        ProfScope psd(ctx, "compact_table_update");
-        int rc = PCLEAN_OK;
-        const int32_t* colp = tw.cols.p + (size_t)tm.cand_col * tw.n_rows;
-        if (via_commit && tw.commit_delta_n > 0) {
-          rc = pclean_update_compact(ctx, pt.d.p, pt.n_obs, pt.n_lat, colp, pt.lat_len.p, tw.commit_delta_rows, tw.commit_delta_n, kpad,
-                                     f.comp[i].p, f.clen[i].p);
-          if (!rc) rc = pclean_update_compact_min(ctx, f.comp[i].p, pt.n_obs, kpad, cstride, tw.commit_delta_rows, tw.commit_delta_n, f.cblk[i].p);
-          if (rc) return rc;
-        }
-        if (un > 0) {
-          rc = pclean_update_compact(ctx, pt.d.p, pt.n_obs, pt.n_lat, colp, pt.lat_len.p, tw.union_rows.p, un, kpad, f.comp[i].p, f.clen[i].p);
-          if (!rc) rc = pclean_update_compact_min(ctx, f.comp[i].p, pt.n_obs, kpad, cstride, tw.union_rows.p, un, f.cblk[i].p);
-          if (rc) return rc;
-        }
-        f.ver[i] = ver;
-      }
-    }
-    if (f.ver[i] != ver || !f.comp[i].p) {
-      ProfScope psd(ctx, "compact_table_rebuild");
-      if (grow(f.comp[i], (size_t)pt.n_obs * kpad) || grow(f.clen[i], (size_t)kpad))
-        return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed (compact tables)");
-      int rc = pclean_build_compact(ctx, pt.d.p, pt.n_obs, pt.n_lat, t.cols.p + (size_t)tm.cand_col * t.n_rows,
-                                    pt.lat_len.p, t.n_rows, kpad, f.comp[i].p, f.clen[i].p);
-      if (rc) return rc;
-      if (grow(f.cblk[i], (size_t)pt.n_obs * cstride))
-        return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed (compact tables)");
-      rc = pclean_build_compact_min(ctx, f.comp[i].p, pt.n_obs, kpad, cstride, f.cblk[i].p);
-      if (rc) return rc;
-      f.ver[i] = ver;
-    }
-    fr.terms[i].comp = f.comp[i].p;
-    fr.terms[i].clen = f.clen[i].p;
-    fr.terms[i].cmin = f.cblk[i].p;
+    const int rc = ensure_compact_term(c, i);
+    if (rc) return rc;
+    ft.comp = f.comp[i].p;
+    ft.clen = f.clen[i].p;
+    ft.cmin = f.cblk[i].p;
   }
-  if ((int)f.zero_row.n < kpad || !f.zero_row.p) {
-    if (f.zero_row.alloc((size_t)kpad + 4096)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  return PCLEAN_OK;
+}
+
+// the zero row, and the prior rows and alive bits at the table's current version
+static int ensure_root_priors(FastRootCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  FastRoot& f = *c.f;
+  const CandTable& t = c.t;
+  if ((int)f.zero_row.n < c.kpad || !f.zero_row.p) {
+    if (f.zero_row.alloc((size_t)c.kpad + 4096)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
     HIPCHK(ctx, hipMemsetAsync(f.zero_row.p, 0, f.zero_row.n, ctx->stream));
   }
   if (f.prior_ver != t.version || !f.prior_n.p) {
-    if ((!leaf && f.prior_e.alloc(kpad)) || f.prior_n.alloc(kpad) || f.alive.alloc(std::max(kpad >> 4, 1)))
+    if ((!c.leaf && f.prior_e.alloc(c.kpad)) || f.prior_n.alloc(c.kpad) || f.alive.alloc(std::max(c.kpad >> 4, 1)))
       return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-    int rc = pclean_build_priors(ctx, leaf ? nullptr : t.counts.p, t.logc_full.p, t.n_rows, kpad, t.scal[1], t.scal[0],
-                                 leaf ? nullptr : f.prior_e.p, f.prior_n.p, f.alive.p);
+    int rc = pclean_build_priors(ctx, c.leaf ? nullptr : t.counts.p, t.logc_full.p, t.n_rows, c.kpad, t.scal[1], t.scal[0],
+                                 c.leaf ? nullptr : f.prior_e.p, f.prior_n.p, f.alive.p);
     if (rc) return rc;
     f.prior_ver = t.version;
     f.logc_max = t.logc_max;  // (maintained with the table: pclean_set_table / pclean_set_options / pclean_commit_device)
   }
-  // pre-filter: the three terms with the longest latent strings discriminate best; c_min = the
-  // smallest density cost of one edit over every (length, distance) the tables hold
-  {
-    fr.n_pre = prefilter_terms(ctx, b, n, fr.pre);
-    const int stride = ctx->max_d + 1;
-    const uint64_t ckey = ((uint64_t)lmax << 40) | ((uint64_t)dmax << 20) | (uint64_t)stride;
-    if (f.cmin_key != ckey) {  // ~lmax x dmax host iterations: once per (table shape), not per launch
-      double cm = INFINITY;
-      for (int L = 1; L <= lmax; ++L)
-        for (int d = 1; d <= dmax; ++d) {
-          const int r = (L + 4) / 5;
-          double l = ctx->h_nb[(size_t)r * stride + d];
-          l -= ctx->h_logl[L] * (double)d;
-          l -= 1.629048269010741 * (double)d;
-          if (l == l) cm = std::min(cm, -l / (double)d);
-        }
-      f.cmin = cm;
-      f.cmin_key = ckey;
-    }
-    const double cmin = f.cmin;
-    if (!(cmin > 1e-6) || !std::isfinite(cmin)) {
-      fr.n_pre = 0;  // no usable bound: evaluate every candidate exactly
-      fr.inv_c = 0.0;
-    } else {
-      fr.inv_c = 1.0 / (cmin * (1.0 - 1e-9));
-    }
-    fr.cstride = cstride;
-    fr.prior_max_e = f.logc_max - t.scal[1];
-    fr.prior_max_n = f.logc_max - t.scal[0];
+  return PCLEAN_OK;
+}
+
+// pre-filter: the three terms with the longest latent strings discriminate best; c_min = the
+// smallest density cost of one edit over every (length, distance) the tables hold
+static void prefilter_bound(FastRootCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  FastRoot& f = *c.f;
+  FastRootDev& fr = c.fr;
+  fr.n_pre = prefilter_terms(ctx, c.b, c.n, fr.pre);
+  const int stride = ctx->max_d + 1;
+  const uint64_t ckey = ((uint64_t)c.lmax << 40) | ((uint64_t)c.dmax << 20) | (uint64_t)stride;
+  if (f.cmin_key != ckey) {  // ~lmax x dmax host iterations: once per (table shape), not per launch
+    double cm = INFINITY;
+    for (int L = 1; L <= c.lmax; ++L)
+      for (int d = 1; d <= c.dmax; ++d) {
+        const int r = (L + 4) / 5;
+        double l = ctx->h_nb[(size_t)r * stride + d];
+        l -= ctx->h_logl[L] * (double)d;
+        l -= 1.629048269010741 * (double)d;
+        if (l == l) cm = std::min(cm, -l / (double)d);
+      }
+    f.cmin = cm;
+    f.cmin_key = ckey;
   }
-  // the observed values row-major, for the launches that look at one row per group (group_gate_kernel, group_desc_kernel);
-  // large tables only; not for evidence sets and not under an observation override (leaf caches)
-  fr.obs_rm = nullptr;
-  static const bool no_obs_rm = getenv("PCLEAN_NO_OBS_ROWMAJOR") != nullptr;
-  if (!leaf && !ev_mode && !ctx->obs_override && !no_obs_rm && ctx->n_rows >= 4096) {
-    const uint64_t key = ctx->obs_version * 1000003ull + (uint64_t)ctx->n_rows + 1ull;
-    if (f.obs_rm_key != key || !f.obs_rm.p) {
-      if (f.obs_rm.alloc((size_t)ctx->n_rows * PCLEAN_MAX_TERMS)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-      const int32_t* cols[PCLEAN_MAX_TERMS] = {};
-      for (int i = 0; i < n.n_terms; ++i) cols[i] = ctx->obs.p + (size_t)b.terms[n.term_begin + i].obs_col * ctx->n_rows;
-      int rc = pclean_build_obs_rowmajor(ctx, cols, n.n_terms, ctx->n_rows, f.obs_rm.p);
-      if (rc) return rc;
-      f.obs_rm_key = key;
-    }
-    fr.obs_rm = f.obs_rm.p + (size_t)ctx->active_begin * PCLEAN_MAX_TERMS;
+  const double cmin = f.cmin;
+  if (!(cmin > 1e-6) || !std::isfinite(cmin)) {
+    fr.n_pre = 0;  // no usable bound: evaluate every candidate exactly
+    fr.inv_c = 0.0;
+  } else {
+    fr.inv_c = 1.0 / (cmin * (1.0 - 1e-9));
   }
+  fr.cstride = c.cstride;
+  fr.prior_max_e = f.logc_max - c.t.scal[1];
+  fr.prior_max_n = f.logc_max - c.t.scal[0];
+}
+
+// the observed values row-major, for the launches that look at one row per group (group_gate_kernel, group_desc_kernel);
+// large tables only; not for evidence sets and not under an observation override (leaf caches)
+static int ensure_obs_rowmajor(FastRootCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  FastRoot& f = *c.f;
+  c.fr.obs_rm = nullptr;
+  if (c.leaf || c.ev_mode || ctx->obs_override || c.sw.no_obs_rm || ctx->n_rows < 4096) return PCLEAN_OK;
+  const uint64_t key = ctx->obs_version * 1000003ull + (uint64_t)ctx->n_rows + 1ull;
+  if (f.obs_rm_key != key || !f.obs_rm.p) {
+    if (f.obs_rm.alloc((size_t)ctx->n_rows * PCLEAN_MAX_TERMS)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+    const int32_t* cols[PCLEAN_MAX_TERMS] = {};
+    for (int i = 0; i < c.n.n_terms; ++i) cols[i] = ctx->obs.p + (size_t)c.term(i).obs_col * ctx->n_rows;
+    int rc = pclean_build_obs_rowmajor(ctx, cols, c.n.n_terms, ctx->n_rows, f.obs_rm.p);
+    if (rc) return rc;
+    f.obs_rm_key = key;
+  }
+  c.fr.obs_rm = f.obs_rm.p + (size_t)ctx->active_begin * PCLEAN_MAX_TERMS;
+  return PCLEAN_OK;
+}
+
+// what is left of FastRootDev: shapes and the pointers of the cache entry
+static void fill_fast_root(const FastRootCall& c) {
+  const FastRoot& f = *c.f;
+  const CandTable& t = c.t;
+  FastRootDev& fr = c.fr;
   fr.n_cand = t.n_rows;
-  fr.kpad = kpad;
-  {
-    static const bool no_kscan = getenv("PCLEAN_NO_KSCAN") != nullptr;
-    const int n_used = (t.n_used > 0 && t.n_used <= t.n_rows && !no_kscan) ? t.n_used : t.n_rows;
-    fr.kscan = std::min(kpad, (n_used + 63) & ~63);
-  }
-  fr.n_terms = n.n_terms;
-  fr.lmax = lmax;
-  fr.dstride = dmax + 1;
-  fr.is_leaf = leaf ? 1 : 0;
-  fr.atd = ctx->atd.p;
-  fr.atd_stride = ctx->max_d + 1;
+  fr.kpad = c.kpad;
+  const int n_used = (t.n_used > 0 && t.n_used <= t.n_rows && !c.sw.no_kscan) ? t.n_used : t.n_rows;
+  fr.kscan = std::min(c.kpad, (n_used + 63) & ~63);
+  fr.n_terms = c.n.n_terms;
+  fr.lmax = c.lmax;
+  fr.dstride = c.dmax + 1;
+  fr.is_leaf = c.leaf ? 1 : 0;
+  fr.atd = c.ctx->atd.p;
+  fr.atd_stride = c.ctx->max_d + 1;
   fr.zero_row = f.zero_row.p;
   fr.alive = f.alive.p;
-  fr.prior_e = leaf ? nullptr : f.prior_e.p;
+  fr.prior_e = c.leaf ? nullptr : f.prior_e.p;
   fr.prior_n = f.prior_n.p;
-  fr.logc_m1 = leaf ? nullptr : t.logc_m1.p;
-  fr.counts = leaf ? nullptr : t.counts.p;
+  fr.logc_m1 = c.leaf ? nullptr : t.logc_m1.p;
+  fr.counts = c.leaf ? nullptr : t.counts.p;
   memcpy(fr.scal, t.scal, sizeof fr.scal);
+}
+
+// Fast path of a reference slot or a long-string option list (root_wave.hip): returns 1 and fills `fr` when the node has many
+// candidates whose terms are all plain AddTypos lookups in byte tables; 0 otherwise, < 0 on errors.
+static int try_fast_root(pclean_ctx* ctx, int block_id, int node_id, FastRootDev& fr, bool ev_mode = false) {
+  if (node_id >= 64) return 0;
+  const Block& b = ctx->block[block_id];
+  const pclean_node& n = b.nodes[node_id];
+  FastRootCall c{ctx, block_id, node_id, ev_mode, EvalSwitches::once(), b, n, ctx->cand[n.table], n.kind == PCLEAN_NODE_LEAF, fr};
+  if (!fast_root_eligible(c)) return 0;
+  int rc = ensure_compact_tables(c);
+  if (!rc) rc = ensure_root_priors(c);
+  if (rc) return rc;
+  prefilter_bound(c);
+  rc = ensure_obs_rowmajor(c);
+  if (rc) return rc;
+  fill_fast_root(c);
   return 1;
 }
 
@@ -739,551 +854,639 @@ __global__ void member_scatter_f64_kernel(int n_pos, const int32_t* uid, const i
   if (mi < n_pos) dst[members[mi]] = src[uid[mi] - 1];
 }
 
-int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, const int32_t* excl,
-                     uint64_t seed, uint32_t sweep, int n_draws, double* lse_out, int32_t* draws_out,
-                     double* scores_out, const double* snew_override, bool time_it) {
-  Block& b = ctx->block[block_id];
-  const pclean_node& n = b.nodes[node_id];
-  SweepState* s = st(ctx);
-  const SweepState::LazyReq lazy_req = s->lazy_req;  // (this evaluation's; the children's evaluations below must not see it)
+// ---- eval_node: a driver over phases (which phase enqueues what) ---------------------------------------------
+struct EvalCall {  // one call: the arguments and what the phases share
+  pclean_ctx* ctx;
+  const int block_id, node_id;
+  const ItemList& il;
+  const int32_t* excl;
+  const uint64_t seed;
+  const uint32_t sweep;
+  const int n_draws;
+  double* lse_out;
+  int32_t* draws_out;
+  double* scores_out;
+  const double* snew_override;
+  const bool time_it;
+  Block& b;
+  const pclean_node& n;
+  SweepState* s;
+  const uint32_t site;
+  const EvalSwitches sw;
+  SweepState::LazyReq lazy_req;  // this evaluation's (eval_begin takes it: the children's evaluations must not see it)
+  bool lazy_ok = false;          // lazy draws (the sweep's last block, see RootExtra): asked for and possible for this list
+  int fast_split_m = 0;          // largest piece of a group of a compact-table launch (0: groups are not cut)
+  bool tabulated = false;        // (generic kernels only; guarded the way nd.g.on is)
+  NodeDev nd;
+  ItemsDev it;
+  ChildrenDev ch{};
+  FastRootDev fr;
+  int fast = 0, fast_ev = 0;
+  // a reference slot whose groups are made BEFORE its new-row branch is looked at: the gate and the children of the branch
+  // then run once per group of identical rows instead of once per row
+  ItemGroups g_pre;
+  ItemGroups ggrp;  // the grouping of the launch (n_groups == 0: none)
+  bool fast_tried = false, groups_tried = false;
+  const double* pre_score = nullptr;  // exact score of every group's current referent (group_gate_kernel)
+  const int32_t* pre_obs = nullptr;   // observed values of every group's row (group_gate_kernel)
+  // the compact-table launch (overflow_setup): overflow markers per item, or the device list that stands for them
+  int32_t* oflag = nullptr;
+  int32_t* over_list = nullptr;
+  unsigned int* over_count = nullptr;
+  bool list_mode = false, ev_list_mode = false;
+};
+
+static int eval_begin(EvalCall& c) {
+  SweepState* s = c.s;
+  const ItemList& il = c.il;
+  c.lazy_req = s->lazy_req;
   s->lazy_req = SweepState::LazyReq();
   s->lazy_out.valid = false;
-  // lazy draws (the sweep's last block, see RootExtra): asked for and possible for this list of items
-  static const bool no_lazy = getenv("PCLEAN_NO_LAZY_DRAWS") != nullptr;
-  const bool lazy_ok = lazy_req.on && !no_lazy && n_draws > 1 && !il.rng_row && !il.ev_lo;
+  c.lazy_ok = c.lazy_req.on && !c.sw.cached.no_lazy && c.n_draws > 1 && !il.rng_row && !il.ev_lo;
   // groups of a compact-table launch: a large group is cut into pieces of at most ~2 x 256 / n_draws member items (a wave
   // writes n_draws draws per member, see item_head_kernel) — unless the launch leaves lists instead of draws: nothing is
   // written per member then, and the pieces (a third of the Measure slot's groups) were descriptors, hand-outs and list
   // copies for nothing (PCLEAN_LAZY_SPLIT=1: cut them all the same)
-  static const bool lazy_split = getenv("PCLEAN_LAZY_SPLIT") != nullptr;
-  // (il.n bounds the number of groups: the lists of the launch are sure to fit, see the launch below)
-  const bool lazy_sure = lazy_ok && (size_t)il.n * ROOT_LZ_CAP * 12 <= ((size_t)4 << 30);
-  const int fast_split_m = (lazy_sure && !lazy_split) ? 0 : std::max(4, 256 / std::max(n_draws, 1));
-  NodeDev nd;
-  int rc = build_node_dev(ctx, b, node_id, nd);
+  // (il.n bounds the number of groups: the lists of the launch are sure to fit, see launch_root_scan)
+  const bool lazy_sure = c.lazy_ok && (size_t)il.n * ROOT_LZ_CAP * 12 <= ((size_t)4 << 30);
+  c.fast_split_m = (lazy_sure && !c.sw.cached.lazy_split) ? 0 : std::max(4, 256 / std::max(c.n_draws, 1));
+  int rc = build_node_dev(c.ctx, c.b, c.node_id, c.nd);
   if (rc) return rc;
-  ChildrenDev ch{};
-  ItemsDev it{il.n, 0, il.row, il.ctx, excl, n_draws == 1 ? il.particle : nullptr, s->row_offset + ctx->active_begin,
-              nullptr, il.ev_lo, il.ev_hi, il.ev_rows, il.ev_ctx, il.rng_row, nullptr, nullptr, il.draw_is, il.draw_ds,
-              nullptr, nullptr};
+  c.it = ItemsDev{il.n, 0, il.row, il.ctx, c.excl, c.n_draws == 1 ? il.particle : nullptr, s->row_offset + c.ctx->active_begin,
+                  nullptr, il.ev_lo, il.ev_hi, il.ev_rows, il.ev_ctx, il.rng_row, nullptr, nullptr, il.draw_is, il.draw_ds,
+                  nullptr, nullptr};
   if (il.ev_lo) {  // evidence sets: aggregated per original latent item (il.origin)
-    rc = ensure_agg(ctx, block_id, node_id, il, &it.agg);
+    rc = ensure_agg(c.ctx, c.block_id, c.node_id, il, &c.it.agg);
     if (rc) return rc;
-    it.ev_item = il.origin;
+    c.it.ev_item = il.origin;
   }
-  FastRootDev fr;
-  int fast = 0, fast_ev = 0;
-  const bool tabulated = node_has_tabulated(b, n);  // (generic kernels only; guarded below the way nd.g.on is)
-  // a reference slot whose groups are made BEFORE its new-row branch is looked at (below): the gate and the children of
-  // the branch then run once per group of identical rows instead of once per row
-  ItemGroups g_pre;
-  bool fast_tried = false, groups_tried = false;
-  const double* pre_score = nullptr;  // exact score of every group's current referent (group_gate_kernel)
-  const int32_t* pre_obs = nullptr;   // observed values of every group's row (group_gate_kernel)
-  if (n.kind == PCLEAN_NODE_FK && ctx->prior_mode) {
-    ch.n = 0;  // the new row's choices are sampled from their priors: the branch carries its CRP term alone
-  } else if (n.kind == PCLEAN_NODE_FK) {
-    if (snew_override) {
-      ch.n = 1;
-      ch.arr[0] = snew_override;
-      ch.obs_col[0] = nullptr;
+  c.tabulated = node_has_tabulated(c.b, c.n);
+  return PCLEAN_OK;
+}
+
+// The generic enumeration of items `it`, with the scratch for its scores where the launch computes them one candidate per
+// thread first (few items with evidence sets and long lists)
+static int launch_enum_scratch(EvalCall& c, const ItemsDev& it, double* scores_out, const ProductDev* product) {
+  double* sc_tmp = nullptr;
+  if (!scores_out && !product) {
+    const size_t sc_n = pclean_enum_split_scores(c.nd, it);
+    if (sc_n && !(sc_tmp = scratch<double>(c.ctx, sc_n))) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  }
+  return pclean_launch_enum(c.ctx, c.nd, it, c.ch, c.seed, c.sweep, c.site, c.n_draws, c.lse_out, scores_out, c.draws_out, sc_tmp,
+                            product);
+}
+
+// The items list[j], j < n, of the call's list as a list of their own (sub_items_kernel).  The caller has requested the arrays
+// every sub-list has and hands them in: the scratch pool is positional, and the two callers ask in their own order (gated
+// items: row, ctx, excl; overflowed items: row, excl, ctx and the particles).  The arrays of evidence sets and RNG rows are
+// requested here (all of n words: the overflowed items' origins used to come before their RNG rows, slot for slot the same).
+// eval_node_lse's twin drops the evidence of its list and sample_children's carries particles (sublist_items_kernel): not this.
+static int sub_items(EvalCall& c, unsigned int n, const int32_t* list, int32_t* row2, int32_t* ctx2, int32_t* excl2, ItemList& sil) {
+  const ItemList& il = c.il;
+  int32_t* evl2 = il.ev_lo ? scratch<int32_t>(c.ctx, n) : nullptr;
+  int32_t* evh2 = il.ev_lo ? scratch<int32_t>(c.ctx, n) : nullptr;
+  int32_t* rng2 = il.rng_row ? scratch<int32_t>(c.ctx, n) : nullptr;
+  int32_t* org2 = il.ev_lo ? scratch<int32_t>(c.ctx, n) : nullptr;
+  if (!row2 || !ctx2 || !excl2 || (il.ev_lo && (!evl2 || !evh2 || !org2)) || (il.rng_row && !rng2))
+    return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  hipLaunchKernelGGL(sub_items_kernel, grid1(n), dim3(256), 0, c.ctx->stream, (int)n, list, il.row, il.ctx, c.excl, il.ev_lo,
+                     il.ev_hi, il.rng_row, il.origin, row2, ctx2, excl2, evl2, evh2, rng2, org2);
+  sil = ItemList{(int)n, row2, il.ctx ? ctx2 : nullptr, nullptr, org2, evl2, evh2, il.ev_rows, il.ev_ctx, rng2};
+  return PCLEAN_OK;
+}
+
+// The units of a new-row branch: the groups of g_pre (rows with the same observed tuple, ctx and referent share the gate's
+// verdict and the children's marginals) or the items of the list; and those of them whose open children are evaluated
+struct OpenUnits {
+  bool grouped = false;
+  int n_all = 0;
+  unsigned int n_need = 0;  // units whose new row can have a non-zero weight (all of them when no gate ran)
+  int32_t* list = nullptr;  // ... which they are (null: every unit, the identity)
+  ItemList sil;             // what the children are evaluated for, with the excluded rows
+  const int32_t* sexcl = nullptr;
+  bool sub() const { return n_need < (unsigned int)n_all; }
+};
+
+// cacheable leaves first: exact marginal per unique observed value (versioned cache); upper bounds of the open children
+static int children_bounds(EvalCall& c, GateDev& gt, int* n_open, bool* gate) {
+  for (int k = 0; k < c.n.n_children; ++k) {
+    const int cid = c.b.children[c.n.child_begin + k];
+    const pclean_node& cn = c.b.nodes[cid];
+    if (cn.kind == PCLEAN_NODE_LEAF && cn.cacheable) {
+      const int rc = ensure_leaf_cache(c.ctx, c.block_id, cid, &c.ch.arr[k], &c.ch.obs_col[k], &c.ch.n_obs[k]);
+      if (rc) return rc;
+      gt.cache[k] = c.ch.arr[k];
+      gt.obs_col[k] = c.ch.obs_col[k];
+      gt.n_obs[k] = c.ch.n_obs[k];
+      gt.ub[k] = 0.0;
+      if (c.il.ev_lo) gt.ub[k] = subtree_ub(c.ctx, c.b, cid);  // evidence sets: no single observed row to look up
     } else {
-      if (n.n_children > PCLEAN_MAX_CHILDREN) return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "too many children");
-      ch.n = n.n_children;
-      const CandTable& t = ctx->cand[n.table];
-      // cacheable leaves first: exact marginal per unique observed value (versioned cache)
-      GateDev gt{};
-      gt.n = n.n_children;
-      int n_open = 0;
-      // (short lists — new-row sampling, tests — are not worth the extra launches and the count read-back)
-      const char* gm = getenv("PCLEAN_GATE_MIN");
-      const int gate_min = gm ? atoi(gm) : 2048;
-      bool gate = excl && !scores_out && il.n >= gate_min && !getenv("PCLEAN_NO_GATE");
-      // (rejuvenation sweeps only: the initialisation's batches have no current referent to compare with)
-      SweepState::GateStat* gstat = (gate && node_id < 64 && sweep < 0x7ffffff0u && !il.ev_lo && !getenv("PCLEAN_GATE_ALWAYS"))
-                                        ? &s->gate_stat[block_id * 64 + node_id] : nullptr;
-      if (gstat && gstat->skip > 0) {
-        --gstat->skip;
-        gate = false;
-        gstat = nullptr;
-      }
-      for (int c = 0; c < n.n_children; ++c) {
-        const int cid = b.children[n.child_begin + c];
-        const pclean_node& cn = b.nodes[cid];
-        if (cn.kind == PCLEAN_NODE_LEAF && cn.cacheable) {
-          rc = ensure_leaf_cache(ctx, block_id, cid, &ch.arr[c], &ch.obs_col[c], &ch.n_obs[c]);
-          if (rc) return rc;
-          gt.cache[c] = ch.arr[c];
-          gt.obs_col[c] = ch.obs_col[c];
-          gt.n_obs[c] = ch.n_obs[c];
-          gt.ub[c] = 0.0;
-          if (il.ev_lo) gt.ub[c] = subtree_ub(ctx, b, cid);  // evidence sets: no single observed row to look up
-        } else {
-          ++n_open;
-          gt.cache[c] = nullptr;
-          gt.ub[c] = subtree_ub(ctx, b, cid);
-          if (!(gt.ub[c] < INFINITY)) gate = false;
-        }
-        if (il.ev_lo && !(gt.ub[c] < INFINITY)) gate = false;
-      }
-      // Gate of the new-row branch (gate_new_kernel): items whose current referent scores so well that
-      // the new row's fixed-point weight is exactly 0 skip the evaluation of the open children.
-      static const bool no_group_gate = getenv("PCLEAN_NO_GROUP_GATE") != nullptr;
-      bool pre_grouped = false;
-      if (n_open > 0 && n_draws > 0 && excl && !scores_out && !ctx->force_generic && !nd.g.on && !tabulated && !il.rng_row &&
-          !il.ev_lo && !no_group_gate) {
-        fast = try_fast_root(ctx, block_id, node_id, fr);
-        if (fast < 0) return fast;
-        fast_tried = true;
-        if (fast) {
-          rc = make_item_groups(ctx, block_id, node_id, il, excl, g_pre, fast_split_m);
-          if (rc) return rc;
-          groups_tried = true;
-          pre_grouped = g_pre.n_groups > 0;
-        }
-      }
-      if (pre_grouped) {
-        // ---- the new-row branch per GROUP: rows with the same (observed tuple, ctx, referent) share the gate's verdict
-        // and the children's marginals; the gate scores the current referent through the compact byte rows
-        // (group_gate_kernel) and hands the score on to the group descriptors
-        const int ng = g_pre.n_groups;
-        ItemsDev itg = it;
-        itg.n = ng;
-        itg.grp_off = g_pre.grp_off;
-        itg.members = g_pre.members;
-        int32_t* list_g = nullptr;
-        unsigned int n_need = (unsigned int)ng;
-        if (gate) {
-          ProfScope ps(ctx, "gate_new_branch");
-          int32_t* flag = scratch<int32_t>(ctx, ng);
-          list_g = scratch<int32_t>(ctx, ng);
-          double* sc = scratch<double>(ctx, ng);
-          int32_t* ow = scratch<int32_t>(ctx, (size_t)ng * PCLEAN_MAX_TERMS);
-          if (!flag || !list_g || !sc || !ow) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-          if (time_it && s->evg0) (void)hipEventRecord(s->evg0, ctx->stream);
-          rc = pclean_launch_group_gate(ctx, fr, itg, gt, flag, sc, ow);
-          if (rc) return rc;
-          if (time_it && s->evg0) {
-            (void)hipEventRecord(s->evg1, ctx->stream);
-            s->gate_timed = true;
-          }
-          unsigned int* need_ctr = fresh_counter(ctx);
-          if (!need_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
-          hipLaunchKernelGGL(compact_new_kernel, grid1(ng), dim3(256), 0, ctx->stream, (size_t)ng, flag, 1, need_ctr, list_g,
-                             nullptr);
-          PCLEAN_READ_COUNT(ctx, need_ctr, &n_need);
-          pre_score = sc;
-          pre_obs = ow;
-          if (gstat) {
-            gstat->all_need_run = n_need == (unsigned int)ng ? gstat->all_need_run + 1 : 0;
-            if (gstat->all_need_run >= 3) {
-              gstat->skip = 16;
-              gstat->all_need_run = 2;
-            }
-          }
-          if (n_need == (unsigned int)ng) list_g = nullptr;  // (every group: the identity)
-        }
-        ItemList sil;
-        const int32_t* sexcl = nullptr;
-        if (n_need > 0) {
-          int32_t* row2 = scratch<int32_t>(ctx, n_need);
-          int32_t* ctx2 = scratch<int32_t>(ctx, (size_t)n_need * PCLEAN_MAX_CTX);
-          int32_t* excl2 = scratch<int32_t>(ctx, n_need);
-          if (!row2 || !ctx2 || !excl2) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-          hipLaunchKernelGGL(group_rep_items_kernel, grid1(n_need), dim3(256), 0, ctx->stream, (int)n_need, list_g, g_pre.grp_off,
-                             g_pre.members, il.row, il.ctx, excl, row2, ctx2, excl2);
-          sil = ItemList{(int)n_need, row2, il.ctx ? ctx2 : nullptr, nullptr, nullptr};
-          sexcl = excl2;
-        }
-        for (int c = 0; c < n.n_children; ++c) {
-          const int cid = b.children[n.child_begin + c];
-          const pclean_node& cn = b.nodes[cid];
-          if (cn.kind == PCLEAN_NODE_LEAF && cn.cacheable) continue;
-          double* child_lse = scratch<double>(ctx, il.n);
-          if (!child_lse) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-          ch.arr[c] = child_lse;
-          ch.obs_col[c] = nullptr;
-          if (n_need < (unsigned int)ng)  // gated groups: the child's marginal is never looked at with a non-zero weight
-            hipLaunchKernelGGL(fill_f64_kernel, grid1(il.n), dim3(256), 0, ctx->stream, child_lse, (size_t)il.n, -__builtin_inf());
-          if (n_need == 0) continue;
-          const int32_t* child_excl = nullptr;
-          if (cn.kind == PCLEAN_NODE_FK) {
-            if (cn.parent_fk_col < 0 || cn.parent_fk_col >= t.n_cols)
-              return pclean_fail(ctx, PCLEAN_ERR_ARG, "node %d: parent_fk_col out of range", cid);
-            int32_t* ce = scratch<int32_t>(ctx, sil.n);
-            if (!ce) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-            hipLaunchKernelGGL(derive_excl_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, sexcl, t.counts.p,
-                               t.cols.p + (size_t)cn.parent_fk_col * t.n_rows, ce);
-            child_excl = ce;
-          }
-          double* dst = scratch<double>(ctx, sil.n);
-          if (!dst) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-          rc = eval_node_lse(ctx, block_id, cid, sil, child_excl, seed, sweep, dst);
-          if (rc) return rc;
-          if (!list_g && g_pre.uid && fast_split_m == 0)  // (unsplit groups may be large)
-            hipLaunchKernelGGL(member_scatter_f64_kernel, grid1(il.n), dim3(256), 0, ctx->stream, il.n, g_pre.uid, g_pre.members, dst,
-                               child_lse);
-          else
-            hipLaunchKernelGGL(group_scatter_f64_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, list_g, g_pre.grp_off,
-                               g_pre.members, dst, child_lse);
-        }
-      } else {
-      int32_t* list = nullptr;
-      unsigned int n_need = (unsigned int)il.n;
-      if (gate && n_open > 0) {
-        ProfScope ps(ctx, "gate_new_branch");
-        int32_t* flag = scratch<int32_t>(ctx, il.n);
-        list = scratch<int32_t>(ctx, il.n);
-        if (!flag || !list) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-        if (s->counter.alloc(4)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
-        rc = pclean_launch_gate(ctx, nd, it, gt, flag);
-        if (rc) return rc;
-        unsigned int* need_ctr = fresh_counter(ctx);
-        if (!need_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
-        hipLaunchKernelGGL(compact_new_kernel, grid1(il.n), dim3(256), 0, ctx->stream, (size_t)il.n, flag, 1, need_ctr, list,
-                           nullptr);
-        PCLEAN_READ_COUNT(ctx, need_ctr, &n_need);
-        if (gstat) {
-          gstat->all_need_run = n_need == (unsigned int)il.n ? gstat->all_need_run + 1 : 0;
-          if (gstat->all_need_run >= 3) {
-            gstat->skip = 16;
-            gstat->all_need_run = 2;  // one more useless evaluation after the pause starts the next one
-          }
-        }
-      } else {
-        gate = false;
-      }
-      const bool sub = gate && n_need < (unsigned int)il.n;
-      ItemList sil = il;
-      const int32_t* sexcl = excl;
-      if (sub && n_need > 0) {
-        int32_t* row2 = scratch<int32_t>(ctx, n_need);
-        int32_t* ctx2 = scratch<int32_t>(ctx, (size_t)n_need * PCLEAN_MAX_CTX);
-        int32_t* excl2 = scratch<int32_t>(ctx, n_need);
-        int32_t* evl2 = il.ev_lo ? scratch<int32_t>(ctx, n_need) : nullptr;
-        int32_t* evh2 = il.ev_lo ? scratch<int32_t>(ctx, n_need) : nullptr;
-        int32_t* rng2 = il.rng_row ? scratch<int32_t>(ctx, n_need) : nullptr;
-        int32_t* org2 = il.ev_lo ? scratch<int32_t>(ctx, n_need) : nullptr;
-        if (!row2 || !ctx2 || !excl2 || (il.ev_lo && (!evl2 || !evh2 || !org2)) || (il.rng_row && !rng2))
-          return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-        hipLaunchKernelGGL(sub_items_kernel, grid1(n_need), dim3(256), 0, ctx->stream, (int)n_need, list, il.row, il.ctx,
-                           excl, il.ev_lo, il.ev_hi, il.rng_row, il.origin, row2, ctx2, excl2, evl2, evh2, rng2, org2);
-        sil = ItemList{(int)n_need, row2, il.ctx ? ctx2 : nullptr, nullptr, org2, evl2, evh2, il.ev_rows, il.ev_ctx, rng2};
-        sexcl = excl2;
-      }
-      for (int c = 0; c < n.n_children; ++c) {
-        const int cid = b.children[n.child_begin + c];
-        const pclean_node& cn = b.nodes[cid];
-        if (cn.kind == PCLEAN_NODE_LEAF && cn.cacheable) continue;
-        double* child_lse = scratch<double>(ctx, il.n);
-        if (!child_lse) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-        ch.arr[c] = child_lse;
-        ch.obs_col[c] = nullptr;
-        if (sub) {  // gated items: the child's marginal is never looked at with a non-zero weight
-          hipLaunchKernelGGL(fill_f64_kernel, grid1(il.n), dim3(256), 0, ctx->stream, child_lse, (size_t)il.n,
-                             -__builtin_inf());
-          if (n_need == 0) continue;
-        }
-        const int32_t* child_excl = nullptr;
-        if (cn.kind == PCLEAN_NODE_FK && sexcl) {
-          if (cn.parent_fk_col < 0 || cn.parent_fk_col >= t.n_cols)
-            return pclean_fail(ctx, PCLEAN_ERR_ARG, "node %d: parent_fk_col out of range", cid);
-          int32_t* ce = scratch<int32_t>(ctx, sil.n);
-          if (!ce) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-          hipLaunchKernelGGL(derive_excl_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, sexcl, t.counts.p,
-                             t.cols.p + (size_t)cn.parent_fk_col * t.n_rows, ce);
-          child_excl = ce;
-        }
-        double* dst = child_lse;
-        if (sub) {
-          dst = scratch<double>(ctx, sil.n);
-          if (!dst) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-        }
-        rc = eval_node_lse(ctx, block_id, cid, sil, child_excl, seed, sweep, dst);
-        if (rc) return rc;
-        if (sub)
-          hipLaunchKernelGGL(scatter_f64_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, list, dst, child_lse);
-      }
-      }  // (item-level gate)
+      ++*n_open;
+      gt.cache[k] = nullptr;
+      gt.ub[k] = subtree_ub(c.ctx, c.b, cid);
+      if (!(gt.ub[k] < INFINITY)) *gate = false;
+    }
+    if (c.il.ev_lo && !(gt.ub[k] < INFINITY)) *gate = false;
+  }
+  return PCLEAN_OK;
+}
+
+// Gate of the new-row branch: units whose current referent scores so well that the new row's fixed-point weight is exactly 0
+// skip the evaluation of the open children.  Per item by gate_new_kernel; per group by group_gate_kernel, which scores the
+// current referent through the compact byte rows and hands the score on to the group descriptors (pre_score, pre_obs).
+// Leaves the list of the units that need the children, and their number (a read-back).
+static int gate_and_compact(EvalCall& c, const GateDev& gt, SweepState::GateStat* gstat, OpenUnits& u) {
+  pclean_ctx* ctx = c.ctx;
+  SweepState* s = c.s;
+  ProfScope ps(ctx, "gate_new_branch");
+  const int n = u.n_all;
+  int32_t* flag = scratch<int32_t>(ctx, n);
+  u.list = scratch<int32_t>(ctx, n);
+  double* sc = u.grouped ? scratch<double>(ctx, n) : nullptr;
+  int32_t* ow = u.grouped ? scratch<int32_t>(ctx, (size_t)n * PCLEAN_MAX_TERMS) : nullptr;
+  if (!flag || !u.list || (u.grouped && (!sc || !ow))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  if (u.grouped) {
+    ItemsDev itg = c.it;
+    itg.n = n;
+    itg.grp_off = c.g_pre.grp_off;
+    itg.members = c.g_pre.members;
+    if (c.time_it && s->evg0) (void)hipEventRecord(s->evg0, ctx->stream);
+    const int rc = pclean_launch_group_gate(ctx, c.fr, itg, gt, flag, sc, ow);
+    if (rc) return rc;
+    if (c.time_it && s->evg0) {
+      (void)hipEventRecord(s->evg1, ctx->stream);
+      s->gate_timed = true;
+    }
+  } else {
+    if (s->counter.alloc(4)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+    const int rc = pclean_launch_gate(ctx, c.nd, c.it, gt, flag);
+    if (rc) return rc;
+  }
+  unsigned int* need_ctr = fresh_counter(ctx);
+  if (!need_ctr) return pclean_fail(ctx, PCLEAN_ERR_HIP, "counter bank: device alloc failed");
+  hipLaunchKernelGGL(compact_new_kernel, grid1(n), dim3(256), 0, ctx->stream, (size_t)n, flag, 1, need_ctr, u.list, nullptr);
+  PCLEAN_READ_COUNT(ctx, need_ctr, &u.n_need);
+  if (u.grouped) {
+    c.pre_score = sc;
+    c.pre_obs = ow;
+  }
+  if (gstat) {  // a gate that keeps letting every unit through pauses for 16 evaluations
+    gstat->all_need_run = !u.sub() ? gstat->all_need_run + 1 : 0;
+    if (gstat->all_need_run >= 3) {
+      gstat->skip = 16;
+      gstat->all_need_run = 2;  // one more useless evaluation after the pause starts the next one
     }
   }
-  // cacheable option list: log-marginal and draws from the per-observed-value coarse prefix (leaf_coarse_draw_kernel)
-  static const bool no_coarse = getenv("PCLEAN_NO_COARSE_LEAF") != nullptr;
-  if (n.kind == PCLEAN_NODE_LEAF && n.cacheable && !il.ev_lo && !scores_out && !ctx->force_generic && !ctx->obs_override &&
-      !no_coarse && !nd.g.on && !tabulated && !ctx->prior_mode) {
-    const double* cache = nullptr;
-    const int32_t* ocol = nullptr;
-    int n_obs = 0;
-    rc = ensure_leaf_cache(ctx, block_id, node_id, &cache, &ocol, &n_obs);
-    if (rc) return rc;
-    ProfScope ps(ctx, "option_list_coarse_draw");
-    return pclean_launch_leaf_coarse_draw(ctx, nd, it, ocol, n_obs, pclean_leaf_coarse_blocks(nd.n_cand), cache,
-                                          b.leaf_m[node_id].p, b.leaf_U[node_id].p, b.leaf_coarse[node_id].p, seed, sweep,
-                                          PCLEAN_SITE_NODE(block_id, node_id), n_draws, lse_out, draws_out);
+  if (!u.sub()) u.list = nullptr;
+  return PCLEAN_OK;
+}
+
+// what the open children are evaluated for: the representatives of the groups that need them; or the items that do, which
+// is the call's own list when the gate let every item through or did not run
+static int open_sublist(EvalCall& c, OpenUnits& u) {
+  const ItemList& il = c.il;
+  if (!u.grouped) {
+    u.sil = il;
+    u.sexcl = c.excl;
   }
+  if (u.n_need == 0 || (!u.grouped && !u.sub())) return PCLEAN_OK;
+  int32_t* row2 = scratch<int32_t>(c.ctx, u.n_need);
+  int32_t* ctx2 = scratch<int32_t>(c.ctx, (size_t)u.n_need * PCLEAN_MAX_CTX);
+  int32_t* excl2 = scratch<int32_t>(c.ctx, u.n_need);
+  if (u.grouped) {
+    if (!row2 || !ctx2 || !excl2) return pclean_fail(c.ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    hipLaunchKernelGGL(group_rep_items_kernel, grid1(u.n_need), dim3(256), 0, c.ctx->stream, (int)u.n_need, u.list, c.g_pre.grp_off,
+                       c.g_pre.members, il.row, il.ctx, c.excl, row2, ctx2, excl2);
+    u.sil = ItemList{(int)u.n_need, row2, il.ctx ? ctx2 : nullptr, nullptr, nullptr};
+  } else {
+    const int rc = sub_items(c, u.n_need, u.list, row2, ctx2, excl2, u.sil);
+    if (rc) return rc;
+  }
+  u.sexcl = excl2;
+  return PCLEAN_OK;
+}
+
+// the log-marginals of the open children (ch.arr[k], one value per item of the list): evaluated for u.sil and scattered to
+// the items they stand for; -inf for the items of gated units
+static int eval_open_children(EvalCall& c, const OpenUnits& u) {
+  pclean_ctx* ctx = c.ctx;
+  const ItemList& il = c.il;
+  const ItemList& sil = u.sil;
+  const CandTable& t = ctx->cand[c.n.table];
+  for (int k = 0; k < c.n.n_children; ++k) {
+    const int cid = c.b.children[c.n.child_begin + k];
+    const pclean_node& cn = c.b.nodes[cid];
+    if (cn.kind == PCLEAN_NODE_LEAF && cn.cacheable) continue;
+    double* child_lse = scratch<double>(ctx, il.n);
+    if (!child_lse) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    c.ch.arr[k] = child_lse;
+    c.ch.obs_col[k] = nullptr;
+    if (u.sub()) {  // gated units: the child's marginal is never looked at with a non-zero weight
+      hipLaunchKernelGGL(fill_f64_kernel, grid1(il.n), dim3(256), 0, ctx->stream, child_lse, (size_t)il.n, -__builtin_inf());
+      if (u.n_need == 0) continue;
+    }
+    const int32_t* child_excl = nullptr;
+    if (cn.kind == PCLEAN_NODE_FK && u.sexcl) {
+      if (cn.parent_fk_col < 0 || cn.parent_fk_col >= t.n_cols)
+        return pclean_fail(ctx, PCLEAN_ERR_ARG, "node %d: parent_fk_col out of range", cid);
+      int32_t* ce = scratch<int32_t>(ctx, sil.n);
+      if (!ce) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+      hipLaunchKernelGGL(derive_excl_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, u.sexcl, t.counts.p,
+                         t.cols.p + (size_t)cn.parent_fk_col * t.n_rows, ce);
+      child_excl = ce;
+    }
+    double* dst = child_lse;
+    if (u.grouped || u.sub()) {
+      dst = scratch<double>(ctx, sil.n);
+      if (!dst) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    }
+    const int rc = eval_node_lse(ctx, c.block_id, cid, sil, child_excl, c.seed, c.sweep, dst);
+    if (rc) return rc;
+    if (u.grouped && !u.list && c.g_pre.uid && c.fast_split_m == 0)  // (unsplit groups may be large)
+      hipLaunchKernelGGL(member_scatter_f64_kernel, grid1(il.n), dim3(256), 0, ctx->stream, il.n, c.g_pre.uid, c.g_pre.members, dst,
+                         child_lse);
+    else if (u.grouped)
+      hipLaunchKernelGGL(group_scatter_f64_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, u.list, c.g_pre.grp_off,
+                         c.g_pre.members, dst, child_lse);
+    else if (u.sub())
+      hipLaunchKernelGGL(scatter_f64_kernel, grid1(sil.n), dim3(256), 0, ctx->stream, sil.n, u.list, dst, child_lse);
+  }
+  return PCLEAN_OK;
+}
+
+// The new-row branch of a reference slot: ch = the log-marginals of the new row's children, from the leaf caches and from
+// evaluations of the open children for the units the gate lets through
+static int new_row_branch(EvalCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  const pclean_node& n = c.n;
+  const ItemList& il = c.il;
+  if (n.kind != PCLEAN_NODE_FK) return PCLEAN_OK;
+  if (ctx->prior_mode) {
+    c.ch.n = 0;  // the new row's choices are sampled from their priors: the branch carries its CRP term alone
+    return PCLEAN_OK;
+  }
+  if (c.snew_override) {
+    c.ch.n = 1;
+    c.ch.arr[0] = c.snew_override;
+    c.ch.obs_col[0] = nullptr;
+    return PCLEAN_OK;
+  }
+  if (n.n_children > PCLEAN_MAX_CHILDREN) return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "too many children");
+  c.ch.n = n.n_children;
+  GateDev gt{};
+  gt.n = n.n_children;
+  // (short lists — new-row sampling, tests — are not worth the extra launches and the count read-back)
+  bool gate = c.excl && !c.scores_out && il.n >= c.sw.live.gate_min() && !c.sw.live.no_gate();
+  // (rejuvenation sweeps only: the initialisation's batches have no current referent to compare with)
+  SweepState::GateStat* gstat = (gate && c.node_id < 64 && c.sweep < 0x7ffffff0u && !il.ev_lo && !c.sw.live.gate_always())
+                                    ? &c.s->gate_stat[c.block_id * 64 + c.node_id] : nullptr;
+  if (gstat && gstat->skip > 0) {
+    --gstat->skip;
+    gate = false;
+    gstat = nullptr;
+  }
+  int n_open = 0;
+  int rc = children_bounds(c, gt, &n_open, &gate);
+  if (rc) return rc;
+  OpenUnits u;
+  if (n_open > 0 && c.n_draws > 0 && c.excl && !c.scores_out && !ctx->force_generic && !c.nd.g.on && !c.tabulated && !il.rng_row &&
+      !il.ev_lo && !c.sw.cached.no_group_gate) {
+    c.fast = try_fast_root(ctx, c.block_id, c.node_id, c.fr);
+    if (c.fast < 0) return c.fast;
+    c.fast_tried = true;
+    if (c.fast) {
+      rc = make_item_groups(ctx, c.block_id, c.node_id, il, c.excl, c.g_pre, c.fast_split_m);
+      if (rc) return rc;
+      c.groups_tried = true;
+      u.grouped = c.g_pre.n_groups > 0;
+    }
+  }
+  u.n_all = u.grouped ? c.g_pre.n_groups : il.n;
+  u.n_need = (unsigned int)u.n_all;
+  if (gate && n_open > 0) {
+    rc = gate_and_compact(c, gt, gstat, u);
+    if (rc) return rc;
+  }
+  rc = open_sublist(c, u);
+  if (rc) return rc;
+  return eval_open_children(c, u);
+}
+
+// cacheable option list: log-marginal and draws from the per-observed-value coarse prefix (leaf_coarse_draw_kernel)
+static int leaf_coarse_draw(EvalCall& c, bool* done) {
+  pclean_ctx* ctx = c.ctx;
+  *done = c.n.kind == PCLEAN_NODE_LEAF && c.n.cacheable && !c.il.ev_lo && !c.scores_out && !ctx->force_generic && !ctx->obs_override &&
+          !c.sw.cached.no_coarse && !c.nd.g.on && !c.tabulated && !ctx->prior_mode;
+  if (!*done) return PCLEAN_OK;
+  const double* cache = nullptr;
+  const int32_t* ocol = nullptr;
+  int n_obs = 0;
+  const int rc = ensure_leaf_cache(ctx, c.block_id, c.node_id, &cache, &ocol, &n_obs);
+  if (rc) return rc;
+  ProfScope ps(ctx, "option_list_coarse_draw");
+  return pclean_launch_leaf_coarse_draw(ctx, c.nd, c.it, ocol, n_obs, pclean_leaf_coarse_blocks(c.nd.n_cand), cache,
+                                        c.b.leaf_m[c.node_id].p, c.b.leaf_U[c.node_id].p, c.b.leaf_coarse[c.node_id].p, c.seed,
+                                        c.sweep, PCLEAN_SITE_NODE(c.block_id, c.node_id), c.n_draws, c.lse_out, c.draws_out);
+}
+
+// fast / fast_ev: whether the launch takes the compact-table kernels (plain, or scanning evidence sets), with fr filled
+static int choose_compact_path(EvalCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  const ItemList& il = c.il;
   // A marginal-only evaluation of a few hundred items (the nested slots of a new-row branch that passed the gate: ~250
   // groups per 1M-row sweep) is one launch of the LDS-resident generic kernel with 1024 threads per item; the compact-table
   // path would spend ~10 launches on it (prior rows, alive bits, descriptors, settle, scan, log-sum-exp, overflow re-run) and
   // refresh the node's prior rows after every commit for nothing.  Same results either way (wave == generic is tested).
-  static const bool no_small_generic = getenv("PCLEAN_NO_SMALL_GENERIC") != nullptr;
-  const bool small_lse = !no_small_generic && n_draws == 0 && il.n <= 1024 && !il.ev_lo &&
-                         (size_t)(nd.n_cand + 2) * 8 + (16 + 64) * 8 <= (size_t)160 * 1024;
-  if (!fast_tried && !scores_out && !snew_override && !ctx->force_generic && !nd.g.on && !tabulated && !ctx->prior_mode &&
-      !small_lse) {
-    static const int ev_slot_min_items = getenv("PCLEAN_EV_SLOT_MIN_ITEMS") ? atoi(getenv("PCLEAN_EV_SLOT_MIN_ITEMS")) : 64;
-    if (!il.ev_lo)
-      fast = try_fast_root(ctx, block_id, node_id, fr);
-    // option lists, and since round 6 reference slots (the latent Places re-choosing their County in one batch, 20 ms ->
-    // 1.6 ms).  The slot's candidate-compact tables follow the referred table's columns: a sub-batch's host commit re-uploads
-    // them with a handful of rows created / collected, and pclean_set_table hands the changed rows on (cols_delta_*) so that
-    // the tables are refreshed for those rows alone — rebuilt whole they cost 0.32 ms per call against the 0.29 ms of generic
-    // enumeration they replace (Hospital sub-batches of 333 rows), which is what PCLEAN_EV_SLOT_MIN_ITEMS=1024 goes back to
-    else if ((n.kind == PCLEAN_NODE_LEAF || (il.n >= ev_slot_min_items && !getenv("PCLEAN_NO_FAST_EV_SLOTS"))) && n_draws <= 1 &&
-             !getenv("PCLEAN_NO_FAST_EV"))
-      fast_ev = try_fast_root(ctx, block_id, node_id, fr, true);
-    if (fast < 0) return fast;
-    if (fast_ev < 0) return fast_ev;
-    if (fast_ev) {  // needs at least one plain (compact-table) term to filter on
-      bool any = false;
-      for (int i = 0; i < fr.n_terms; ++i) any |= fr.terms[i].comp != nullptr;
-      if (!any) fast_ev = 0;
-    }
+  const bool small_lse = !c.sw.cached.no_small_generic && c.n_draws == 0 && il.n <= 1024 && !il.ev_lo &&
+                         (size_t)(c.nd.n_cand + 2) * 8 + (16 + 64) * 8 <= (size_t)160 * 1024;
+  if (c.fast_tried || c.scores_out || c.snew_override || ctx->force_generic || c.nd.g.on || c.tabulated || ctx->prior_mode || small_lse)
+    return PCLEAN_OK;
+  if (!il.ev_lo)
+    c.fast = try_fast_root(ctx, c.block_id, c.node_id, c.fr);
+  // option lists, and since round 6 reference slots (the latent Places re-choosing their County in one batch, 20 ms ->
+  // 1.6 ms).  The slot's candidate-compact tables follow the referred table's columns: a sub-batch's host commit re-uploads
+  // them with a handful of rows created / collected, and pclean_set_table hands the changed rows on (cols_delta_*) so that
+  // the tables are refreshed for those rows alone — rebuilt whole they cost 0.32 ms per call against the 0.29 ms of generic
+  // enumeration they replace (Hospital sub-batches of 333 rows), which is what PCLEAN_EV_SLOT_MIN_ITEMS=1024 goes back to
+  else if ((c.n.kind == PCLEAN_NODE_LEAF || (il.n >= c.sw.cached.ev_slot_min_items && !c.sw.live.no_fast_ev_slots())) && c.n_draws <= 1 &&
+           !c.sw.live.no_fast_ev())
+    c.fast_ev = try_fast_root(ctx, c.block_id, c.node_id, c.fr, true);
+  if (c.fast < 0) return c.fast;
+  if (c.fast_ev < 0) return c.fast_ev;
+  if (c.fast_ev) {  // needs at least one plain (compact-table) term to filter on
+    bool any = false;
+    for (int i = 0; i < c.fr.n_terms; ++i) any |= c.fr.terms[i].comp != nullptr;
+    if (!any) c.fast_ev = 0;
   }
-  // Items with identical score vectors (same observed tuple, ctx and excluded row) share one
-  // wavefront / workgroup: scores once, draws per member item.
-  ItemGroups ggrp;  // the grouping of the launch below (n_groups == 0: none)
-  {
-    const int nc = nd.n_cand + (n.kind == PCLEAN_NODE_FK ? 1 : 0);
-    const bool lds_kernel = (size_t)((nc + 1) & ~1) * 8 + (16 + 64) * 8 <= 160 * 1024;
-    if (n_draws > 0 && !scores_out && !snew_override && !ctx->force_generic && !il.rng_row && !il.ev_lo &&
-        (fast || lds_kernel)) {
-      ItemGroups g = g_pre;
-      // wave kernel: at most ~2 x 256 draws per group (see item_head_kernel)
-      if (!groups_tried) {
-        rc = make_item_groups(ctx, block_id, node_id, il, excl, g, fast ? fast_split_m : 0);
-        if (rc) return rc;
-      }
-      if (g.n_groups > 0) {
-        it.n = g.n_groups;
-        it.grp_off = g.grp_off;
-        it.members = g.members;
-        if (fast && fast_split_m == 0) it.grp_uid = g.uid;  // (unsplit groups: per-member outputs by position)
-        ggrp = g;
-      }
-    }
+  return PCLEAN_OK;
+}
+
+// Items with identical score vectors (same observed tuple, ctx and excluded row) share one
+// wavefront / workgroup: scores once, draws per member item.
+static int group_for_launch(EvalCall& c) {
+  const ItemList& il = c.il;
+  const int nc = c.nd.n_cand + (c.n.kind == PCLEAN_NODE_FK ? 1 : 0);
+  const bool lds_kernel = (size_t)((nc + 1) & ~1) * 8 + (16 + 64) * 8 <= 160 * 1024;
+  if (!(c.n_draws > 0 && !c.scores_out && !c.snew_override && !c.ctx->force_generic && !il.rng_row && !il.ev_lo &&
+        (c.fast || lds_kernel)))
+    return PCLEAN_OK;
+  ItemGroups g = c.g_pre;
+  // wave kernel: at most ~2 x 256 draws per group (see item_head_kernel)
+  if (!c.groups_tried) {
+    const int rc = make_item_groups(c.ctx, c.block_id, c.node_id, il, c.excl, g, c.fast ? c.fast_split_m : 0);
+    if (rc) return rc;
   }
-  const uint32_t site = PCLEAN_SITE_NODE(block_id, node_id);
-  if (time_it) {
-    pclean_root_stats& rs = ctx->root_stats;
-    rs = pclean_root_stats{};
-    rs.fast = fast;
-    rs.n_items = il.n;
-    rs.n_groups = it.n;
-    rs.n_cand = nd.n_cand;
-    rs.n_terms = n.n_terms;
-    rs.n_draws = n_draws;
-    rs.pre_scored = pre_score ? 1 : 0;
-    if (fast) {
-      rs.kpad = fr.kscan;  // (what the scans walk: the candidates below the table's high-water mark, FastRootDev::kscan)
-      rs.cstride = std::min(fr.cstride, (((fr.kscan + 63) >> 6) + 15) & ~15);
-      rs.n_pre = fr.n_pre;
-      for (int p = 0; p < 3; ++p) rs.pre_obs_col[p] = p < fr.n_pre ? b.terms[n.term_begin + fr.pre[p]].obs_col : -1;
-    }
+  if (g.n_groups > 0) {
+    c.it.n = g.n_groups;
+    c.it.grp_off = g.grp_off;
+    c.it.members = g.members;
+    if (c.fast && c.fast_split_m == 0) c.it.grp_uid = g.uid;  // (unsplit groups: per-member outputs by position)
+    c.ggrp = g;
   }
-  if (!fast && !fast_ev) {
-    ProductDev prd;
-    const bool product = pclean_product_plan(ctx->cand[n.table], nd, it, &prd);  // (the phase name says which path a leaf took)
-    ProfScope ps(ctx, n.kind == PCLEAN_NODE_FK ? "enum_fk_generic" : (product ? "enum_leaf_product" : "enum_leaf_generic"));
-    if (time_it) (void)hipEventRecord(s->ev0, ctx->stream);
-    double* sc_tmp = nullptr;  // (few items with evidence sets and long lists: the scores one candidate per thread first)
-    if (!scores_out && !product) {
-      const size_t sc_n = pclean_enum_split_scores(nd, it);
-      if (sc_n && !(sc_tmp = scratch<double>(ctx, sc_n))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-    }
-    rc = pclean_launch_enum(ctx, nd, it, ch, seed, sweep, site, n_draws, lse_out, scores_out, draws_out, sc_tmp,
-                            product ? &prd : nullptr);
-    if (time_it) (void)hipEventRecord(s->ev1, ctx->stream);
-    return rc;
+  return PCLEAN_OK;
+}
+
+static void note_root_stats(EvalCall& c) {  // the timed launch (a block's root): what pclean_get_root_stats reports
+  pclean_root_stats& rs = c.ctx->root_stats;
+  rs = pclean_root_stats{};
+  rs.fast = c.fast;
+  rs.n_items = c.il.n;
+  rs.n_groups = c.it.n;
+  rs.n_cand = c.nd.n_cand;
+  rs.n_terms = c.n.n_terms;
+  rs.n_draws = c.n_draws;
+  rs.pre_scored = c.pre_score ? 1 : 0;
+  if (c.fast) {
+    const FastRootDev& fr = c.fr;
+    rs.kpad = fr.kscan;  // (what the scans walk: the candidates below the table's high-water mark, FastRootDev::kscan)
+    rs.cstride = std::min(fr.cstride, (((fr.kscan + 63) >> 6) + 15) & ~15);
+    rs.n_pre = fr.n_pre;
+    for (int p = 0; p < 3; ++p) rs.pre_obs_col[p] = p < fr.n_pre ? c.b.terms[c.n.term_begin + fr.pre[p]].obs_col : -1;
   }
-  // compact-table kernels; items whose survivor list overflows are re-run over all candidates
-  int32_t* oflag = scratch<int32_t>(ctx, il.n);
-  if (!oflag || s->counter.alloc(4)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+}
+
+static int launch_generic(EvalCall& c) {
+  ProductDev prd;
+  const bool product = pclean_product_plan(c.ctx->cand[c.n.table], c.nd, c.it, &prd);  // (the phase name says which path a leaf took)
+  ProfScope ps(c.ctx, c.n.kind == PCLEAN_NODE_FK ? "enum_fk_generic" : (product ? "enum_leaf_product" : "enum_leaf_generic"));
+  if (c.time_it) (void)hipEventRecord(c.s->ev0, c.ctx->stream);
+  const int rc = launch_enum_scratch(c, c.it, c.scores_out, product ? &prd : nullptr);
+  if (c.time_it) (void)hipEventRecord(c.s->ev1, c.ctx->stream);
+  return rc;
+}
+
+// compact-table kernels; items whose survivor list overflows are re-run over all candidates: the markers, or the device
+// list that stands for them
+static int overflow_setup(EvalCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  SweepState* s = c.s;
+  const ItemList& il = c.il;
+  c.oflag = scratch<int32_t>(ctx, il.n);
+  if (!c.oflag || s->counter.alloc(4)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
   // Sync-free re-run: the scan kernel appends the overflowed items to a device list that overflow_lds_kernel
   // (root_wave.hip) consumes with a fixed grid; the count is only read at the end of the call, for the statistics.
-  static const bool no_fast_over = getenv("PCLEAN_NO_FAST_OVERFLOW") != nullptr;
-  const bool list_mode = fast && !no_fast_over && pclean_overflow_fast_ok(fr, it) && s->over_rec.size() < OVER_SLOTS &&
-                         s->over_ctr.p != nullptr;
+  c.list_mode = c.fast && !c.sw.cached.no_fast_over && pclean_overflow_fast_ok(c.fr, c.it) && s->over_rec.size() < OVER_SLOTS &&
+                s->over_ctr.p != nullptr;
   // Evidence sets: the scan appends the items it could not settle to a device list as well, and the generic kernel
   // re-runs them as an indirect launch (ItemsDev::sel) of il.n workgroups that retire beyond the list's length — a
   // latent sub-batch evaluates a dozen option lists, each of which used to wait for its count here.
-  static const bool no_ev_list = getenv("PCLEAN_NO_EV_LIST") != nullptr;
-  const bool ev_list_mode = fast_ev && !no_ev_list && s->over_rec.size() < OVER_SLOTS && s->over_ctr.p != nullptr;
-  unsigned int* over_count = (list_mode || ev_list_mode) ? s->over_ctr.p + s->over_rec.size() : s->counter.p + 1;
-  int32_t* over_list = nullptr;
-  if (list_mode || ev_list_mode) {
-    over_list = scratch<int32_t>(ctx, il.n);
-    if (!over_list) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-    s->over_rec.push_back(SweepState::OverRec{block_id, node_id, il.n, time_it, n.kind == PCLEAN_NODE_LEAF, fast_ev ? 64 : 1024});
+  c.ev_list_mode = c.fast_ev && !c.sw.cached.no_ev_list && s->over_rec.size() < OVER_SLOTS && s->over_ctr.p != nullptr;
+  const bool listed = c.list_mode || c.ev_list_mode;
+  c.over_count = listed ? s->over_ctr.p + s->over_rec.size() : s->counter.p + 1;
+  if (listed) {
+    c.over_list = scratch<int32_t>(ctx, il.n);
+    if (!c.over_list) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    s->over_rec.push_back(SweepState::OverRec{c.block_id, c.node_id, il.n, c.time_it, c.n.kind == PCLEAN_NODE_LEAF, c.fast_ev ? 64 : 1024});
   } else {
-    { const int rcz = dev_zero(ctx, s->counter.p + 1, sizeof(unsigned int)); if (rcz) return rcz; }
+    const int rcz = dev_zero(ctx, s->counter.p + 1, sizeof(unsigned int));
+    if (rcz) return rcz;
   }
-  if (!ev_list_mode)  // (the list stands for the markers there)
-    { const int rcz = dev_zero(ctx, oflag, (size_t)il.n * sizeof(int32_t)); if (rcz) return rcz; }  // kernels only set overflow markers
-  if (fast) {
-    int32_t* desc = scratch<int32_t>(ctx, pclean_fast_desc_words(it.n));
-    if (!desc) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-    ProfScope ps(ctx, (time_it && block_id == 0) ? "root_scan_block0" : (n.kind == PCLEAN_NODE_FK ? "slot_scan" : "option_scan"));
-    if (time_it) (void)hipEventRecord(s->ev0, ctx->stream);
-    unsigned int* scan_stats = nullptr;
-    if (time_it && s->over_ctr.p) {  // the timed launch (block 0's root): what it read, for bench.py's byte model
-      scan_stats = s->over_ctr.p + OVER_SLOTS;
-      s->scan_stats_used = true;
-    }
-    // the work list of the groups the settle kernel leaves pays when it settles most of them; how many it left last time
-    // comes back with the call's statistics (apply_over_stats)
-    FastRoot& fwl = s->fast[block_id * 64 + node_id];
-    unsigned int* wl_stat = nullptr;
-    if (!fwl.wl_off && node_id < 64 && s->over_rec.size() < OVER_SLOTS && s->over_ctr.p) {
-      wl_stat = s->over_ctr.p + s->over_rec.size();
-      s->over_rec.push_back(SweepState::OverRec{block_id, node_id, it.n, false, false, -1});  // min_items -1: a work-list record
-    }
-    if (fwl.wl_off > 0) --fwl.wl_off;
-    RootExtra ex{};
-    bool use_ex = false;
-    // lazy draws (the sweep's last block): lists instead of n_draws draws per member item
-    if (lazy_ok && !it.particle && !it.out_pos &&
-        (size_t)it.n * ROOT_LZ_CAP * 12 <= ((size_t)4 << 30)) {
-      ex.lz_k = scratch<int32_t>(ctx, (size_t)it.n * ROOT_LZ_CAP);
-      ex.lz_p = scratch<uint64_t>(ctx, (size_t)it.n * ROOT_LZ_CAP);
-      ex.lz_ns = scratch<int32_t>(ctx, (size_t)it.n);
-      if (!ex.lz_k || !ex.lz_p || !ex.lz_ns) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      ex.eager_rows = lazy_req.eager_rows;
-      use_ex = true;
-    }
-    rc = pclean_launch_root_fast(ctx, fr, it, ch, seed, sweep, site, n_draws, lse_out, draws_out, oflag, over_count, desc,
-                                 over_list, scan_stats, il.n, pre_score, wl_stat != nullptr, wl_stat, pre_obs, use_ex ? &ex : nullptr);
-    if (!rc && ex.lz_ns) {
-      SweepState::LazyOut& lo = s->lazy_out;
-      lo.valid = true;
-      lo.site = site;
-      lo.args = LazyDrawArgs{};
-      lo.args.n_pos = il.n;
-      lo.args.members = it.grp_off ? it.members : nullptr;
-      lo.args.uid = it.grp_off ? ggrp.uid : nullptr;
-      lo.args.item_row = il.row;
-      lo.args.eager_rows = lazy_req.eager_rows;
-      lo.args.draws_item = draws_out;
-      lo.args.lz_k = ex.lz_k;
-      lo.args.lz_p = ex.lz_p;
-      lo.args.lz_ns = ex.lz_ns;
-      lo.args.g_U = ex.g_U;
-      lo.args.row_offset = it.row_offset;
-      lo.args.res_new = fr.is_leaf ? fr.n_cand - 1 : PCLEAN_CHOICE_NEW;
-    }
-    if (time_it) {
-      (void)hipEventRecord(s->ev1, ctx->stream);
-      s->dbg_desc = desc;
-      s->dbg_grp_off = it.grp_off;
-      s->dbg_members = it.members;
-      s->dbg_oflag = oflag;
-      s->dbg_groups = it.n;
-      s->dbg_items = il.n;
-    }
-    if (!rc && list_mode) {
-      ProfScope ps2(ctx, "overflow_rerun");
-      ItemsDev itf = it;  // the scan's items, ungrouped: list entries index them
-      itf.n = il.n;
-      itf.grp_off = nullptr;
-      itf.members = nullptr;
-      const int done = pclean_launch_overflow_fast(ctx, fr, itf, ch, seed, sweep, site, n_draws, lse_out, draws_out, over_list,
-                                                   over_count);
-      return done < 0 ? done : PCLEAN_OK;
-    }
-  } else {
-    {
-      ProfScope ps(ctx, "evidence_option_scan");
-      // a handful of latent rows with evidence sets of 10^4 rows and more each: one workgroup per row would walk options x
-      // evidence entries alone (12 ms for the one HospitalType row of the 1M-row table) — the sums come from a chip-wide kernel
-      uint32_t* dsum = nullptr;
-      static const bool no_split = getenv("PCLEAN_NO_EV_SPLIT") != nullptr;
-      if (!no_split && il.n <= 64 && s->lat_max_ev >= 16384 && fr.kpad >= 256 && (size_t)il.n * fr.kpad * 4 <= ((size_t)1 << 28)) {
-        dsum = scratch<uint32_t>(ctx, (size_t)il.n * fr.kpad);
-        if (!dsum) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-        const int rcz = dev_zero(ctx, dsum, (size_t)il.n * fr.kpad * sizeof(uint32_t));
-        if (rcz) return rcz;
-      }
-      rc = pclean_launch_ev_leaf(ctx, nd, it, fr, seed, sweep, site, n_draws, lse_out, draws_out, oflag, over_count, over_list,
-                                 n.kind == PCLEAN_NODE_FK ? &ch : nullptr, dsum);
-    }
-    if (!rc && ev_list_mode) {
-      ProfScope ps2(ctx, "overflow_rerun");
-      ItemsDev itr = it;
-      itr.sel = over_list;
-      itr.sel_n = over_count;
-      double* sc_tmp = nullptr;
-      const size_t sc_n = pclean_enum_split_scores(nd, itr);
-      if (sc_n && !(sc_tmp = scratch<double>(ctx, sc_n))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      return pclean_launch_enum(ctx, nd, itr, ch, seed, sweep, site, n_draws, lse_out, nullptr, draws_out, sc_tmp);
-    }
+  if (!c.ev_list_mode)  // (the list stands for the markers there); kernels only set overflow markers
+    return dev_zero(ctx, c.oflag, (size_t)il.n * sizeof(int32_t));
+  return PCLEAN_OK;
+}
+
+// the compact-table launch of a plain list (root_wave.hip) and, in list mode, the sync-free re-run behind it (*done)
+static int launch_root_scan(EvalCall& c, bool* done) {
+  pclean_ctx* ctx = c.ctx;
+  SweepState* s = c.s;
+  const ItemList& il = c.il;
+  const ItemsDev& it = c.it;
+  int32_t* desc = scratch<int32_t>(ctx, pclean_fast_desc_words(it.n));
+  if (!desc) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  ProfScope ps(ctx, (c.time_it && c.block_id == 0) ? "root_scan_block0" : (c.n.kind == PCLEAN_NODE_FK ? "slot_scan" : "option_scan"));
+  if (c.time_it) (void)hipEventRecord(s->ev0, ctx->stream);
+  unsigned int* scan_stats = nullptr;
+  if (c.time_it && s->over_ctr.p) {  // the timed launch (block 0's root): what it read, for bench.py's byte model
+    scan_stats = s->over_ctr.p + OVER_SLOTS;
+    s->scan_stats_used = true;
   }
-  if (rc) return rc;
+  // the work list of the groups the settle kernel leaves pays when it settles most of them; how many it left last time
+  // comes back with the call's statistics (apply_over_stats)
+  FastRoot& fwl = s->fast[c.block_id * 64 + c.node_id];
+  unsigned int* wl_stat = nullptr;
+  if (!fwl.wl_off && c.node_id < 64 && s->over_rec.size() < OVER_SLOTS && s->over_ctr.p) {
+    wl_stat = s->over_ctr.p + s->over_rec.size();
+    s->over_rec.push_back(SweepState::OverRec{c.block_id, c.node_id, it.n, false, false, -1});  // min_items -1: a work-list record
+  }
+  if (fwl.wl_off > 0) --fwl.wl_off;
+  RootExtra ex{};
+  bool use_ex = false;
+  // lazy draws (the sweep's last block): lists instead of n_draws draws per member item
+  if (c.lazy_ok && !it.particle && !it.out_pos && (size_t)it.n * ROOT_LZ_CAP * 12 <= ((size_t)4 << 30)) {
+    ex.lz_k = scratch<int32_t>(ctx, (size_t)it.n * ROOT_LZ_CAP);
+    ex.lz_p = scratch<uint64_t>(ctx, (size_t)it.n * ROOT_LZ_CAP);
+    ex.lz_ns = scratch<int32_t>(ctx, (size_t)it.n);
+    if (!ex.lz_k || !ex.lz_p || !ex.lz_ns) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    ex.eager_rows = c.lazy_req.eager_rows;
+    use_ex = true;
+  }
+  const int rc = pclean_launch_root_fast(ctx, c.fr, it, c.ch, c.seed, c.sweep, c.site, c.n_draws, c.lse_out, c.draws_out, c.oflag,
+                                         c.over_count, desc, c.over_list, scan_stats, il.n, c.pre_score, wl_stat != nullptr, wl_stat,
+                                         c.pre_obs, use_ex ? &ex : nullptr);
+  if (!rc && ex.lz_ns) {
+    SweepState::LazyOut& lo = s->lazy_out;
+    lo.valid = true;
+    lo.site = c.site;
+    lo.args = LazyDrawArgs{};
+    lo.args.n_pos = il.n;
+    lo.args.members = it.grp_off ? it.members : nullptr;
+    lo.args.uid = it.grp_off ? c.ggrp.uid : nullptr;
+    lo.args.item_row = il.row;
+    lo.args.eager_rows = c.lazy_req.eager_rows;
+    lo.args.draws_item = c.draws_out;
+    lo.args.lz_k = ex.lz_k;
+    lo.args.lz_p = ex.lz_p;
+    lo.args.lz_ns = ex.lz_ns;
+    lo.args.g_U = ex.g_U;
+    lo.args.row_offset = it.row_offset;
+    lo.args.res_new = c.fr.is_leaf ? c.fr.n_cand - 1 : PCLEAN_CHOICE_NEW;
+  }
+  if (c.time_it) {
+    (void)hipEventRecord(s->ev1, ctx->stream);
+    s->dbg_desc = desc;
+    s->dbg_grp_off = it.grp_off;
+    s->dbg_members = it.members;
+    s->dbg_oflag = c.oflag;
+    s->dbg_groups = it.n;
+    s->dbg_items = il.n;
+  }
+  if (rc || !c.list_mode) return rc;
+  *done = true;
+  ProfScope ps2(ctx, "overflow_rerun");
+  ItemsDev itf = it;  // the scan's items, ungrouped: list entries index them
+  itf.n = il.n;
+  itf.grp_off = nullptr;
+  itf.members = nullptr;
+  const int rr = pclean_launch_overflow_fast(ctx, c.fr, itf, c.ch, c.seed, c.sweep, c.site, c.n_draws, c.lse_out, c.draws_out,
+                                             c.over_list, c.over_count);
+  return rr < 0 ? rr : PCLEAN_OK;
+}
+
+// the compact-table scan of a list with evidence sets and, in list mode, the indirect re-run behind it (*done)
+static int launch_evidence_scan(EvalCall& c, bool* done) {
+  pclean_ctx* ctx = c.ctx;
+  const ItemList& il = c.il;
+  int rc;
+  {
+    ProfScope ps(ctx, "evidence_option_scan");
+    // a handful of latent rows with evidence sets of 10^4 rows and more each: one workgroup per row would walk options x
+    // evidence entries alone (12 ms for the one HospitalType row of the 1M-row table) — the sums come from a chip-wide kernel
+    uint32_t* dsum = nullptr;
+    if (!c.sw.cached.no_ev_split && il.n <= 64 && c.s->lat_max_ev >= 16384 && c.fr.kpad >= 256 &&
+        (size_t)il.n * c.fr.kpad * 4 <= ((size_t)1 << 28)) {
+      dsum = scratch<uint32_t>(ctx, (size_t)il.n * c.fr.kpad);
+      if (!dsum) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+      const int rcz = dev_zero(ctx, dsum, (size_t)il.n * c.fr.kpad * sizeof(uint32_t));
+      if (rcz) return rcz;
+    }
+    rc = pclean_launch_ev_leaf(ctx, c.nd, c.it, c.fr, c.seed, c.sweep, c.site, c.n_draws, c.lse_out, c.draws_out, c.oflag, c.over_count,
+                               c.over_list, c.n.kind == PCLEAN_NODE_FK ? &c.ch : nullptr, dsum);
+  }
+  if (rc || !c.ev_list_mode) return rc;
+  *done = true;
+  ProfScope ps2(ctx, "overflow_rerun");
+  ItemsDev itr = c.it;
+  itr.sel = c.over_list;
+  itr.sel_n = c.over_count;
+  return launch_enum_scratch(c, itr, nullptr, nullptr);
+}
+
+// The re-run after a count (no list mode): the overflowed items as a list of their own, over all candidates — by
+// overflow_lds_kernel where it applies, else by the generic kernel.  The back-off rule of option lists lives here too.
+static int rerun_overflowed(EvalCall& c) {
+  pclean_ctx* ctx = c.ctx;
+  SweepState* s = c.s;
+  const ItemList& il = c.il;
   unsigned int n_over = 0;
   PCLEAN_READ_COUNT(ctx, s->counter.p + 1, &n_over);
   ctx->timing.reserved += (int32_t)n_over;  // items that fell back to the generic kernel
-  if (time_it) ctx->root_stats.overflow_items = (int32_t)n_over;
+  if (c.time_it) ctx->root_stats.overflow_items = (int32_t)n_over;
   // short strings / flat posteriors: when a quarter of the items overflow the survivor list the integer pre-filter
   // does not pay for this option list -> its next evaluations go straight to the generic kernel (64, then 128, 256, ...
   // between retries)
   // (latent sub-batches hold a few hundred rows: the same rule from 64 items on — an option list of short strings, where
   // the pre-filter keeps everything, otherwise pays a scan AND a full re-run in every sub-batch)
-  if (n.kind == PCLEAN_NODE_LEAF && il.n >= (il.ev_lo ? 64 : 1024) &&
+  if (c.n.kind == PCLEAN_NODE_LEAF && il.n >= (il.ev_lo ? 64 : 1024) &&
       (il.ev_lo ? n_over >= (unsigned int)il.n : (size_t)n_over * 4 > (size_t)il.n)) {  // (see apply_over_stats)
-    FastRoot& f = s->fast[block_id * 64 + node_id];
+    FastRoot& f = s->fast[c.block_id * 64 + c.node_id];
     f.disabled = f.backoff;
     f.backoff = std::min(f.backoff * 2, 1 << 20);
   }
-  if (n_over && getenv("PCLEAN_DEBUG_OVERFLOW"))
-    fprintf(stderr, "[pclean] block %d node %d: %u of %d items re-run by the generic kernel\n", block_id, node_id, n_over,
-            il.n);
-  if (n_over) {
-    ProfScope ps(ctx, "overflow_rerun");
-    int32_t* list = scratch<int32_t>(ctx, n_over);
-    int32_t* row2 = scratch<int32_t>(ctx, n_over);
-    int32_t* excl2 = scratch<int32_t>(ctx, n_over);
-    int32_t* ctx2 = scratch<int32_t>(ctx, (size_t)n_over * PCLEAN_MAX_CTX);
-    int32_t* part2 = scratch<int32_t>(ctx, n_over);
-    int32_t* evl2 = il.ev_lo ? scratch<int32_t>(ctx, n_over) : nullptr;
-    int32_t* evh2 = il.ev_lo ? scratch<int32_t>(ctx, n_over) : nullptr;
-    int32_t* org2 = il.ev_lo ? scratch<int32_t>(ctx, n_over) : nullptr;
-    int32_t* rng2 = il.rng_row ? scratch<int32_t>(ctx, n_over) : nullptr;
-    if (!list || !row2 || !excl2 || !ctx2 || !part2 || (il.ev_lo && (!evl2 || !evh2 || !org2)) || (il.rng_row && !rng2))
-      return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-    { const int rcz = dev_zero(ctx, s->counter.p + 1, sizeof(unsigned int)); if (rcz) return rcz; }
-    hipLaunchKernelGGL(compact_new_kernel, grid1(il.n), dim3(256), 0, ctx->stream, (size_t)il.n, oflag, 1,
-                       s->counter.p + 1, list, nullptr);
-    hipLaunchKernelGGL(sub_items_kernel, grid1(n_over), dim3(256), 0, ctx->stream, (int)n_over, list, il.row, il.ctx, excl,
-                       il.ev_lo, il.ev_hi, il.rng_row, il.origin, row2, ctx2, excl2, evl2, evh2, rng2, org2);
-    if (it.particle)
-      hipLaunchKernelGGL(gather_i32_kernel, grid1(n_over), dim3(256), 0, ctx->stream, (int)n_over, list, it.particle, part2);
-    ItemsDev it2{(int)n_over, 0, row2, il.ctx ? ctx2 : nullptr, excl ? excl2 : nullptr, it.particle ? part2 : nullptr,
-                 s->row_offset + ctx->active_begin, list, evl2, evh2, il.ev_rows, il.ev_ctx, rng2, nullptr, nullptr,
-                 il.draw_is, il.draw_ds, it.agg, org2};
-    // compact-row exact scoring of every candidate (root_wave.hip: overflow_lds_kernel); evidence sets, groups and
-    // tables beyond one workgroup's LDS go through the generic kernel
-    int done = 0;
-    static const bool no_fast_over = getenv("PCLEAN_NO_FAST_OVERFLOW") != nullptr;
-    if (fast && !no_fast_over) {
-      done = pclean_launch_overflow_fast(ctx, fr, it2, ch, seed, sweep, site, n_draws, lse_out, draws_out, nullptr, nullptr);
-      if (done < 0) return done;
-    }
-    if (!done) {
-      double* sc_tmp = nullptr;
-      const size_t sc_n = pclean_enum_split_scores(nd, it2);
-      if (sc_n && !(sc_tmp = scratch<double>(ctx, sc_n))) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
-      rc = pclean_launch_enum(ctx, nd, it2, ch, seed, sweep, site, n_draws, lse_out, nullptr, draws_out, sc_tmp);
-    }
+  if (n_over && c.sw.live.debug_overflow())
+    fprintf(stderr, "[pclean] block %d node %d: %u of %d items re-run by the generic kernel\n", c.block_id, c.node_id, n_over, il.n);
+  if (!n_over) return PCLEAN_OK;
+  ProfScope ps(ctx, "overflow_rerun");
+  int32_t* list = scratch<int32_t>(ctx, n_over);
+  int32_t* row2 = scratch<int32_t>(ctx, n_over);
+  int32_t* excl2 = scratch<int32_t>(ctx, n_over);
+  int32_t* ctx2 = scratch<int32_t>(ctx, (size_t)n_over * PCLEAN_MAX_CTX);
+  int32_t* part2 = scratch<int32_t>(ctx, n_over);
+  if (!list || !part2) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  const int rcz = dev_zero(ctx, s->counter.p + 1, sizeof(unsigned int));
+  if (rcz) return rcz;
+  hipLaunchKernelGGL(compact_new_kernel, grid1(il.n), dim3(256), 0, ctx->stream, (size_t)il.n, c.oflag, 1, s->counter.p + 1, list,
+                     nullptr);
+  ItemList sil;
+  const int rc = sub_items(c, n_over, list, row2, ctx2, excl2, sil);
+  if (rc) return rc;
+  if (c.it.particle)
+    hipLaunchKernelGGL(gather_i32_kernel, grid1(n_over), dim3(256), 0, ctx->stream, (int)n_over, list, c.it.particle, part2);
+  ItemsDev it2{(int)n_over, 0, sil.row, sil.ctx, c.excl ? excl2 : nullptr, c.it.particle ? part2 : nullptr,
+               s->row_offset + ctx->active_begin, list, sil.ev_lo, sil.ev_hi, il.ev_rows, il.ev_ctx, sil.rng_row, nullptr, nullptr,
+               il.draw_is, il.draw_ds, c.it.agg, sil.origin};
+  // compact-row exact scoring of every candidate (root_wave.hip: overflow_lds_kernel); evidence sets, groups and
+  // tables beyond one workgroup's LDS go through the generic kernel
+  int done = 0;
+  if (c.fast && !c.sw.cached.no_fast_over) {
+    done = pclean_launch_overflow_fast(ctx, c.fr, it2, c.ch, c.seed, c.sweep, c.site, c.n_draws, c.lse_out, c.draws_out, nullptr, nullptr);
+    if (done < 0) return done;
   }
-  return rc;
+  return done ? PCLEAN_OK : launch_enum_scratch(c, it2, nullptr, nullptr);
+}
+
+int eval_node(pclean_ctx* ctx, int block_id, int node_id, const ItemList& il, const int32_t* excl,
+                     uint64_t seed, uint32_t sweep, int n_draws, double* lse_out, int32_t* draws_out,
+                     double* scores_out, const double* snew_override, bool time_it) {
+  Block& b = ctx->block[block_id];
+  EvalCall c{ctx, block_id, node_id, il, excl, seed, sweep, n_draws, lse_out, draws_out, scores_out, snew_override, time_it,
+             b, b.nodes[node_id], st(ctx), PCLEAN_SITE_NODE(block_id, node_id)};
+  int rc = eval_begin(c);
+  if (!rc) rc = new_row_branch(c);
+  if (rc) return rc;
+  bool done = false;
+  rc = leaf_coarse_draw(c, &done);
+  if (rc || done) return rc;
+  rc = choose_compact_path(c);
+  if (!rc) rc = group_for_launch(c);
+  if (rc) return rc;
+  if (time_it) note_root_stats(c);
+  if (!c.fast && !c.fast_ev) return launch_generic(c);
+  rc = overflow_setup(c);
+  if (rc) return rc;
+  rc = c.fast ? launch_root_scan(c, &done) : launch_evidence_scan(c, &done);
+  if (rc || done) return rc;
+  return rerun_overflowed(c);
 }
 
 // rocPRIM's radix sort switches to a merge sort for inputs of up to 2^20 keys (radix_sort_config's MergeSortLimit);
