@@ -11,12 +11,16 @@ high precision (mpmath when it imports, else math.fsum of shifted exponentials).
   * MH (P = 2), one block: w0 == w1, accepted with 0.5 / (1e-10 + 0.5)                           -> pi (up to 2e-10)
   * MH (P = 2), two blocks, block 1 depends on block 0's value: proposal q(t) = pi0(t0) pi1(t1 | t0),
     accepted with a(t) = min(1, exp(Z1(t0) - Z1(s0)))                                             -> q a + [t == s] (1 - sum q a)
+  * PG, P particles, the same two blocks: nothing is resampled after block 0 (equal weights), particle p ends with the
+    weight z(x_p) = exp(Z1(x_p)) of its block-0 value, the final pick is proportional to the weights: pg_two_blocks,
+    one one-dimensional integral per distinct block-0 value (E[1 / (c + S_k)] = int exp(-c u) E[exp(-u z)]^k du)
 
 A candidate is a referent key of the block's root table, or ('NEW', value) — a fresh row together with its sampled
-own choice (the nested conditional of the new-row branch: the option's prior mass times its likelihood).  PG with
-P > 2 over two dependent blocks (conditional SMC with resampling) has no short closed form and is not covered; neither
-are rows that can draw a ProposalDummyValue (the weight correction changes the kernel): root classes here hold a
-single ChooseUniformly choice, which has none.
+own choice (the nested conditional of the new-row branch: the option's prior mass times its likelihood).  Not covered:
+resampling that fires inside a sweep (three or more blocks, or prior proposals) together with apply_ancestors_kernel,
+which stay pinned to the oracle (tests/particle_exact.py pins the primitive they call); rows that can draw a
+ProposalDummyValue (the weight correction changes the kernel): root classes here hold a single ChooseUniformly choice,
+which has none; and the hospital workload itself.
 
 draw_program holds AddTypos observations; tab_draw_program the tabulated kind (FormatName, ExpandOnShortVersion) next
 to one AddTypos term, whose pi comes from the literal interpreter's densities on the strings.
@@ -174,7 +178,8 @@ class RowConditionals:
             ctx_path = self._ctx_path()
             xs = {self.value(0, t) for t, p in pi0.items() if p >= 1e-13}  # (two_block_expected's floor)
             cur0 = int(self.tr.cur[0, i])
-            xs.add(self._cur_value(0, cur0))
+            if cur0 >= 0:
+                xs.add(self._cur_value(0, cur0))
             b1 = {}
             for x in xs:
                 sc1, z1 = self._block_scores(i, 1, {ctx_path: x})
@@ -225,6 +230,86 @@ def mh_two_blocks(pi0, b1, s, value0, invert=False):
             acc.append(qa)
     stay = 1.0 - math.fsum(acc)
     out[s] = out.get(s, 0.0) + stay
+    return {k: v for k, v in out.items() if v > 0}
+
+
+def inv_moment(c, k, mu, z, enumerate_it=False):
+    """E[1 / (c + S_k)], S_k the sum of k iid z(X), X ~ mu ({x: mass}, z: {x: weight}): by 1 / a = int_0^inf exp(-a u) du
+    the one-dimensional integral int exp(-c u) (sum_x mu(x) exp(-u z(x)))^k du.  enumerate_it: the sum over all k-tuples
+    instead (the check of the integral, small k only)."""
+    xs = list(mu)
+    if enumerate_it:
+        import itertools
+        tot = mpmath.mpf(0)
+        for tup in itertools.product(xs, repeat=k):
+            pr = mpmath.mpf(1)
+            for x in tup:
+                pr *= mu[x]
+            tot += pr / (c + mpmath.fsum(z[x] for x in tup))
+        return tot
+    if k == 0 or len({z[x] for x in xs}) == 1:  # (S_k is the constant k z: nothing to integrate)
+        return mpmath.fsum(mu.values()) ** k / (mpmath.mpf(c) + k * mpmath.mpf(z[xs[0]]))
+    with mpmath.workdps(25):
+        m = [(mpmath.mpf(mu[x]), mpmath.mpf(z[x])) for x in xs]
+        c = mpmath.mpf(c)
+        return +mpmath.quad(lambda u: mpmath.exp(-c * u) * mpmath.fsum(a * mpmath.exp(-u * b) for a, b in m) ** k,
+                            [0, 1, 10, 100, mpmath.inf])
+
+
+PG_MUTATIONS = ("uniform pick", "retained as a fresh draw", "weights squared", "Z1 at the retained value")
+
+
+def pg_two_blocks(pi0, b1, s, value0, P, mutation=None, enumerate_it=False):
+    """output over (t0, t1) of PG with P particles over two blocks, block 1 given block 0's value (data-driven proposals).
+    Every particle carries block 0's log marginal after block 0 and nothing is resampled there; after block 1 particle p
+    weighs z(x_p) = exp(Z1(x_p)), x_p its block-0 value.  With q(t) = pi0(t0) pi1(t1 | t0), mu(x) the pi0 mass of the
+    candidates holding x, S_k the sum of k iid z(X), X ~ mu, and the retained particle s of weight z_s:
+
+      P(out = t) = (P-1) q(t) z(t0) E[1 / (z_s + z(t0) + S_{P-2})]  +  [t == s] z_s E[1 / (z_s + S_{P-1})]
+      s = None (no current referent):  P q(t) z(t0) E[1 / (z(t0) + S_{P-1})]
+
+    z is scaled to a maximum of 1.  mutation: one of PG_MUTATIONS (the power self-test); enumerate_it: see inv_moment."""
+    assert mpmath is not None, "the closed form of PG over two blocks needs mpmath"
+    assert mutation is None or mutation in PG_MUTATIONS
+    mu = {}
+    for t0, p0 in pi0.items():
+        mu[value0(t0)] = mu.get(value0(t0), 0.0) + p0
+    xs = set(mu) | ({value0(s[0])} if s is not None else set())
+    top = max(b1[x][1] for x in xs)
+    z = {x: mpmath.exp(mpmath.mpf(b1[x][1]) - top) for x in xs}
+    if mutation == "weights squared":
+        z = {x: v * v for x, v in z.items()}
+    if mutation == "retained as a fresh draw":
+        s_w = None
+    else:
+        s_w = s
+    if s_w is not None:
+        z_s = z[value0(s[0])]
+        if mutation == "Z1 at the retained value":
+            z = {x: z_s for x in z}
+    memo = {}
+
+    def E(c, k):
+        if (c, k) not in memo:
+            memo[(c, k)] = inv_moment(c, k, mu, z, enumerate_it)
+        return memo[(c, k)]
+
+    out = {}
+    for t0, p0 in pi0.items():
+        x = value0(t0)
+        if mutation == "uniform pick":
+            f = (P - 1.0) / P if s is not None else 1.0
+        elif s_w is not None:
+            f = float((P - 1) * z[x] * E(z_s + z[x], P - 2)) if P > 1 else 0.0
+        else:
+            f = float(P * z[x] * E(z[x], P - 1))
+        for t1, p1 in b1[x][0].items():
+            out[(t0, t1)] = p0 * p1 * f
+    if mutation == "uniform pick":
+        if s is not None:
+            out[s] = out.get(s, 0.0) + 1.0 / P
+    elif s_w is not None:
+        out[s] = out.get(s, 0.0) + float(z_s * E(z_s, P - 1))
     return {k: v for k, v in out.items() if v > 0}
 
 
@@ -786,28 +871,41 @@ def one_block_case(eng, S, rc, rows, P, mh, n_sweeps, seed):
     return gof(items), dev, n_new
 
 
-def two_block_expected(S, rc, rows, invert=False, floor=1e-13):
-    """closed form of MH over the two blocks of draw_program(two_blocks=True) per row, in the encoders' codes
-    (t0 code, t1 code); block-0 candidates below `floor` are left out (their mass, < 1e-10 in all, stays put)"""
+def two_block_expected(S, rc, rows, invert=False, floor=1e-13, P=2, mh=True, mutation=None, enumerate_it=False):
+    """closed form of MH (mh_two_blocks) or of PG with P particles (pg_two_blocks) over the two blocks of
+    draw_program(two_blocks=True) per row, in the encoders' codes (t0 code, t1 code); block-0 candidates below `floor` are
+    left out (their mass, < 1e-10 in all, stays put).  A row without current referents (cur = -1) has no retained
+    particle.  Rows with the same conditionals and referents share one computation."""
     tr = S["trace"]
     e0, e1 = Encoder(S["lw"], tr, 0), Encoder(S["lw"], tr, 1)
-    out = []
+    out, memo = [], {}
     for i in rows:
-        pi0, z0, b1 = rc.two_blocks(int(i))
-        pi0 = {k: v for k, v in pi0.items() if v >= floor}
-        val = {k: rc.value(0, k) for k in pi0}
-        cur = (int(tr.cur[0, i]), int(tr.cur[1, i]))
-        val[cur[0]] = rc._cur_value(0, cur[0])
-        ex = mh_two_blocks(pi0, b1, cur, lambda t: val[t], invert=invert)
-        out.append({(e0.code(t[0]), e1.code(t[1])): v for t, v in ex.items()})
+        key = rc._key(int(i), 2)
+        if key not in memo:
+            pi0, z0, b1 = rc.two_blocks(int(i))
+            pi0 = {k: v for k, v in pi0.items() if v >= floor}
+            val = {k: rc.value(0, k) for k in pi0}
+            cur = (int(tr.cur[0, i]), int(tr.cur[1, i]))
+            assert (cur[0] < 0) == (cur[1] < 0)
+            if cur[0] < 0:
+                cur = None
+            else:
+                val[cur[0]] = rc._cur_value(0, cur[0])
+            if mh:
+                assert cur is not None and P == 2 and mutation is None
+                ex = mh_two_blocks(pi0, b1, cur, lambda t: val[t], invert=invert)
+            else:
+                ex = pg_two_blocks(pi0, b1, cur, lambda t: val[t], P, mutation=mutation, enumerate_it=enumerate_it)
+            memo[key] = {(e0.code(t[0]), e1.code(t[1])): v for t, v in ex.items()}
+        out.append(memo[key])
     return out
 
 
-def two_block_case(eng, S, rc, rows, n_sweeps, seed):
+def two_block_case(eng, S, rc, rows, n_sweeps, seed, P=2, mh=True):
     from pclean_amd.engine import InferenceConfig
     tr = S["trace"]
     e0, e1 = Encoder(S["lw"], tr, 0), Encoder(S["lw"], tr, 1)
-    cfg = InferenceConfig(1, 2, use_mh_instead_of_pg=True)
+    cfg = InferenceConfig(1, P, use_mh_instead_of_pg=mh)
     n = tr.cur.shape[1]
     D0 = np.empty((n_sweeps, len(rows)), dtype=np.int64)
     D1 = np.empty_like(D0)
@@ -815,7 +913,7 @@ def two_block_case(eng, S, rc, rows, n_sweeps, seed):
         choice, chosen, logml, new_rows = eng.sweep(tr, cfg, seed, s)
         D0[s] = e0.codes(choice[0], new_rows.get(0), n)[rows]
         D1[s] = e1.codes(choice[1], new_rows.get(1), n)[rows]
-    exp = two_block_expected(S, rc, rows)
+    exp = two_block_expected(S, rc, rows, P=P, mh=mh)
     items = [(int(i), exp[j], tabulate(list(zip(D0[:, j].tolist(), D1[:, j].tolist())))) for j, i in enumerate(rows)]
     return gof(items)
 
@@ -834,6 +932,15 @@ TAB_MIXED = dict(PROGRAMS_TAB["large"], second_block=1100)  # block 1's table: 1
 
 def two_block_rows(S):
     return np.array([i for i, k in enumerate(S["kind"]) if k in ("peaked", "spread", "tied", "new")][::2])
+
+
+TWO_BLOCK_PG = [3, 9, 33]  # particle counts of the two-block PG cases: one DISPATCH_PMAX bucket each
+
+
+def two_block_free_rows(S):
+    """the rows the case without current referents frees in both blocks: the peaked and spread rows of two_block_rows
+    (free_rows checks that their referents keep another reference)"""
+    return np.array([i for i in two_block_rows(S) if S["kind"][i] in ("peaked", "spread")], dtype=np.int64)
 
 
 def near_candidate(pi, s):

@@ -11,14 +11,17 @@ the flat rows re-run by the overflow kernel, lazy draws of the last block), with
 and kpad % 64 != 0.  Cases: every particle count at an edge of the DISPATCH_PMAX buckets; a spread-row case with
 SPREAD_SWEEPS draws per row (the power to see a 0.1-nat shift of a near candidate, which the all-row cases at S_GPU
 do not have); rows without a current referent (cur = -1, no retained particle); latent sweeps of A's own choice
-against its evidence sets (latent.hip's own final pick and MH ratio); MH over two dependent blocks.
+against its evidence sets (latent.hip's own final pick and MH ratio); MH over two dependent blocks; PG with 3, 9 and
+33 particles over the same two blocks, where the particles end with unequal weights and the final pick must be
+proportional to them (posterior_exact.pg_two_blocks), with and without current referents.
 tests/test_posterior_draws_cpu.py samples each of these cases with NumPy under mutations: the power self-test.
 
-Not covered: PG with P > 2 over two dependent blocks (conditional SMC with resampling has no short closed form),
-rows that can draw a ProposalDummyValue (the weight correction changes the kernel: the programs have none), and the
-hospital workload itself (helpers.truth_workload): its nested new rows have no enumerable closed form here, so the
-two-block case runs on draw_program's two-block stand-in with the same dependence (block 1 reads block 0's value
-through a JuliaNode)."""
+Not covered: rows that can draw a ProposalDummyValue (the weight correction changes the kernel: the programs have
+none), and the hospital workload itself (helpers.truth_workload): its nested new rows have no enumerable closed form
+here, so the two-block cases run on draw_program's two-block stand-in with the same dependence (block 1 reads block
+0's value through a JuliaNode).  Resampling that fires inside a sweep (three or more blocks, or prior proposals) and
+apply_ancestors_kernel stay pinned to the oracle only; tests/test_gpu_particle_primitives.py pins the primitive they
+call to an exact restatement."""
 import numpy as np
 import pytest
 
@@ -66,19 +69,55 @@ def test_device_draws_follow_exact_posterior(prog, P, mh):
         assert res["df"] == 0 and not np.isinf(res["G"])
 
 
-def test_device_two_block_mh_follows_closed_form():
-    """MH (P = 2) over two blocks, block 1 reading block 0's value through a JuliaNode: q(t) a(t) + [t == s] (1 - sum q a)
-    with block 0 on the fast root path"""
+@pytest.fixture(scope="module")
+def two_block():
+    """the two-block program, its literal conditionals (computed once for the MH and the PG cases) and its engine"""
     S = pe.draw_program(**pe.TWO_BLOCK)
-    rows = pe.two_block_rows(S)
     eng = Engine(S["lw"], S["obs"], dist_mode=1)
     try:
         eng.upload_trace(S["trace"])
-        res = pe.two_block_case(eng, S, pe.RowConditionals(S), rows, S_SWEEPS, seed=77)
+        yield S, pe.RowConditionals(S), pe.two_block_rows(S), eng
+    finally:
+        eng.close()
+
+
+def test_device_two_block_mh_follows_closed_form(two_block):
+    """MH (P = 2) over two blocks, block 1 reading block 0's value through a JuliaNode: q(t) a(t) + [t == s] (1 - sum q a)
+    with block 0 on the fast root path"""
+    S, rc, rows, eng = two_block
+    res = pe.two_block_case(eng, S, rc, rows, S_SWEEPS, seed=77)
+    rs = eng.hip.get_root_stats()
+    print(f"\n[two blocks MH] block 0 path fast={rs.fast}; {pe.describe(res)}")
+    assert rs.fast == 1
+    assert res["p"] > pe.ALPHA, pe.describe(res)
+
+
+@pytest.mark.parametrize("P", pe.TWO_BLOCK_PG)
+def test_device_two_block_pg_follows_closed_form(two_block, P):
+    """PG with P > 2 over the same two blocks: the particles end with unequal weights exp(Z1(x_p)) and the final pick is
+    proportional to them (posterior_exact.pg_two_blocks) — the normal state of a hospital sweep"""
+    S, rc, rows, eng = two_block
+    res = pe.two_block_case(eng, S, rc, rows, S_SWEEPS, seed=1300 + P, P=P, mh=False)
+    rs = eng.hip.get_root_stats()
+    print(f"\n[two blocks PG P={P}] block 0 path fast={rs.fast}; {pe.describe(res)}")
+    assert rs.fast == 1
+    assert res["p"] > pe.ALPHA, pe.describe(res)
+
+
+def test_device_two_block_pg_without_current_referent():
+    """cur = -1 in both blocks: no retained particle, P q(t) z(t0) E[1 / (z(t0) + S_{P-1})]"""
+    S = pe.draw_program(**pe.TWO_BLOCK)
+    rows = pe.two_block_free_rows(S)
+    assert len(rows) >= 40
+    pe.free_rows(S, rows, blocks=(0, 1))
+    eng = Engine(S["lw"], S["obs"], dist_mode=1)
+    try:
+        eng.upload_trace(S["trace"])
+        res = pe.two_block_case(eng, S, pe.RowConditionals(S), rows, S_SWEEPS, seed=1400, P=3, mh=False)
         rs = eng.hip.get_root_stats()
     finally:
         eng.close()
-    print(f"\n[two blocks MH] block 0 path fast={rs.fast}; {pe.describe(res)}")
+    print(f"\n[two blocks PG cur=-1 P=3] block 0 path fast={rs.fast}; {pe.describe(res)}")
     assert rs.fast == 1
     assert res["p"] > pe.ALPHA, pe.describe(res)
 

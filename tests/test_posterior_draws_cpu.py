@@ -14,6 +14,14 @@ inverted MH acceptance, paired sweep indices); a 0.1-nat shift of a near candida
 0.1 p (1 - p) and is caught by the spread-row case (SPREAD_SWEEPS draws of the rows that hold a near candidate),
 not by the all-row cases at S_GPU.
 
+PG with P > 2 over two dependent blocks ends with unequal particle weights; its closed form
+(posterior_exact.pg_two_blocks, one integral per distinct block-0 value) is checked here against the direct
+enumeration of the particles' values for P <= 4, against the oracle's draws at P = 3 and 9, and for its power against
+four mistakes of the final pick.  Not covered by an exact posterior: rows that can draw a ProposalDummyValue, the
+hospital workload, and resampling that fires inside a sweep (three or more blocks, or prior proposals) together with
+apply_ancestors_kernel — those stay pinned to the oracle, and tests/test_particle_exact_cpu.py pins the primitive
+they call.
+
 The tabulated kind (FormatName, ExpandOnShortVersion) has no CPU oracle leg: neither oracle layer below the literal
 interpreter knows the two distributions.  Its part here states the conditions the device leg's inputs must meet
 (posterior_exact.tab_draw_program) and measures the power of tests/test_gpu_tabulated_draws.py's cases against four
@@ -78,6 +86,53 @@ def test_oracle_two_block_mh_follows_closed_form(oracle, prog2):
     res = pe.two_block_case(_engine(oracle, S), S, rc, rows, S_SWEEPS, seed=31)
     print(f"oracle two blocks MH: {pe.describe(res)}")
     assert res["p"] > pe.ALPHA, pe.describe(res)
+
+
+@pytest.mark.parametrize("P", [3, 9])
+def test_oracle_two_block_pg_follows_closed_form(oracle, prog2, P):
+    """PG with P > 2 over two dependent blocks: unequal final weights exp(Z1(x_p)), posterior_exact.pg_two_blocks"""
+    S, rc, rows = prog2
+    res = pe.two_block_case(_engine(oracle, S), S, rc, rows, S_SWEEPS, seed=31 + P, P=P, mh=False)
+    print(f"oracle two blocks PG P={P}: {pe.describe(res)}")
+    assert res["p"] > pe.ALPHA, pe.describe(res)
+
+
+def test_oracle_two_block_pg_without_current_referent(oracle):
+    S = pe.draw_program(300, seed=1, two_blocks=True)
+    rows = pe.two_block_free_rows(S)
+    assert len(rows) >= 40
+    pe.free_rows(S, rows, blocks=(0, 1))
+    res = pe.two_block_case(_engine(oracle, S), S, pe.RowConditionals(S), rows, S_SWEEPS, seed=41, P=3, mh=False)
+    print(f"oracle two blocks PG cur=-1 P=3: {pe.describe(res)}")
+    assert res["p"] > pe.ALPHA, pe.describe(res)
+
+
+@pytest.mark.parametrize("P", [2, 3, 4])
+def test_pg_two_block_integral_agrees_with_enumeration(prog2, P):
+    """E[1 / (c + S_k)] as the one-dimensional integral against the sum over all k-tuples of block-0 values, on every
+    sixth row with and without the retained particle, and with each mutation of the power test"""
+    S, rc, rows = prog2
+    worst, several = 0.0, 0
+    for i in rows[::6]:
+        pi0, z0, b1 = rc.two_blocks(int(i))
+        pi0 = {k: v for k, v in pi0.items() if v >= 1e-13}
+        val = {k: rc.value(0, k) for k in pi0}
+        cur = (int(S["trace"].cur[0, i]), int(S["trace"].cur[1, i]))
+        val[cur[0]] = rc._cur_value(0, cur[0])
+        several += len({val[k] for k in pi0}) > 1
+        for s in (cur, None):
+            for mut in (None,) + pe.PG_MUTATIONS:
+                a = pe.pg_two_blocks(pi0, b1, s, lambda t: val[t], P, mutation=mut)
+                b = pe.pg_two_blocks(pi0, b1, s, lambda t: val[t], P, mutation=mut, enumerate_it=True)
+                assert set(a) == set(b)
+                worst = max(worst, max(abs(a[k] - b[k]) for k in a))
+                assert abs(sum(a.values()) - 1.0) < 1e-9, (i, s, mut, sum(a.values()))
+    print(f"P={P}: integral against enumeration, largest difference {worst:.3g}; {several} rows with several block-0 values")
+    assert several >= 5 and worst <= 1e-12
+    if P == 2:  # two particles, no referent: P q z / (z + z') summed over the second particle's value by hand
+        mu, z = {"a": 0.25, "b": 0.75}, {"a": 1.0, "b": 0.5}
+        for c, k, want in [(1.0, 1, 0.25 / 2.0 + 0.75 / 1.5), (0.5, 2, 0.0625 / 2.5 + 0.375 / 2.0 + 0.5625 / 1.5)]:
+            assert abs(float(pe.inv_moment(c, k, mu, z)) - want) < 1e-15
 
 
 def test_oracle_latent_draws_follow_exact_posterior(oracle, prog):
@@ -172,6 +227,36 @@ def test_power_mh_acceptance_inverted(gpu_two_block):
     res = pe.gof(_items(rng, exact, bad, pe.S_GPU))
     print("MH acceptance inverted:", pe.describe(res))
     assert res["p"] < 1e-6
+
+
+@pytest.fixture(scope="module", params=pe.TWO_BLOCK_PG[:2])
+def gpu_two_block_pg(request, gpu_two_block):
+    """the exact closed form of the device leg's two-block PG case at P particles, and P"""
+    S, rc, rows = gpu_two_block
+    return request.param, pe.two_block_expected(S, rc, rows, P=request.param, mh=False)
+
+
+def test_power_two_block_pg_exact_samples_pass(gpu_two_block_pg):
+    P, exact = gpu_two_block_pg
+    res = pe.gof(_items(np.random.default_rng(20 + P), exact, exact, pe.S_GPU))
+    print(f"two blocks PG P={P}, exact samples:", pe.describe(res))
+    assert res["p"] > pe.ALPHA, pe.describe(res)
+
+
+@pytest.mark.parametrize("mutation", pe.PG_MUTATIONS)
+def test_power_two_block_pg_mutation_is_rejected(gpu_two_block, gpu_two_block_pg, mutation):
+    """the device leg's rows and S_GPU draws per row: a uniform final pick, a retained particle weighted like a fresh
+    draw, a pick proportional to w^2 and Z1 taken at the retained value for every particle each fail at p < 1e-6 — at
+    nine particles every one of them, at three all but w^2: with two free particles, most of them on one block-0 value,
+    squaring the weights moves too little mass for S_GPU draws (p = 0.77 measured); the nine- and 33-particle cases of
+    the device leg carry that mutation."""
+    S, rc, rows = gpu_two_block
+    P, exact = gpu_two_block_pg
+    bad = pe.two_block_expected(S, rc, rows, P=P, mh=False, mutation=mutation)
+    res = pe.gof(_items(np.random.default_rng(30 + P), exact, bad, pe.S_GPU))
+    print(f"two blocks PG P={P}, {mutation}:", pe.describe(res))
+    if (P, mutation) != (3, "weights squared"):
+        assert res["p"] < 1e-6
 
 
 def test_power_sweep_indices_identical(gpu_case):
