@@ -11,7 +11,7 @@
 # function the pgibbs_sweep! patch at the bottom calls is defined in this file.
 #
 # NOT BOUND HERE: the own-block entry points of a flat observed class (pclean_load_own_block, pclean_set_own, pclean_get_own,
-# pclean_sweep_own, pclean_score_own, pclean_own_counts, pclean_get_own_stats; DESIGN.md section 11) — `lower` below refuses a block
+# pclean_link_own_star, pclean_sweep_own, pclean_score_own, pclean_own_counts, pclean_get_own_stats; DESIGN.md section 11) — `lower` below refuses a block
 # without a reference slot that holds anything but MaybeSwap observations, as it always did.
 #
 # Include after `using PClean` from the package's own module scope:  include("PCleanHIP.jl")

@@ -77,7 +77,7 @@ class OwnStats(C.Structure):
     """pclean_own_stats: what the last pclean_sweep_own / pclean_score_own call did"""
     _fields_ = [("variants", C.c_int32), ("n_runs", C.c_int32), ("longest_run", C.c_int32), ("n_workgroups", C.c_int32),
                 ("impossible_rows", C.c_int32), ("first_impossible_row", C.c_int32), ("lds_options", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("reserved", C.c_int32), ("star_weighed", C.c_int64), ("star_skipped", C.c_int64)]
 
 
 class CommitSlot(C.Structure):
@@ -1036,6 +1036,12 @@ class HipContext:
         check(self.h, self.lib.pclean_load_own_block(
             self.h, C.c_int32(block_id), C.c_int32(len(nodes)), nodes.ctypes.data_as(C.c_void_p), C.c_int32(len(terms)),
             terms.ctypes.data_as(C.c_void_p)), "pclean_load_own_block")
+
+    def link_own_star(self, block_id, head_node, arm_nodes):
+        """pclean_link_own_star: nodes head_node + 1 .. of a loaded own block are the arms of the star headed by head_node"""
+        arms = np.ascontiguousarray(arm_nodes, dtype=np.int32)
+        check(self.h, self.lib.pclean_link_own_star(self.h, C.c_int32(block_id), C.c_int32(head_node), C.c_int32(len(arms)),
+                                                    _p(arms, C.c_int32)), "pclean_link_own_star")
 
     def set_own(self, block_id, vals):
         """current values int32 [n_nodes][n_rows] of every loaded row (-1 = none yet); None clears them"""

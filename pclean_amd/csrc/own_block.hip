@@ -24,11 +24,16 @@
 // sibling own choice, enumerated jointly): every term once per value of the factor it reads, then the grid from the cached
 // values — the same doubles in the same order, so the same bits (see the kernel).
 //
+// own_star_kernel serves a star (pclean_link_own_star): an index and two to four choices indexed by it, as a head node and one
+// arm node per dependent.  The dependents are independent given the index: every one is summed out per index value in fixed
+// point, the index is drawn, then every dependent given it (see the kernel).
+//
 // own_marginal_kernel (pclean_own_marginals) reports what the sweep holds before it draws: passes 1 and 2 as above, then
 // instead of the draws the `top` options of largest u_k (ties: the smaller index) with u_k / U, and u_cur / U of every row's
 // current value.  It writes no value.
 #include "sweep_internal.h"
 #include "../../include/pclean_ownq.h"
+#include "own_star_check.h"
 
 #define OWN_BT 256
 #define OWN_LDS_OPTIONS 4096                   // options whose fixed-point weights stay in LDS (32 KiB of a workgroup)
@@ -53,9 +58,21 @@ struct OwnLeaf {
   std::vector<int32_t> gauss_e;
 };
 
+// a star (pclean_link_own_star): the head's node, its arms' nodes, and the grouping over the terms of all of them
+struct OwnStar {
+  int head = -1;
+  std::vector<int> arms;
+  OwnLeaf grp;                          // (terms: the head's, then every arm's; node unused)
+  std::vector<uint64_t> cols_version;   // of the nodes' option tables when the grid was last checked
+  std::vector<int32_t> kj;
+  DevBuf<double> cmax;                  // [n_arms][ka]: the bound of every arm's prior row, as of the last launch
+};
+
 struct OwnBlock {
   bool valid = false;
   std::vector<OwnLeaf> leaves;
+  std::vector<OwnStar> stars;
+  std::vector<int> star_of;  // per leaf: its star, -1: none
   DevBuf<int32_t> vals;  // [n_leaves][vals_rows]
   int vals_rows = 0;
 };
@@ -67,6 +84,8 @@ struct OwnState {
   DevBuf<int32_t> bad;       // {rows with logml == -inf, the smallest of them}
   DevBuf<unsigned long long> hist;
   DevBuf<unsigned long long> gstat;  // pclean_own_gauss_stats: [count | qsum]
+  DevBuf<unsigned long long> star_ctr;  // own_star_kernel: {index values weighed, skipped}
+  bool star_attr_set = false;
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the launches of the last pclean_sweep_own (pclean_timing.total_ms)
   bool product_attr_set = false;          // own_product_kernel's dynamic-LDS limit is raised on this context's device
 };
@@ -997,6 +1016,534 @@ __global__ __launch_bounds__(256) void own_gauss_stats_kernel(int n_rows, int K,
   }
 }
 
+// ---- star: several dependents on one index, enumerated collapsed ------------------------------------------------------------
+// (pclean_link_own_star; model.py, _lower_own_star.)  The head node holds the index a with its terms, arm j holds dependent
+// b_j on the grid a * K_j + b with prior log theta_j[a][b] alone.  The dependents are independent given the index, so
+//   t_j(a, b) = log theta_j[a K_j + b] + arm j's terms at b (plan order)      M_j(a) = max_b t_j    v_j = fixw(t_j - M_j(a))
+//   V_j(a) = sum_b v_j      L_j(a) = lse_from_fix(M_j(a), V_j(a))
+//   S(a) = logp[a] + the head's terms at a + L_1(a) + .. + L_D(a)             m = max_a S   u_a = fixw(S(a) - m)   U = sum u_a
+// and the row draws a from u, then every b_j from v_j(a, .).  One workgroup per piece of a tuple run over the terms of ALL nodes:
+//   phase 1  every term once per value of the factor it reads, into LDS (own_product_kernel's phase 1)
+//   phase 2  H(a) = logp[a] + head terms into S[a];  per arm the maximum of its cached term sums
+//   skip     B(a) = H(a) + sum_j (taumax_j + cmax_j[a]) >= S(a), cmax_j[a] = max_b log theta_j[a][b] + log K_j (own_star_cmax_kernel,
+//            from the table as it is at the call).  S is evaluated exactly at a* = argmax B; an a with B(a) < S(a*) - OWN_SKIP_BELOW
+//            has S(a) - m < -30 + (the rounding of a dozen additions), far below the -28.5 under which pclean_fixw is 0: its u_a
+//            is the 0 it would have computed and its arms are never touched.  PCLEAN_NO_OWN_SKIP and a probe that asks for the
+//            head's scores weigh every a.
+//   arms     the surviving a dealt to the wavefronts, lanes over b: M, V by wave reductions, S[a] += L_j(a) in arm order
+//   head     m, u_a, one sum per 64 values, their prefix; one row per lane draws a (own_leaf_kernel's search) and stores it
+//   draws    one (row, particle) per wavefront at a time: M_j(a), the chunk sums of v_j(a, .) (lane c keeps chunk c: K_j <= 4096)
+//            and V_j(a) again — kept while the next row drew the same a — then the chunk by ballot and the option by ballot
+// MARG: instead of the draws the top values of the head (u_a / U), or for an arm the top b at the head's first value a*
+// (v_j(a*, b) / V_j(a*): P(b | a*, obs), neither a per-column marginal nor the joint).
+struct OwnStarDev {
+  int32_t n_arms, ka, total, use_skip;
+  int32_t target;                          // -1: the sweep (every node); probe / marginals: 0 the head, 1 + j arm j
+  int32_t kj[OWN_STAR_MAX_ARMS];
+  const double* alogp[OWN_STAR_MAX_ARMS];  // log theta_j, [ka * kj]
+  const double* cmax[OWN_STAR_MAX_ARMS];   // [ka]
+  int32_t tbeg[1 + OWN_STAR_MAX_ARMS], tend[1 + OWN_STAR_MAX_ARMS];  // the terms of node n in nd.terms (head first, arms in order)
+  int32_t off[PCLEAN_MAX_TERMS];           // cached values of term ti: tv[off[ti] + option of its node's factor]
+  uint32_t site[1 + OWN_STAR_MAX_ARMS];
+  int32_t* vals[1 + OWN_STAR_MAX_ARMS];    // sweep: the nodes' current values, indexed by row
+  int32_t* abuf;                           // probe: the head's draw of every (item, particle)
+  unsigned long long* ctr;                 // {index values weighed, skipped} over the call's workgroups
+};
+
+__global__ __launch_bounds__(256) void own_star_cmax_kernel(int ka, int kj, const double* __restrict__ logt, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int a = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (a >= ka) return;  // (a whole wavefront)
+  double m = -__builtin_inf();
+  for (int b = lane; b < kj; b += 64) m = fmax(m, logt[(size_t)a * kj + b]);
+  m = own_wave_max(m);
+  if (lane == 0) out[a] = m + log((double)kj);
+}
+
+// joint histogram of (head value, arm value) over the loaded rows; a row unset in either node is skipped
+__global__ __launch_bounds__(256) void own_star_counts_kernel(int n_rows, int ka, int kj, const int32_t* __restrict__ va,
+                                                              const int32_t* __restrict__ vb, unsigned long long* __restrict__ hist) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n_rows; i += stride) {
+    const int a = va[i], b = vb[i];
+    if (a < 0 || a >= ka || b < 0 || b >= kj) continue;
+    atomicAdd(&hist[(size_t)a * kj + b], 1ull);
+  }
+}
+
+// t_j(a, b): own_score's sum on arm j — the ONE place where it is written
+__device__ __forceinline__ double own_star_arm_score(const OwnStarDev& sd, const double* tv, unsigned int skip, int j, int a, int b) {
+  double t = sd.alogp[j][(size_t)a * sd.kj[j] + b];
+  for (int ti = sd.tbeg[1 + j]; ti < sd.tend[1 + j]; ++ti)
+    if (!((skip >> ti) & 1u)) t += tv[sd.off[ti] + b];
+  return t;
+}
+
+struct OwnStarArm {
+  double M, t0;              // the maximum; this lane's score of chunk 0
+  unsigned long long pre, V;  // lane c: inclusive prefix of the chunk sums; their total
+};
+
+// M_j(a), the chunk sums and V_j(a) on one wavefront (every lane takes part; j and a are the same for all of them)
+__device__ __forceinline__ void own_star_arm_eval(const OwnStarDev& sd, const double* tv, unsigned int skip, int j, int a, int lane,
+                                                  OwnStarArm& r) {
+  const int K = sd.kj[j], steps = (K + 63) >> 6;
+  r.t0 = lane < K ? own_star_arm_score(sd, tv, skip, j, a, lane) : -__builtin_inf();
+  double m = r.t0;
+  for (int c = 1; c < steps; ++c) {
+    const int k = (c << 6) + lane;
+    if (k < K) m = fmax(m, own_star_arm_score(sd, tv, skip, j, a, k));
+  }
+  m = own_wave_max(m);
+  r.M = m;
+  const bool dead = m == -__builtin_inf();
+  unsigned long long pre = 0ull;
+  for (int c = 0; c < steps; ++c) {
+    const int k = (c << 6) + lane;
+    unsigned long long v = (k < K && !dead) ? pclean_fixw((c == 0 ? r.t0 : own_star_arm_score(sd, tv, skip, j, a, k)) - m) : 0ull;
+    v = own_wave_sum(v);
+    if (lane == c) pre = v;
+  }
+  pre = own_wave_scan(pre, lane);
+  r.pre = pre;
+  r.V = __shfl(pre, 63, 64);
+}
+
+// min{b : v_j(a, 0) + .. + v_j(a, b) > x} from the arm as own_star_arm_eval left it (V != 0, x < V)
+__device__ __forceinline__ int own_star_arm_pick(const OwnStarDev& sd, const double* tv, unsigned int skip, int j, int a, int lane,
+                                                 const OwnStarArm& r, unsigned long long x) {
+  const int K = sd.kj[j], steps = (K + 63) >> 6;
+  const unsigned long long cm = __ballot(lane < steps && r.pre > x);
+  const int chunk = cm ? __builtin_ctzll(cm) : steps - 1;
+  unsigned long long acc0 = __shfl(r.pre, chunk ? chunk - 1 : 0, 64);
+  if (!chunk) acc0 = 0ull;
+  const int k = (chunk << 6) + lane;
+  unsigned long long v = k < K ? pclean_fixw((chunk == 0 ? r.t0 : own_star_arm_score(sd, tv, skip, j, a, k)) - r.M) : 0ull;
+  v = own_wave_scan(v, lane);
+  const unsigned long long hit = __ballot(k < K && acc0 + v > x);
+  return hit ? (chunk << 6) + __builtin_ctzll(hit) : min(K, (chunk + 1) << 6) - 1;
+}
+
+template <bool MARG>
+__global__ __launch_bounds__(OWN_BT) void own_star_kernel(const OwnNodeDev nd, const DensDev dn, const OwnStarDev sd, const OwnLaunch L,
+                                                          const OwnMarginal M) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char own_smem[];
+  constexpr int NW = OWN_BT / 64;
+  __shared__ double s_red[NW];
+  __shared__ double s_thr;
+  __shared__ int s_obs[PCLEAN_MAX_TERMS];
+  // one small array used twice (the static LDS has to stay within the 512 bytes that OWN_PRODUCT_LDS_MAX leaves): the arms'
+  // largest term sums and the argmax of the bound before the head's pass, the marginals' top values after it
+  __shared__ unsigned long long s_misc[OWN_STAR_MAX_ARMS * NW + NW / 2];
+  static_assert(OWN_STAR_MAX_ARMS * NW + NW / 2 >= OWN_MAX_TOP + OWN_MAX_TOP / 2 + 2, "s_misc holds the marginals' top values");
+  double(*s_tau)[NW] = reinterpret_cast<double(*)[NW]>(s_misc);                 // [OWN_STAR_MAX_ARMS][NW]
+  int* s_redk = reinterpret_cast<int*>(s_misc + OWN_STAR_MAX_ARMS * NW);        // [NW]
+  unsigned long long* s_topu = s_misc;                                          // [OWN_MAX_TOP]
+  int* s_topk = reinterpret_cast<int*>(s_misc + OWN_MAX_TOP);                   // [OWN_MAX_TOP]
+  double& s_am = *reinterpret_cast<double*>(s_misc + OWN_MAX_TOP + OWN_MAX_TOP / 2);
+  unsigned long long& s_av = s_misc[OWN_MAX_TOP + OWN_MAX_TOP / 2 + 1];
+  const int ka = sd.ka, nchA = (ka + 63) >> 6;
+  double* tv = reinterpret_cast<double*>(own_smem);                             // [sd.total]
+  double* S = tv + sd.total;                                                    // [ka]
+  unsigned long long* pre = reinterpret_cast<unsigned long long*>(S + ka);      // [nchA]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int32_t* piece_off = MARG ? M.piece_off : L.piece_off;
+  const int32_t* members = MARG ? M.members : L.members;
+  const int win_lo = MARG ? M.win_lo : L.win_lo, win_hi = MARG ? M.win_hi : L.win_hi;
+  const bool probe = !MARG && L.probe;
+  const int m_lo = piece_off[blockIdx.x], m_hi = piece_off[blockIdx.x + 1];
+  if (!probe) {  // a run none of whose rows lies in the window has nothing to do
+    int any = 0;
+    for (int q = m_lo + tid; q < m_hi; q += OWN_BT) {
+      const int r = members[q];
+      any |= (r >= win_lo && r < win_hi) ? 1 : 0;
+    }
+    if (!__syncthreads_or(any)) return;
+  }
+  {
+    const int row0 = probe ? L.item_row[members[m_lo]] : members[m_lo];
+    for (int ti = 0; ti < nd.n_terms; ++ti)
+      if (tid == ti) s_obs[ti] = nd.terms[ti].obs_col[row0];
+  }
+  __syncthreads();
+
+  // ---- phase 1: the terms, once per value of the factor they read
+  unsigned int skip = 0;
+  for (int n = 0; n <= sd.n_arms; ++n) {
+    const int nf = n == 0 ? ka : sd.kj[n - 1];
+    for (int ti = sd.tbeg[n]; ti < sd.tend[n]; ++ti) {
+      const TermDev& tm = nd.terms[ti];
+      const int o = s_obs[ti];
+      if (tm.dens_kind != PCLEAN_DENS_TABULATED && o < 0) {  // a missing observation: the term adds nothing
+        skip |= 1u << ti;
+        continue;
+      }
+      double* dst = tv + sd.off[ti];
+      for (int j = tid; j < nf; j += OWN_BT) {  // (the head's column, or the first K_j entries of the arm's column 1: b's value)
+        const int val = tm.cand_col[j];
+        dst[j] = (unsigned)val < (unsigned)tm.n_lat ? own_term_value(tm, dn, o, val) : -__builtin_inf();
+      }
+    }
+  }
+  __syncthreads();
+  if (probe && L.scores_out && sd.target > 0) {  // an arm's probe: t_j(a, b) of the whole grid
+    const int j = sd.target - 1, K = sd.kj[j], n = ka * K;
+    for (int k = tid; k < n; k += OWN_BT) {
+      const int a = k / K;
+      const double t = own_star_arm_score(sd, tv, skip, j, a, k - a * K);
+      for (int mi = m_lo; mi < m_hi; ++mi) L.scores_out[(size_t)members[mi] * n + k] = t;
+    }
+  }
+
+  // ---- phase 2: the head's own part of S, and the largest cached term sum of every arm
+  for (int a = tid; a < ka; a += OWN_BT) {
+    double h = nd.logp[a];
+    for (int ti = sd.tbeg[0]; ti < sd.tend[0]; ++ti)
+      if (!((skip >> ti) & 1u)) h += tv[sd.off[ti] + a];
+    S[a] = h;
+  }
+  for (int j = 0; j < sd.n_arms; ++j) {
+    double tm = -__builtin_inf();
+    for (int b = tid; b < sd.kj[j]; b += OWN_BT) {
+      double t = 0.0;
+      for (int ti = sd.tbeg[1 + j]; ti < sd.tend[1 + j]; ++ti)
+        if (!((skip >> ti) & 1u)) t += tv[sd.off[ti] + b];
+      tm = fmax(tm, t);
+    }
+    tm = own_wave_max(tm);
+    if (lane == 0) s_tau[j][wave] = tm;
+  }
+  __syncthreads();
+  double add_tau[OWN_STAR_MAX_ARMS];
+#pragma unroll
+  for (int j = 0; j < OWN_STAR_MAX_ARMS; ++j) {
+    double t = -__builtin_inf();
+    if (j < sd.n_arms)
+      for (int w = 0; w < NW; ++w) t = fmax(t, s_tau[j][w]);
+    add_tau[j] = t;
+  }
+  auto bound = [&](int a) -> double {  // B(a) >= S(a)
+    double b = S[a];
+#pragma unroll
+    for (int j = 0; j < OWN_STAR_MAX_ARMS; ++j)
+      if (j < sd.n_arms) b += add_tau[j] + sd.cmax[j][a];
+    return b;
+  };
+  auto exact = [&](int a) -> double {  // S(a), on one wavefront: the arms in arm order
+    double acc = S[a];
+    for (int j = 0; j < sd.n_arms; ++j) {
+      OwnStarArm r;
+      own_star_arm_eval(sd, tv, skip, j, a, lane, r);
+      acc += pclean_lse_from_fix(r.M, r.V);
+    }
+    return acc;
+  };
+
+  // ---- the exact skip: S at argmax B
+  const bool skipping = sd.use_skip && !(probe && L.scores_out && sd.target == 0);
+  double thr = -__builtin_inf();
+  if (skipping) {
+    double bb = -__builtin_inf();
+    int bk = 0x7fffffff;
+    for (int a = tid; a < ka; a += OWN_BT) {
+      const double b = bound(a);
+      if (b > bb || (b == bb && a < bk)) {
+        bb = b;
+        bk = a;
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double bo = __shfl_xor(bb, o, 64);
+      const int ko = __shfl_xor(bk, o, 64);
+      if (bo > bb || (bo == bb && ko < bk)) {
+        bb = bo;
+        bk = ko;
+      }
+    }
+    if (lane == 0) {
+      s_red[wave] = bb;
+      s_redk[wave] = bk;
+    }
+    __syncthreads();
+    if (wave == 0) {  // (uniform per wavefront)
+      bb = s_red[0];
+      bk = s_redk[0];
+      for (int w = 1; w < NW; ++w)
+        if (s_red[w] > bb || (s_red[w] == bb && s_redk[w] < bk)) {
+          bb = s_red[w];
+          bk = s_redk[w];
+        }
+      if (bk >= ka) bk = 0;  // (every bound NaN: nothing is skipped below, whatever a)
+      const double sx = exact(bk);
+      if (lane == 0) s_thr = sx - OWN_SKIP_BELOW;
+    }
+    __syncthreads();
+    thr = s_thr;
+  }
+
+  // ---- the arms of every surviving a
+  {
+    unsigned long long n_w = 0ull, n_s = 0ull;
+    for (int a = wave; a < ka; a += NW) {
+      if (skipping && bound(a) < thr) {  // (the same for every lane of the wavefront)
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) S[a] = -__builtin_inf();
+        ++n_s;
+        continue;
+      }
+      const double sx = exact(a);
+      if (lane == 0) S[a] = sx;
+      ++n_w;
+    }
+    if (lane == 0 && sd.ctr) {
+      atomicAdd(&sd.ctr[0], n_w);
+      atomicAdd(&sd.ctr[1], n_s);
+    }
+  }
+  __syncthreads();
+  if (probe && L.scores_out && sd.target == 0)
+    for (int a = tid; a < ka; a += OWN_BT) {
+      const double sa = S[a];
+      for (int mi = m_lo; mi < m_hi; ++mi) L.scores_out[(size_t)members[mi] * ka + a] = sa;
+    }
+
+  // ---- the head: m, u_a, one sum per 64 values, their inclusive prefix
+  double lmax = -__builtin_inf();
+  for (int a = tid; a < ka; a += OWN_BT) lmax = fmax(lmax, S[a]);
+  lmax = own_wave_max(lmax);
+  if (lane == 0) s_red[wave] = lmax;
+  __syncthreads();
+  double m = s_red[0];
+  for (int w = 1; w < NW; ++w) m = fmax(m, s_red[w]);
+  const bool dead = m == -__builtin_inf();
+  auto weight = [&](int a) -> unsigned long long { return dead ? 0ull : pclean_fixw(S[a] - m); };
+  for (int c = wave; c < nchA; c += NW) {
+    const int a = (c << 6) + lane;
+    const unsigned long long v = own_wave_sum(a < ka ? weight(a) : 0ull);
+    if (lane == 0) pre[c] = v;
+  }
+  __syncthreads();
+  if (wave == 0) {  // (nchA <= 64)
+    const unsigned long long v = own_wave_scan(lane < nchA ? pre[lane] : 0ull, lane);
+    if (lane < nchA) pre[lane] = v;
+  }
+  __syncthreads();
+  const unsigned long long U = pre[nchA - 1];
+  const double lse = pclean_lse_from_fix(m, U);
+
+  if (!MARG) {
+    // ---- stage A: one (row, particle) per lane draws a
+    const int nd_eff = probe ? max(L.n_draws, 1) : 1;
+    const int n_out = (m_hi - m_lo) * nd_eff;
+    for (int q = tid; q < n_out; q += OWN_BT) {
+      const int mem = members[m_lo + q / nd_eff], j = q % nd_eff;
+      int row, pid;
+      if (probe) {
+        row = L.item_row[mem];
+        pid = j;
+        if (j == 0 && L.lse_out && sd.target == 0) L.lse_out[mem] = lse;
+      } else {
+        row = mem;
+        if (row < win_lo || row >= win_hi) continue;
+        const int i = row - win_lo;
+        L.logml[i] += lse;  // (once: the arms add nothing)
+        if (L.keep[i]) continue;
+        pid = L.chosen[i];
+      }
+      int res = ka - 1;
+      if (U != 0ull) {
+        const uint32_t rng_row = (uint32_t)((int64_t)row + L.row_offset);
+        const unsigned long long x = pclean_mulhi64(pclean_rand64(L.seed, rng_row, sd.site[0], (uint32_t)pid, L.sweep), U);
+        int a = 0, b = nchA - 1;
+        while (a < b) {  // the first chunk whose inclusive prefix exceeds x
+          const int mid = (a + b) >> 1;
+          if (pre[mid] > x)
+            b = mid;
+          else
+            a = mid + 1;
+        }
+        unsigned long long acc = a ? pre[a - 1] : 0ull;
+        int k = a << 6;
+        const int k_end = min(ka, k + 64) - 1;  // (the chunk's total exceeds x - acc: the walk stops inside it)
+        for (; k < k_end; ++k) {
+          acc += weight(k);
+          if (acc > x) break;
+        }
+        res = k;
+      }
+      if (!probe)
+        sd.vals[0][row] = res;
+      else if (sd.target == 0) {
+        if (L.n_draws > 0) L.draws_out[(size_t)mem * L.n_draws + j] = res;
+      } else
+        sd.abuf[(size_t)mem * nd_eff + j] = res;
+    }
+    if (probe && sd.target == 0) return;  // (uniform)
+    __syncthreads();  // (the head's draws, written by other wavefronts of this workgroup, are read below)
+
+    // ---- stage B: one (row, particle) per wavefront at a time draws the arms at its a
+    const int j_lo = probe ? sd.target - 1 : 0, j_hi = probe ? sd.target : sd.n_arms;
+    OwnStarArm arm[OWN_STAR_MAX_ARMS];
+    int arm_a[OWN_STAR_MAX_ARMS];
+#pragma unroll
+    for (int j = 0; j < OWN_STAR_MAX_ARMS; ++j) arm_a[j] = -1;
+    for (int q = wave; q < n_out; q += NW) {  // (everything below is the same for every lane of the wavefront)
+      const int mem = members[m_lo + q / nd_eff], dj = q % nd_eff;
+      int row, pid, a;
+      if (probe) {
+        row = L.item_row[mem];
+        pid = dj;
+        a = sd.abuf[(size_t)mem * nd_eff + dj];
+      } else {
+        row = mem;
+        if (row < win_lo || row >= win_hi) continue;
+        const int i = row - win_lo;
+        if (L.keep[i]) continue;
+        pid = L.chosen[i];
+        a = sd.vals[0][row];
+      }
+      if (a < 0 || a >= ka) continue;  // (never: stage A wrote it)
+      const uint32_t rng_row = (uint32_t)((int64_t)row + L.row_offset);
+#pragma unroll
+      for (int j = 0; j < OWN_STAR_MAX_ARMS; ++j) {
+        if (j < j_lo || j >= j_hi) continue;
+        if (arm_a[j] != a) {
+          own_star_arm_eval(sd, tv, skip, j, a, lane, arm[j]);
+          arm_a[j] = a;
+        }
+        int res = sd.kj[j] - 1;
+        if (U != 0ull && arm[j].V != 0ull) {
+          const unsigned long long x =
+              pclean_mulhi64(pclean_rand64(L.seed, rng_row, sd.site[1 + j], (uint32_t)pid, L.sweep), arm[j].V);
+          res = own_star_arm_pick(sd, tv, skip, j, a, lane, arm[j], x);
+        }
+        if (lane == 0) {
+          if (!probe)
+            sd.vals[1 + j][row] = res;
+          else {
+            if (L.n_draws > 0) L.draws_out[(size_t)mem * L.n_draws + dj] = res;
+            if (dj == 0 && L.lse_out) L.lse_out[mem] = pclean_lse_from_fix(arm[j].M, arm[j].V);
+          }
+        }
+      }
+    }
+  } else {
+    // ---- marginals: the head's top values (every lane of wavefront 0 scans its share of a, `top` rounds)
+    const double Ud = (double)U;
+    if (wave == 0) {
+      unsigned long long last_u = 0ull;
+      int last_k = -1;
+      bool open = true;
+      for (int t = 0; t < M.top; ++t) {
+        unsigned long long bu = 0ull;
+        int bk = -1;
+        for (int a = lane; a < ka && open; a += 64) {
+          const unsigned long long u = weight(a);
+          if (u != 0ull && (last_k < 0 || own_before(last_u, last_k, u, a)) && own_before(u, a, bu, bk)) {
+            bu = u;
+            bk = a;
+          }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+          const unsigned long long uo = __shfl_xor(bu, o, 64);
+          const int ko = __shfl_xor(bk, o, 64);
+          if (own_before(uo, ko, bu, bk)) {
+            bu = uo;
+            bk = ko;
+          }
+        }
+        if (bu != 0ull) {
+          last_u = bu;
+          last_k = bk;
+        } else {
+          open = false;
+          bk = -1;
+        }
+        if (lane == 0) {
+          s_topk[t] = bk;
+          s_topu[t] = bu;
+        }
+      }
+    }
+    __syncthreads();
+    const int a_star = s_topk[0];
+    const int j = sd.target - 1;
+    if (sd.target > 0) {  // an arm: the top b at a*
+      __syncthreads();
+      if (wave == 0) {
+        OwnStarArm r;
+        r.M = -__builtin_inf();
+        r.V = 0ull;
+        if (a_star >= 0) own_star_arm_eval(sd, tv, skip, j, a_star, lane, r);
+        unsigned long long last_u = 0ull;
+        int last_k = -1;
+        bool open = a_star >= 0 && r.V != 0ull;
+        for (int t = 0; t < M.top; ++t) {
+          unsigned long long bu = 0ull;
+          int bk = -1;
+          for (int b = lane; b < sd.kj[j] && open; b += 64) {
+            const unsigned long long u = pclean_fixw(own_star_arm_score(sd, tv, skip, j, a_star, b) - r.M);
+            if (u != 0ull && (last_k < 0 || own_before(last_u, last_k, u, b)) && own_before(u, b, bu, bk)) {
+              bu = u;
+              bk = b;
+            }
+          }
+          for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long uo = __shfl_xor(bu, o, 64);
+            const int ko = __shfl_xor(bk, o, 64);
+            if (own_before(uo, ko, bu, bk)) {
+              bu = uo;
+              bk = ko;
+            }
+          }
+          if (bu != 0ull) {
+            last_u = bu;
+            last_k = bk;
+          } else {
+            open = false;
+            bk = -1;
+          }
+          if (lane == 0) {
+            s_topk[t] = bk;
+            s_topu[t] = bu;
+          }
+        }
+        if (lane == 0) {
+          s_am = r.M;
+          s_av = r.V;
+        }
+      }
+      __syncthreads();
+    }
+    const double den = sd.target > 0 ? (double)s_av : Ud;
+    const size_t nw = (size_t)(win_hi - win_lo);
+    for (int q = m_lo + tid; q < m_hi; q += OWN_BT) {
+      const int row = members[q];
+      if (row < win_lo || row >= win_hi) continue;
+      const size_t i = (size_t)(row - win_lo);
+      for (int t = 0; t < M.top; ++t) {
+        const bool has = s_topk[t] >= 0;
+        M.top_option[(size_t)t * nw + i] = has ? s_topk[t] : -1;
+        M.top_prob[(size_t)t * nw + i] = has ? (double)s_topu[t] / den : 0.0;
+      }
+      if (M.cur_prob) {
+        const int cur = M.vals[row];
+        double p = 0.0;
+        if (sd.target == 0) {
+          if (U != 0ull && cur >= 0 && cur < ka) p = (double)weight(cur) / Ud;
+        } else if (a_star >= 0 && s_av != 0ull && cur >= 0 && cur < sd.kj[j]) {
+          p = (double)pclean_fixw(own_star_arm_score(sd, tv, skip, j, a_star, cur) - s_am) / den;
+        }
+        M.cur_prob[i] = p;
+      }
+      if (U == 0ull) {
+        atomicAdd(&M.bad[0], 1);
+        atomicMin(&M.bad[1], row);
+      }
+    }
+  }
+}
+
 // row_inference.jl:158-165 on equal weights — final_choice_kernel's operations (sweep.hip) with every weight 0.0
 template <int PMAX>
 __global__ void own_choice_kernel(int N, int P, int use_mh, const double* __restrict__ zero, const int32_t* __restrict__ vals0,
@@ -1345,10 +1892,152 @@ int launch_leaf(pclean_ctx* ctx, const OwnLeaf& lf, const OwnNodeDev& od, const 
   return PCLEAN_OK;
 }
 
+// ---- star ---------------------------------------------------------------------------------------------------------------------
+void release_stars(OwnBlock& b) {
+  for (OwnStar& st : b.stars) {
+    st.grp.piece_off.release();
+    st.grp.piece_rows.release();
+    st.cmax.release();
+  }
+  b.stars.clear();
+  b.star_of.clear();
+}
+
+// The grid rule of a star on the tables as they are now (own_star_check.h): the head's values, every arm a key-major grid over
+// them, and every value a term reads inside the term's latent domain.  Fills kj and cols_version; `status` for a refusal.
+int check_star_tables(pclean_ctx* ctx, const OwnBlock& b, int head, const std::vector<int>& arms, int status, const char* who,
+                      std::vector<int32_t>* kj_out, std::vector<uint64_t>* ver_out) {
+  const OwnLeaf& hl = b.leaves[head];
+  const CandTable& ht = ctx->cand[hl.node.table];
+  if (!ht.valid || !ht.is_options || ht.n_cols != 1 || (int)ht.h_vals.size() != ht.n_rows)
+    return pclean_fail(ctx, status, "%s: the head's option table %d is not set as a one-column option table", who, hl.node.table);
+  const int ka = ht.n_rows;
+  if (ka > OWN_STAR_MAX_K) return pclean_fail(ctx, status, "%s: the head holds %d options (at most %d)", who, ka, OWN_STAR_MAX_K);
+  auto values_ok = [&](const OwnLeaf& lf, int64_t n, const int32_t* vals, int col) -> int {
+    for (const pclean_term& tm : lf.terms) {
+      if (tm.cand_col != col) return pclean_fail(ctx, status, "%s: a term reads column %d, a star's terms read column %d", who, tm.cand_col, col);
+      const PairTable& pt = ctx->pair[tm.pair_table];
+      if (!pt.valid) return pclean_fail(ctx, PCLEAN_ERR_STATE, "%s: pair table %d not built", who, tm.pair_table);
+      const int64_t bad = own_star_check_values(n, vals, pt.n_lat);
+      if (bad) return pclean_fail(ctx, status, "%s: option %lld holds value %d outside pair table %d's %d latent values", who,
+                                  (long long)(bad - 1), vals[bad - 1], tm.pair_table, pt.n_lat);
+    }
+    return PCLEAN_OK;
+  };
+  int rc = values_ok(hl, ka, ht.h_vals.data(), 0);
+  if (rc) return rc;
+  kj_out->clear();
+  ver_out->assign(1, ht.cols_version);
+  std::vector<int32_t> cols;
+  for (int an : arms) {
+    const OwnLeaf& al = b.leaves[an];
+    const CandTable& at = ctx->cand[al.node.table];
+    if (!at.valid || !at.is_options || at.n_cols != 2)
+      return pclean_fail(ctx, status, "%s: the option table %d of arm node %d is not set with two value columns", who, al.node.table, an);
+    cols.resize((size_t)2 * at.n_rows);
+    HIPCHK(ctx, hipMemcpy(cols.data(), at.cols.p, cols.size() * 4, hipMemcpyDeviceToHost));
+    char msg[200];
+    int32_t kj = 0;
+    if (own_star_check_grid(ka, ht.h_vals.data(), at.n_rows, cols.data(), cols.data() + at.n_rows, &kj, msg, sizeof msg))
+      return pclean_fail(ctx, status, "%s: arm node %d: %s", who, an, msg);
+    rc = values_ok(al, kj, cols.data() + at.n_rows, 1);
+    if (rc) return rc;
+    kj_out->push_back(kj);
+    ver_out->push_back(at.cols_version);
+  }
+  return PCLEAN_OK;
+}
+
+// The device view of a star: the nodes' views (leaf_dev) with their terms in one list, the layout of the cached values, and
+// room for the bound of every arm's prior rows (launch_star fills it).  target: see OwnStarDev.
+int star_dev(pclean_ctx* ctx, OwnBlock& b, OwnStar& st, int block_id, int target, OwnNodeDev& od, OwnStarDev& sd, size_t* lds) {
+  static const bool no_skip = getenv("PCLEAN_NO_OWN_SKIP") != nullptr;
+  const int D = (int)st.arms.size();
+  bool moved = (int)st.cols_version.size() != 1 + D;
+  for (int n = 0; n <= D && !moved; ++n)
+    moved = ctx->cand[b.leaves[n == 0 ? st.head : st.arms[n - 1]].node.table].cols_version != st.cols_version[n];
+  if (moved) {  // an option table was set anew since the star was linked: its lengths and values are checked again
+    const int rc = check_star_tables(ctx, b, st.head, st.arms, PCLEAN_ERR_STATE, "own block (star)", &st.kj, &st.cols_version);
+    if (rc) {
+      st.cols_version.clear();
+      return rc;
+    }
+  }
+  memset(&sd, 0, sizeof sd);
+  int rc = leaf_dev(ctx, b.leaves[st.head], od);
+  if (rc) return rc;
+  sd.n_arms = D;
+  sd.ka = od.n_cand;
+  sd.target = target;
+  sd.use_skip = no_skip ? 0 : 1;
+  sd.tbeg[0] = 0;
+  sd.tend[0] = od.n_terms;
+  sd.site[0] = PCLEAN_SITE_NODE(block_id, st.head);
+  int32_t tpn[1 + OWN_STAR_MAX_ARMS] = {od.n_terms, 0, 0, 0, 0};
+  int total = 0;
+  for (int ti = 0; ti < od.n_terms; ++ti, total += sd.ka) sd.off[ti] = total;
+  if (st.cmax.alloc((size_t)D * sd.ka)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  for (int j = 0; j < D; ++j) {
+    OwnNodeDev ad;
+    rc = leaf_dev(ctx, b.leaves[st.arms[j]], ad);
+    if (rc) return rc;
+    if (ad.n_cand != sd.ka * st.kj[j]) return pclean_fail(ctx, PCLEAN_ERR_STATE, "own block (star): arm %d holds %d options, not %d x %d", j, ad.n_cand, sd.ka, st.kj[j]);
+    if (od.n_terms + ad.n_terms > PCLEAN_MAX_TERMS)
+      return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "own block (star): more than %d terms over the star", PCLEAN_MAX_TERMS);
+    sd.kj[j] = st.kj[j];
+    sd.alogp[j] = ad.logp;
+    sd.cmax[j] = st.cmax.p + (size_t)j * sd.ka;
+    sd.tbeg[1 + j] = od.n_terms;
+    for (int ti = 0; ti < ad.n_terms; ++ti, total += sd.kj[j]) {
+      sd.off[od.n_terms] = total;
+      od.terms[od.n_terms++] = ad.terms[ti];
+    }
+    sd.tend[1 + j] = od.n_terms;
+    tpn[1 + j] = ad.n_terms;
+    sd.site[1 + j] = PCLEAN_SITE_NODE(block_id, st.arms[j]);
+  }
+  sd.total = total;
+  *lds = own_star_lds_bytes(sd.ka, D, sd.kj, tpn);
+  if (*lds > OWN_PRODUCT_LDS_MAX)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "own block (star): %zu bytes of cached values, more than the %zu of a workgroup's LDS", *lds,
+                       (size_t)OWN_PRODUCT_LDS_MAX);
+  return PCLEAN_OK;
+}
+
+struct StarPlan {
+  OwnNodeDev od;
+  OwnStarDev sd;
+  size_t lds = 0;
+};
+
+int launch_star(pclean_ctx* ctx, OwnState* s, const OwnNodeDev& od, const OwnStarDev& sd, size_t lds, const OwnLaunch& L, const OwnMarginal* M,
+                int n_pieces) {
+  if (n_pieces <= 0) return PCLEAN_OK;
+  if (!s->star_attr_set) {
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)own_star_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OWN_PRODUCT_LDS_MAX));
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)own_star_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OWN_PRODUCT_LDS_MAX));
+    s->star_attr_set = true;
+  }
+  const DensDev dn{ctx->nb.p, ctx->logl.p, ctx->max_d + 1, 0, ctx->prob_same.p, ctx->prob_diff.p, ctx->logn.p};
+  for (int j = 0; j < sd.n_arms; ++j) {  // the bound of every arm's prior rows, from the priors as they are at this call
+    hipLaunchKernelGGL(own_star_cmax_kernel, dim3((sd.ka + 3) / 4), dim3(256), 0, ctx->stream, sd.ka, sd.kj[j], sd.alogp[j],
+                       const_cast<double*>(sd.cmax[j]));
+    HIPCHK(ctx, hipGetLastError());
+  }
+  if (M)
+    hipLaunchKernelGGL(own_star_kernel<true>, dim3(n_pieces), dim3(OWN_BT), lds, ctx->stream, od, dn, sd, OwnLaunch{}, *M);
+  else
+    hipLaunchKernelGGL(own_star_kernel<false>, dim3(n_pieces), dim3(OWN_BT), lds, ctx->stream, od, dn, sd, L, OwnMarginal{});
+  HIPCHK(ctx, hipGetLastError());
+  s->stats.variants |= 16;
+  s->stats.n_workgroups += n_pieces;
+  return PCLEAN_OK;
+}
+
 // the constant, the counters of impossible rows and the events around a call's launches
 int ensure_aux(pclean_ctx* ctx, OwnState* s) {
   if (s->zero.p) return PCLEAN_OK;
-  if (s->zero.alloc(1) || s->bad.alloc(2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
+  if (s->zero.alloc(1) || s->bad.alloc(2) || s->star_ctr.alloc(2)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
   const double z = 0.0;
   HIPCHK(ctx, hipMemcpy(s->zero.p, &z, 8, hipMemcpyHostToDevice));
   HIPCHK(ctx, hipEventCreate(&s->ev[0]));
@@ -1373,6 +2062,7 @@ void pclean_own_state_free(pclean_ctx* ctx) {
   OwnState* s = static_cast<OwnState*>(ctx->own_state);
   for (OwnBlock& b : s->block) {
     b.vals.release();
+    release_stars(b);
     for (OwnLeaf& lf : b.leaves) {
       lf.piece_off.release();
       lf.piece_rows.release();
@@ -1382,6 +2072,7 @@ void pclean_own_state_free(pclean_ctx* ctx) {
   s->bad.release();
   s->hist.release();
   s->gstat.release();
+  s->star_ctr.release();
   for (hipEvent_t e : s->ev)
     if (e) (void)hipEventDestroy(e);
   delete s;
@@ -1406,6 +2097,8 @@ extern "C" int pclean_load_own_block(pclean_ctx* ctx, int32_t block_id, int32_t 
   }
   b.leaves.clear();
   b.leaves.resize(n_nodes);
+  release_stars(b);  // (pclean_link_own_star comes after the load)
+  b.star_of.assign(n_nodes, -1);
   for (int i = 0; i < n_nodes; ++i) {
     b.leaves[i].node = nodes[i];
     b.leaves[i].terms.assign(terms + nodes[i].term_begin, terms + nodes[i].term_begin + nodes[i].n_terms);
@@ -1413,6 +2106,51 @@ extern "C" int pclean_load_own_block(pclean_ctx* ctx, int32_t block_id, int32_t 
   b.vals.release();
   b.vals_rows = -1;
   b.valid = true;
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_link_own_star(pclean_ctx* ctx, int32_t block_id, int32_t head_node, int32_t n_arms, const int32_t* arm_nodes) {
+  OwnBlock* b = find_block(ctx, block_id);
+  if (!b) return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_link_own_star: block %d is not a loaded own block", block_id);
+  const int nn = (int)b->leaves.size();
+  if (n_arms < 2 || n_arms > OWN_STAR_MAX_ARMS || !arm_nodes)
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_link_own_star: %d arms (2 .. %d are served; one dependent is a product leaf)", n_arms,
+                       OWN_STAR_MAX_ARMS);
+  if (head_node < 0 || head_node >= nn || b->star_of[head_node] >= 0 || !b->leaves[head_node].gauss.empty())
+    return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_link_own_star: head node %d is no free node of block %d without Gaussian terms", head_node,
+                       block_id);
+  std::vector<int> arms(arm_nodes, arm_nodes + n_arms);
+  size_t n_terms = b->leaves[head_node].terms.size();
+  for (int j = 0; j < n_arms; ++j) {
+    const int an = arms[j];
+    if (an != head_node + 1 + j || an >= nn || b->star_of[an] >= 0 || !b->leaves[an].gauss.empty())
+      return pclean_fail(ctx, PCLEAN_ERR_ARG, "pclean_link_own_star: arm %d is node %d; the arms are the free nodes that follow the head "
+                                              "(%d), in order, without Gaussian terms", j, an, head_node);
+    n_terms += b->leaves[an].terms.size();
+  }
+  if (n_terms > PCLEAN_MAX_TERMS)
+    return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "pclean_link_own_star: %zu terms over the star (at most %d)", n_terms, PCLEAN_MAX_TERMS);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  OwnStar st;
+  st.head = head_node;
+  st.arms = arms;
+  int rc = check_star_tables(ctx, *b, head_node, arms, PCLEAN_ERR_ARG, "pclean_link_own_star", &st.kj, &st.cols_version);
+  if (rc) return rc;  // (nothing modified)
+  {
+    int32_t tpn[1 + OWN_STAR_MAX_ARMS] = {0, 0, 0, 0, 0};
+    tpn[0] = (int32_t)b->leaves[head_node].terms.size();
+    for (int j = 0; j < n_arms; ++j) tpn[1 + j] = (int32_t)b->leaves[arms[j]].terms.size();
+    const size_t lds = own_star_lds_bytes(ctx->cand[b->leaves[head_node].node.table].n_rows, n_arms, st.kj.data(), tpn);
+    if (lds > OWN_PRODUCT_LDS_MAX)
+      return pclean_fail(ctx, PCLEAN_ERR_CAPACITY, "pclean_link_own_star: %zu bytes of cached values, more than the %zu of a workgroup's LDS", lds,
+                         (size_t)OWN_PRODUCT_LDS_MAX);
+  }
+  st.grp.terms = b->leaves[head_node].terms;
+  for (int an : arms) st.grp.terms.insert(st.grp.terms.end(), b->leaves[an].terms.begin(), b->leaves[an].terms.end());
+  const int si = (int)b->stars.size();
+  b->stars.push_back(st);
+  b->star_of[head_node] = si;
+  for (int an : arms) b->star_of[an] = si;
   return PCLEAN_OK;
 }
 
@@ -1468,6 +2206,7 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
   if (N == 0) return PCLEAN_OK;
   // everything that can fail for want of a table comes before the first write: a refused sweep changes nothing
   std::vector<OwnNodeDev> ods;
+  std::vector<StarPlan> stars;  // (in block order, a block's in link order)
   for (int bi = 0; bi < PCLEAN_MAX_BLOCKS; ++bi) {
     OwnBlock& b = s->block[bi];
     if (!b.valid) continue;
@@ -1484,11 +2223,21 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
       }
       if (rc) return rc;
     }
+    for (OwnStar& st : b.stars) {
+      stars.emplace_back();
+      StarPlan& sp = stars.back();
+      rc = ensure_groups(ctx, st.grp);
+      if (!rc) rc = star_dev(ctx, b, st, bi, -1, sp.od, sp.sd, &sp.lds);
+      if (rc) return rc;
+      for (int n = 0; n <= sp.sd.n_arms; ++n) sp.sd.vals[n] = b.vals.p + (size_t)(n == 0 ? st.head : st.arms[n - 1]) * ctx->n_rows;
+    }
   }
   {
     const int rc = ensure_aux(ctx, s);
     if (rc) return rc;
   }
+  if (!stars.empty()) HIPCHK(ctx, hipMemsetAsync(s->star_ctr.p, 0, 16, ctx->stream));
+  for (StarPlan& sp : stars) sp.sd.ctr = s->star_ctr.p;
   int32_t* d_chosen = scratch<int32_t>(ctx, N);
   int32_t* d_keep = scratch<int32_t>(ctx, N);
   double* d_logml = scratch<double>(ctx, N);
@@ -1505,12 +2254,14 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
                                       (const double*)s->zero.p, (const int32_t*)(s->block[first].vals.p + win_lo), seed, sweep_idx,
                                       row_offset + win_lo, d_chosen, d_keep));
   HIPCHK(ctx, hipGetLastError());
-  size_t li = 0;
+  size_t li = 0, star0 = 0;
   for (int bi = 0; bi < PCLEAN_MAX_BLOCKS; ++bi) {
     OwnBlock& b = s->block[bi];
     if (!b.valid) continue;
     for (size_t ni = 0; ni < b.leaves.size(); ++ni, ++li) {
-      OwnLeaf& lf = b.leaves[ni];
+      const int si = b.star_of[ni];
+      if (si >= 0 && b.stars[si].head != (int)ni) continue;  // (an arm: drawn in its head's launch)
+      OwnLeaf& lf = si >= 0 ? b.stars[si].grp : b.leaves[ni];
       OwnLaunch L{};
       L.piece_off = lf.piece_off.p;
       L.members = lf.piece_rows.p;
@@ -1524,17 +2275,21 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
       L.seed = seed;
       L.sweep = sweep_idx;
       L.site = PCLEAN_SITE_NODE(bi, ni);
-      const int rc = launch_leaf(ctx, lf, ods[li], L, lf.n_pieces, s);
+      const StarPlan* sp = si >= 0 ? &stars[star0 + si] : nullptr;
+      const int rc = sp ? launch_star(ctx, s, sp->od, sp->sd, sp->lds, L, nullptr, lf.n_pieces) : launch_leaf(ctx, lf, ods[li], L, lf.n_pieces, s);
       if (rc) return rc;
       s->stats.n_runs += lf.n_runs;
       s->stats.longest_run = std::max(s->stats.longest_run, lf.longest);
     }
+    star0 += b.stars.size();
   }
   hipLaunchKernelGGL(own_bad_rows_kernel, grid1(N), dim3(256), 0, ctx->stream, N, win_lo, (const double*)d_logml, s->bad.p);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipEventRecord(s->ev[1], ctx->stream));
   int32_t bad[2] = {0, 0};
+  unsigned long long ctr[2] = {0ull, 0ull};
   HIPCHK(ctx, hipMemcpyAsync(bad, s->bad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (!stars.empty()) HIPCHK(ctx, hipMemcpyAsync(ctr, s->star_ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
   if (chosen_particle) HIPCHK(ctx, hipMemcpyAsync(chosen_particle, d_chosen, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (logml) HIPCHK(ctx, hipMemcpyAsync(logml, d_logml, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCLEAN_SYNC(ctx);
@@ -1542,6 +2297,8 @@ extern "C" int pclean_sweep_own(pclean_ctx* ctx, const pclean_infer_config* cfg,
   (void)hipEventElapsedTime(&ctx->timing.total_ms, s->ev[0], s->ev[1]);
   s->stats.impossible_rows = bad[0];
   s->stats.first_impossible_row = bad[0] ? bad[1] : -1;
+  s->stats.star_weighed = (int64_t)ctr[0];
+  s->stats.star_skipped = (int64_t)ctr[1];
   return finish_call(ctx);
 }
 
@@ -1562,10 +2319,20 @@ extern "C" int pclean_score_own(pclean_ctx* ctx, int32_t block_id, int32_t node_
   }
   OwnState* s = own(ctx);
   reset_stats(s);
-  OwnLeaf& lf = b->leaves[node_id];
+  OwnStar* star = b->star_of[node_id] >= 0 ? &b->stars[b->star_of[node_id]] : nullptr;
+  OwnLeaf& lf = star ? star->grp : b->leaves[node_id];  // (a star: the grouping over the terms of all its nodes)
   OwnNodeDev od;
-  int rc = leaf_dev(ctx, lf, od);
-  if (!rc) rc = ensure_groups(ctx, lf);
+  OwnStarDev sd;
+  size_t star_lds = 0;
+  int rc;
+  if (star) {
+    rc = ensure_groups(ctx, lf);
+    if (!rc) rc = ensure_aux(ctx, s);
+    if (!rc) rc = star_dev(ctx, *b, *star, block_id, node_id - star->head, od, sd, &star_lds);
+  } else {
+    rc = leaf_dev(ctx, lf, od);
+    if (!rc) rc = ensure_groups(ctx, lf);
+  }
   if (rc) return rc;
   // the items grouped by the piece of a tuple run their row lies in (stable): the sweep's grouping, restricted to the items
   std::vector<int32_t> h_row(n_items), order(n_items), poff;
@@ -1583,7 +2350,7 @@ extern "C" int pclean_score_own(pclean_ctx* ctx, int32_t block_id, int32_t node_
   const int n_pieces = (int)poff.size();
   poff.push_back(n_items);
   s->stats.n_runs = (int)runs.size();
-  const int K = od.n_cand;
+  const int K = !star ? od.n_cand : sd.target == 0 ? sd.ka : sd.ka * sd.kj[sd.target - 1];
   int32_t* d_row = scratch<int32_t>(ctx, n_items);
   int32_t* d_order = scratch<int32_t>(ctx, n_items);
   int32_t* d_poff = scratch<int32_t>(ctx, poff.size());
@@ -1592,6 +2359,12 @@ extern "C" int pclean_score_own(pclean_ctx* ctx, int32_t block_id, int32_t node_
   int32_t* d_draws = n_draws ? scratch<int32_t>(ctx, (size_t)n_items * n_draws) : nullptr;
   if (!d_row || !d_order || !d_poff || !d_lse || (scores && !d_scores) || (n_draws && !d_draws))
     return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+  if (star) {
+    sd.abuf = scratch<int32_t>(ctx, (size_t)n_items * std::max(n_draws, 1));
+    if (!sd.abuf) return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed");
+    sd.ctr = s->star_ctr.p;
+    HIPCHK(ctx, hipMemsetAsync(s->star_ctr.p, 0, 16, ctx->stream));
+  }
   HIPCHK(ctx, hipMemcpyAsync(d_row, h_row.data(), (size_t)n_items * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_order, order.data(), (size_t)n_items * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_poff, poff.data(), poff.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1608,12 +2381,16 @@ extern "C" int pclean_score_own(pclean_ctx* ctx, int32_t block_id, int32_t node_
   L.seed = seed;
   L.sweep = sweep;
   L.site = PCLEAN_SITE_NODE(block_id, node_id);
-  rc = launch_leaf(ctx, lf, od, L, n_pieces, s);
+  rc = star ? launch_star(ctx, s, od, sd, star_lds, L, nullptr, n_pieces) : launch_leaf(ctx, lf, od, L, n_pieces, s);
   if (rc) return rc;
+  unsigned long long ctr[2] = {0ull, 0ull};
+  if (star) HIPCHK(ctx, hipMemcpyAsync(ctr, s->star_ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
   if (lse) HIPCHK(ctx, hipMemcpyAsync(lse, d_lse, (size_t)n_items * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (scores) HIPCHK(ctx, hipMemcpyAsync(scores, d_scores, (size_t)n_items * K * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (n_draws) HIPCHK(ctx, hipMemcpyAsync(draws, d_draws, (size_t)n_items * n_draws * 4, hipMemcpyDeviceToHost, ctx->stream));
   PCLEAN_SYNC(ctx);  // (h_row / order / poff are read by the copies queued above)
+  s->stats.star_weighed = (int64_t)ctr[0];
+  s->stats.star_skipped = (int64_t)ctr[1];
   return finish_call(ctx);
 }
 
@@ -1636,12 +2413,16 @@ extern "C" int pclean_own_marginals(pclean_ctx* ctx, int32_t block_id, int32_t n
   OwnState* s = own(ctx);
   reset_stats(s);
   if (N == 0) return PCLEAN_OK;
-  OwnLeaf& lf = b->leaves[node_id];
+  OwnStar* star = b->star_of[node_id] >= 0 ? &b->stars[b->star_of[node_id]] : nullptr;
+  OwnLeaf& lf = star ? star->grp : b->leaves[node_id];
   OwnNodeDev od;
-  int rc = leaf_dev(ctx, lf, od);
+  OwnStarDev sd;
+  size_t star_lds = 0;
+  int rc = star ? PCLEAN_OK : leaf_dev(ctx, lf, od);
   if (!rc) rc = ensure_groups(ctx, lf);
   if (!rc && cur_prob) rc = ensure_vals(ctx, *b);
   if (!rc) rc = ensure_aux(ctx, s);
+  if (!rc && star) rc = star_dev(ctx, *b, *star, block_id, node_id - star->head, od, sd, &star_lds);
   if (rc) return rc;
   int32_t* d_opt = scratch<int32_t>(ctx, (size_t)top * N);
   double* d_prob = scratch<double>(ctx, (size_t)top * N);
@@ -1669,7 +2450,10 @@ extern "C" int pclean_own_marginals(pclean_ctx* ctx, int32_t block_id, int32_t n
     if (rc) return rc;
   }
   HIPCHK(ctx, hipEventRecord(s->ev[0], ctx->stream));
-  if (lf.n_pieces > 0 && !lf.gauss.empty()) {
+  if (star) {  // the head's exact marginal, or an arm's conditional at the head's first value
+    rc = launch_star(ctx, s, od, sd, star_lds, OwnLaunch{}, &L, lf.n_pieces);
+    if (rc) return rc;
+  } else if (lf.n_pieces > 0 && !lf.gauss.empty()) {
     hipLaunchKernelGGL(own_gauss_kernel<true>, dim3(lf.n_pieces), dim3(OWN_BT), glds, ctx->stream, od, dn, gd, OwnLaunch{}, L);
     HIPCHK(ctx, hipGetLastError());
     s->stats.variants |= 8;
@@ -1717,7 +2501,18 @@ extern "C" int pclean_own_counts(pclean_ctx* ctx, int32_t block_id, int32_t node
   const int K = t.n_rows;
   if (s->hist.alloc(K)) return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed");
   HIPCHK(ctx, hipMemsetAsync(s->hist.p, 0, (size_t)K * 8, ctx->stream));
-  if (ctx->n_rows) {
+  const OwnStar* star = b->star_of[node_id] >= 0 ? &b->stars[b->star_of[node_id]] : nullptr;
+  if (star && node_id != star->head) {  // an arm: the joint histogram of (head value, arm value)
+    const int ka = ctx->cand[b->leaves[star->head].node.table].n_rows;
+    if (ka < 1 || K % ka) return pclean_fail(ctx, PCLEAN_ERR_STATE, "pclean_own_counts: the arm's table is no grid over the head's %d options", ka);
+    if (ctx->n_rows) {
+      const unsigned blocks = (unsigned)std::min<size_t>(((size_t)ctx->n_rows + 255) / 256, 1024);
+      hipLaunchKernelGGL(own_star_counts_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->n_rows, ka, K / ka,
+                         (const int32_t*)(b->vals.p + (size_t)star->head * ctx->n_rows),
+                         (const int32_t*)(b->vals.p + (size_t)node_id * ctx->n_rows), s->hist.p);
+      HIPCHK(ctx, hipGetLastError());
+    }
+  } else if (ctx->n_rows) {
     const unsigned blocks = (unsigned)std::min<size_t>(((size_t)ctx->n_rows + 255) / 256, 1024);
     hipLaunchKernelGGL(own_counts_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->n_rows, K,
                        (const int32_t*)(b->vals.p + (size_t)node_id * ctx->n_rows), s->hist.p);

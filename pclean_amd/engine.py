@@ -105,7 +105,8 @@ class InferenceConfig:
 def option_prior(lw, trace, cname, aname):
     """log prior of every option of the ChooseProportionally choice cname.aname, in option order: logprobs() (utils.jl:33-36);
     an IndexedProportionsParameter: log theta_key[option], key-major as the options; a product leaf: the joint prior
-    log pA(a) + log theta_a[b], added in that order"""
+    log pA(a) + log theta_a[b], added in that order; an arm of a star (LoweredModel.own_star): log theta_a[b] ALONE, key-major —
+    log pA(a) belongs to the star's head"""
     m = lw.model
     d = m.classes[cname].attr(aname).dist
     with np.errstate(divide="ignore"):
@@ -307,6 +308,7 @@ class Engine:
         lw.load_blocks_into(hip)
         self._gauss_pending = bool(getattr(lw, "gauss", {}))
         self._own_gauss_pending = bool(getattr(lw, "own_gauss", {}))  # (pclean_load_own_block forgot the terms)
+        self._own_star_pending = bool(getattr(lw, "own_star", {}))  # (... and the stars: linked once the option tables are set)
 
     def _upload_class_tables(self):
         """Tabulated terms (ExpandOnShortVersion / FormatName): the class table of every such pair, built on the device
@@ -400,6 +402,10 @@ class Engine:
                 else:
                     hip.set_options(lw.option_id[(cname, aname)], lw.option_values[(cname, aname)], logp)
                 last[("options", cname, aname)] = logp.copy()
+        if getattr(self, "_own_star_pending", False):  # after pclean_load_own_block and the nodes' option tables
+            for (bi, head), arms in lw.own_star.items():
+                hip.link_own_star(bi, head, arms)
+            self._own_star_pending = False
         if lw.prob_spec is not None:
             pt = trace.prob_table()
             if last.get("prob") is None or not np.array_equal(last["prob"], pt):
@@ -544,6 +550,8 @@ class Engine:
         cfg = config.as_c() if isinstance(config, InferenceConfig) else config
         if not cfg.use_dd_proposals:
             raise NotImplementedError("use_dd_proposals=False (prior proposals) is not served for a flat observed class")
+        if getattr(self.lw, "own_star", None) and getattr(self, "_dev_comm", False):
+            raise NotImplementedError("several ranks (init_device_comm): a star of own choices is served on one rank alone")
         hi = trace._own.shape[1] if hi is None else hi
         if hi <= lo:
             return (np.zeros(0, np.int32), np.zeros(0)) if want_outputs else (None, None)
@@ -570,7 +578,9 @@ class Engine:
         them; nothing is drawn, written or pulled, and no count changes.  A choice indexed by a sibling choice and that
         index (one product leaf): the top options are those of the PAIR — entry t of both is the t-th most probable pair,
         decoded per choice — and every probability is the pair's JOINT probability, not a per-column marginal; the probability
-        of the current value is that of the current pair."""
+        of the current value is that of the current pair.  The choices of a STAR (own_star=True) each have an entry of their
+        own: the index's is its exact marginal u_a / U; a dependent's is CONDITIONAL on the index's first value a* — the top b
+        with P(b | a*, obs) and that probability of the row's current b — neither a per-column marginal nor the joint."""
         if not getattr(self.lw, "flat", False):
             raise _lib.PCleanHipError("Engine.own_marginals: the observed class is not flat (it has reference-slot blocks)")
         hi = trace._own.shape[1] if hi is None else hi

@@ -240,25 +240,37 @@ def flat_vocabulary(clean, columns=FLAT_COLUMNS):
     return {c: list(dict.fromkeys(v for v in clean[c] if v is not None)) for c in columns}
 
 
-def flat_model(vocab, dependent=None):
+FLAT_STAR_COLUMNS = ("City", "State", "CountyName", "Condition")
+FLAT_STAR = ("City", ("State", "CountyName"))  # the hospital's State and CountyName given its City
+
+
+def flat_model(vocab, dependent=None, star=None):
     """`@class Obs`: per column one own block  `col ~ ChooseProportionally(vocab[col], col_p); col_obs ~ AddTypos(col)`
     with a learned ProportionsParameter — no latent class, no reference slot (a FLAT class: LoweredModel.flat).
     dependent = (index column, column): the two share one block and the column's choice is indexed by the index column's,
     `col ~ ChooseProportionally(vocab[col], col_p, index=index column)` with an IndexedProportionsParameter — e.g. the
-    hospital's State given its City (one product leaf: own_block.hip)."""
+    hospital's State given its City (one product leaf: own_block.hip).
+    star = (index column, (column, ...)): the same with SEVERAL columns indexed by the index column, all in its block, each
+    with an IndexedProportionsParameter — a functional dependency from one key column to several others.  Lower it with
+    LoweredModel(..., own_star=True) (a star: a head node and one arm per column, enumerated collapsed)."""
     m = Model()
     o = m.add_class("Obs")
-    ix, dep = dependent or (None, None)
+    if dependent and star:
+        raise ValueError("flat_model: dependent= and star= are alternatives")
+    ix, deps = (dependent[0], (dependent[1],)) if dependent else (star or (None, ()))
+    deps = tuple(deps)
     for c in vocab:
-        o.param(f"{c}_p", IndexedProportionsParameter(1.0) if c == dep else ProportionsParameter(1.0))
+        o.param(f"{c}_p", IndexedProportionsParameter(1.0) if c in deps else ProportionsParameter(1.0))
     for c, words in vocab.items():
-        if c == dep:
+        if c in deps:
             continue  # (declared in its index's block)
         with o.block():
             o.choice(c, ChooseProportionally(words, f"{c}_p"))
             if c == ix:
-                o.choice(dep, ChooseProportionally(vocab[dep], f"{dep}_p", index=ix))
-                o.choice(f"{dep}_obs", AddTypos(dep))
+                for dep in deps:
+                    o.choice(dep, ChooseProportionally(vocab[dep], f"{dep}_p", index=ix))
+                for dep in deps:
+                    o.choice(f"{dep}_obs", AddTypos(dep))
             o.choice(f"{c}_obs", AddTypos(c))
     return m
 

@@ -93,6 +93,9 @@ TABULATED = (ExpandOnShortVersion, FormatName)
 NAME3_LOG_THREE = math.log(0.9) + math.log(0.9) + math.log(0.9)
 NAME3_LOG_TWO = math.log(0.1)
 OWN_MAX_OPTIONS = 64 * 4096  # options of one own option list (csrc/own_block.hip: OWN_MAX_OPTIONS)
+OWN_STAR_MAX_ARMS = 4  # dependents of one index in a star (csrc/own_star_check.h)
+OWN_STAR_MAX_K = 4096  # values of a star's index or of one of its dependents
+OWN_STAR_LDS_MAX = 160 * 1024 - 512  # bytes of cached values of a star (csrc/own_block.hip: OWN_PRODUCT_LDS_MAX)
 OWN_GAUSS_MAX_OPTIONS = 4096  # options of an own leaf that carries Gaussian terms (csrc/own_block.hip: OWN_GAUSS_MAX_OPTIONS)
 
 
@@ -330,12 +333,16 @@ class MappedDomain:
 class LoweredModel:
     """Domains, flattened table layouts, option tables and per-block plans."""
 
-    def __init__(self, model, query, dirty_columns, pool=None, extra_latent=None):
-        """extra_latent {(class, attribute): [strings]}: values a latent attribute holds although they are neither
+    def __init__(self, model, query, dirty_columns, pool=None, extra_latent=None, own_star=False):
+        """own_star: a flat observed class may hold several dependents on one index in one own block; they are lowered as a
+        star (_lower_own_block: a head node and one arm per dependent, enumerated collapsed).  Off, every plan and refusal is
+        what it was.
+        extra_latent {(class, attribute): [strings]}: values a latent attribute holds although they are neither
         proposal atoms nor the dummy — strings drawn by random(StringPrior / TimePrior) for a chosen
         ProposalDummyValue (block_proposal.jl:58-60).  They are appended to the attribute's domain (ids of the
         atoms and the dummy do not move) and are never options of a proposal."""
         self.model, self.query = model, query
+        self.own_star_enabled = bool(own_star)
         self._dirty_columns = dirty_columns
         self.extra_latent = {k: list(v) for k, v in (extra_latent or {}).items()}
         self.pool = pool or StringPool()
@@ -464,6 +471,7 @@ class LoweredModel:
         m = self.model
         self.indexed = {}
         self.product_index = {}  # (class, index attribute) -> its dependent: the two are enumerated as one product leaf
+        self.star_index = {}     # (observed class, index attribute) -> [its dependents, two and more]: a star (own_star=True)
         for cname in m.class_order:
             cls = m.classes[cname]
             seen = {}
@@ -527,6 +535,7 @@ class LoweredModel:
                         raise NotImplementedError(f"{who}: the index {ix} is observed through {obsname}, which has missing "
                                                   "values; the keyed form needs the key of every row")
                 self.indexed[(cname, a.name)] = ("keyed", ix)
+        self._resolve_own_stars()
 
     def _resolve_own_indexed(self, cname, cls, a, ia, seen):
         """An indexed own choice of the OBSERVED class: served in a flat class when its index is a sibling own
@@ -550,7 +559,8 @@ class LoweredModel:
                                       "choice")
         if ia.dist.index is not None:
             raise NotImplementedError(f"{who}: the index {ix} is itself indexed")
-        if ix in seen:
+        star = self.own_star_enabled
+        if ix in seen and not star:
             raise NotImplementedError(f"{who}: {ix} already indexes {seen[ix]}; two dependents on one index are not lowered")
         seen[ix] = a.name
         names = [x.name for x in cls.attrs]
@@ -560,6 +570,8 @@ class LoweredModel:
         if names.index(ix) > names.index(a.name):
             raise NotImplementedError(f"{who}: the index {ix} must be declared before the choice")
         for mid in cls.attrs[names.index(ix) + 1:names.index(a.name)]:
+            if star and mid.kind == "choice" and isinstance(mid.dist, ChooseProportionally) and mid.dist.index == ix:
+                continue  # (an earlier dependent of the same index: an arm of the same star)
             reads = list(getattr(mid, "args", ())) if mid.kind == "julia" else [
                 getattr(getattr(mid, "dist", None), f, None) for f in ("keyed_by", "index", "ref", "mean", "unit", "val", "key")]
             if ix in reads:
@@ -572,7 +584,32 @@ class LoweredModel:
             raise NotImplementedError(f"{who}: the product with {ix} has {na} x {nb} = {na * nb} options, more than the "
                                       f"{OWN_MAX_OPTIONS} an own option list holds (OWN_MAX_OPTIONS)")
         self.indexed[(cname, a.name)] = ("product", ix)
+        if star:
+            self.star_index.setdefault((cname, ix), []).append(a.name)
         self.product_index[(cname, ix)] = a.name
+
+    def _resolve_own_stars(self):
+        """own_star=True: an index of the observed class with two and more dependents becomes a star — the dependents are
+        marked ("star", index) and leave product_index; an index with ONE dependent stays the product leaf."""
+        for (cname, ix), deps in list(self.star_index.items()):
+            if len(deps) < 2:
+                del self.star_index[(cname, ix)]
+                continue
+            who = f"{cname}.{ix}"
+            if len(deps) > OWN_STAR_MAX_ARMS:
+                raise NotImplementedError(f"{who}: {len(deps)} dependents on one index ({', '.join(deps)}); a star holds at most "
+                                          f"{OWN_STAR_MAX_ARMS} (OWN_STAR_MAX_ARMS)")
+            cls = self.model.classes[cname]
+            sizes = {n: len(cls.attr(n).dist.options) for n in [ix] + deps}
+            for n, k in sizes.items():
+                if k > OWN_STAR_MAX_K:
+                    raise NotImplementedError(f"{cname}.{n}: {k} options; the index and the dependents of a star hold at most "
+                                              f"{OWN_STAR_MAX_K} each")
+            for d in deps:
+                if (cname, d) not in self.latent_dom:
+                    raise NotImplementedError(f"{cname}.{d}: the options of a star's dependent are not strings")
+                self.indexed[(cname, d)] = ("star", ix)
+            del self.product_index[(cname, ix)]
 
     def keyed_index(self, cname, aname):
         """attribute whose (directly observed) value selects the options of choice aname: StringPrior / TimePrior atoms
@@ -605,7 +642,7 @@ class LoweredModel:
             have = merged.setdefault(k, [])
             have.extend(x for x in dict.fromkeys(v) if x not in have)
         dirty = self._dirty_columns
-        self.__init__(self.model, self.query, dirty, None, merged)
+        self.__init__(self.model, self.query, dirty, None, merged, own_star=self.own_star_enabled)
         self.encode_observations(dirty)
 
     def encode_observations(self, dirty_columns):
@@ -680,7 +717,7 @@ class LoweredModel:
                     # column 2: number of atoms of the option's key group (MaybeSwap's length(options))
                     nk = {kdom.get(k): len(atoms) for k, atoms in d.atoms.items()}
                     self.option_ncol[(cname, aname)] = np.array([nk[k] for k in keys], dtype=np.int32)
-                elif self.indexed.get((cname, aname), ("", ""))[0] == "product":
+                elif self.indexed.get((cname, aname), ("", ""))[0] in ("product", "star"):
                     # option a * |B| + b; two value columns: the index's value, the choice's value
                     na, nb = len(self.latent_dom[(cname, self.indexed[(cname, aname)][1])]), len(d.options)
                     self.option_cols[(cname, aname)] = np.stack([np.repeat(np.arange(na, dtype=np.int32), nb),
@@ -792,6 +829,7 @@ class LoweredModel:
         # of the particles inside the sweep.
         self.own_leaf = {}   # own choice of the observed class -> (block, node) of its leaf
         self.own_product = {}  # own choice indexed by a sibling own choice -> that index: the two share ONE product leaf
+        self.own_star = {}   # (block, head node) of a star -> [its arm nodes] (own_star=True: _lower_own_star)
         self.own_gauss = {}  # (block, node) of a Gaussian leaf -> dict(table, factors, sizes, cols, specs): _lower_own_gauss
         own_blocks = [bi for bi, names in enumerate(eblocks) if root_of_block[bi] is None and any(
             ocls.attr(n).kind == "choice" and not isinstance(ocls.attr(n).dist, MaybeSwap) for n in names)]
@@ -1107,7 +1145,7 @@ class LoweredModel:
                 raise NotImplementedError(f"{who}: a {type(d).__name__} own choice is not lowered (its proposal holds a dummy value "
                                           "or none at all); own choices are ChooseProportionally or ChooseUniformly")
             elif isinstance(d, ChooseProportionally):
-                if d.index is not None and self.indexed.get((cls, n), ("", ""))[0] != "product":  # (_resolve_indexed refuses it first)
+                if d.index is not None and self.indexed.get((cls, n), ("", ""))[0] not in ("product", "star"):  # (_resolve_indexed refuses it first)
                     raise NotImplementedError(f"{who}: an indexed choice among the observed class's own choices is not lowered")
                 choices.append(a)
             elif isinstance(d, ChooseUniformly):
@@ -1168,6 +1206,11 @@ class LoweredModel:
                 continue
             if key in self.product_index:
                 continue  # enumerated jointly with its dependent: value column 0 of that leaf
+            if self.indexed.get(key, ("", ""))[0] == "star":
+                continue  # an arm of its index's star: lowered right after the head
+            if key in self.star_index:
+                self._lower_own_star(bi, blk, ocls, c, emit_terms)
+                continue
             tb = len(blk["terms"])
             index = self.indexed.get(key, ("", ""))
             index = index[1] if index[0] == "product" else None
@@ -1192,6 +1235,35 @@ class LoweredModel:
             raise NotImplementedError(f"{cls}: a block without a reference slot and without an own choice "
                                       f"({', '.join(names)}) is not lowered")
         return blk
+
+    def _lower_own_star(self, bi, blk, ocls, c, emit_terms):
+        """The star of index c: 1 + D consecutive NODE_LEAF nodes at the index's place.  The HEAD on the index's own option
+        table with the index's terms (value column 0); then arm j on dependent j's two-column table a * K_j + b (option_cols,
+        key-major) with the dependent's terms on value column 1 — the arm's prior is log theta_j[a][b] alone (engine.py,
+        option_prior), log p(a) belongs to the head.  own_leaf maps every choice to its own node and
+        own_star[(block, head node)] lists the arm nodes; Trace.own keeps one row per choice holding its own option index."""
+        cls = self.query.cls
+        deps = self.star_index[(cls, c.name)]
+        head = len(blk["nodes"])
+        t0 = len(blk["terms"])
+        per_node = []
+        for n, col in [(c.name, 0)] + [(d, 1) for d in deps]:
+            tb = len(blk["terms"])
+            emit_terms(ocls.attr(n), col)
+            per_node.append(len(blk["terms"]) - tb)
+            self.own_leaf[n] = (bi, len(blk["nodes"]))
+            blk["nodes"].append((_lib.NODE_LEAF, self.option_id[(cls, n)], tb, per_node[-1], 0, 0, -1, -1, 0, 0, 0, 0))
+            blk["node_info"].append(dict(kind="leaf", cls=cls, attr=n, path=n, star=(c.name, tuple(deps))))
+        if len(blk["terms"]) - t0 > _lib.MAX_TERMS:
+            raise NotImplementedError(f"{cls}.{c.name}: the star with {', '.join(deps)} carries more than {_lib.MAX_TERMS} terms "
+                                      "(PCLEAN_MAX_TERMS)")
+        ka = len(c.dist.options)
+        ks = [len(ocls.attr(d).dist.options) for d in deps]
+        lds = 8 * (per_node[0] * ka + sum(t * k for t, k in zip(per_node[1:], ks)) + ka + (ka + 63) // 64)
+        if lds > OWN_STAR_LDS_MAX:
+            raise NotImplementedError(f"{cls}.{c.name}: the star with {', '.join(deps)} caches {lds} bytes of term values, more "
+                                      f"than the {OWN_STAR_LDS_MAX} of a workgroup's LDS (no second kernel variant)")
+        self.own_star[(bi, head)] = [head + 1 + j for j in range(len(deps))]
 
     def _own_gauss_factors(self, bi, ocls, names, choices, gauss_obs, gauss_units):
         """(factors, lookups) of the Gaussian observations of own block bi.  The factors are the choices of the block that
@@ -1257,7 +1329,7 @@ class LoweredModel:
                 raise NotImplementedError(f"{cls}.{u}: a directly observed unit choice is not lowered")
         for f in strings:
             d = by_name[f].dist
-            if (isinstance(d, ChooseProportionally) and d.index is not None) or (cls, f) in self.product_index:
+            if (isinstance(d, ChooseProportionally) and d.index is not None) or (cls, f) in self.product_index or (cls, f) in self.star_index:
                 raise NotImplementedError(f"{cls}.{f}: a factor of a Gaussian observation that is itself indexed, or that indexes "
                                           "a sibling choice, is not lowered (no product leaf inside a Gaussian leaf)")
         factors = [c.name for c in choices if c.name in strings or c.name in gauss_units]

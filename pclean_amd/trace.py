@@ -244,9 +244,36 @@ class Trace:
 
     @own.setter
     def own(self, value):
+        value = np.ascontiguousarray(value, dtype=np.int32)
+        names = self.own_leaves()
+        for head, arms in self.own_stars().items():  # the choices of a star are drawn together: all set on a row, or none
+            rows = [head] + arms
+            unset = value[rows] < 0
+            part = unset.any(axis=0) & ~unset.all(axis=0)
+            if part.any():
+                i = int(np.flatnonzero(part)[0])
+                raise ValueError(f"row {i}: only some of the own choices {', '.join(names[r][0] for r in rows)} of one star are "
+                                 f"set ({', '.join(names[r][0] for r in rows if value[r, i] >= 0)}); they are enumerated together")
         self._own_dev = None
         self._own_version += 1
-        self._own = np.ascontiguousarray(value, dtype=np.int32)
+        self._own = value
+
+    def own_stars(self):
+        """{row of `own` of a star's index: [rows of its dependents, in arm order]} (LoweredModel.own_star): every choice of a
+        star is a row of its own here and a node of its own on the device, each holding its own option index"""
+        at = {(b, n): li for li, (_, b, n) in enumerate(self.own_leaves())}
+        return {at[(b, h)]: [at[(b, n)] for n in arms] for (b, h), arms in getattr(self.lw, "own_star", {}).items()}
+
+    def own_star_counts(self, li, head):
+        """[index][choice] histogram of a star's arm (row li of `own`, its head's row): IndexedProportionsState.counts — from
+        the device while it is ahead (pclean_own_counts on the arm's node), else the same integers from the host arrays"""
+        ka, kb = self._own_sizes((head, li))
+        dev = getattr(self, "_own_dev", None)
+        if dev is not None:
+            _, b, n = self.own_leaves()[li]
+            return dev.hip.own_counts(b, n, ka * kb).reshape(ka, kb)
+        v = self.own_joint(self._own, head, li)
+        return np.bincount(v[v >= 0], minlength=ka * kb).astype(np.int64).reshape(ka, kb)
 
     def _own_params(self):
         """[(row of `own`, parameter state)] of the own ChooseProportionally choices"""
@@ -363,6 +390,9 @@ class Trace:
         """histogram of row li of `own` over the choice's options: from the device while it is ahead (pclean_own_counts:
         nothing per row crosses PCIe), else from the host array.  An indexed choice: [index][option], the joint histogram
         of its product leaf; its index: the row sums of that."""
+        for head, arms in self.own_stars().items():
+            if li in arms:  # (an arm of a star: the joint histogram with its head)
+                return self.own_star_counts(li, head)
         pairs = self.own_pairs()
         if li in pairs and li in self._own_gauss_rows():  # (the second factor of a Gaussian leaf: the column sums)
             return self.own_joint_counts(li).sum(axis=0)
@@ -772,7 +802,8 @@ class Trace:
             assert np.all((own >= 0).all(axis=0) | (own < 0).all(axis=0)), "own choices: a row holds some but not all"
             for li, (a, _, _) in enumerate(self.own_leaves()):
                 assert own[li].max(initial=-1) < self._own_sizes((li,))[0], f"{a}: a value beyond the options"
-            pairs = self.own_pairs()
+            pairs = dict(self.own_pairs())
+            pairs.update({arm: head for head, arms in self.own_stars().items() for arm in arms})  # (a star's arm: with its head)
             for li, state in self._own_params():
                 # (an indexed choice: [index][option]; a factor of a Gaussian leaf has a plain parameter: its own histogram)
                 v = self.own_joint(own, pairs[li], li) if li in pairs and state.counts.ndim == 2 else own[li]

@@ -32,7 +32,13 @@ string-only sweep of the same rows and string factor with the Gaussian terms lef
 nearest thing the parent computes); the ratio is stated, not asserted.  --processes N (default 3) fresh processes; the
 lines go into --out (default profiles/own_gauss_bench.json).
 
+--star: City with State and CountyName as its dependents (a star: own_star_kernel), one process; --star --alternate N: N
+rounds of fresh processes — the star, the star with PCLEAN_NO_OWN_SKIP=1, and the two one-dependent programs City x State and
+City x CountyName through own_product_kernel, whose device times summed are the nearest computation without the star — into
+profiles/own_star_bench.json.
+
 usage: own_block_bench.py [--rows N] [--runs R] [--particles P] [--marginals [--out FILE]] [--product [--alternate N] [--out FILE]]
+                          [--star [--alternate N] [--out FILE]]
                           [--gauss [--processes N] [--out FILE]]"""
 import json
 import os
@@ -231,6 +237,112 @@ def product_main():
                                           "product_without_skip_median_ms", "same_values")}))
 
 
+# ---- --star: City with State and CountyName as its dependents --------------------------------------------------------------
+def star_data(n):
+    """City, State and CountyName of the synthetic generator (both determined by the city).  The stated rule: the most
+    frequent cities such that K_a <= 4096 and K_a x max(K_state, K_county) <= OWN_MAX_OPTIONS, their rows alone."""
+    dirty, clean, _ = synth_hospital(n_rows=n, n_hosp=max(n // 100, 10))
+    cols = ("City", "State", "CountyName")
+    freq = {}
+    for c in clean["City"]:
+        freq[c] = freq.get(c, 0) + 1
+    order = sorted(freq, key=lambda c: -freq[c])
+    county_of = dict(zip(clean["City"], clean["CountyName"]))
+    n_states = len(set(clean["State"]))
+    keep = min(len(order), 4096)
+    while keep * max(n_states, len({county_of[c] for c in order[:keep]})) > OWN_MAX_OPTIONS:
+        keep -= 1
+    kept = set(order[:keep])
+    rows = [i for i, c in enumerate(clean["City"]) if c in kept]
+    dirty = {k: [dirty[k][i] for i in rows] for k in cols}
+    clean = {k: [clean[k][i] for i in rows] for k in cols}
+    return dict(dirty=dirty, clean=clean, vocab={k: list(dict.fromkeys(clean[k])) for k in cols}, dropped_cities=len(order) - keep)
+
+
+def star_run(D, runs, P, what):
+    """one process: the JSON line of --star.  what: "star" (both dependents, own_star=True) or the name of ONE dependent (the
+    one-dependent program through own_product_kernel: the nearest computation without the star)"""
+    from pclean_amd import experiments as ex
+    deps = ("State", "CountyName") if what == "star" else (what,)
+    cols = ("City",) + deps
+    dirty = {k: D["dirty"][k] for k in cols}
+    vocab = {k: D["vocab"][k] for k in cols}
+    n = len(dirty["City"])
+    m = ex.flat_model(vocab, star=("City", deps)) if what == "star" else ex.flat_model(vocab, dependent=("City", what))
+    lw = LoweredModel(m, ex.flat_query(m, cols), dirty, own_star=what == "star")
+    eng = Engine(lw, lw.encode_observations(dirty))
+    try:
+        tr = Trace.from_clean_values(lw, {0: {k: D["clean"][k] for k in cols}}, n)
+        tr.resample_parameters()
+        eng.upload_trace(tr)
+        eng._push_own(tr)
+        hip, c = eng.hip, InferenceConfig(1, P).as_c()
+        hip.set_active_rows(0, n)
+        dev_ms = []
+        for r in range(runs + 2):
+            hip.sweep_own(c, 1, r, n)
+            dev_ms.append(float(hip.get_timing().total_ms))
+        st = hip.get_own_stats()
+        vals = hip.get_own(0, len(cols) if what == "star" else 1, n)
+        assert vals.min() >= 0
+    finally:
+        eng.close()
+    mix = np.zeros(n, dtype=np.int64)
+    for v in vals:
+        mix = mix * 1000003 + v
+    return dict(rows=n, what=what, sizes=[len(vocab[k]) for k in cols], dropped_cities=D["dropped_cities"], particles=P, warmups=2,
+                runs=runs, no_skip=bool(os.environ.get("PCLEAN_NO_OWN_SKIP")), variants=int(st.variants), distinct_tuples=int(st.n_runs),
+                longest_run=int(st.longest_run), workgroups=int(st.n_workgroups), star_weighed=int(st.star_weighed),
+                star_skipped=int(st.star_skipped), sweep_own_device_ms=_summary(dev_ms[2:]),
+                checksum=int(np.bitwise_xor.reduce(mix * (np.arange(n) + 1))))
+
+
+def star_main():
+    import pickle
+    import subprocess
+    import tempfile
+    a = sys.argv[1:]
+    n, runs, P = _arg("--rows", 1_000_000), _arg("--runs", 7), _arg("--particles", 20)
+    if "--data" in a:  # a child of --alternate
+        with open(a[a.index("--data") + 1], "rb") as f:
+            D = pickle.load(f)
+        print(json.dumps(star_run(D, runs, P, a[a.index("--what") + 1])))
+        return
+    D = star_data(n)
+    rounds = _arg("--alternate", 0)
+    if not rounds:
+        print(json.dumps(star_run(D, runs, P, "star")))
+        return
+    lines = {"star": [], "star_no_skip": [], "State": [], "CountyName": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "data.pkl")
+        with open(path, "wb") as f:
+            pickle.dump(D, f)
+        for k in range(rounds):
+            for name in lines:
+                env = dict(os.environ)
+                env.pop("PCLEAN_NO_OWN_PRODUCT", None)
+                env.pop("PCLEAN_NO_OWN_SKIP", None)
+                if name == "star_no_skip":
+                    env["PCLEAN_NO_OWN_SKIP"] = "1"
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--star", "--data", path, "--what",
+                                    "star" if name.startswith("star") else name, "--runs", str(runs), "--particles", str(P)], env=env,
+                                   stdout=subprocess.PIPE, text=True, timeout=900, check=True)
+                lines[name].append(json.loads(r.stdout.strip().splitlines()[-1]))
+                print(f"[{name} {k}] {lines[name][-1]['sweep_own_device_ms']}", flush=True)
+    med = {name: float(np.median([x["sweep_own_device_ms"]["median"] for x in v])) for name, v in lines.items()}
+    pairs = med["State"] + med["CountyName"]
+    out = dict(star_median_ms=round(med["star"], 3), star_without_skip_median_ms=round(med["star_no_skip"], 3),
+               two_pairs_summed_median_ms=round(pairs, 3), star_within_1_1_of_the_pairs=bool(med["star"] <= 1.1 * pairs),
+               same_values_with_and_without_skip=len({x["checksum"] for k in ("star", "star_no_skip") for x in lines[k]}) == 1, **lines)
+    dst = a[a.index("--out") + 1] if "--out" in a else os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "own_star_bench.json")
+    with open(dst, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: v for k, v in out.items() if k not in lines}))
+
+
 GAUSS_SHAPES = ((5, 2), (1000, 4))
 
 
@@ -423,4 +535,4 @@ if __name__ == "__main__":
     if "--gauss" in sys.argv[1:]:
         gauss_main()
     else:
-        product_main() if "--product" in sys.argv[1:] else main()
+        star_main() if "--star" in sys.argv[1:] else product_main() if "--product" in sys.argv[1:] else main()

@@ -11,12 +11,17 @@ accuracy and F1 of its most probable value next to the last sample's, and with t
 the accuracy of the two models side by side — of the last sample and, with the joint MAP repair (Engine.own_marginals:
 for the pair these are JOINT probabilities), per column.
 
+--star: City with State AND CountyName as its dependents (experiments.flat_model(star=("City", ("State", "CountyName"))),
+lowered with own_star=True: a head node and two arm nodes, enumerated collapsed by own_star_kernel) next to the independent
+model over the same four columns: accuracy of the last sample and of the MAP repair (the index's exact marginal; a
+dependent's most probable value GIVEN the index's most probable value).  Reported, not asserted.
+
 --numeric: another table — Room Type and Monthly Rent of datasets/rents_*.csv as ONE own block with a Gaussian observation
 (experiments.flat_numeric_model: the rent's mean depends on the room type, some rents are stated in thousands): no latent
 class.  Prints the accuracy and F1 of the last sample and of the MAP repair (the numeric cell under the MAP unit); the
 figures are reported, not asserted.
 
-usage: run_flat.py [particles] [pg|mh] [iterations] [rows] [--map] [--dependent] [--numeric]"""
+usage: run_flat.py [particles] [pg|mh] [iterations] [rows] [--map] [--dependent] [--star] [--numeric]"""
 import os
 import sys
 import time
@@ -33,14 +38,14 @@ from pclean_amd.model import LoweredModel
 from pclean_amd.trace import Trace
 
 
-def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, with_map=False, dependent=None):
+def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, with_map=False, dependent=None, star=None,
+         cols=ex.FLAT_COLUMNS):
     dirty, clean = ex.hospital_data()
-    cols = ex.FLAT_COLUMNS
     n = len(dirty[cols[0]]) if n_rows is None else int(n_rows)
     dirty = {c: dirty[c][:n] for c in cols}
     clean = {c: clean[c][:n] for c in cols}
-    m = ex.flat_model(ex.flat_vocabulary(clean), dependent=dependent)
-    lw = LoweredModel(m, ex.flat_query(m), dirty)
+    m = ex.flat_model(ex.flat_vocabulary(clean, cols), dependent=dependent, star=star)
+    lw = LoweredModel(m, ex.flat_query(m, cols), dirty, own_star=star is not None)
     eng = Engine(lw, lw.encode_observations(dirty))
     try:
         tr = Trace(lw, n, seed)
@@ -52,12 +57,12 @@ def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, wit
         t2 = time.time()
         tr.check_consistency()
         acc = evaluate_accuracy(lw, tr, dirty, clean)
-        acc["accuracy"] = ex.cell_accuracy(reconstructed_table(lw, tr, dirty), clean)
+        acc["accuracy"] = ex.cell_accuracy(reconstructed_table(lw, tr, dirty), clean, cols)
         if verbose:
             st = eng.hip.get_own_stats()
             print(f"{n} rows, {iters} iterations, {particles} particles ({'MH' if mh else 'PG'}): init {t1 - t0:.2f}s, "
                   f"inference {t2 - t1:.2f}s; last window: {st.n_runs} tuple runs, longest {st.longest_run} rows")
-            print(f"accuracy {acc['accuracy']:.4f} (dirty: {ex.cell_accuracy(dirty, clean):.4f})  F1 {acc['f1']:.4f}")
+            print(f"accuracy {acc['accuracy']:.4f} (dirty: {ex.cell_accuracy(dirty, clean, cols):.4f})  F1 {acc['f1']:.4f}")
             print(acc)
         if with_map:
             marg = eng.own_marginals(tr, top=1)
@@ -65,7 +70,7 @@ def main(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True, wit
             for thr in (0.0, 0.5, 0.9):
                 table, conf = map_table(lw, marg, dirty, min_confidence=thr)
                 a = evaluate_map_accuracy(lw, marg, dirty, clean, min_confidence=thr)
-                a["accuracy"] = ex.cell_accuracy(table, clean)
+                a["accuracy"] = ex.cell_accuracy(table, clean, cols)
                 a["by_column"] = {c: ex.cell_accuracy(table, clean, (c,)) for c in cols}
                 present = {c: np.array([v is not None for v in dirty[c]]) for c in cols}
                 a["left_dirty"] = sum(int(((conf[c] < thr) & present[c]).sum()) for c in cols) / float(n * len(cols))
@@ -123,26 +128,33 @@ def numeric(particles=20, mh=False, iters=5, n_rows=None, seed=0, verbose=True):
         eng.close()
 
 
-def compare(**kw):
-    """the independent model and the one with State indexed by City, side by side"""
+def compare(star=False, **kw):
+    """the independent model and the one with State indexed by City, side by side; star: over City, State, CountyName and
+    Condition, the independent model, State | City alone, and the star State, CountyName | City"""
     out = {}
-    for name, dep in (("independent", None), ("State | City", ("City", "State"))):
+    cols = ex.FLAT_STAR_COLUMNS if star else ex.FLAT_COLUMNS
+    runs = [("independent", {}), ("State | City", dict(dependent=("City", "State")))]
+    if star:
+        runs.append(("State, County | City", dict(star=ex.FLAT_STAR)))
+    for name, how in runs:
         print(f"---- {name}")
-        out[name] = main(with_map=True, dependent=dep, **kw)
-    print(f"{'model':<14} {'sample acc':>10} {'MAP acc':>8} {'MAP F1':>7}  " + "  ".join(f"{c:>9}" for c in ex.FLAT_COLUMNS))
+        out[name] = main(with_map=True, cols=cols, **how, **kw)
+    print(f"{'model':<22} {'sample acc':>10} {'MAP acc':>8} {'MAP F1':>7}  " + "  ".join(f"{c:>10}" for c in cols))
     for name, a in out.items():
         m0 = a["map"][0.0]
-        print(f"{name:<14} {a['accuracy']:>10.4f} {m0['accuracy']:>8.4f} {m0['f1']:>7.4f}  " +
-              "  ".join(f"{m0['by_column'][c]:>9.4f}" for c in ex.FLAT_COLUMNS))
+        print(f"{name:<22} {a['accuracy']:>10.4f} {m0['accuracy']:>8.4f} {m0['f1']:>7.4f}  " +
+              "  ".join(f"{m0['by_column'][c]:>10.4f}" for c in cols))
     return out
 
 
 if __name__ == "__main__":
-    a = [x for x in sys.argv[1:] if x not in ("--map", "--dependent", "--numeric")]
+    a = [x for x in sys.argv[1:] if x not in ("--map", "--dependent", "--numeric", "--star")]
     kw = dict(particles=int(a[0]) if a else 20, mh=(a[1] == "mh") if len(a) > 1 else False, iters=int(a[2]) if len(a) > 2 else 5,
               n_rows=int(a[3]) if len(a) > 3 else None)
     if "--numeric" in sys.argv[1:]:
         numeric(**kw)
+    elif "--star" in sys.argv[1:]:
+        compare(star=True, **kw)
     elif "--dependent" in sys.argv[1:]:
         compare(**kw)
     else:
