@@ -327,6 +327,19 @@ class HipContext:
         check(self.h, self.lib.pclean_debug_root_launches(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_root_launches")
         return dict(zip(self.ROOT_LAUNCH_SLOTS, out.tolist()))
 
+    DIST_LAUNCH_SLOTS = (tuple(f"osa_bitpar_{w}_s{s}_o{o}" for o in (8, 16) for s in (8, 16) for w in (1, 2, 3, 4))
+                         + ("osa_tile_o8", "osa_tile_o16")
+                         + tuple(f"dl_seg_{n}_s{s}" for s in (8, 16) for n in (1, 2, 4, 8))
+                         + ("dl_wave_16_1", "dl_wave_32_1", "dl_wave_64_1", "dl_wave_64_2", "dl_wave_64_3", "dl_wave_64_4",
+                            "dl_lds", "dl_pair_o8", "dl_pair_o16"))
+
+    def dist_launches(self, reset=False):
+        """which kernel instantiation built the pair tables since the last reset, by DIST_LAUNCH_SLOTS name (counted on
+        the host, one per launch)"""
+        out = np.zeros(len(self.DIST_LAUNCH_SLOTS), dtype=np.int64)
+        check(self.h, self.lib.pclean_debug_dist_launches(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_dist_launches")
+        return dict(zip(self.DIST_LAUNCH_SLOTS, out.tolist()))
+
     def set_table(self, table_id, cols, counts, strength, discount, n_cols=None):
         """cols None (with n_cols given) keeps the columns uploaded before and refreshes the counts only."""
         counts = np.ascontiguousarray(counts, dtype=np.int64)

@@ -308,6 +308,11 @@ struct pclean_ctx {
   // host.  [0..5) fk_root_wave_kernel<2|4|8|12|16>, 5 group_settle_kernel, 6 worklist_pack_kernel, 7 a scan launch that was
   // given the lazy-draw lists, 8 overflow_lds_kernel, 9 resolved_draws_kernel
   int64_t root_launches[PCLEAN_ROOT_LAUNCH_SLOTS] = {};
+  // debug (pclean_debug_dist_launches): the table-building kernel pclean_launch_dist / launch_dl_seg launched, counted on the
+  // host.  [0..16) osa_bitpar_kernel: 8 * (OutT 16-bit) + 4 * (SymT 16-bit) + W - 1; [16..18) osa_tile_kernel<u8 | u16>;
+  // [18..26) dl_seg_kernel: 18 + 4 * (SymT 16-bit) + log2(NSEG); [26..32) dl_wave_kernel<16,1 | 32,1 | 64,1..4>; 32
+  // dl_lds_kernel; [33..35) dl_pair_kernel<u8 | u16>
+  int64_t dist_launches[PCLEAN_DIST_LAUNCH_SLOTS] = {};
   void* sweep_state = nullptr;  // owned by sweep.hip
   void* rccl_comm = nullptr;    // ncclComm_t of pclean_comm_init (comm.hip)
   void* recon_state = nullptr;  // owned by recon.hip

@@ -580,9 +580,11 @@ static int launch_dl_seg(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_id
                                           (int)lds);                                                                     \
       if (ea != hipSuccess) rc = pclean_fail(ctx, PCLEAN_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(ea));       \
     }                                                                                                                    \
-    if (!rc)                                                                                                             \
+    if (!rc) {                                                                                                           \
+      ++ctx->dist_launches[18 + 4 * (sizeof(ST) == 2) + (NS == 1 ? 0 : NS == 2 ? 1 : NS == 4 ? 2 : 3)];                  \
       hipLaunchKernelGGL((dl_seg_kernel<NS, ST>), grid, dim3(256), lds, ctx->stream, ctx->sym.p, ctx->off.p, d_obs_ids,  \
                          d_sorted.p + p, pt.n_obs, n_cls, p, n_lat, segcap, max_la, u_chunk, tmp.p);                     \
+    }                                                                                                                    \
   } while (0)
 #define LAUNCH_DLS_N(ST)      \
   do {                        \
@@ -640,6 +642,7 @@ int pclean_launch_dist(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids,
   do {                                                                                                                 \
     HIPCHK(ctx, hipFuncSetAttribute((const void*)osa_bitpar_kernel<WW, ST, OT>,                                        \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
+    ++ctx->dist_launches[8 * (sizeof(OT) == 2) + 4 * (sizeof(ST) == 2) + WW - 1];                                      \
     hipLaunchKernelGGL((osa_bitpar_kernel<WW, ST, OT>), grid, dim3(256), lds, ctx->stream, ctx->sym.p, ctx->off.p,     \
                        d_obs_ids, d_lat_ids, pt.n_obs, pt.n_lat, max_lb, ctx->n_symbols, u_chunk, (OT*)pt.d.p);        \
   } while (0)
@@ -695,6 +698,7 @@ int pclean_launch_dist(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids,
   do {                                                                                                                 \
     HIPCHK(ctx, hipFuncSetAttribute((const void*)dl_wave_kernel<WGv, Cv>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
                                     (int)lds));                                                                        \
+    ++ctx->dist_launches[26 + (WGv == 16 ? 0 : WGv == 32 ? 1 : 1 + Cv)];                                               \
     hipLaunchKernelGGL((dl_wave_kernel<WGv, Cv>), grid, dim3(64 * n_waves), lds, ctx->stream, ctx->sym.p, ctx->off.p,  \
                        d_obs_ids, d_lat_ids, pt.n_obs, pt.n_lat, max_la, max_lb, u_chunk, (uint8_t*)pt.d.p);           \
   } while (0)
@@ -724,6 +728,7 @@ int pclean_launch_dist(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids,
       dim3 grid((pt.n_lat + 63) / 64, (pt.n_obs + u_chunk - 1) / u_chunk);
       HIPCHK(ctx, hipFuncSetAttribute((const void*)dl_lds_kernel<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds));
+      ++ctx->dist_launches[32];
       hipLaunchKernelGGL(dl_lds_kernel<uint8_t>, grid, dim3(64), lds, ctx->stream, ctx->sym.p, ctx->off.p, d_obs_ids,
                          d_lat_ids, pt.n_obs, pt.n_lat, max_la, max_lb, ctx->n_symbols, u_chunk, (uint8_t*)pt.d.p);
       HIPCHK(ctx, hipGetLastError());
@@ -743,11 +748,13 @@ int pclean_launch_dist(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids,
     if (pt.elem_bytes == 1) {
       HIPCHK(ctx, hipFuncSetAttribute((const void*)osa_tile_kernel<uint8_t>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ++ctx->dist_launches[16];
       hipLaunchKernelGGL(osa_tile_kernel<uint8_t>, grid, dim3(T), lds, ctx->stream, ctx->sym.p, ctx->off.p,
                          d_obs_ids, d_lat_ids, pt.n_lat, max_lb, (uint8_t*)pt.d.p);
     } else {
       HIPCHK(ctx, hipFuncSetAttribute((const void*)osa_tile_kernel<uint16_t>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ++ctx->dist_launches[17];
       hipLaunchKernelGGL(osa_tile_kernel<uint16_t>, grid, dim3(T), lds, ctx->stream, ctx->sym.p, ctx->off.p,
                          d_obs_ids, d_lat_ids, pt.n_lat, max_lb, (uint16_t*)pt.d.p);
     }
@@ -761,6 +768,7 @@ int pclean_launch_dist(pclean_ctx* ctx, PairTable& pt, const int32_t* d_obs_ids,
     DevBuf<uint16_t> scratch;
     if (scratch.alloc(per_thread * (size_t)blocks * threads))
       return pclean_fail(ctx, PCLEAN_ERR_HIP, "scratch alloc failed for DL kernel");
+    ++ctx->dist_launches[pt.elem_bytes == 1 ? 33 : 34];
     if (pt.elem_bytes == 1)
       hipLaunchKernelGGL(dl_pair_kernel<uint8_t>, dim3(blocks), dim3(threads), 0, ctx->stream, ctx->sym.p,
                          ctx->off.p, d_obs_ids, d_lat_ids, pt.n_obs, pt.n_lat, max_la, max_lb,

@@ -1450,6 +1450,13 @@ extern "C" int pclean_debug_root_launches(pclean_ctx* ctx, int64_t* out, int32_t
   return PCLEAN_OK;
 }
 
+extern "C" int pclean_debug_dist_launches(pclean_ctx* ctx, int64_t* out, int32_t reset) {
+  if (!ctx) return PCLEAN_ERR_ARG;
+  if (out) memcpy(out, ctx->dist_launches, sizeof(ctx->dist_launches));
+  if (reset) memset(ctx->dist_launches, 0, sizeof(ctx->dist_launches));
+  return PCLEAN_OK;
+}
+
 extern "C" int pclean_set_row_offset(pclean_ctx* ctx, int64_t row_offset) {
   if (!ctx || row_offset < 0) return pclean_fail(ctx, PCLEAN_ERR_ARG, "bad row offset");
   st(ctx)->row_offset = row_offset;

@@ -24,6 +24,29 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/pclean_hip.h but not exported"
 
 
+def test_launch_counters_are_declared_exported_and_named_slot_for_slot():
+    """The three launch counters of the debug interface: each is declared with its slot count in the header, exported by
+    the library, and bound in pclean_amd._lib with exactly one distinct name per slot."""
+    from pclean_amd import _lib, build
+    build.build(verbose=False)
+    lib = ctypes.CDLL(build.LIB)
+    src = open(os.path.join(ROOT, "include", "pclean_hip.h")).read()
+    for kind in ("enum", "root", "dist"):
+        m = re.search(rf"#define PCLEAN_{kind.upper()}_LAUNCH_SLOTS (\d+)", src)
+        assert m, kind
+        assert re.search(rf"int pclean_debug_{kind}_launches\(pclean_ctx\* ctx, int64_t\* out, int32_t reset\);", src), kind
+        assert hasattr(lib, f"pclean_debug_{kind}_launches"), kind
+        names = getattr(_lib.HipContext, f"{kind.upper()}_LAUNCH_SLOTS")
+        assert len(names) == len(set(names)) == int(m.group(1)), kind
+        assert callable(getattr(_lib.HipContext, f"{kind}_launches"))
+        # a NULL context is refused, not dereferenced
+        assert getattr(lib, f"pclean_debug_{kind}_launches")(None, None, 0) != 0
+    # the table builders: 16 + 2 + 8 + 6 + 1 + 2 instantiations
+    d = _lib.HipContext.DIST_LAUNCH_SLOTS
+    assert [sum(n.startswith(p) for n in d) for p in ("osa_bitpar", "osa_tile", "dl_seg", "dl_wave", "dl_lds", "dl_pair")] == \
+        [16, 2, 8, 6, 1, 2]
+
+
 def test_no_cpu_fallback():
     import torch
     from pclean_amd import HipContext, PCleanHipError

@@ -108,7 +108,9 @@ def test_detmath_and_philox_bit_exact_on_device(hip, oracle):
 
 def test_pair_table_long_patterns_and_dl_random(hip, oracle):
     """Multi-word bit-parallel OSA (observed strings of 65..250 symbols incl. transpositions across the 64-bit
-    word boundaries) and the LDS-matrix unrestricted DL kernel on random short strings, against the oracle's DP."""
+    word boundaries) and unrestricted DL on the same strings and on random short ones, against the oracle's DP.  The
+    unrestricted tables here are built by dl_seg_kernel, the default since it replaced dl_wave_kernel (strings of at most
+    254 symbols); tests/test_gpu_dist_variants.py runs every instantiation of both kernels and asserts which one ran."""
     rnd = np.random.default_rng(11)
     alpha = list("abcdefgh ")
     long_words = []
@@ -127,11 +129,12 @@ def test_pair_table_long_patterns_and_dl_random(hip, oracle):
     ids = np.unique(ids)
     hip.build_pair_table(31, ids, ids, 0)
     assert np.array_equal(hip.get_pair_table(31, len(ids), len(ids)), oracle.pair_table(sym, off, ids, ids, 0))
-    # the same long strings through the unrestricted-DL kernel (dl_wave_kernel: 64 lanes per pair, up to 4 column chunks
-    # per lane; the 9-letter alphabet makes gapped transpositions common)
+    # the same long strings through the unrestricted-DL default (dl_seg_kernel: every length class at once, up to 8 lanes
+    # per pair; the 9-letter alphabet makes gapped transpositions common)
     hip.build_pair_table(31, ids, ids, 1)
     assert np.array_equal(hip.get_pair_table(31, len(ids), len(ids)), oracle.pair_table(sym, off, ids, ids, 1))
-    # every lane-group shape of that kernel: strings of at most 16 / 32 / 64 / 128 / 192 symbols, empty strings included
+    # tables whose longest string is 16 / 32 / 33 / 64 / 100 / 160 symbols, empty strings included: dl_seg_kernel with one to
+    # eight lanes per pair (these sizes were the lane-group shapes of dl_wave_kernel when it was the default)
     for top in (16, 32, 33, 64, 100, 160):
         words = ["".join(rnd.choice(list("abcx"), size=int(rnd.integers(0, top + 1)))) for _ in range(90)] + ["", "a" * top]
         pool2, ids2 = _pool(words)
