@@ -340,6 +340,16 @@ class HipContext:
         check(self.h, self.lib.pclean_debug_dist_launches(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_dist_launches")
         return dict(zip(self.DIST_LAUNCH_SLOTS, out.tolist()))
 
+    MEMO_STAT_SLOTS = ("calls", "lookups", "misses", "resets", "stored")
+
+    def memo_stats(self, reset=False):
+        """the memo of option-list marginals since the last reset, by MEMO_STAT_SLOTS name: evaluations on the memo path,
+        items looked up, items missed, wipes after a version change; "stored" = entries held right now (read from the
+        device, never reset)"""
+        out = np.zeros(len(self.MEMO_STAT_SLOTS), dtype=np.int64)
+        check(self.h, self.lib.pclean_debug_memo_stats(self.h, _p(out, C.c_int64), C.c_int32(int(reset))), "pclean_debug_memo_stats")
+        return dict(zip(self.MEMO_STAT_SLOTS, out.tolist()))
+
     def set_table(self, table_id, cols, counts, strength, discount, n_cols=None):
         """cols None (with n_cols given) keeps the columns uploaded before and refreshes the counts only."""
         counts = np.ascontiguousarray(counts, dtype=np.int64)

@@ -1069,6 +1069,7 @@ extern "C" int pclean_set_fn_table(pclean_ctx* ctx, int32_t fn_id, int32_t n_a, 
   f.n_a = n_a;
   f.n_b = n_b;
   f.valid = true;
+  f.version = ++g_pclean_version;
   return PCLEAN_OK;
 }
 

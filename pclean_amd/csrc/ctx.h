@@ -156,6 +156,7 @@ struct FnTable {
   bool valid = false;
   int32_t n_a = 0, n_b = 0;
   DevBuf<int32_t> fn;
+  uint64_t version = 0;  // bumped by every pclean_set_fn_table of this id (keys the memo of option-list marginals)
 };
 
 struct MeanTable {

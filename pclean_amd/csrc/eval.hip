@@ -2430,7 +2430,8 @@ static int make_item_groups(pclean_ctx* ctx, int block_id, int node_id, const It
 // log marginal of sub-tree `node_id` for every item (no draws), evaluated once per distinct item tuple
 // ---- memo of option-list marginals ---------------------------------------------------------------------------
 // The log-marginal of an option list (LEAF node) is a pure function of (observed values of its terms, ctx) as long
-// as its option table, pair tables and fn tables stay what they are — the data never changes, so the same tuples
+// as its option table, pair tables, fn tables and the block's plan stay what they are (`ver` below folds a version of
+// each: a re-upload of any of them wipes the table) — the data never changes, so the same tuples
 // come back sweep after sweep (the reference memoises its AddTypos densities the same way, add_typos.jl:47,55).
 // Open-addressing table in HBM: 3 x uint64 key (up to 6 values, each stored +1) + the fp64 marginal.  Lookups
 // and inserts run in different kernels, so a reader never meets a half-written entry; two inserts of one key may
@@ -2526,15 +2527,20 @@ static int eval_node_lse(pclean_ctx* ctx, int block_id, int node_id, const ItemL
   for (int i = 0; i < n.n_terms; ++i) {
     const pclean_term& tm = b.terms[n.term_begin + i];
     ver = ver * 1000003ull + ctx->pair[tm.pair_table].version;
-    if (tm.ctx_slot >= 0) ver = ver * 1000003ull + (uint64_t)(tm.fn_table + 1);
-    if (tm.dens_kind == PCLEAN_DENS_NAME3) {  // (its suffix table, and whatever pclean_set_term_name3 last set)
+    if (tm.ctx_slot >= 0) ver = ver * 1000003ull + ctx->fn[tm.fn_table].version;  // (the contents, not the id)
+    if (tm.dens_kind == PCLEAN_DENS_NAME3)  // (its suffix table)
       for (const Name3Term& x : b.name3)
         if (x.term == n.term_begin + i) ver = ver * 1000003ull + ctx->pair[x.suffix_table].version;
-      ver = ver * 1000003ull + b.version;
-    }
   }
+  // the terms themselves (obs_col, dens_kind, max_typos, ...) and whatever pclean_set_term_name3 last set: any reload
+  ver = ver * 1000003ull + b.version;
   SweepState::LeafMemo& mm = s->memo[block_id * 64 + node_id];
-  const int cap = 1 << 21;
+  // (PCLEAN_MEMO_CAP: a smaller table, so that tests reach the fill limit and the probe limit)
+  static const int cap = [] {
+    const char* e = getenv("PCLEAN_MEMO_CAP");
+    const long v = e ? atol(e) : 0;
+    return v >= 64 && v <= (1 << 21) && (v & (v - 1)) == 0 ? (int)v : 1 << 21;
+  }();
   if (mm.cap != cap) {
     if (mm.keys.alloc((size_t)cap * 3) || mm.vals.alloc(cap) || mm.count.alloc(4))
       return pclean_fail(ctx, PCLEAN_ERR_HIP, "device alloc failed (memo)");
@@ -2545,6 +2551,7 @@ static int eval_node_lse(pclean_ctx* ctx, int block_id, int node_id, const ItemL
     HIPCHK(ctx, hipMemsetAsync(mm.keys.p, 0xff, (size_t)cap * 3 * sizeof(uint64_t), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(mm.count.p, 0, sizeof(unsigned int), ctx->stream));
     mm.ver = ver;
+    ++s->memo_stats[3];
   }
   MemoDev md{mm.keys.p, mm.vals.p, mm.count.p, (unsigned int)(cap - 1), (unsigned int)(cap / 2)};
   KeyColsDev kc{};
@@ -2560,6 +2567,9 @@ static int eval_node_lse(pclean_ctx* ctx, int block_id, int node_id, const ItemL
   hipLaunchKernelGGL(compact_new_kernel, grid1(N), dim3(256), 0, ctx->stream, (size_t)N, flag, 1, miss_ctr, list, nullptr);
   unsigned int n_miss = 0;
   PCLEAN_READ_COUNT(ctx, miss_ctr, &n_miss);
+  ++s->memo_stats[0];
+  s->memo_stats[1] += N;
+  s->memo_stats[2] += n_miss;
   if (n_miss == 0) return PCLEAN_OK;
   if (n_miss == (unsigned int)N) {
     int rc = eval_node_lse_core(ctx, block_id, node_id, il, excl, seed, sweep, lse_out);
@@ -2582,6 +2592,25 @@ static int eval_node_lse(pclean_ctx* ctx, int block_id, int node_id, const ItemL
   hipLaunchKernelGGL(scatter_f64_kernel, grid1(n_miss), dim3(256), 0, ctx->stream, (int)n_miss, list, dst, lse_out);
   hipLaunchKernelGGL(memo_insert_kernel, grid1(n_miss), dim3(256), 0, ctx->stream, (int)n_miss, list, kc, il.row, il.ctx, md,
                      dst);
+  return PCLEAN_OK;
+}
+
+extern "C" int pclean_debug_memo_stats(pclean_ctx* ctx, int64_t* out, int32_t reset) {
+  if (!ctx) return PCLEAN_ERR_ARG;
+  SweepState* s = st(ctx);
+  if (out) {
+    memcpy(out, s->memo_stats, sizeof(s->memo_stats));
+    out[PCLEAN_MEMO_STAT_SLOTS - 1] = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (auto& kv : s->memo) {
+      if (!kv.second.cap) continue;
+      unsigned int stored = 0;
+      HIPCHK(ctx, hipMemcpy(&stored, kv.second.count.p, sizeof(stored), hipMemcpyDeviceToHost));
+      out[PCLEAN_MEMO_STAT_SLOTS - 1] += stored;
+    }
+  }
+  if (reset) memset(s->memo_stats, 0, sizeof(s->memo_stats));
   return PCLEAN_OK;
 }
 

@@ -103,6 +103,7 @@ struct SweepState {
     int cap = 0;
   };
   std::map<int, LeafMemo> memo;
+  int64_t memo_stats[4] = {};  // pclean_debug_memo_stats: calls on the memo path, items looked up, items missed, wipes
   struct TupleIds {  // ensure_tuple_ids: key = block * 64 + node
     DevBuf<int32_t> id;
     DevBuf<uint32_t> pre;

@@ -47,6 +47,26 @@ def test_launch_counters_are_declared_exported_and_named_slot_for_slot():
         [16, 2, 8, 6, 1, 2]
 
 
+def test_memo_counter_is_declared_exported_and_named_slot_for_slot():
+    """pclean_debug_memo_stats, the counter of the memo of option-list marginals: declared with its slot count, exported,
+    bound with one distinct name per slot, and a NULL context is refused"""
+    from pclean_amd import _lib, build
+    build.build(verbose=False)
+    lib = ctypes.CDLL(build.LIB)
+    src = open(os.path.join(ROOT, "include", "pclean_hip.h")).read()
+    m = re.search(r"#define PCLEAN_MEMO_STAT_SLOTS (\d+)", src)
+    assert m
+    assert re.search(r"int pclean_debug_memo_stats\(pclean_ctx\* ctx, int64_t\* out, int32_t reset\);", src)
+    assert hasattr(lib, "pclean_debug_memo_stats")
+    names = _lib.HipContext.MEMO_STAT_SLOTS
+    assert len(names) == len(set(names)) == int(m.group(1)) == 5
+    assert names == ("calls", "lookups", "misses", "resets", "stored")
+    assert callable(_lib.HipContext.memo_stats)
+    assert lib.pclean_debug_memo_stats(None, None, 0) != 0
+    out = (ctypes.c_int64 * 5)()
+    assert lib.pclean_debug_memo_stats(None, out, 1) != 0
+
+
 def test_no_cpu_fallback():
     import torch
     from pclean_amd import HipContext, PCleanHipError
